@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the geodesic ray-march hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 A "step" is one full frame of the BASELINE.json workload: 3840x2160, Kerr a = 0.9,
 full volumetric disk + dust + Doppler/redshift, the reference's start-up camera
@@ -19,6 +19,9 @@ alongside.  `cpu_baseline` is the reference's own kernel body (OpenMP, all host 
 oracle port beside it) on a strided sample of the same frame, on every N -- a reported
 baseline, not a target.  `within_tolerance_mode` = RRT_ARITH_FMAD (the arithmetic class of the
 reference's own build) with its account; never `value`.
+
+--dump-outputs DIR writes the frame of the last timed step (rank 0's assembled RGBA8 frame) as a fixed
+seeded sample of its pixels (dump_frame), so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -150,6 +153,27 @@ def cpu_baseline(width, height, spin, stride, sky, cam_arr=None, time_=1.0, nthr
             "step_counts_equal_port": same_steps, "port": port}, means
 
 
+DUMP_SAMPLE_PIXELS = 1 << 21   # 2 M pixels: 32 MB of float32 RGBA + 16 MB of float64 indices, 48 MB in all
+DUMP_SEED = 0
+
+
+def dump_frame(out_dir, frame_u8, width, height):
+    """Writes out_dir/frame_rgba_sample.npy (n, 4) float32 = the RGBA8 bytes of n pixels of the frame (in the library's row
+    order) and out_dir/frame_pixel_index.npy (n,) float64 = their flat indices y * width + x, ascending.
+    The pixels are the same for every run with the same --width / --height: the whole frame when it has at most
+    DUMP_SAMPLE_PIXELS pixels, else that many drawn without replacement by a generator seeded with DUMP_SEED."""
+    import numpy as np
+    rgba = np.asarray(frame_u8).reshape(height * width, 4)
+    n_pix = width * height
+    if n_pix <= DUMP_SAMPLE_PIXELS:
+        idx = np.arange(n_pix)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n_pix, DUMP_SAMPLE_PIXELS, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "frame_rgba_sample.npy"), rgba[idx].astype(np.float32))
+    np.save(os.path.join(out_dir, "frame_pixel_index.npy"), idx.astype(np.float64))
+
+
 def self_launch(n, argv):
     """`python bench.py --gpus N` without a launcher: start the N ranks as CHILD processes (one per GPU,
     torch.distributed.run, rendezvous on 127.0.0.1) before this process has touched torch or the GPU,
@@ -196,7 +220,11 @@ def main():
                          "the tracebacks of all threads (instead of hanging)")
     ap.add_argument("--run-timeout", type=float, default=900.0,
                     help="seconds everything after the bring-up may take before the same happens (0: no limit)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's frame (a fixed seeded pixel sample, float32) under DIR as .npy files")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args.gpus, sys.argv[1:]))
@@ -386,6 +414,8 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     kernel_ms = [a.elapsed_time(b) for a, b in ev[args.warmup:args.warmup + args.steps]]
+    if args.dump_outputs and rank == 0:
+        dump_frame(args.dump_outputs, fs.frame.cpu().numpy(), w, h)
 
     if world == 1:
         if clock_when is None:                 # --warmup 0: beside two untimed frames of the same workload, afterwards

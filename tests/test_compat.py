@@ -9,7 +9,7 @@ import pytest
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 EXE = os.path.join(ROOT, "tests", "compat", "dropin_main")
-REF_EXE = os.path.join(ROOT, "tests", "compat", "ref_header_main")
+REF_EXE = os.path.join(ROOT, "oracle", "_ref", "ref_header_main")      # with the other reference-built binaries, which travel
 REF_INC = "/root/reference/include"
 
 
@@ -33,10 +33,13 @@ def build_ref_header_main():
     """Build container only: compile against the reference's include/raymarcher.h, link librrt_hip.so."""
     from relativisticraytracer_amd import build
     build.build_lib()
+    os.makedirs(os.path.dirname(REF_EXE), exist_ok=True)
+    # rpath relative to the binary: it runs wherever the tree is copied
+    lib_rel = os.path.relpath(os.path.dirname(build.LIB), os.path.dirname(REF_EXE))
     cmd = ["g++", "-std=c++17", "-O1", "-w", "-I" + _cuda_inc(), "-I" + REF_INC, "-I" + os.path.join(ROOT, "include"),
            os.path.join(ROOT, "tests", "compat", "ref_header_main.cpp"),
            "-L" + os.path.dirname(build.LIB), "-lrrt_hip", "-L/opt/rocm/lib", "-lamdhip64",
-           "-Wl,-rpath," + os.path.dirname(build.LIB) + ":/opt/rocm/lib", "-o", REF_EXE]
+           "-Wl,-rpath,$ORIGIN/" + lib_rel + ":/opt/rocm/lib", "-o", REF_EXE]
     subprocess.run(cmd, check=True)
 
 
