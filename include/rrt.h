@@ -379,6 +379,32 @@ int rrt_launch_raymarch_ex(void* d_out_rgba8, int width, int height, float time,
                            const rrt_camera* cam, rrt_sky_t sky, const rrt_effects* fx,
                            const rrt_params* prm, const rrt_debug_outputs* dbg, void* stream);
 
+/* ---- s x s supersampled (anti-aliased) frames, s = samples_per_axis in {1, 2, 4, 8}; no counterpart in the reference, which
+ *      casts one ray per pixel at the pixel's corner (raymarcher.cu:20).  The frame is DEFINED by the 1x frame of
+ *      (s*width) x (s*height):
+ *        - output pixel (x, y) has sub-samples (i, j), 0 <= i, j < s; sub-sample (i, j) is rendered exactly like pixel
+ *          (s*x + i, s*y + j) of the (s*width) x (s*height) frame -- primary ray, lens distortion, the nudge hash
+ *          (rrt_params.nudge_ulps) on those coordinates, march, sky, bloom and the vignette at that sub-sample's uv.  The grid is
+ *          corner-aligned: it tiles the pixel's footprint [x, x+1) x [y, y+1), so the image sits (s-1)/(2s) px right of and
+ *          below the 1x frame's.  (float)(s*w)/(float)(s*h) == (float)w/(float)h: the aspect ratio is unchanged;
+ *        - the pixel's HDR value is the mean of its s^2 sub-samples' post-FX HDR (what rrt_debug_outputs.d_hdr holds for them
+ *          in the big frame), summed in THIS order: a pairwise tree over i within each sub-row j in natural order (s = 4:
+ *          ((h0 + h1) + (h2 + h3))), then the same tree over the s row sums; then multiplied by 1/(s*s), which is exact;
+ *        - that mean is tone-mapped once as raymarcher.cu:164-173 does and stored as RGBA8, bottom-up rows.
+ *      s = 1 gives the bytes of rrt_launch_raymarch.  d_hdr_rgba32f (may be NULL): the mean HDR, 4 floats per pixel (alpha 1),
+ *      indexed like the RGBA8 frame -- linear frames for compositing.
+ *      rrt_params: spin, max_steps, volumetrics, sky_frac_bits, arith_mode, noise_table, nudge_ulps / nudge_seed are honoured;
+ *      workspace, path_policy, pool_rounds, pass_chains and tile_order are IGNORED -- a supersampled launch is always the single
+ *      kernel in the static dispatch order.  Size limits (RRT_ERR_INVALID_ARGUMENT): those of rrt_launch_raymarch for width x
+ *      height, and for the virtual frame (s*width)*(s*height) < 2^31, s*height <= 524 280.  No memset, no synchronisation: a
+ *      launch can be captured into a hipGraph. ---- */
+int rrt_launch_raymarch_ss(void* d_out_rgba8, float* d_hdr_rgba32f /* may be NULL */, int width, int height, int samples_per_axis,
+                           float time, const rrt_camera* cam, rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm, void* stream);
+/* The same frame's row tiles of `shard` (tile t = OUTPUT rows [t*tile_rows, (t+1)*tile_rows) belongs to shard t mod n_shards), in
+ * exactly the buffer layout of rrt_launch_raymarch_tiles: rrt_tile_shard_rows and rrt_assemble_(all_)tiles serve it unchanged. */
+int rrt_launch_raymarch_ss_tiles(void* d_out_tiles, int width, int height, int samples_per_axis, int tile_rows, int shard, int n_shards,
+                                 float time, const rrt_camera* cam, rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm, void* stream);
+
 /* ---- which path a rank's share takes while several frames of a sequence are in flight (host only; no GPU call) ----
  * New in this repo (the reference renders one frame at a time on one GPU: src/main.cpp:505-529).  A launch of <= 1.5 M rays
  * with a pool can take the three-pass path (RRT_PATH_AUTO) or the single kernel (RRT_PATH_SINGLE); under frames in flight the

@@ -24,6 +24,7 @@ from ._lib import RRTError, rrt_camera, rrt_debug_outputs, rrt_effects, rrt_para
 __all__ = ["CameraState", "CameraEffects", "RenderParams", "SkyTexture", "Workspace", "NoiseTable", "launch_raymarch",
            "set_launch_defaults", "get_launch_defaults",
            "launch_raymarch_rows", "launch_raymarch_tiles", "assemble_tiles", "assemble_all_tiles",
+           "launch_raymarch_ss", "launch_raymarch_ss_tiles",
            "tile_shard_rows",
            "launch_raymarch_debug", "RRTError", "device_count", "abi_version", "TileOrder", "TileMap",
            "probe_tile_costs", "balance_tiles", "launch_raymarch_tilemap", "assemble_all_tilemap", "clock_probe", "clock_probe_ghz"]
@@ -482,6 +483,27 @@ def launch_raymarch_tiles(d_out_tiles, w, h, tile_rows, shard, n_shards, time, c
                                                      C.byref(effects),
                                                      C.byref(params) if params is not None else None,
                                                      _stream(stream)), "rrt_launch_raymarch_tiles")
+
+
+def launch_raymarch_ss(d_out, w, h, samples, time, cam, skyboxTex, effects, params=None, stream=None, hdr=None):
+    """samples x samples supersampled w x h frame (include/rrt.h: rrt_launch_raymarch_ss): every pixel is the mean of the
+    post-FX HDR of the samples^2 pixels it covers in the (samples w) x (samples h) frame, tone-mapped once; RGBA8, bottom-up.
+    `hdr` (optional): a device buffer of w*h*4 float32 that receives the mean HDR, indexed like the frame.  samples in
+    {1, 2, 4, 8}; the params' workspace, path_policy, pool_rounds, pass_chains and tile_order are ignored."""
+    _lib.check(_lib.load().rrt_launch_raymarch_ss(_ptr(d_out), _ptr(hdr), w, h, samples, float(time), C.byref(cam),
+                                                  _sky_handle(skyboxTex), C.byref(effects),
+                                                  C.byref(params) if params is not None else None,
+                                                  _stream(stream)), "rrt_launch_raymarch_ss")
+
+
+def launch_raymarch_ss_tiles(d_out_tiles, w, h, samples, tile_rows, shard, n_shards, time, cam, skyboxTex, effects,
+                             params=None, stream=None):
+    """The row tiles of `shard` of launch_raymarch_ss's frame, in launch_raymarch_tiles' buffer layout (assemble_tiles /
+    assemble_all_tiles serve it unchanged)."""
+    _lib.check(_lib.load().rrt_launch_raymarch_ss_tiles(_ptr(d_out_tiles), w, h, samples, tile_rows, shard, n_shards,
+                                                        float(time), C.byref(cam), _sky_handle(skyboxTex), C.byref(effects),
+                                                        C.byref(params) if params is not None else None,
+                                                        _stream(stream)), "rrt_launch_raymarch_ss_tiles")
 
 
 def tile_shard_rows(h, tile_rows, shard, n_shards):

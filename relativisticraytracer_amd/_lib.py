@@ -110,6 +110,8 @@ SYMBOLS = [
     ("rrt_launch_raymarch", _i, [_vp, _i, _i, _f, _cam, _ull, _fx, _prm, _vp]),
     ("rrt_launch_raymarch_rows", _i, [_vp, _i, _i, _i, _i, _f, _cam, _ull, _fx, _prm, _vp]),
     ("rrt_launch_raymarch_tiles", _i, [_vp, _i, _i, _i, _i, _i, _f, _cam, _ull, _fx, _prm, _vp]),
+    ("rrt_launch_raymarch_ss", _i, [_vp, _vp, _i, _i, _i, _f, _cam, _ull, _fx, _prm, _vp]),
+    ("rrt_launch_raymarch_ss_tiles", _i, [_vp, _i, _i, _i, _i, _i, _i, _f, _cam, _ull, _fx, _prm, _vp]),
     ("rrt_tile_shard_rows", _i, [_i, _i, _i, _i, C.POINTER(_i)]),
     ("rrt_assemble_tiles", _i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     ("rrt_assemble_all_tiles", _i, [_vp, _vp, C.c_size_t, _i, _i, _i, _i, _vp]),

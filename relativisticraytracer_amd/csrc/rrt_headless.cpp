@@ -8,6 +8,7 @@
 //                [--gpus N] [--tile-rows 16] [--workspace-gib G] [--noise-table-gib B | --no-noise-table]
 //                [--arith strict|fmad|fast] [--path-window F | --path-window -1 | --path-policy auto|single|three-pass]
 //                [--init-timeout 300] [--frame-timeout 120]      (watchdog, seconds; exit status 3 when it fires)
+//                [--supersample 1|2|4|8]       (S x S sub-samples per pixel: rrt_launch_raymarch_ss*, single kernel, no pool)
 //
 // Noise tables: the reference's simTime runs without bound (main.cpp:515) and a table's size grows with the times
 // it covers, so each device keeps ONE table over a window of the clock that fits --noise-table-gib (default 2;
@@ -228,6 +229,7 @@ int main(int argc, char** argv) {
                                    // three-pass path for every small share as in rounds 1-5
     int gpus = 1, tile_rows = 16, workspace_gib = 2, use_table = 1, force_collective = 0;
     int tile_order = -1;           // cost-ordered dispatch: -1 auto (on when frames are rendered one at a time), 0 off, 1 on
+    int supersample = 1;           // --supersample S: S x S sub-samples per pixel (rrt_launch_raymarch_ss*); 1 = one ray per pixel
     int kSlots = 3;                // frames in flight: frame k renders on stream k mod kSlots while its predecessors are
                                    // gathered / assembled / copied out (a rank's share of a frame is only a few rounds of
                                    // wavefronts; 3 measured best at 8 shards of a 4K frame: profiles/r02_frames_in_flight.txt)
@@ -259,6 +261,11 @@ int main(int argc, char** argv) {
             else { fprintf(stderr, "--path-policy auto | single | three-pass\n"); return 2; }
             path_window = -1;
         }
+        else if (a == "--supersample") {
+            const std::string m = i + 1 < argc ? argv[++i] : "";
+            if (m == "1" || m == "2" || m == "4" || m == "8") supersample = atoi(m.c_str());
+            else { fprintf(stderr, "--supersample 1 | 2 | 4 | 8 (sub-samples per pixel along each axis)\n"); return 2; }
+        }
         else if (a == "--arith" && i + 1 < argc) {
             const std::string m = argv[++i];
             if (m == "strict") arith = RRT_ARITH_STRICT; else if (m == "fmad") arith = RRT_ARITH_FMAD; else if (m == "fast") arith = RRT_ARITH_FAST;
@@ -269,6 +276,8 @@ int main(int argc, char** argv) {
     if (w <= 0 || h <= 0 || frames < 0 || fps <= 0 || gpus < 1 || tile_rows < 1 || kSlots < 1 || kSlots > kMaxSlots) {
         fprintf(stderr, "bad arguments\n"); return 2;
     }
+    // a supersampled launch is always the single kernel in the static order (include/rrt.h): no pool, no path choice, no tile order
+    if (supersample > 1) { workspace_gib = 0; path_window = -1; tile_order = 0; }
     int n_dev = 0, rc;
     if ((rc = rrt_device_count(&n_dev)) != RRT_OK) return fail("no GPU", rc);
     if (gpus > n_dev) { fprintf(stderr, "rrt_headless: --gpus %d but %d device(s) visible\n", gpus, n_dev); return 2; }
@@ -476,7 +485,11 @@ int main(int argc, char** argv) {
             if (D.chooser) { int pol = RRT_PATH_AUTO; rrt_path_chooser_policy(D.chooser, k, &pol); prm.path_policy = pol; }
             else if (path_policy >= 0) prm.path_policy = path_policy;
             void* dst = collective ? D.tiles[slot] : frame[slot];
-            if (collective) rc = rrt_launch_raymarch_tiles(dst, w, h, tile_rows, d, gpus, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
+            if (supersample > 1) {
+                if (collective) rc = rrt_launch_raymarch_ss_tiles(dst, w, h, supersample, tile_rows, d, gpus, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
+                else rc = rrt_launch_raymarch_ss(dst, nullptr, w, h, supersample, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
+            }
+            else if (collective) rc = rrt_launch_raymarch_tiles(dst, w, h, tile_rows, d, gpus, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
             else rc = rrt_launch_raymarch(dst, w, h, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
             if (rc != RRT_OK) return fail("launch", rc);
             if (D.chooser) HIPCHK(hipEventRecord(D.render_end[k % (2 * kSlots)], D.stream[slot]));
@@ -531,11 +544,11 @@ int main(int argc, char** argv) {
     printf("{\"frames\": %d, \"width\": %d, \"height\": %d, \"n_gpus\": %d, \"seconds\": %.4f, \"fps\": %.3f, \"Mrays_per_s\": %.3f, "
            "\"path\": \"%s\", \"spin\": %g, \"arith_mode\": \"%s\", \"noise_tables\": {\"builds\": %d, \"table_frames\": %d, "
            "\"arith_frames\": %d, \"coarsest_coverage\": %d, \"peak_bytes\": %zu, \"budget_bytes\": %zu}, \"tile_order\": %s, \"collective\": \"%s\", "
-           "\"path_choice\": %s}\n",
+           "\"path_choice\": %s, \"supersample\": %d}\n",
            frames, w, h, gpus, dt, frames / dt, (double)frames * w * h / dt / 1e6, path_name, spin,
            arith == RRT_ARITH_FAST ? "fast" : (arith == RRT_ARITH_FMAD ? "fmad" : "strict"),
            table_builds, table_frames, arith_frames, coarsest, table_peak, table_budget, dev[0].order[0] ? "true" : "false",
-           collective ? "rccl grouped send/recv gather" : "none", choice.c_str());
+           collective ? "rccl grouped send/recv gather" : "none", choice.c_str(), supersample);
 
     for (int d = 0; d < gpus; ++d) {
         Device& D = dev[d];

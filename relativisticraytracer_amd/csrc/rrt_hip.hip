@@ -546,6 +546,48 @@ int launch(const FrameArgs& a, const LaunchOpts& o, bool debug, hipStream_t st) 
     return RRT_OK;
 }
 
+/* ---- s x s supersampled launches (rrt_launch_raymarch_ss*): one kernel, static order, nothing else */
+bool valid_samples(int s) { return s == 1 || s == 2 || s == 4 || s == 8; }
+
+/* the checks of check_common plus the virtual (s w) x (s h) frame's limits; all before any device call */
+int check_ss(const void* out, int width, int height, int s, const rrt_camera* cam, const rrt_effects* fx, const rrt_params* prm) {
+    if (!valid_samples(s)) return RRT_ERR_INVALID_ARGUMENT;
+    const int rc = check_common(out, width, height, cam, fx, prm);
+    if (rc != RRT_OK) return rc;
+    if ((long long)s * width * ((long long)s * height) >= (1ll << 31)) return RRT_ERR_INVALID_ARGUMENT;
+    if ((long long)s * height > (long long)kMaxGridY * kWGPixY) return RRT_ERR_INVALID_ARGUMENT;   /* 524 280 virtual rows */
+    return RRT_OK;
+}
+
+/* `rows` in OUTPUT rows of the w x h frame.  The params that pick a path or an order (workspace, path_policy, pool_rounds,
+ * pass_chains, tile_order) are dropped before fill_args looks at them: a supersampled launch neither takes the three-pass
+ * path nor reads or records a tile order. */
+int launch_ss(void* out, float4* hdr, int width, int height, int s, const RowMap& rows, float time, const rrt_camera* cam,
+              rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm_in, hipStream_t st) {
+    rrt_params prm;
+    load_params(prm_in, prm);
+    prm.workspace = 0; prm.path_policy = RRT_PATH_AUTO; prm.pool_rounds = 0; prm.pass_chains = 0; prm.tile_order = 0;
+    FrameArgs a;
+    LaunchOpts o;
+    const int rc = fill_args(a, o, out, s * width, s * height, time, cam, sky, fx, &prm);
+    if (rc) return rc;
+    a.rows = rows;
+    if (rows.n_local_rows == 0) return RRT_OK;
+    const dim3 grid((a.width + kWGPixX - 1) / kWGPixX, (s * rows.n_local_rows + kWGPixY - 1) / kWGPixY), block(kWGThreads);
+    const bool spin = a.spin != 0.0f;
+    const int media = o.media, arith = o.arith;
+#define RRT_SS3(S, M, F) hipLaunchKernelGGL((supersample_pixels<S, M, F>), grid, block, 0, st, a, s, hdr)
+#define RRT_SS2(S, M) do { if (arith == kArithFast) RRT_SS3(S, M, kArithFast); else if (arith == kArithFmad) RRT_SS3(S, M, kArithFmad); \
+                           else RRT_SS3(S, M, kArithStrict); } while (0)
+#define RRT_SS1(S) do { if (media == 3) RRT_SS2(S, 3); else if (media == 2) RRT_SS2(S, 2); else if (media == 1) RRT_SS2(S, 1); else RRT_SS2(S, 0); } while (0)
+    if (spin) RRT_SS1(true); else RRT_SS1(false);
+#undef RRT_SS1
+#undef RRT_SS2
+#undef RRT_SS3
+    RRT_HIP(hipGetLastError());
+    return RRT_OK;
+}
+
 int shard_rows(int height, int tile_rows, int shard, int n_shards) {
     int n_tiles = (height + tile_rows - 1) / tile_rows;
     int rows = 0;
@@ -1209,6 +1251,25 @@ int rrt_launch_raymarch_tiles(void* d_out_tiles, int width, int height, int tile
     if (rc) return rc;
     a.rows = RowMap{shard_rows(height, tile_rows, shard, n_shards), 0, tile_rows, shard, n_shards, nullptr};
     return launch(a, o, false, static_cast<hipStream_t>(stream));
+}
+
+int rrt_launch_raymarch_ss(void* d_out_rgba8, float* d_hdr_rgba32f, int width, int height, int samples_per_axis, float time,
+                           const rrt_camera* cam, rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm, void* stream) {
+    const int rc = check_ss(d_out_rgba8, width, height, samples_per_axis, cam, fx, prm);
+    if (rc) return rc;
+    return launch_ss(d_out_rgba8, reinterpret_cast<float4*>(d_hdr_rgba32f), width, height, samples_per_axis,
+                     RowMap{height, 0, height, 0, 1, nullptr}, time, cam, sky, fx, prm, static_cast<hipStream_t>(stream));
+}
+
+int rrt_launch_raymarch_ss_tiles(void* d_out_tiles, int width, int height, int samples_per_axis, int tile_rows, int shard, int n_shards,
+                                 float time, const rrt_camera* cam, rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm,
+                                 void* stream) {
+    const int rc = check_ss(d_out_tiles, width, height, samples_per_axis, cam, fx, prm);
+    if (rc) return rc;
+    if (tile_rows <= 0 || n_shards <= 0 || shard < 0 || shard >= n_shards) return RRT_ERR_INVALID_ARGUMENT;
+    return launch_ss(d_out_tiles, nullptr, width, height, samples_per_axis,
+                     RowMap{shard_rows(height, tile_rows, shard, n_shards), 0, tile_rows, shard, n_shards, nullptr}, time, cam, sky,
+                     fx, prm, static_cast<hipStream_t>(stream));
 }
 
 int rrt_assemble_tiles(void* d_frame, const void* d_tiles, int width, int height, int tile_rows, int shard,

@@ -185,10 +185,9 @@ __device__ __forceinline__ void primary_ray(const FrameArgs& a, int x, int y, fl
     }
 }
 
-/* Everything after the march: sky, composition, post-FX, tone map, RGBA8 store -- raymarcher.cu:124-173. */
-template <bool DEBUG>
-__device__ __forceinline__ void shade_and_store(const FrameArgs& a, int x, int y, int out_row, float uvx, float uvy,
-                                                bool hit, v3 p, v3 vel, Radiance acc, int steps) {
+/* Everything after the march up to the tone map: sky, composition, post-FX -- raymarcher.cu:124-161.  The ray's HDR value
+ * (rrt_debug_outputs.d_hdr). */
+__device__ __forceinline__ v3 shade_hdr(const FrameArgs& a, float uvx, float uvy, bool hit, v3 vel, Radiance acc) {
     float bg_r = 0.f, bg_g = 0.f, bg_b = 0.f;
     if (!hit) {
         v3 d = normalize(vel);
@@ -217,14 +216,30 @@ __device__ __forceinline__ void shade_and_store(const FrameArgs& a, int x, int y
         const v3 vg = vignette(mk(hx, hy, hz), uvx, uvy, a.vignette_intensity);
         hx = vg.x; hy = vg.y; hz = vg.z;
     }
+    return mk(hx, hy, hz);
+}
 
-    /* raymarcher.cu:164-173 */
-    float out_r = 1.0f - rrt_expf(-hx * kExposure);
-    float out_g = 1.0f - rrt_expf(-hy * kExposure);
-    float out_b = 1.0f - rrt_expf(-hz * kExposure);
+/* Tone map of an HDR value (before the u8 cast) and the RGBA8 store -- raymarcher.cu:164-173. */
+__device__ __forceinline__ void tone_map(v3 hdr, float& out_r, float& out_g, float& out_b) {
+    out_r = 1.0f - rrt_expf(-hdr.x * kExposure);
+    out_g = 1.0f - rrt_expf(-hdr.y * kExposure);
+    out_b = 1.0f - rrt_expf(-hdr.z * kExposure);
+}
+__device__ __forceinline__ void store_rgba8(uchar4* out, size_t oi, float out_r, float out_g, float out_b) {
+    out[oi] = make_uchar4((unsigned char)(int)(out_r * 255.0f), (unsigned char)(int)(out_g * 255.0f),
+                          (unsigned char)(int)(out_b * 255.0f), 255);
+}
+
+/* Everything after the march: sky, composition, post-FX, tone map, RGBA8 store -- raymarcher.cu:124-173. */
+template <bool DEBUG>
+__device__ __forceinline__ void shade_and_store(const FrameArgs& a, int x, int y, int out_row, float uvx, float uvy,
+                                                bool hit, v3 p, v3 vel, Radiance acc, int steps) {
+    const v3 c = shade_hdr(a, uvx, uvy, hit, vel, acc);
+    const float hx = c.x, hy = c.y, hz = c.z;
+    float out_r, out_g, out_b;
+    tone_map(c, out_r, out_g, out_b);
     const size_t oi = (size_t)out_row * a.width + x;
-    a.out[oi] = make_uchar4((unsigned char)(int)(out_r * 255.0f), (unsigned char)(int)(out_g * 255.0f),
-                            (unsigned char)(int)(out_b * 255.0f), 255);
+    store_rgba8(a.out, oi, out_r, out_g, out_b);
     if (DEBUG) {
         const size_t di = (size_t)y * a.width + x;
         if (a.dbg.d_ldr) { float* q = a.dbg.d_ldr + 4 * oi; q[0] = out_r; q[1] = out_g; q[2] = out_b; q[3] = 1.0f; }
@@ -630,6 +645,53 @@ void raymarch_pixels(const FrameArgs a) {
         const unsigned long long dt = (__builtin_readcyclecounter() - t_start) >> 4;
         a.tile_cost[wave_tile(a)] = dt > kTileCostMax ? kTileCostMax : (unsigned)dt;
     }
+}
+
+/* s x s supersampled frame (rrt_launch_raymarch_ss, include/rrt.h has the contract): sub-sample (i, j) of output pixel (x, y) is
+ * pixel (s x + i, s y + j) of the (s w) x (s h) frame, and the pixel is the mean of its s^2 post-FX HDR values, tone-mapped once.
+ * `a` describes that VIRTUAL frame (a.width = s w, a.height = s h: primary_ray, the nudge hash and the vignette see its pixel
+ * coordinates) except for a.rows, which maps OUTPUT rows of the w x h frame.  A wave covers an 8x8 tile of the virtual sample
+ * grid -- (8/s)^2 output pixels, a pixel's sub-samples in lanes of the same wave -- so the waves are exactly those of
+ * raymarch_pixels on the big frame (same coherence, same wave-uniform vacuum loop).  Virtual local row lr' is output local row
+ * lr' / s, sub-row lr' mod s: a pixel's lanes are all valid or all invalid.  Sub-sample (i, j) sits in lane
+ * (8 j' + i') with i = i' mod s, j = j' mod s, so an xor butterfly over lane masks 1 .. s/2, then 8 .. 8 s/2 sums a pixel's row
+ * pairwise in natural order and then its row sums the same way; the sum lands in every lane of the pixel (addition commutes
+ * exactly) and its first lane, which holds the low operand at every level, tone-maps and stores.  hdr_out (may be NULL): the
+ * mean HDR, alpha 1, indexed like the frame. */
+static_assert(kTileW == 8 && kTileH == 8, "supersample_pixels maps a pixel's sub-samples into an 8x8 wave tile (s = 8: one pixel per wave)");
+template <bool SPIN, int MEDIA, int ARITH>
+__global__ __launch_bounds__(kWGThreads, (MEDIA != 0 ? RRT_MEDIA_WAVES : 1))      /* raymarch_pixels' register budget */
+void supersample_pixels(const FrameArgs a, const int s, float4* const hdr_out) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int vx = tile_column(a) * kWGPixX + (wave & 1) * kTileW + (lane & (kTileW - 1));      /* virtual column */
+    const int vlr = row_block(a) * kWGPixY + (wave >> 1) * kTileH + lane / kTileW;              /* virtual local row */
+    const int w = a.width / s, h = a.height / s;
+    const int x = vx / s;
+    int y, out_row;
+    if (x >= w || !map_row(a.rows, h, vlr / s, y, out_row)) return;
+    const int vy = s * y + (vlr - (vlr / s) * s);
+    float uvx, uvy;
+    v3 p, vel;
+    primary_ray(a, vx, vy, uvx, uvy, p, vel);
+    Radiance acc = {0.f, 0.f, 0.f, 1.0f};
+    bool hit = false;
+    int i = 0;
+    march_inline<SPIN, MEDIA, ARITH, true>(a, p, vel, acc, hit, i, nullptr);
+    v3 c = shade_hdr(a, uvx, uvy, hit, vel, acc);
+    for (int m = 1; m < s; m <<= 1) {                   /* the sub-row: ((s0 + s1) + (s2 + s3)) ... */
+        c.x = c.x + __shfl_xor(c.x, m); c.y = c.y + __shfl_xor(c.y, m); c.z = c.z + __shfl_xor(c.z, m);
+    }
+    for (int m = kTileW; m < s * kTileW; m <<= 1) {     /* ... then the row sums */
+        c.x = c.x + __shfl_xor(c.x, m); c.y = c.y + __shfl_xor(c.y, m); c.z = c.z + __shfl_xor(c.z, m);
+    }
+    if (((vx | vlr) & (s - 1)) != 0) return;            /* the pixel's first lane stores */
+    const float inv = 1.0f / (float)(s * s);            /* a power of two: the mean is exact given the sum */
+    c = mk(c.x * inv, c.y * inv, c.z * inv);
+    float out_r, out_g, out_b;
+    tone_map(c, out_r, out_g, out_b);
+    const size_t oi = (size_t)out_row * w + x;
+    store_rgba8(a.out, oi, out_r, out_g, out_b);
+    if (hdr_out) hdr_out[oi] = make_float4(c.x, c.y, c.z, 1.0f);
 }
 
 /* ---- three-pass path, pass 1: geodesics only; sample points of in-medium steps go to the pool ---- */

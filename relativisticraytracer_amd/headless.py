@@ -1,7 +1,7 @@
 """Headless frame driver: the reference's main loop (src/main.cpp:505-529) without a window.
 
     python -m relativisticraytracer_amd.headless --width 1920 --height 1080 --spin 0.9 \\
-           --path 0 --frames 300 [--out frames.rgba | --out ppm_dir/] [--all-effects]
+           --path 0 --frames 300 [--out frames.rgba | --out ppm_dir/] [--all-effects] [--supersample 2]
     python -m torch.distributed.run --nproc-per-node 8 -m relativisticraytracer_amd.headless ...
 
 Per frame k = 1..N it does what `main()` does while recording: advance the fixed 1/24 s clock
@@ -49,6 +49,9 @@ def main(argv=None):
     ap.add_argument("--noise-table-gib", type=float, default=2.0,
                     help="per-GPU byte budget of the noise tables: the window of sim time one table covers (and, for long "
                          "sequences, its coverage) is chosen to fit; the table is rebuilt when the clock leaves the window")
+    ap.add_argument("--supersample", type=int, choices=(1, 2, 4, 8), default=1,
+                    help="S x S sub-samples per pixel, averaged in HDR before the tone map (rrt_launch_raymarch_ss*; 1 = one ray per "
+                         "pixel).  S > 1 always renders with the single kernel in the static order: no pool, path choice or tile order")
     ap.add_argument("--out", default=None, help="x.rgba (raw, bottom-up) | dir/ (PPM per frame) | x.mp4 (needs ffmpeg)")
     ap.add_argument("--init-timeout", type=float, default=300.0,
                     help="several ranks: seconds the process-group bring-up may take before the run exits non-zero with "
@@ -97,12 +100,13 @@ def main(argv=None):
 
     trace("process group ready" if world > 1 else "single rank")
     w, h = args.width, args.height
+    ss = args.supersample
     tex = rrt.SkyTexture(load_sky(args.sky) if args.sky else synthetic_sky())
     fx = rrt.CameraEffects(useChromaticAberration=bool(args.all_effects))
     # with several ranks --frames-in-flight frames are in flight (FrameSharder pipeline mode), each with its own
     # share of the pool
     n_slots = max(2, args.frames_in_flight) if world > 1 else 1
-    pools = [rrt.Workspace((args.workspace_gib << 30) // n_slots) for _ in range(n_slots)] if args.workspace_gib > 0 else []
+    pools = [rrt.Workspace((args.workspace_gib << 30) // n_slots) for _ in range(n_slots)] if args.workspace_gib > 0 and ss == 1 else []
     # lattice-hash tables for the volumetric noise over a sliding window of the recording clock (main.cpp:511-516 lets
     # simTime grow without bound; the table's size grows with it): one table within the byte budget, rebuilt when the
     # clock leaves its window -- never a silent fall-back: frames rendered without a table are counted in the summary
@@ -113,7 +117,7 @@ def main(argv=None):
     # with a pool) it piles the expensive tiles into the first of the two chains and was measured slower: auto leaves it off there
     my_rays = w * sharding.shard_rows(h, args.tile_rows, rank, world)
     three_pass_likely = bool(pools) and my_rays <= rrt._lib.load().rrt_path_auto_max_rays()      # RRT_PATH_AUTO's own threshold
-    use_order = args.tile_order == "on" or (args.tile_order == "auto" and n_slots == 1 and not three_pass_likely)
+    use_order = ss == 1 and (args.tile_order == "on" or (args.tile_order == "auto" and n_slots == 1 and not three_pass_likely))
     orders = [rrt.TileOrder() for _ in range(n_slots)] if use_order else []
     arith_name = args.arith or ("fast" if args.fast else "strict")
     arith_mode = {"strict": 0, "fast": 1, "fmad": 2}[arith_name]
@@ -139,7 +143,10 @@ def main(argv=None):
         k = state["k"]
         if chooser is not None:
             prms[slot].path_policy = chooser.policy(k)
-        rrt.launch_raymarch_tiles(buf, w, h, args.tile_rows, rank, world, state["t"], state["cam"], tex, fx, prms[slot])
+        if ss > 1:
+            rrt.launch_raymarch_ss_tiles(buf, w, h, ss, args.tile_rows, rank, world, state["t"], state["cam"], tex, fx, prms[slot])
+        else:
+            rrt.launch_raymarch_tiles(buf, w, h, args.tile_rows, rank, world, state["t"], state["cam"], tex, fx, prms[slot])
         if chooser is not None:
             e = torch.cuda.Event(enable_timing=True)
             e.record()                                        # on the slot's stream (FrameSharder runs the callback inside it)
@@ -201,7 +208,7 @@ def main(argv=None):
                           "arith_mode": arith_name, "sink": args.out,
                           "path_choice": chooser.stats() if chooser else None,
                           "noise_tables": nwin.summary(),
-                          "tile_order": orders[0].info() if orders else None}), flush=True)
+                          "tile_order": orders[0].info() if orders else None, "supersample": ss}), flush=True)
     if world > 1:
         dist.destroy_process_group()
     nwin.close()
