@@ -405,6 +405,29 @@ int rrt_launch_raymarch_ss(void* d_out_rgba8, float* d_hdr_rgba32f /* may be NUL
 int rrt_launch_raymarch_ss_tiles(void* d_out_tiles, int width, int height, int samples_per_axis, int tile_rows, int shard, int n_shards,
                                  float time, const rrt_camera* cam, rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm, void* stream);
 
+/* ---- motion-blurred frames: K = n_times in {1, 2, 4, 8, 16} shutter-time sub-frames, each s x s supersampled (s in {1, 2, 4, 8});
+ *      no counterpart in the reference, whose every frame is one instant.  times[k] and cams[k] (k < n_times) are HOST arrays, read
+ *      during the call.  The frame is DEFINED by rrt_launch_raymarch_ss:
+ *        - sub-frame k's sum T_k is exactly the sum rrt_launch_raymarch_ss(width, height, s, times[k], &cams[k], ...) forms before it
+ *          scales: the pairwise sub-row / row-sum tree over the post-FX HDR of the (s*width) x (s*height) frame rendered at
+ *          (times[k], cams[k]) -- same nudge hash, lens, bloom, vignette and CA;
+ *        - the pixel's HDR value is tree(T_0 ... T_{K-1}) * (1 / (s*s*K)), tree the same pairwise tree in natural k order
+ *          (((T0 + T1) + (T2 + T3)) ...), the scale a power of two (exact); tone-mapped once, stored as RGBA8, bottom-up rows.
+ *      Hence K = 1 gives the bytes of rrt_launch_raymarch_ss, K equal (time, camera) pairs the bytes of K = 1, and s = 1, K = 1 the
+ *      bytes of rrt_launch_raymarch.  d_hdr_rgba32f (may be NULL): the mean HDR as in rrt_launch_raymarch_ss.
+ *      The noise table (rrt_params.noise_table) is used only if EVERY times[k] lies in its window; otherwise every sub-frame hashes
+ *      arithmetically (same bytes).  Params honoured and ignored as in rrt_launch_raymarch_ss: a blurred launch is always the single
+ *      kernel in the static order.  RRT_ERR_INVALID_ARGUMENT, before any device call: everything rrt_launch_raymarch_ss refuses,
+ *      n_times outside the set, a NULL times or cams, a non-finite time.  No memset, no synchronisation: a launch can be captured
+ *      into a hipGraph. ---- */
+int rrt_launch_raymarch_mb(void* d_out_rgba8, float* d_hdr_rgba32f /* may be NULL */, int width, int height, int samples_per_axis,
+                           int n_times, const float* times, const rrt_camera* cams, rrt_sky_t sky, const rrt_effects* fx,
+                           const rrt_params* prm, void* stream);
+/* The same frame's row tiles of `shard`, in the buffer layout of rrt_launch_raymarch_ss_tiles (rrt_assemble_(all_)tiles serve it). */
+int rrt_launch_raymarch_mb_tiles(void* d_out_tiles, int width, int height, int samples_per_axis, int tile_rows, int shard, int n_shards,
+                                 int n_times, const float* times, const rrt_camera* cams, rrt_sky_t sky, const rrt_effects* fx,
+                                 const rrt_params* prm, void* stream);
+
 /* ---- which path a rank's share takes while several frames of a sequence are in flight (host only; no GPU call) ----
  * New in this repo (the reference renders one frame at a time on one GPU: src/main.cpp:505-529).  A launch of <= 1.5 M rays
  * with a pool can take the three-pass path (RRT_PATH_AUTO) or the single kernel (RRT_PATH_SINGLE); under frames in flight the
@@ -443,6 +466,12 @@ int rrt_path_keyframes(int path, float* out6, int cap_keys);
 int rrt_path_camera_at(int path, float path_time, rrt_camera* out);
 /* recording clock of the main loop, src/main.cpp:511-516: times seen by 1-based frame k */
 int rrt_recording_clock(int frame_k, int fps, float* sim_time, float* path_time);
+/* the shutter of a motion-blurred frame k (rrt_launch_raymarch_mb; no counterpart in the reference), in binary32:
+ * (S, P) = rrt_recording_clock(frame_k, fps), d = shutter * (1.0f / fps), u_m = ((float)(n_times - m) - 0.5f) / (float)n_times,
+ * sim_times[m] = S - d * u_m and path_times[m] = P - d * u_m for m < n_times: the midpoints of n_times equal slices of the
+ * trailing interval (S - d, S], increasing.  shutter in [0, 1] (0: every sub-time is the frame's own), n_times in
+ * {1, 2, 4, 8, 16}; either output may be NULL. */
+int rrt_motion_clock(int frame_k, int fps, float shutter, int n_times, float* sim_times, float* path_times);
 
 #ifdef __cplusplus
 }

@@ -24,7 +24,7 @@ from ._lib import RRTError, rrt_camera, rrt_debug_outputs, rrt_effects, rrt_para
 __all__ = ["CameraState", "CameraEffects", "RenderParams", "SkyTexture", "Workspace", "NoiseTable", "launch_raymarch",
            "set_launch_defaults", "get_launch_defaults",
            "launch_raymarch_rows", "launch_raymarch_tiles", "assemble_tiles", "assemble_all_tiles",
-           "launch_raymarch_ss", "launch_raymarch_ss_tiles",
+           "launch_raymarch_ss", "launch_raymarch_ss_tiles", "launch_raymarch_mb", "launch_raymarch_mb_tiles",
            "tile_shard_rows",
            "launch_raymarch_debug", "RRTError", "device_count", "abi_version", "TileOrder", "TileMap",
            "probe_tile_costs", "balance_tiles", "launch_raymarch_tilemap", "assemble_all_tilemap", "clock_probe", "clock_probe_ghz"]
@@ -504,6 +504,36 @@ def launch_raymarch_ss_tiles(d_out_tiles, w, h, samples, tile_rows, shard, n_sha
                                                         float(time), C.byref(cam), _sky_handle(skyboxTex), C.byref(effects),
                                                         C.byref(params) if params is not None else None,
                                                         _stream(stream)), "rrt_launch_raymarch_ss_tiles")
+
+
+def _sub_frames(times, cams):
+    """host arrays of the sub-frames' times (float32) and cameras (rrt_camera), for the _mb entry points"""
+    times, cams = list(times), list(cams)
+    if len(times) != len(cams):
+        raise ValueError(f"{len(times)} times but {len(cams)} cameras")
+    return (C.c_float * len(times))(*[float(t) for t in times]), (rrt_camera * len(cams))(*cams), len(times)
+
+
+def launch_raymarch_mb(d_out, w, h, samples, times, cams, skyboxTex, effects, params=None, stream=None, hdr=None):
+    """Motion-blurred w x h frame (include/rrt.h: rrt_launch_raymarch_mb): len(times) in {1, 2, 4, 8, 16} sub-frames, sub-frame k
+    the samples x samples supersampled frame at (times[k], cams[k]); the pixel is the mean of all their sub-samples' post-FX HDR,
+    summed in a fixed pairwise order and tone-mapped once; RGBA8, bottom-up.  `hdr` (optional): w*h*4 float32 for the mean HDR.
+    The params' workspace, path_policy, pool_rounds, pass_chains and tile_order are ignored."""
+    t, c, n = _sub_frames(times, cams)
+    _lib.check(_lib.load().rrt_launch_raymarch_mb(_ptr(d_out), _ptr(hdr), w, h, samples, n, t, c, _sky_handle(skyboxTex),
+                                                  C.byref(effects), C.byref(params) if params is not None else None,
+                                                  _stream(stream)), "rrt_launch_raymarch_mb")
+
+
+def launch_raymarch_mb_tiles(d_out_tiles, w, h, samples, tile_rows, shard, n_shards, times, cams, skyboxTex, effects,
+                             params=None, stream=None):
+    """The row tiles of `shard` of launch_raymarch_mb's frame, in launch_raymarch_tiles' buffer layout (assemble_tiles /
+    assemble_all_tiles serve it unchanged)."""
+    t, c, n = _sub_frames(times, cams)
+    _lib.check(_lib.load().rrt_launch_raymarch_mb_tiles(_ptr(d_out_tiles), w, h, samples, tile_rows, shard, n_shards, n, t, c,
+                                                        _sky_handle(skyboxTex), C.byref(effects),
+                                                        C.byref(params) if params is not None else None,
+                                                        _stream(stream)), "rrt_launch_raymarch_mb_tiles")
 
 
 def tile_shard_rows(h, tile_rows, shard, n_shards):

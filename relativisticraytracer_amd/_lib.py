@@ -112,6 +112,8 @@ SYMBOLS = [
     ("rrt_launch_raymarch_tiles", _i, [_vp, _i, _i, _i, _i, _i, _f, _cam, _ull, _fx, _prm, _vp]),
     ("rrt_launch_raymarch_ss", _i, [_vp, _vp, _i, _i, _i, _f, _cam, _ull, _fx, _prm, _vp]),
     ("rrt_launch_raymarch_ss_tiles", _i, [_vp, _i, _i, _i, _i, _i, _i, _f, _cam, _ull, _fx, _prm, _vp]),
+    ("rrt_launch_raymarch_mb", _i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(_f), _cam, _ull, _fx, _prm, _vp]),
+    ("rrt_launch_raymarch_mb_tiles", _i, [_vp, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_f), _cam, _ull, _fx, _prm, _vp]),
     ("rrt_tile_shard_rows", _i, [_i, _i, _i, _i, C.POINTER(_i)]),
     ("rrt_assemble_tiles", _i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     ("rrt_assemble_all_tiles", _i, [_vp, _vp, C.c_size_t, _i, _i, _i, _i, _vp]),
@@ -125,6 +127,7 @@ SYMBOLS = [
     ("rrt_path_keyframes", _i, [_i, _vp, _i]),
     ("rrt_path_camera_at", _i, [_i, _f, _cam]),
     ("rrt_recording_clock", _i, [_i, _i, C.POINTER(_f), C.POINTER(_f)]),
+    ("rrt_motion_clock", _i, [_i, _i, _f, _i, C.POINTER(_f), C.POINTER(_f)]),
     ("rrt_path_chooser_create", _i, [_i, _i, C.POINTER(_i)]),
     ("rrt_path_chooser_destroy", _i, [_i]),
     ("rrt_path_chooser_policy", _i, [_i, _i, C.POINTER(_i)]),

@@ -54,3 +54,14 @@ def recording_clock(frame_k, fps=24):
     s, p = C.c_float(0), C.c_float(0)
     _lib.check(_lib.load().rrt_recording_clock(int(frame_k), int(fps), C.byref(s), C.byref(p)), "rrt_recording_clock")
     return s.value, p.value
+
+
+def motion_clock(frame_k, fps, shutter, n_times):
+    """(sim_times, path_times), float32 arrays of n_times: the shutter of motion-blurred frame k (include/rrt.h:
+    rrt_motion_clock) -- the midpoints of n_times equal slices of the trailing shutter * (1 / fps) of the frame interval, in
+    increasing order; shutter 0 gives recording_clock(frame_k, fps) n_times over."""
+    s, p = np.zeros(n_times, np.float32), np.zeros(n_times, np.float32)
+    fp = C.POINTER(C.c_float)
+    _lib.check(_lib.load().rrt_motion_clock(int(frame_k), int(fps), float(shutter), int(n_times), s.ctypes.data_as(fp),
+                                            p.ctypes.data_as(fp)), "rrt_motion_clock")
+    return s, p

@@ -112,6 +112,24 @@ int rrt_recording_clock(int frame_k, int fps, float* sim_time, float* path_time)
     return RRT_OK;
 }
 
+/* The shutter of motion-blurred frame k (include/rrt.h): the midpoints of n_times equal slices of (S - d, S], binary32, one
+ * rounding per operation, so every driver gets the same sub-times. */
+int rrt_motion_clock(int frame_k, int fps, float shutter, int n_times, float* sim_times, float* path_times) {
+    if (!(shutter >= 0.0f && shutter <= 1.0f)) return RRT_ERR_INVALID_ARGUMENT;
+    if (n_times != 1 && n_times != 2 && n_times != 4 && n_times != 8 && n_times != 16) return RRT_ERR_INVALID_ARGUMENT;
+    float s = 0.0f, p = 0.0f;
+    const int rc = rrt_recording_clock(frame_k, fps, &s, &p);
+    if (rc != RRT_OK) return rc;
+    const float d = shutter * (1.0f / (float)fps);
+    for (int m = 0; m < n_times; ++m) {
+        const float u = ((float)(n_times - m) - 0.5f) / (float)n_times;
+        const float du = d * u;
+        if (sim_times) sim_times[m] = s - du;
+        if (path_times) path_times[m] = p - du;
+    }
+    return RRT_OK;
+}
+
 /* CameraController::getCUDAStateFrom, reference src/main.cpp:141-167 (host C++ there too).
  * Note the reference's 3.14159f, not PI. */
 int rrt_camera_from_angles(const float pos[3], float yaw, float pitch, rrt_camera* out) {

@@ -9,6 +9,8 @@
 //                [--arith strict|fmad|fast] [--path-window F | --path-window -1 | --path-policy auto|single|three-pass]
 //                [--init-timeout 300] [--frame-timeout 120]      (watchdog, seconds; exit status 3 when it fires)
 //                [--supersample 1|2|4|8]       (S x S sub-samples per pixel: rrt_launch_raymarch_ss*, single kernel, no pool)
+//                [--motion-blur 1|2|4|8|16 [--shutter F]]   (K sub-frames over the last F of the frame interval, default 0.5:
+//                                              rrt_motion_clock, rrt_launch_raymarch_mb*, single kernel, no pool)
 //
 // Noise tables: the reference's simTime runs without bound (main.cpp:515) and a table's size grows with the times
 // it covers, so each device keeps ONE table over a window of the clock that fits --noise-table-gib (default 2;
@@ -230,6 +232,8 @@ int main(int argc, char** argv) {
     int gpus = 1, tile_rows = 16, workspace_gib = 2, use_table = 1, force_collective = 0;
     int tile_order = -1;           // cost-ordered dispatch: -1 auto (on when frames are rendered one at a time), 0 off, 1 on
     int supersample = 1;           // --supersample S: S x S sub-samples per pixel (rrt_launch_raymarch_ss*); 1 = one ray per pixel
+    int motion = 1;                // --motion-blur K: K shutter sub-frames per frame (rrt_launch_raymarch_mb*); 1 = one instant
+    float shutter = 0.5f;          // --shutter F: the fraction of the frame interval the shutter is open (180 degrees)
     int kSlots = 3;                // frames in flight: frame k renders on stream k mod kSlots while its predecessors are
                                    // gathered / assembled / copied out (a rank's share of a frame is only a few rounds of
                                    // wavefronts; 3 measured best at 8 shards of a 4K frame: profiles/r02_frames_in_flight.txt)
@@ -266,6 +270,18 @@ int main(int argc, char** argv) {
             if (m == "1" || m == "2" || m == "4" || m == "8") supersample = atoi(m.c_str());
             else { fprintf(stderr, "--supersample 1 | 2 | 4 | 8 (sub-samples per pixel along each axis)\n"); return 2; }
         }
+        else if (a == "--motion-blur") {
+            const std::string m = i + 1 < argc ? argv[++i] : "";
+            if (m == "1" || m == "2" || m == "4" || m == "8" || m == "16") motion = atoi(m.c_str());
+            else { fprintf(stderr, "--motion-blur 1 | 2 | 4 | 8 | 16 (sub-frames per frame)\n"); return 2; }
+        }
+        else if (a == "--shutter") {
+            const char* m = i + 1 < argc ? argv[++i] : "";
+            char* end = nullptr;
+            const float f = strtof(m, &end);
+            if (end != m && *end == 0 && f >= 0.0f && f <= 1.0f) shutter = f;
+            else { fprintf(stderr, "--shutter F: a fraction of the frame interval in [0, 1]\n"); return 2; }
+        }
         else if (a == "--arith" && i + 1 < argc) {
             const std::string m = argv[++i];
             if (m == "strict") arith = RRT_ARITH_STRICT; else if (m == "fmad") arith = RRT_ARITH_FMAD; else if (m == "fast") arith = RRT_ARITH_FAST;
@@ -277,7 +293,7 @@ int main(int argc, char** argv) {
         fprintf(stderr, "bad arguments\n"); return 2;
     }
     // a supersampled launch is always the single kernel in the static order (include/rrt.h): no pool, no path choice, no tile order
-    if (supersample > 1) { workspace_gib = 0; path_window = -1; tile_order = 0; }
+    if (supersample > 1 || motion > 1) { workspace_gib = 0; path_window = -1; tile_order = 0; }
     int n_dev = 0, rc;
     if ((rc = rrt_device_count(&n_dev)) != RRT_OK) return fail("no GPU", rc);
     if (gpus > n_dev) { fprintf(stderr, "rrt_headless: --gpus %d but %d device(s) visible\n", gpus, n_dev); return 2; }
@@ -425,6 +441,18 @@ int main(int argc, char** argv) {
         float sim_t = 0.0f, path_t = 0.0f;
         rrt_recording_clock(k, fps, &sim_t, &path_t);
         if (path >= 0 && (rc = rrt_path_camera_at(path, path_t, &cam)) != RRT_OK) return fail("camera", rc);
+        // motion blur: the shutter's sub-times and the path camera at each; the noise table's window is fitted from the earliest
+        float sub_t[16], sub_p[16];
+        rrt_camera sub_cam[16];
+        float fit_t = sim_t;
+        if (motion > 1) {
+            rrt_motion_clock(k, fps, shutter, motion, sub_t, sub_p);
+            for (int m = 0; m < motion; ++m) {
+                sub_cam[m] = cam;
+                if (path >= 0 && (rc = rrt_path_camera_at(path, sub_p[m], &sub_cam[m])) != RRT_OK) return fail("camera", rc);
+            }
+            fit_t = sub_t[0];
+        }
         trace("frame", k);
         // slot reuse: frame k-kSlots used the same buffers; its host copy must have been written out
         if (k > kSlots && deliver(slot)) return 1;
@@ -433,14 +461,14 @@ int main(int argc, char** argv) {
         //    cannot be built on any of them (nothing fits the budget, out of memory) it is dropped on all of them and
         //    REMEMBERED -- no new fit, no device synchronise, no retry until the clock has left it (retrying
         //    every frame serialised the frames in flight and rebuilt the other devices' tables for nothing).
-        const bool in_window = sim_t >= win_t0 && sim_t <= win_t1;
+        const bool in_window = fit_t >= win_t0 && fit_t <= win_t1;
         if (use_table && !in_window) {
-            float t1 = sim_t; int cov = RRT_TABLE_FULL; size_t bytes = 0;
+            float t1 = fit_t; int cov = RRT_TABLE_FULL; size_t bytes = 0;
             // trace points around the rebuild: it synchronises every device and creates a table on each, which on a
             // starved box takes time that must neither count against --frame-timeout under the name of the last frame nor
             // leave the watchdog's notices pointing at the wrong phase
             trace("noise table window: fitting", k);
-            rrt_noise_table_fit_window(sim_t, seq_end > sim_t ? seq_end : sim_t, table_budget, &t1, &cov, &bytes);
+            rrt_noise_table_fit_window(fit_t, seq_end > fit_t ? seq_end : fit_t, table_budget, &t1, &cov, &bytes);
             bool ok = bytes != 0;
             for (int d = 0; d < gpus; ++d) {
                 Device& D = dev[d];
@@ -448,21 +476,21 @@ int main(int argc, char** argv) {
                 trace("noise table window: draining and rebuilding on device", d);
                 HIPCHK(hipDeviceSynchronize());
                 if (D.noise_table) { rrt_noise_table_destroy(D.noise_table); D.noise_table = 0; }
-                if (ok && (rc = rrt_noise_table_create_window(sim_t, t1, cov, &D.noise_table)) != RRT_OK) {
+                if (ok && (rc = rrt_noise_table_create_window(fit_t, t1, cov, &D.noise_table)) != RRT_OK) {
                     D.noise_table = 0;
                     ok = false;
                     if (!table_warned) {
                         fprintf(stderr, "rrt_headless: noise table [%g, %g] not built on device %d: %s (%s); hashing arithmetically\n",
-                                sim_t, t1, d, rrt_status_string(rc), rrt_last_hip_error());
+                                fit_t, t1, d, rrt_status_string(rc), rrt_last_hip_error());
                         table_warned = true;
                     }
                 }
             }
             if (!ok) {      // all or nothing: the devices must agree on which kernels a frame runs for the timing to mean anything
                 for (int d = 0; d < gpus; ++d) if (dev[d].noise_table) { HIPCHK(hipSetDevice(d)); rrt_noise_table_destroy(dev[d].noise_table); dev[d].noise_table = 0; }
-                if (bytes == 0) t1 = sim_t + 5.0f;          // nothing fits: look again after 5 s of sim time
+                if (bytes == 0) t1 = fit_t + 5.0f;          // nothing fits: look again after 5 s of sim time
             }
-            win_t0 = sim_t; win_t1 = t1; win_has_table = ok;
+            win_t0 = fit_t; win_t1 = t1; win_has_table = ok;
             trace("noise table window: done", k);
             if (ok) { ++table_builds; if (cov > coarsest) coarsest = cov; if (bytes > table_peak) table_peak = bytes; }
         }
@@ -485,7 +513,11 @@ int main(int argc, char** argv) {
             if (D.chooser) { int pol = RRT_PATH_AUTO; rrt_path_chooser_policy(D.chooser, k, &pol); prm.path_policy = pol; }
             else if (path_policy >= 0) prm.path_policy = path_policy;
             void* dst = collective ? D.tiles[slot] : frame[slot];
-            if (supersample > 1) {
+            if (motion > 1) {
+                if (collective) rc = rrt_launch_raymarch_mb_tiles(dst, w, h, supersample, tile_rows, d, gpus, motion, sub_t, sub_cam, D.sky, &fx, &prm, D.stream[slot]);
+                else rc = rrt_launch_raymarch_mb(dst, nullptr, w, h, supersample, motion, sub_t, sub_cam, D.sky, &fx, &prm, D.stream[slot]);
+            }
+            else if (supersample > 1) {
                 if (collective) rc = rrt_launch_raymarch_ss_tiles(dst, w, h, supersample, tile_rows, d, gpus, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
                 else rc = rrt_launch_raymarch_ss(dst, nullptr, w, h, supersample, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
             }
@@ -544,11 +576,11 @@ int main(int argc, char** argv) {
     printf("{\"frames\": %d, \"width\": %d, \"height\": %d, \"n_gpus\": %d, \"seconds\": %.4f, \"fps\": %.3f, \"Mrays_per_s\": %.3f, "
            "\"path\": \"%s\", \"spin\": %g, \"arith_mode\": \"%s\", \"noise_tables\": {\"builds\": %d, \"table_frames\": %d, "
            "\"arith_frames\": %d, \"coarsest_coverage\": %d, \"peak_bytes\": %zu, \"budget_bytes\": %zu}, \"tile_order\": %s, \"collective\": \"%s\", "
-           "\"path_choice\": %s, \"supersample\": %d}\n",
+           "\"path_choice\": %s, \"supersample\": %d, \"motion_blur\": %d, \"shutter\": %g}\n",
            frames, w, h, gpus, dt, frames / dt, (double)frames * w * h / dt / 1e6, path_name, spin,
            arith == RRT_ARITH_FAST ? "fast" : (arith == RRT_ARITH_FMAD ? "fmad" : "strict"),
            table_builds, table_frames, arith_frames, coarsest, table_peak, table_budget, dev[0].order[0] ? "true" : "false",
-           collective ? "rccl grouped send/recv gather" : "none", choice.c_str(), supersample);
+           collective ? "rccl grouped send/recv gather" : "none", choice.c_str(), supersample, motion, shutter);
 
     for (int d = 0; d < gpus; ++d) {
         Device& D = dev[d];

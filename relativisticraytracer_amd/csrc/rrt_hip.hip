@@ -547,6 +547,12 @@ int launch(const FrameArgs& a, const LaunchOpts& o, bool debug, hipStream_t st) 
 }
 
 /* ---- s x s supersampled launches (rrt_launch_raymarch_ss*): one kernel, static order, nothing else */
+/* the template instance of a single-kernel launch: LAUNCH3(spin, media, arith) for the local `spin`, `media` and `arith` */
+#define RRT_SS_DISPATCH2(LAUNCH3, S, M) do { if (arith == kArithFast) LAUNCH3(S, M, kArithFast); \
+                                             else if (arith == kArithFmad) LAUNCH3(S, M, kArithFmad); else LAUNCH3(S, M, kArithStrict); } while (0)
+#define RRT_SS_DISPATCH1(LAUNCH3, S) do { if (media == 3) RRT_SS_DISPATCH2(LAUNCH3, S, 3); else if (media == 2) RRT_SS_DISPATCH2(LAUNCH3, S, 2); \
+                                          else if (media == 1) RRT_SS_DISPATCH2(LAUNCH3, S, 1); else RRT_SS_DISPATCH2(LAUNCH3, S, 0); } while (0)
+#define RRT_SS_DISPATCH(LAUNCH3) do { if (spin) RRT_SS_DISPATCH1(LAUNCH3, true); else RRT_SS_DISPATCH1(LAUNCH3, false); } while (0)
 bool valid_samples(int s) { return s == 1 || s == 2 || s == 4 || s == 8; }
 
 /* the checks of check_common plus the virtual (s w) x (s h) frame's limits; all before any device call */
@@ -577,13 +583,65 @@ int launch_ss(void* out, float4* hdr, int width, int height, int s, const RowMap
     const bool spin = a.spin != 0.0f;
     const int media = o.media, arith = o.arith;
 #define RRT_SS3(S, M, F) hipLaunchKernelGGL((supersample_pixels<S, M, F>), grid, block, 0, st, a, s, hdr)
-#define RRT_SS2(S, M) do { if (arith == kArithFast) RRT_SS3(S, M, kArithFast); else if (arith == kArithFmad) RRT_SS3(S, M, kArithFmad); \
-                           else RRT_SS3(S, M, kArithStrict); } while (0)
-#define RRT_SS1(S) do { if (media == 3) RRT_SS2(S, 3); else if (media == 2) RRT_SS2(S, 2); else if (media == 1) RRT_SS2(S, 1); else RRT_SS2(S, 0); } while (0)
-    if (spin) RRT_SS1(true); else RRT_SS1(false);
-#undef RRT_SS1
-#undef RRT_SS2
+    RRT_SS_DISPATCH(RRT_SS3);
 #undef RRT_SS3
+    RRT_HIP(hipGetLastError());
+    return RRT_OK;
+}
+
+/* ---- motion-blurred launches (rrt_launch_raymarch_mb*): supersampled sub-frames at n_times (time, camera) pairs, one kernel */
+bool valid_times(int n) { return n == 1 || n == 2 || n == 4 || n == 8 || n == 16; }
+static_assert(kMaxTimes == 16, "valid_times and MotionArgs agree on the largest n_times");
+
+/* the checks of check_ss plus the sub-frames' own; all before any device call */
+int check_mb(const void* out, int width, int height, int s, int n_times, const float* times, const rrt_camera* cams,
+             const rrt_effects* fx, const rrt_params* prm) {
+    if (!valid_times(n_times) || !times || !cams) return RRT_ERR_INVALID_ARGUMENT;
+    const int rc = check_ss(out, width, height, s, cams, fx, prm);
+    if (rc != RRT_OK) return rc;
+    for (int k = 0; k < n_times; ++k)
+        if (!std::isfinite(times[k])) return RRT_ERR_INVALID_ARGUMENT;
+    return RRT_OK;
+}
+
+/* launch_ss with n_times sub-frames.  The media mode is picked once for all of them: fill_args at the earliest and at the latest
+ * time -- a table's window is an interval, so it holds every time iff it holds both -- and the arithmetic kernels unless both
+ * found the table. */
+int launch_mb(void* out, float4* hdr, int width, int height, int s, const RowMap& rows, int n_times, const float* times,
+              const rrt_camera* cams, rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm_in, hipStream_t st) {
+    rrt_params prm;
+    load_params(prm_in, prm);
+    prm.workspace = 0; prm.path_policy = RRT_PATH_AUTO; prm.pool_rounds = 0; prm.pass_chains = 0; prm.tile_order = 0;
+    float t_lo = times[0], t_hi = times[0];
+    MotionLaunch L;
+    MotionArgs& m = L.m;
+    for (int k = 0; k < kMaxTimes; ++k) {           /* the unused slots repeat the last sub-frame: no uninitialised kernel argument */
+        const int j = k < n_times ? k : n_times - 1;
+        m.time[k] = times[j];
+        m.cam[k] = cams[j];
+        if (times[j] < t_lo) t_lo = times[j];
+        if (times[j] > t_hi) t_hi = times[j];
+    }
+    FrameArgs& a = L.a;
+    FrameArgs a_hi;
+    LaunchOpts o, o_hi;
+    int rc = fill_args(a, o, out, s * width, s * height, t_lo, &cams[0], sky, fx, &prm);
+    if (rc) return rc;
+    rc = fill_args(a_hi, o_hi, out, s * width, s * height, t_hi, &cams[0], sky, fx, &prm);
+    if (rc) return rc;
+    if (o.media != o_hi.media) {                    /* some time outside the window: every sub-frame hashes arithmetically */
+        o.media = 1;
+        memset(&a.lut_acc, 0, sizeof(a.lut_acc)); memset(&a.lut_dust, 0, sizeof(a.lut_dust)); memset(&a.dust_bands, 0, sizeof(a.dust_bands));
+    }
+    a.rows = rows;
+    L.s = s; L.n_times = n_times; L.hdr_out = hdr;
+    if (rows.n_local_rows == 0) return RRT_OK;
+    const dim3 grid((a.width + kWGPixX - 1) / kWGPixX, (s * rows.n_local_rows + kWGPixY - 1) / kWGPixY), block(kWGThreads);
+    const bool spin = a.spin != 0.0f;
+    const int media = o.media, arith = o.arith;
+#define RRT_MB3(S, M, F) hipLaunchKernelGGL((motion_pixels<S, M, F>), grid, block, 0, st, L)
+    RRT_SS_DISPATCH(RRT_MB3);
+#undef RRT_MB3
     RRT_HIP(hipGetLastError());
     return RRT_OK;
 }
@@ -1270,6 +1328,26 @@ int rrt_launch_raymarch_ss_tiles(void* d_out_tiles, int width, int height, int s
     return launch_ss(d_out_tiles, nullptr, width, height, samples_per_axis,
                      RowMap{shard_rows(height, tile_rows, shard, n_shards), 0, tile_rows, shard, n_shards, nullptr}, time, cam, sky,
                      fx, prm, static_cast<hipStream_t>(stream));
+}
+
+int rrt_launch_raymarch_mb(void* d_out_rgba8, float* d_hdr_rgba32f, int width, int height, int samples_per_axis, int n_times,
+                           const float* times, const rrt_camera* cams, rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm,
+                           void* stream) {
+    const int rc = check_mb(d_out_rgba8, width, height, samples_per_axis, n_times, times, cams, fx, prm);
+    if (rc) return rc;
+    return launch_mb(d_out_rgba8, reinterpret_cast<float4*>(d_hdr_rgba32f), width, height, samples_per_axis,
+                     RowMap{height, 0, height, 0, 1, nullptr}, n_times, times, cams, sky, fx, prm, static_cast<hipStream_t>(stream));
+}
+
+int rrt_launch_raymarch_mb_tiles(void* d_out_tiles, int width, int height, int samples_per_axis, int tile_rows, int shard, int n_shards,
+                                 int n_times, const float* times, const rrt_camera* cams, rrt_sky_t sky, const rrt_effects* fx,
+                                 const rrt_params* prm, void* stream) {
+    const int rc = check_mb(d_out_tiles, width, height, samples_per_axis, n_times, times, cams, fx, prm);
+    if (rc) return rc;
+    if (tile_rows <= 0 || n_shards <= 0 || shard < 0 || shard >= n_shards) return RRT_ERR_INVALID_ARGUMENT;
+    return launch_mb(d_out_tiles, nullptr, width, height, samples_per_axis,
+                     RowMap{shard_rows(height, tile_rows, shard, n_shards), 0, tile_rows, shard, n_shards, nullptr}, n_times, times,
+                     cams, sky, fx, prm, static_cast<hipStream_t>(stream));
 }
 
 int rrt_assemble_tiles(void* d_frame, const void* d_tiles, int width, int height, int tile_rows, int shard,

@@ -658,6 +658,16 @@ void raymarch_pixels(const FrameArgs a) {
  * pairwise in natural order and then its row sums the same way; the sum lands in every lane of the pixel (addition commutes
  * exactly) and its first lane, which holds the low operand at every level, tone-maps and stores.  hdr_out (may be NULL): the
  * mean HDR, alpha 1, indexed like the frame. */
+/* The sum of an output pixel's s x s sub-samples (lane mapping: supersample_pixels), in every lane of the pixel. */
+__device__ __forceinline__ void pixel_sum(v3& c, const int s) {
+    for (int m = 1; m < s; m <<= 1) {                   /* the sub-row: ((s0 + s1) + (s2 + s3)) ... */
+        c.x = c.x + __shfl_xor(c.x, m); c.y = c.y + __shfl_xor(c.y, m); c.z = c.z + __shfl_xor(c.z, m);
+    }
+    for (int m = kTileW; m < s * kTileW; m <<= 1) {     /* ... then the row sums */
+        c.x = c.x + __shfl_xor(c.x, m); c.y = c.y + __shfl_xor(c.y, m); c.z = c.z + __shfl_xor(c.z, m);
+    }
+}
+
 static_assert(kTileW == 8 && kTileH == 8, "supersample_pixels maps a pixel's sub-samples into an 8x8 wave tile (s = 8: one pixel per wave)");
 template <bool SPIN, int MEDIA, int ARITH>
 __global__ __launch_bounds__(kWGThreads, (MEDIA != 0 ? RRT_MEDIA_WAVES : 1))      /* raymarch_pixels' register budget */
@@ -678,12 +688,7 @@ void supersample_pixels(const FrameArgs a, const int s, float4* const hdr_out) {
     int i = 0;
     march_inline<SPIN, MEDIA, ARITH, true>(a, p, vel, acc, hit, i, nullptr);
     v3 c = shade_hdr(a, uvx, uvy, hit, vel, acc);
-    for (int m = 1; m < s; m <<= 1) {                   /* the sub-row: ((s0 + s1) + (s2 + s3)) ... */
-        c.x = c.x + __shfl_xor(c.x, m); c.y = c.y + __shfl_xor(c.y, m); c.z = c.z + __shfl_xor(c.z, m);
-    }
-    for (int m = kTileW; m < s * kTileW; m <<= 1) {     /* ... then the row sums */
-        c.x = c.x + __shfl_xor(c.x, m); c.y = c.y + __shfl_xor(c.y, m); c.z = c.z + __shfl_xor(c.z, m);
-    }
+    pixel_sum(c, s);
     if (((vx | vlr) & (s - 1)) != 0) return;            /* the pixel's first lane stores */
     const float inv = 1.0f / (float)(s * s);            /* a power of two: the mean is exact given the sum */
     c = mk(c.x * inv, c.y * inv, c.z * inv);
@@ -691,6 +696,98 @@ void supersample_pixels(const FrameArgs a, const int s, float4* const hdr_out) {
     tone_map(c, out_r, out_g, out_b);
     const size_t oi = (size_t)out_row * w + x;
     store_rgba8(a.out, oi, out_r, out_g, out_b);
+    if (hdr_out) hdr_out[oi] = make_float4(c.x, c.y, c.z, 1.0f);
+}
+
+/* Motion-blurred frame (rrt_launch_raymarch_mb, include/rrt.h has the contract): sub-frame k is supersample_pixels' frame at
+ * (m.time[k], m.cam[k]), and the pixel is the mean of the K sub-frames' sums, tone-mapped once.  The waves are supersample_pixels'
+ * (an 8x8 tile of the virtual sample grid); a wave-uniform loop over k runs the march once per sub-frame in the same lanes -- a
+ * pixel's K rays are nearly coherent -- forms T_k with the same butterfly and folds it into the temporal tree.  Time and camera are
+ * read from the by-value MotionArgs at the uniform k, so they stay scalar and the march is raymarch_pixels' code.
+ * Registers: the media kernels use every scalar register across the march, so nothing else may stay live across it.  The tree's
+ * partials (level l: the sum of the 2^l sub-frames before k) and the lane's pixel coordinates live in per-lane LDS slots (<= 4
+ * levels x 3 floats + 3 ints, x 64 lanes = 3.75 KB per one-wave workgroup), and the launch's scalars are read afresh where they are
+ * used (motion_arg) -- hoisted out of the loop, they would hold registers across the march and spill.  Every lane of a pixel folds
+ * the same bits (the butterfly leaves the sum in all of them); its first lane stores. */
+constexpr int kMaxTimes = 16;
+struct MotionArgs { float time[kMaxTimes]; rrt_camera cam[kMaxTimes]; };
+struct MotionLaunch {                                   /* motion_pixels' one kernel argument */
+    FrameArgs a;                                        /* the virtual frame, as supersample_pixels' */
+    MotionArgs m;
+    int s, n_times;
+    float4* hdr_out;
+};
+
+/* A field of the kernel argument read where it is used: the load cannot be hoisted out of the loop over the sub-frames. */
+template <class T>
+__device__ __forceinline__ T motion_arg(size_t offset) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef const __attribute__((address_space(4))) char* KP;
+    KP base = (KP)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(base));
+    return *(const __attribute__((address_space(4))) T*)(base + offset);
+#else
+    return T();
+#endif
+}
+#define RRT_MB_ARG(field) motion_arg<decltype(((MotionLaunch*)nullptr)->field)>(offsetof(MotionLaunch, field))
+
+static_assert(kWGWaves == 1, "motion_pixels' LDS slots are sized for one-wave workgroups");
+template <bool SPIN, int MEDIA, int ARITH>
+__global__ __launch_bounds__(kWGThreads, (MEDIA != 0 ? RRT_MEDIA_WAVES : 1))      /* raymarch_pixels' register budget */
+void motion_pixels(const MotionLaunch L) {
+    __shared__ float part[4][3][kWGThreads];            /* levels 0..3: n_times <= 16 never stores level 4 */
+    __shared__ volatile int where[3][kWGThreads];       /* vx, vy, the output index (-1: another lane of the pixel stores) */
+    const int t = threadIdx.x;
+    {
+        const FrameArgs& a = L.a;
+        const int s = L.s;
+        const int lane = t & 63, wave = t >> 6;
+        const int vx = tile_column(a) * kWGPixX + (wave & 1) * kTileW + (lane & (kTileW - 1));      /* virtual column */
+        const int vlr = row_block(a) * kWGPixY + (wave >> 1) * kTileH + lane / kTileW;              /* virtual local row */
+        const int w = a.width / s, h = a.height / s;
+        const int x = vx / s;
+        int y, out_row;
+        if (x >= w || !map_row(a.rows, h, vlr / s, y, out_row)) return;
+        where[0][t] = vx;
+        where[1][t] = s * y + (vlr - (vlr / s) * s);
+        where[2][t] = ((vx | vlr) & (s - 1)) != 0 ? -1 : out_row * w + x;       /* the pixel's first lane stores */
+    }
+    v3 c;
+    for (int k = 0; k < L.n_times; ++k) {
+        FrameArgs b = L.a;
+        b.time = L.m.time[k];
+        b.cam = L.m.cam[k];
+        b.width = RRT_MB_ARG(a.width); b.height = RRT_MB_ARG(a.height);                 /* what primary_ray reads */
+        b.use_lens = RRT_MB_ARG(a.use_lens); b.distortion_amount = RRT_MB_ARG(a.distortion_amount);
+        b.nudge_ulps = RRT_MB_ARG(a.nudge_ulps); b.nudge_seed = RRT_MB_ARG(a.nudge_seed);
+        float uvx, uvy;
+        v3 p, vel;
+        primary_ray(b, where[0][t], where[1][t], uvx, uvy, p, vel);
+        Radiance acc = {0.f, 0.f, 0.f, 1.0f};
+        bool hit = false;
+        int i = 0;
+        march_inline<SPIN, MEDIA, ARITH, true>(b, p, vel, acc, hit, i, nullptr);
+        b.sky = RRT_MB_ARG(a.sky);                                                       /* what shade_hdr reads */
+        b.use_bloom = RRT_MB_ARG(a.use_bloom); b.bloom_threshold = RRT_MB_ARG(a.bloom_threshold);
+        b.bloom_intensity = RRT_MB_ARG(a.bloom_intensity); b.use_vignette = RRT_MB_ARG(a.use_vignette);
+        b.vignette_intensity = RRT_MB_ARG(a.vignette_intensity); b.use_ca = RRT_MB_ARG(a.use_ca); b.ca_amount = RRT_MB_ARG(a.ca_amount);
+        c = shade_hdr(b, uvx, uvy, hit, vel, acc);
+        pixel_sum(c, L.s);
+        int l = 0;                                      /* ((T0 + T1) + (T2 + T3)) ...: close the levels sub-frame k completes */
+        for (int j = k; j & 1; j >>= 1, ++l)
+            c = add(mk(part[l][0][t], part[l][1][t], part[l][2][t]), c);
+        if (k + 1 < L.n_times) { part[l][0][t] = c.x; part[l][1][t] = c.y; part[l][2][t] = c.z; }
+    }
+    const int oi = where[2][t];
+    if (oi < 0) return;
+    const int s = RRT_MB_ARG(s);
+    const float inv = 1.0f / (float)(s * s * RRT_MB_ARG(n_times));  /* a power of two: the mean is exact given the sum */
+    c = mk(c.x * inv, c.y * inv, c.z * inv);
+    float out_r, out_g, out_b;
+    tone_map(c, out_r, out_g, out_b);
+    store_rgba8(RRT_MB_ARG(a.out), (size_t)oi, out_r, out_g, out_b);
+    float4* const hdr_out = RRT_MB_ARG(hdr_out);
     if (hdr_out) hdr_out[oi] = make_float4(c.x, c.y, c.z, 1.0f);
 }
 

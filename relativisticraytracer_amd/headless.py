@@ -1,7 +1,7 @@
 """Headless frame driver: the reference's main loop (src/main.cpp:505-529) without a window.
 
     python -m relativisticraytracer_amd.headless --width 1920 --height 1080 --spin 0.9 \\
-           --path 0 --frames 300 [--out frames.rgba | --out ppm_dir/] [--all-effects] [--supersample 2]
+           --path 0 --frames 300 [--out frames.rgba | --out ppm_dir/] [--all-effects] [--supersample 2] [--motion-blur 4 --shutter 0.5]
     python -m torch.distributed.run --nproc-per-node 8 -m relativisticraytracer_amd.headless ...
 
 Per frame k = 1..N it does what `main()` does while recording: advance the fixed 1/24 s clock
@@ -52,12 +52,20 @@ def main(argv=None):
     ap.add_argument("--supersample", type=int, choices=(1, 2, 4, 8), default=1,
                     help="S x S sub-samples per pixel, averaged in HDR before the tone map (rrt_launch_raymarch_ss*; 1 = one ray per "
                          "pixel).  S > 1 always renders with the single kernel in the static order: no pool, path choice or tile order")
+    ap.add_argument("--motion-blur", type=int, choices=(1, 2, 4, 8, 16), default=1,
+                    help="K sub-frames over the shutter interval, averaged in HDR before the tone map (rrt_launch_raymarch_mb*; 1 = "
+                         "one instant per frame).  K > 1 always renders with the single kernel in the static order, as --supersample")
+    ap.add_argument("--shutter", type=float, default=0.5,
+                    help="with --motion-blur K > 1: the fraction of the frame interval the shutter is open, ending at the frame's "
+                         "time (rrt_motion_clock; 0.5 = 180 degrees)")
     ap.add_argument("--out", default=None, help="x.rgba (raw, bottom-up) | dir/ (PPM per frame) | x.mp4 (needs ffmpeg)")
     ap.add_argument("--init-timeout", type=float, default=300.0,
                     help="several ranks: seconds the process-group bring-up may take before the run exits non-zero with "
                          "the tracebacks of all threads, instead of hanging")
     ap.add_argument("--frame-timeout", type=float, default=120.0, help="the same for any single frame (0: no limit)")
     args = ap.parse_args(argv)
+    if not 0.0 <= args.shutter <= 1.0:
+        ap.error("--shutter: a fraction of the frame interval in [0, 1]")
 
     t_start = time.perf_counter()
 
@@ -100,13 +108,14 @@ def main(argv=None):
 
     trace("process group ready" if world > 1 else "single rank")
     w, h = args.width, args.height
-    ss = args.supersample
+    ss, mb = args.supersample, args.motion_blur
+    single = ss > 1 or mb > 1            # a supersampled or blurred launch: the single kernel, static order, no pool
     tex = rrt.SkyTexture(load_sky(args.sky) if args.sky else synthetic_sky())
     fx = rrt.CameraEffects(useChromaticAberration=bool(args.all_effects))
     # with several ranks --frames-in-flight frames are in flight (FrameSharder pipeline mode), each with its own
     # share of the pool
     n_slots = max(2, args.frames_in_flight) if world > 1 else 1
-    pools = [rrt.Workspace((args.workspace_gib << 30) // n_slots) for _ in range(n_slots)] if args.workspace_gib > 0 and ss == 1 else []
+    pools = [rrt.Workspace((args.workspace_gib << 30) // n_slots) for _ in range(n_slots)] if args.workspace_gib > 0 and not single else []
     # lattice-hash tables for the volumetric noise over a sliding window of the recording clock (main.cpp:511-516 lets
     # simTime grow without bound; the table's size grows with it): one table within the byte budget, rebuilt when the
     # clock leaves its window -- never a silent fall-back: frames rendered without a table are counted in the summary
@@ -117,7 +126,7 @@ def main(argv=None):
     # with a pool) it piles the expensive tiles into the first of the two chains and was measured slower: auto leaves it off there
     my_rays = w * sharding.shard_rows(h, args.tile_rows, rank, world)
     three_pass_likely = bool(pools) and my_rays <= rrt._lib.load().rrt_path_auto_max_rays()      # RRT_PATH_AUTO's own threshold
-    use_order = ss == 1 and (args.tile_order == "on" or (args.tile_order == "auto" and n_slots == 1 and not three_pass_likely))
+    use_order = not single and (args.tile_order == "on" or (args.tile_order == "auto" and n_slots == 1 and not three_pass_likely))
     orders = [rrt.TileOrder() for _ in range(n_slots)] if use_order else []
     arith_name = args.arith or ("fast" if args.fast else "strict")
     arith_mode = {"strict": 0, "fast": 1, "fmad": 2}[arith_name]
@@ -143,7 +152,9 @@ def main(argv=None):
         k = state["k"]
         if chooser is not None:
             prms[slot].path_policy = chooser.policy(k)
-        if ss > 1:
+        if mb > 1:
+            rrt.launch_raymarch_mb_tiles(buf, w, h, ss, args.tile_rows, rank, world, state["times"], state["cams"], tex, fx, prms[slot])
+        elif ss > 1:
             rrt.launch_raymarch_ss_tiles(buf, w, h, ss, args.tile_rows, rank, world, state["t"], state["cam"], tex, fx, prms[slot])
         else:
             rrt.launch_raymarch_tiles(buf, w, h, args.tile_rows, rank, world, state["t"], state["cam"], tex, fx, prms[slot])
@@ -183,7 +194,14 @@ def main(argv=None):
         sim_t, path_t = camera_paths.recording_clock(k, args.fps)
         state["t"] = sim_t
         state["k"] = k
-        state["table"] = nwin.table_id(sim_t)
+        if mb > 1:
+            # the shutter's sub-times; the table's window is fitted from the earliest, so that the later ones fall inside it
+            sub_t, sub_p = camera_paths.motion_clock(k, args.fps, args.shutter, mb)
+            state["times"] = sub_t
+            state["cams"] = [path.camera_at(p) for p in sub_p] if path is not None else [state["cam"]] * mb
+            state["table"] = nwin.table_id(float(sub_t[0]))
+        else:
+            state["table"] = nwin.table_id(sim_t)
         if path is not None:
             state["cam"] = path.camera_at(path_t)
         frame = fs.step()
@@ -208,7 +226,8 @@ def main(argv=None):
                           "arith_mode": arith_name, "sink": args.out,
                           "path_choice": chooser.stats() if chooser else None,
                           "noise_tables": nwin.summary(),
-                          "tile_order": orders[0].info() if orders else None, "supersample": ss}), flush=True)
+                          "tile_order": orders[0].info() if orders else None, "supersample": ss,
+                          "motion_blur": mb, "shutter": args.shutter}), flush=True)
     if world > 1:
         dist.destroy_process_group()
     nwin.close()

@@ -135,12 +135,16 @@ def analyse(src, name, pretty):
     # straight path: from the inner header until control returns to it; conditional branches fall through (rejected seeds, small
     # radii, exits are the unlikely successors) EXCEPT a `s_cbranch_vccz` whose target is a stub of <= 2 instructions -- that is the
     # "no lane is beyond r = 250" skip of the escape test's dot product, taken on all but a ray's last few steps.
-    inner = None
+    # (motion_pixels runs the march inside a loop over its sub-frames: there the vacuum loop is at depth 3 -- the deepest loop that
+    # qualifies is taken)
+    inner, inner_depth = None, 0
     for b in blocks:
-        if re.search(r"Inner Loop Header: Depth=2", b["comment"]) and not b["label"].count("+"):
-            members = [x for x in blocks if x["label"].split("+")[0] == b["label"] or re.search(r"Header=%s Depth=2" % b["label"][2:], x["comment"])]
-            if sum(len(x["ins"]) for x in members) > 250 and any(VAC_LIT in t for x in members for t in x["ins"]):
-                inner = (b["label"], {x["label"] for x in members})
+        mh = re.search(r"Inner Loop Header: Depth=(\d+)", b["comment"])
+        if mh and not b["label"].count("+"):
+            depth = int(mh.group(1))
+            members = [x for x in blocks if x["label"].split("+")[0] == b["label"] or re.search(r"Header=%s Depth=%d" % (b["label"][2:], depth), x["comment"])]
+            if sum(len(x["ins"]) for x in members) > 250 and any(VAC_LIT in t for x in members for t in x["ins"]) and depth >= inner_depth:
+                inner, inner_depth = (b["label"], {x["label"] for x in members}), depth
     nested = []
     if inner:
         ihdr, ilabels = inner
