@@ -428,6 +428,45 @@ int rrt_launch_raymarch_mb_tiles(void* d_out_tiles, int width, int height, int s
                                  int n_times, const float* times, const rrt_camera* cams, rrt_sky_t sky, const rrt_effects* fx,
                                  const rrt_params* prm, void* stream);
 
+/* ---- HDR glow: a soft-knee bright pass spread by L separable Gaussian lobes and added back onto a frame's HDR, tone-mapped; no
+ *      counterpart in the reference, whose "bloom" (rrt_effects.use_bloom, post_processing.h:27-31) only brightens a pixel above a
+ *      threshold and never reaches its neighbours.  That effect is unchanged and runs inside the march, before the glow.
+ *      H is the w x h float4 frame rrt_launch_raymarch_ss / _mb write to d_hdr_rgba32f (bottom-up rows; rgb read).  Every
+ *      operation is binary32, uncontracted, no flush to zero:
+ *        1. bright pass: luma = (r*0.2126f + g*0.7152f) + b*0.0722f; luma > T: f = (luma - T) / luma, B = (r*f, g*f, b*f);
+ *           otherwise B = 0 (a soft knee);
+ *        2. lobe l < L: sigma_l = ((double)radius * height) * 2^l output pixels (radius is a fraction of the frame height),
+ *           R_l = ceil(3 sigma_l), taps w_l[k + R_l] = exp(-k^2 / (2 sigma_l^2)) / sum_j exp(-j^2 / (2 sigma_l^2)) for
+ *           |k| <= R_l, in double with the sum over ascending j, rounded to float (rrt_glow_weights returns them);
+ *        3. per lobe a horizontal pass over B, then a vertical pass over its result, giving V_l: acc = 0.0f, then for
+ *           k = -R_l ... R_l ascending acc = acc + w_l[k + R_l] * X[clamp(i + k)], i the column, then the STORED row index
+ *           (bottom-up), clamped to the frame's edge;
+ *        4. G = V_0, G = G + V_l for l = 1 ... L-1; s = intensity / (float)L; out = H + G * s per channel, tone-mapped as
+ *           raymarcher.cu:164-173 and stored as RGBA8 in H's layout.
+ *      So intensity = 0, or a threshold above every luma, gives the bytes the _ss / _mb launch wrote with H. */
+typedef struct rrt_glow {
+    uint32_t struct_size;    /* sizeof(rrt_glow): rrt_glow_default sets it; any other value is RRT_ERR_ABI_MISMATCH */
+    float radius;            /* sigma_0 as a fraction of the frame height, > 0 and finite */
+    int32_t lobes;           /* L in {1, 2, 3, 4} */
+    float threshold;         /* T >= 0 and finite */
+    float intensity;         /* >= 0 and finite */
+} rrt_glow;
+/* radius 0.004, lobes 4, threshold 1.0, intensity 0.25: a look, not a measurement */
+int rrt_glow_default(rrt_glow* g);
+/* lobe `lobe`'s taps for a frame `height` rows high: R_l in *radius_out (may be NULL) and, if out is not NULL, its 2 R_l + 1
+ * weights (cap >= 2 R_l + 1).  Host only. */
+int rrt_glow_weights(const rrt_glow* g, int height, int lobe, float* out, int cap, int* radius_out);
+/* the bytes of the caller-owned scratch rrt_launch_glow needs for a width x height frame.  Host only. */
+int rrt_glow_scratch_bytes(int width, int height, const rrt_glow* g, size_t* bytes);
+/* The glowed RGBA8 frame of H into d_out_rgba8 (width*height*4 bytes; it may not overlap H or the scratch).  The library
+ * allocates nothing: d_scratch (>= rrt_glow_scratch_bytes) belongs to the caller; no memset, no synchronisation, so _ss / _mb
+ * followed by this launch can be captured into a hipGraph.  RRT_ERR_INVALID_ARGUMENT, before any device call: NULL pointers,
+ * d_hdr_rgba32f or d_scratch not 16-byte aligned, width or height <= 0, width*height >= 2^31, lobes outside {1 ... 4}, a radius
+ * <= 0, a threshold or intensity < 0, any of them not finite, a widest R_{L-1} > 1024, scratch_bytes below the query's;
+ * RRT_ERR_ABI_MISMATCH for another struct_size.  Full frames only: no _tiles form. */
+int rrt_launch_glow(void* d_out_rgba8, const float* d_hdr_rgba32f, int width, int height, const rrt_glow* g, void* d_scratch,
+                    size_t scratch_bytes, void* stream);
+
 /* ---- which path a rank's share takes while several frames of a sequence are in flight (host only; no GPU call) ----
  * New in this repo (the reference renders one frame at a time on one GPU: src/main.cpp:505-529).  A launch of <= 1.5 M rays
  * with a pool can take the three-pass path (RRT_PATH_AUTO) or the single kernel (RRT_PATH_SINGLE); under frames in flight the

@@ -19,12 +19,13 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import RRTError, rrt_camera, rrt_debug_outputs, rrt_effects, rrt_params  # noqa: F401
+from ._lib import RRTError, rrt_camera, rrt_debug_outputs, rrt_effects, rrt_glow, rrt_params  # noqa: F401
 
 __all__ = ["CameraState", "CameraEffects", "RenderParams", "SkyTexture", "Workspace", "NoiseTable", "launch_raymarch",
            "set_launch_defaults", "get_launch_defaults",
            "launch_raymarch_rows", "launch_raymarch_tiles", "assemble_tiles", "assemble_all_tiles",
            "launch_raymarch_ss", "launch_raymarch_ss_tiles", "launch_raymarch_mb", "launch_raymarch_mb_tiles",
+           "GlowSettings", "glow_weights", "glow_scratch_bytes", "launch_glow",
            "tile_shard_rows",
            "launch_raymarch_debug", "RRTError", "device_count", "abi_version", "TileOrder", "TileMap",
            "probe_tile_costs", "balance_tiles", "launch_raymarch_tilemap", "assemble_all_tilemap", "clock_probe", "clock_probe_ghz"]
@@ -121,6 +122,22 @@ class RenderParams(rrt_params):
             if not hasattr(self, k):
                 raise AttributeError(k)
             setattr(self, k, v)
+
+
+class GlowSettings(rrt_glow):
+    """HDR glow settings (include/rrt.h: rrt_glow): radius (sigma_0 as a fraction of the frame height), lobes (1-4), threshold,
+    intensity.  Defaults == rrt_glow_default."""
+
+    def __init__(self, **kw):
+        super().__init__()
+        _lib.check(_lib.load().rrt_glow_default(C.byref(self)), "rrt_glow_default")
+        for k, v in kw.items():
+            if not hasattr(self, k):
+                raise AttributeError(k)
+            setattr(self, k, v)
+
+    def info(self):
+        return {"radius": self.radius, "lobes": self.lobes, "threshold": self.threshold, "intensity": self.intensity}
 
 
 class SkyTexture:
@@ -534,6 +551,32 @@ def launch_raymarch_mb_tiles(d_out_tiles, w, h, samples, tile_rows, shard, n_sha
                                                         _sky_handle(skyboxTex), C.byref(effects),
                                                         C.byref(params) if params is not None else None,
                                                         _stream(stream)), "rrt_launch_raymarch_mb_tiles")
+
+
+def glow_weights(glow, height, lobe):
+    """lobe `lobe`'s taps for a frame `height` rows high (rrt_glow_weights): float32 array of 2 R + 1 weights, tap k at [k + R]"""
+    lib, r = _lib.load(), C.c_int(0)
+    _lib.check(lib.rrt_glow_weights(C.byref(glow), height, lobe, None, 0, C.byref(r)), "rrt_glow_weights")
+    out = np.zeros(2 * r.value + 1, np.float32)
+    _lib.check(lib.rrt_glow_weights(C.byref(glow), height, lobe, out.ctypes.data_as(C.POINTER(C.c_float)), out.size, C.byref(r)),
+               "rrt_glow_weights")
+    return out
+
+
+def glow_scratch_bytes(w, h, glow):
+    n = C.c_size_t(0)
+    _lib.check(_lib.load().rrt_glow_scratch_bytes(w, h, C.byref(glow), C.byref(n)), "rrt_glow_scratch_bytes")
+    return n.value
+
+
+def launch_glow(d_out, hdr, w, h, glow, scratch, stream=None, scratch_bytes=None):
+    """The glowed RGBA8 frame (include/rrt.h: rrt_launch_glow) of `hdr` (w*h*4 float32 on the device, the layout launch_raymarch_ss
+    / launch_raymarch_mb write) into d_out (w*h*4 uint8).  `scratch`: device memory of glow_scratch_bytes(w, h, glow) bytes or
+    more -- its size is a tensor's own, or scratch_bytes for a raw pointer."""
+    if scratch_bytes is None:
+        scratch_bytes = scratch.numel() * scratch.element_size() if hasattr(scratch, "element_size") else glow_scratch_bytes(w, h, glow)
+    _lib.check(_lib.load().rrt_launch_glow(_ptr(d_out), _ptr(hdr), w, h, C.byref(glow), _ptr(scratch), scratch_bytes,
+                                           _stream(stream)), "rrt_launch_glow")
 
 
 def tile_shard_rows(h, tile_rows, shard, n_shards):

@@ -61,6 +61,11 @@ class rrt_path_chooser_stats(C.Structure):
                 ("switches", C.c_int32), ("outliers", C.c_int32), ("frames", C.c_int32 * 2), ("last_three_pass_mean_ms", C.c_float)]
 
 
+class rrt_glow(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("radius", C.c_float), ("lobes", C.c_int32), ("threshold", C.c_float),
+                ("intensity", C.c_float)]
+
+
 # every symbol include/rrt.h declares: (name, restype, argtypes)
 _vp, _i, _f, _ull = C.c_void_p, C.c_int, C.c_float, C.c_ulonglong
 _cam, _fx, _prm = C.POINTER(rrt_camera), C.POINTER(rrt_effects), C.POINTER(rrt_params)
@@ -114,6 +119,10 @@ SYMBOLS = [
     ("rrt_launch_raymarch_ss_tiles", _i, [_vp, _i, _i, _i, _i, _i, _i, _f, _cam, _ull, _fx, _prm, _vp]),
     ("rrt_launch_raymarch_mb", _i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(_f), _cam, _ull, _fx, _prm, _vp]),
     ("rrt_launch_raymarch_mb_tiles", _i, [_vp, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_f), _cam, _ull, _fx, _prm, _vp]),
+    ("rrt_glow_default", _i, [C.POINTER(rrt_glow)]),
+    ("rrt_glow_weights", _i, [C.POINTER(rrt_glow), _i, _i, C.POINTER(_f), _i, C.POINTER(_i)]),
+    ("rrt_glow_scratch_bytes", _i, [_i, _i, C.POINTER(rrt_glow), C.POINTER(C.c_size_t)]),
+    ("rrt_launch_glow", _i, [_vp, _vp, _i, _i, C.POINTER(rrt_glow), _vp, C.c_size_t, _vp]),
     ("rrt_tile_shard_rows", _i, [_i, _i, _i, _i, C.POINTER(_i)]),
     ("rrt_assemble_tiles", _i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     ("rrt_assemble_all_tiles", _i, [_vp, _vp, C.c_size_t, _i, _i, _i, _i, _vp]),

@@ -11,6 +11,9 @@
 //                [--supersample 1|2|4|8]       (S x S sub-samples per pixel: rrt_launch_raymarch_ss*, single kernel, no pool)
 //                [--motion-blur 1|2|4|8|16 [--shutter F]]   (K sub-frames over the last F of the frame interval, default 0.5:
 //                                              rrt_motion_clock, rrt_launch_raymarch_mb*, single kernel, no pool)
+//                [--glow INTENSITY [--glow-radius R] [--glow-threshold T] [--glow-lobes L]]   (HDR glow: the frame renders through
+//                                              rrt_launch_raymarch_ss / _mb into an HDR buffer, rrt_launch_glow writes its RGBA8;
+//                                              one GPU only, single kernel, no pool)
 //
 // Noise tables: the reference's simTime runs without bound (main.cpp:515) and a table's size grows with the times
 // it covers, so each device keeps ONE table over a window of the clock that fits --noise-table-gib (default 2;
@@ -35,6 +38,7 @@
 
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -234,6 +238,9 @@ int main(int argc, char** argv) {
     int supersample = 1;           // --supersample S: S x S sub-samples per pixel (rrt_launch_raymarch_ss*); 1 = one ray per pixel
     int motion = 1;                // --motion-blur K: K shutter sub-frames per frame (rrt_launch_raymarch_mb*); 1 = one instant
     float shutter = 0.5f;          // --shutter F: the fraction of the frame interval the shutter is open (180 degrees)
+    rrt_glow glow;                 // --glow INTENSITY (+ --glow-radius / -threshold / -lobes): rrt_launch_glow on every frame
+    rrt_glow_default(&glow);
+    bool use_glow = false;
     int kSlots = 3;                // frames in flight: frame k renders on stream k mod kSlots while its predecessors are
                                    // gathered / assembled / copied out (a rank's share of a frame is only a few rounds of
                                    // wavefronts; 3 measured best at 8 shards of a 4K frame: profiles/r02_frames_in_flight.txt)
@@ -282,6 +289,17 @@ int main(int argc, char** argv) {
             if (end != m && *end == 0 && f >= 0.0f && f <= 1.0f) shutter = f;
             else { fprintf(stderr, "--shutter F: a fraction of the frame interval in [0, 1]\n"); return 2; }
         }
+        else if (a == "--glow" || a == "--glow-radius" || a == "--glow-threshold" || a == "--glow-lobes") {
+            const char* m = i + 1 < argc ? argv[++i] : "";
+            char* end = nullptr;
+            const float v = strtof(m, &end);
+            if (end == m || *end != 0 || !std::isfinite(v)) { fprintf(stderr, "%s: a number\n", a.c_str()); return 2; }
+            if (a == "--glow") { glow.intensity = v; use_glow = true; }
+            else if (a == "--glow-radius") glow.radius = v;
+            else if (a == "--glow-threshold") glow.threshold = v;
+            else if (v == (float)(int)v) glow.lobes = (int)v;
+            else { fprintf(stderr, "--glow-lobes 1 | 2 | 3 | 4\n"); return 2; }
+        }
         else if (a == "--arith" && i + 1 < argc) {
             const std::string m = argv[++i];
             if (m == "strict") arith = RRT_ARITH_STRICT; else if (m == "fmad") arith = RRT_ARITH_FMAD; else if (m == "fast") arith = RRT_ARITH_FAST;
@@ -292,8 +310,18 @@ int main(int argc, char** argv) {
     if (w <= 0 || h <= 0 || frames < 0 || fps <= 0 || gpus < 1 || tile_rows < 1 || kSlots < 1 || kSlots > kMaxSlots) {
         fprintf(stderr, "bad arguments\n"); return 2;
     }
+    // the glow needs the whole frame's HDR on one device (rrt_launch_glow has no _tiles form); its settings are checked up front
+    size_t glow_bytes = 0;
+    if (use_glow) {
+        if (gpus > 1 || force_collective) { fprintf(stderr, "rrt_headless: --glow renders on one GPU only (--gpus 1)\n"); return 2; }
+        if (rrt_glow_scratch_bytes(w, h, &glow, &glow_bytes) != RRT_OK) {
+            fprintf(stderr, "--glow INTENSITY >= 0, --glow-radius R > 0 (a fraction of the height; widest lobe <= 1024 px), "
+                            "--glow-threshold T >= 0, --glow-lobes 1 | 2 | 3 | 4\n");
+            return 2;
+        }
+    }
     // a supersampled launch is always the single kernel in the static order (include/rrt.h): no pool, no path choice, no tile order
-    if (supersample > 1 || motion > 1) { workspace_gib = 0; path_window = -1; tile_order = 0; }
+    if (supersample > 1 || motion > 1 || use_glow) { workspace_gib = 0; path_window = -1; tile_order = 0; }
     int n_dev = 0, rc;
     if ((rc = rrt_device_count(&n_dev)) != RRT_OK) return fail("no GPU", rc);
     if (gpus > n_dev) { fprintf(stderr, "rrt_headless: --gpus %d but %d device(s) visible\n", gpus, n_dev); return 2; }
@@ -396,11 +424,14 @@ int main(int argc, char** argv) {
     void* gathered[kMaxSlots] = {};
     void* frame[kMaxSlots] = {};
     void* host[kMaxSlots] = {};
+    void* hdr[kMaxSlots] = {};         // --glow: each slot's linear frame and the glow's scratch
+    void* glow_scratch[kMaxSlots] = {};
     hipEvent_t done[kMaxSlots];
     const size_t frame_bytes = (size_t)w * h * 4;
     for (int s = 0; s < kSlots; ++s) {
         HIPCHK(hipMalloc(&gathered[s], shard_stride * gpus));
         HIPCHK(hipMalloc(&frame[s], frame_bytes));
+        if (use_glow) { HIPCHK(hipMalloc(&hdr[s], frame_bytes * sizeof(float))); HIPCHK(hipMalloc(&glow_scratch[s], glow_bytes)); }
         HIPCHK(hipEventCreateWithFlags(&done[s], hipEventDisableTiming));
     }
     FILE* f = out_path.empty() ? nullptr : fopen(out_path.c_str(), "wb");
@@ -513,7 +544,13 @@ int main(int argc, char** argv) {
             if (D.chooser) { int pol = RRT_PATH_AUTO; rrt_path_chooser_policy(D.chooser, k, &pol); prm.path_policy = pol; }
             else if (path_policy >= 0) prm.path_policy = path_policy;
             void* dst = collective ? D.tiles[slot] : frame[slot];
-            if (motion > 1) {
+            if (use_glow) {     // one device (checked above): the slot's HDR through _ss / _mb, then the glow on the same stream
+                float* lin = static_cast<float*>(hdr[slot]);
+                if (motion > 1) rc = rrt_launch_raymarch_mb(dst, lin, w, h, supersample, motion, sub_t, sub_cam, D.sky, &fx, &prm, D.stream[slot]);
+                else rc = rrt_launch_raymarch_ss(dst, lin, w, h, supersample, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
+                if (rc == RRT_OK) rc = rrt_launch_glow(dst, lin, w, h, &glow, glow_scratch[slot], glow_bytes, D.stream[slot]);
+            }
+            else if (motion > 1) {
                 if (collective) rc = rrt_launch_raymarch_mb_tiles(dst, w, h, supersample, tile_rows, d, gpus, motion, sub_t, sub_cam, D.sky, &fx, &prm, D.stream[slot]);
                 else rc = rrt_launch_raymarch_mb(dst, nullptr, w, h, supersample, motion, sub_t, sub_cam, D.sky, &fx, &prm, D.stream[slot]);
             }
@@ -573,14 +610,21 @@ int main(int argc, char** argv) {
         }
         choice += "]";
     }
+    std::string glow_json = "null";
+    if (use_glow) {
+        char buf[160];
+        snprintf(buf, sizeof(buf), "{\"radius\": %g, \"lobes\": %d, \"threshold\": %g, \"intensity\": %g}", glow.radius, glow.lobes,
+                 glow.threshold, glow.intensity);
+        glow_json = buf;
+    }
     printf("{\"frames\": %d, \"width\": %d, \"height\": %d, \"n_gpus\": %d, \"seconds\": %.4f, \"fps\": %.3f, \"Mrays_per_s\": %.3f, "
            "\"path\": \"%s\", \"spin\": %g, \"arith_mode\": \"%s\", \"noise_tables\": {\"builds\": %d, \"table_frames\": %d, "
            "\"arith_frames\": %d, \"coarsest_coverage\": %d, \"peak_bytes\": %zu, \"budget_bytes\": %zu}, \"tile_order\": %s, \"collective\": \"%s\", "
-           "\"path_choice\": %s, \"supersample\": %d, \"motion_blur\": %d, \"shutter\": %g}\n",
+           "\"path_choice\": %s, \"supersample\": %d, \"motion_blur\": %d, \"shutter\": %g, \"glow\": %s}\n",
            frames, w, h, gpus, dt, frames / dt, (double)frames * w * h / dt / 1e6, path_name, spin,
            arith == RRT_ARITH_FAST ? "fast" : (arith == RRT_ARITH_FMAD ? "fmad" : "strict"),
            table_builds, table_frames, arith_frames, coarsest, table_peak, table_budget, dev[0].order[0] ? "true" : "false",
-           collective ? "rccl grouped send/recv gather" : "none", choice.c_str(), supersample, motion, shutter);
+           collective ? "rccl grouped send/recv gather" : "none", choice.c_str(), supersample, motion, shutter, glow_json.c_str());
 
     for (int d = 0; d < gpus; ++d) {
         Device& D = dev[d];
@@ -599,6 +643,9 @@ int main(int argc, char** argv) {
         rrt_sky_destroy(D.sky);
     }
     HIPCHK(hipSetDevice(0));
-    for (int s = 0; s < kSlots; ++s) { (void)hipFree(gathered[s]); (void)hipFree(frame[s]); if (host[s]) (void)hipHostFree(host[s]); }
+    for (int s = 0; s < kSlots; ++s) {
+        (void)hipFree(gathered[s]); (void)hipFree(frame[s]); (void)hipFree(hdr[s]); (void)hipFree(glow_scratch[s]);
+        if (host[s]) (void)hipHostFree(host[s]);
+    }
     return 0;
 }

@@ -111,6 +111,7 @@ rrt_sky_t sky_register(const SkyObject& s) {
 
 /* ------------------------------------------------------------------ device code (kernels, kernel arguments, pool layout) */
 #include "rrt_kernels.h"
+#include "rrt_glow.h"                   /* the glow's kernels (rrt_launch_glow) */
 
 struct WorkspaceObject {
     uint8_t* d_base; size_t bytes; int device;
@@ -651,6 +652,88 @@ int shard_rows(int height, int tile_rows, int shard, int n_shards) {
     int rows = 0;
     for (int t = shard; t < n_tiles; t += n_shards) rows += (t * tile_rows + tile_rows <= height) ? tile_rows : (height - t * tile_rows);
     return rows;
+}
+
+/* ---- HDR glow (rrt_launch_glow): the lobes' taps in double, the checks, the three launches */
+struct GlowPlan {
+    int lobes, rmax, n_weights;
+    int radius[kGlowMaxLobes], woff[kGlowMaxLobes];
+    double sigma[kGlowMaxLobes];
+};
+
+/* the settings' checks and the lobes' sigma_l = (radius * height) * 2^l, R_l = ceil(3 sigma_l); all on the host */
+int glow_plan(const rrt_glow* g, int height, GlowPlan& p) {
+    if (!g) return RRT_ERR_INVALID_ARGUMENT;
+    if (g->struct_size != (uint32_t)sizeof(rrt_glow)) {
+        snprintf(g_hip_err, sizeof(g_hip_err), "rrt_glow.struct_size %u, this library's is %zu: recompile against include/rrt.h",
+                 g->struct_size, sizeof(rrt_glow));
+        return RRT_ERR_ABI_MISMATCH;
+    }
+    if (g->lobes < 1 || g->lobes > kGlowMaxLobes || height <= 0) return RRT_ERR_INVALID_ARGUMENT;
+    if (!std::isfinite(g->radius) || !(g->radius > 0.0f)) return RRT_ERR_INVALID_ARGUMENT;
+    if (!std::isfinite(g->threshold) || g->threshold < 0.0f) return RRT_ERR_INVALID_ARGUMENT;
+    if (!std::isfinite(g->intensity) || g->intensity < 0.0f) return RRT_ERR_INVALID_ARGUMENT;
+    p.lobes = g->lobes;
+    p.n_weights = 0;
+    for (int l = 0; l < p.lobes; ++l) {
+        const double sigma = ((double)g->radius * (double)height) * (double)(1 << l);
+        const double r = std::ceil(3.0 * sigma);
+        if (!(r <= (double)kGlowMaxRadius)) return RRT_ERR_INVALID_ARGUMENT;
+        p.sigma[l] = sigma;
+        p.radius[l] = (int)r;
+        p.woff[l] = p.n_weights;
+        p.n_weights += 2 * p.radius[l] + 1;
+    }
+    p.rmax = p.radius[p.lobes - 1];
+    return RRT_OK;
+}
+
+/* w[k + R] = exp(-k^2 / (2 sigma^2)) / sum_j exp(-j^2 / (2 sigma^2)), in double (the sum over ascending j), rounded to float */
+void glow_taps_host(double sigma, int r, float* out) {
+    const double d = 2.0 * sigma * sigma;
+    double sum = 0.0;
+    for (int j = -r; j <= r; ++j) sum += std::exp(-(double)j * (double)j / d);
+    for (int k = -r; k <= r; ++k) out[k + r] = (float)(std::exp(-(double)k * (double)k / d) / sum);
+}
+
+size_t glow_weight_bytes(const GlowPlan& p) { return ((size_t)p.n_weights * sizeof(float) + 15) & ~(size_t)15; }
+size_t glow_scratch(const GlowPlan& p, int width, int height) {
+    return glow_weight_bytes(p) + (size_t)p.lobes * (size_t)width * (size_t)height * sizeof(float4);
+}
+bool glow_frame_ok(int width, int height) {
+    return width > 0 && height > 0 && (int64_t)width * (int64_t)height < ((int64_t)1 << 31);
+}
+
+int launch_glow(uchar4* out, const float4* hdr, int width, int height, const rrt_glow* g, const GlowPlan& p, void* scratch,
+                hipStream_t st) {
+    float* weights = static_cast<float*>(scratch);
+    std::vector<float> taps(p.n_weights);
+    for (int l = 0; l < p.lobes; ++l) glow_taps_host(p.sigma[l], p.radius[l], taps.data() + p.woff[l]);
+    for (int off = 0; off < p.n_weights; off += kGlowWeightChunk) {
+        GlowWeightChunk c;
+        c.offset = off;
+        c.count = std::min(kGlowWeightChunk, p.n_weights - off);
+        memcpy(c.w, taps.data() + off, c.count * sizeof(float));
+        memset(c.w + c.count, 0, (kGlowWeightChunk - c.count) * sizeof(float));
+        hipLaunchKernelGGL(glow_load_weights, dim3(1), dim3(256), 0, st, weights, c);
+    }
+    GlowArgs a;
+    memset(&a, 0, sizeof(a));
+    a.hdr = hdr;
+    a.planes = reinterpret_cast<float4*>(static_cast<uint8_t*>(scratch) + glow_weight_bytes(p));
+    a.weights = weights;
+    a.out = out;
+    a.width = width; a.height = height; a.lobes = p.lobes; a.rmax = p.rmax;
+    a.seg = glow_seg(p.rmax);
+    for (int l = 0; l < p.lobes; ++l) { a.radius[l] = p.radius[l]; a.woff[l] = p.woff[l]; }
+    a.threshold = g->threshold;
+    a.scale = g->intensity / (float)p.lobes;
+    const int n_seg = (width + a.seg - 1) / a.seg;
+    hipLaunchKernelGGL((glow_hpass<kGlowM>), dim3(n_seg * height), dim3(kGlowHThreads), glow_hpass_lds(a.seg, p.rmax), st, a);
+    const int n_yb = (height + kGlowVWaves * kGlowM - 1) / (kGlowVWaves * kGlowM), n_strips = (width + 63) / 64;
+    hipLaunchKernelGGL((glow_vpass<kGlowM>), dim3(n_yb * n_strips), dim3(64, kGlowVWaves), 0, st, a);
+    RRT_HIP(hipGetLastError());
+    return RRT_OK;
 }
 
 }  // namespace
@@ -1554,6 +1637,49 @@ int rrt_clock_probe(unsigned long long* d_counters2, unsigned duration_us, void*
                        (unsigned long long)duration_us * 100ull);
     RRT_HIP(hipGetLastError());
     return RRT_OK;
+}
+
+int rrt_glow_default(rrt_glow* g) {
+    if (!g) return RRT_ERR_INVALID_ARGUMENT;
+    g->struct_size = (uint32_t)sizeof(rrt_glow);
+    g->radius = 0.004f;
+    g->lobes = 4;
+    g->threshold = 1.0f;
+    g->intensity = 0.25f;
+    return RRT_OK;
+}
+
+int rrt_glow_weights(const rrt_glow* g, int height, int lobe, float* out, int cap, int* radius_out) {
+    GlowPlan p;
+    const int rc = glow_plan(g, height, p);
+    if (rc) return rc;
+    if (lobe < 0 || lobe >= p.lobes) return RRT_ERR_INVALID_ARGUMENT;
+    const int r = p.radius[lobe];
+    if (out && cap < 2 * r + 1) return RRT_ERR_INVALID_ARGUMENT;
+    if (out) glow_taps_host(p.sigma[lobe], r, out);
+    if (radius_out) *radius_out = r;
+    return RRT_OK;
+}
+
+int rrt_glow_scratch_bytes(int width, int height, const rrt_glow* g, size_t* bytes) {
+    if (!bytes || !glow_frame_ok(width, height)) return RRT_ERR_INVALID_ARGUMENT;
+    GlowPlan p;
+    const int rc = glow_plan(g, height, p);
+    if (rc) return rc;
+    *bytes = glow_scratch(p, width, height);
+    return RRT_OK;
+}
+
+int rrt_launch_glow(void* d_out_rgba8, const float* d_hdr_rgba32f, int width, int height, const rrt_glow* g, void* d_scratch,
+                    size_t scratch_bytes, void* stream) {
+    if (!d_out_rgba8 || !d_hdr_rgba32f || !d_scratch || !glow_frame_ok(width, height)) return RRT_ERR_INVALID_ARGUMENT;
+    if ((reinterpret_cast<uintptr_t>(d_hdr_rgba32f) | reinterpret_cast<uintptr_t>(d_scratch)) & 15) return RRT_ERR_INVALID_ARGUMENT;
+    GlowPlan p;
+    const int rc = glow_plan(g, height, p);
+    if (rc) return rc;
+    if (scratch_bytes < glow_scratch(p, width, height)) return RRT_ERR_INVALID_ARGUMENT;
+    return launch_glow(static_cast<uchar4*>(d_out_rgba8), reinterpret_cast<const float4*>(d_hdr_rgba32f), width, height, g, p,
+                       d_scratch, static_cast<hipStream_t>(stream));
 }
 
 #ifdef RRT_TEST_HOOKS

@@ -2,6 +2,7 @@
 
     python -m relativisticraytracer_amd.headless --width 1920 --height 1080 --spin 0.9 \\
            --path 0 --frames 300 [--out frames.rgba | --out ppm_dir/] [--all-effects] [--supersample 2] [--motion-blur 4 --shutter 0.5]
+           [--glow 0.25 [--glow-radius 0.004] [--glow-threshold 1.0] [--glow-lobes 4]]
     python -m torch.distributed.run --nproc-per-node 8 -m relativisticraytracer_amd.headless ...
 
 Per frame k = 1..N it does what `main()` does while recording: advance the fixed 1/24 s clock
@@ -58,6 +59,12 @@ def main(argv=None):
     ap.add_argument("--shutter", type=float, default=0.5,
                     help="with --motion-blur K > 1: the fraction of the frame interval the shutter is open, ending at the frame's "
                          "time (rrt_motion_clock; 0.5 = 180 degrees)")
+    ap.add_argument("--glow", type=float, default=None, metavar="INTENSITY",
+                    help="HDR glow (rrt_launch_glow) of this intensity on every frame: the frame renders through "
+                         "rrt_launch_raymarch_ss / _mb into an HDR buffer, the glow writes its RGBA8.  One GPU only; single kernel, no pool")
+    ap.add_argument("--glow-radius", type=float, default=0.004, help="with --glow: the first lobe's sigma as a fraction of the height")
+    ap.add_argument("--glow-threshold", type=float, default=1.0, help="with --glow: the bright pass' luma threshold (a soft knee)")
+    ap.add_argument("--glow-lobes", type=int, choices=(1, 2, 3, 4), default=4, help="with --glow: Gaussian lobes, each twice as wide")
     ap.add_argument("--out", default=None, help="x.rgba (raw, bottom-up) | dir/ (PPM per frame) | x.mp4 (needs ffmpeg)")
     ap.add_argument("--init-timeout", type=float, default=300.0,
                     help="several ranks: seconds the process-group bring-up may take before the run exits non-zero with "
@@ -66,6 +73,9 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if not 0.0 <= args.shutter <= 1.0:
         ap.error("--shutter: a fraction of the frame interval in [0, 1]")
+    # the glow needs the whole frame's HDR on one GPU (no _tiles form); checked before any device is touched
+    if args.glow is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        ap.error("--glow: one GPU only (WORLD_SIZE > 1)")
 
     t_start = time.perf_counter()
 
@@ -85,6 +95,14 @@ def main(argv=None):
     import relativisticraytracer_amd as rrt
     from relativisticraytracer_amd import camera_paths, sharding, sinks
     from relativisticraytracer_amd.sky import load_sky, synthetic_sky
+    glow = None
+    if args.glow is not None:       # the settings' checks are host arithmetic (rrt_glow_scratch_bytes)
+        glow = rrt.GlowSettings(radius=args.glow_radius, lobes=args.glow_lobes, threshold=args.glow_threshold, intensity=args.glow)
+        try:
+            rrt.glow_scratch_bytes(args.width, args.height, glow)
+        except rrt.RRTError:
+            ap.error("--glow INTENSITY >= 0, --glow-radius R > 0 (a fraction of the height; widest lobe <= 1024 px), "
+                     "--glow-threshold T >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1")); rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -109,7 +127,7 @@ def main(argv=None):
     trace("process group ready" if world > 1 else "single rank")
     w, h = args.width, args.height
     ss, mb = args.supersample, args.motion_blur
-    single = ss > 1 or mb > 1            # a supersampled or blurred launch: the single kernel, static order, no pool
+    single = ss > 1 or mb > 1 or glow is not None    # a supersampled, blurred or glowed launch: the single kernel, static order, no pool
     tex = rrt.SkyTexture(load_sky(args.sky) if args.sky else synthetic_sky())
     fx = rrt.CameraEffects(useChromaticAberration=bool(args.all_effects))
     # with several ranks --frames-in-flight frames are in flight (FrameSharder pipeline mode), each with its own
@@ -146,6 +164,20 @@ def main(argv=None):
                              path_policy=int(os.environ.get("RRT_PATH_POLICY", "0"))) for j in range(n_slots)]
     path = camera_paths.CameraPath(args.path) if args.path >= 0 else None
     state = {"t": 0.0, "cam": rrt.CameraState.default(), "table": 0, "k": 0}
+    if glow is not None:        # one rank (checked above): the whole frame's HDR, the glow's scratch, the glowed frame
+        glow_hdr = torch.zeros(h * w * 4, dtype=torch.float32, device=dev)
+        glow_scratch = torch.empty(rrt.glow_scratch_bytes(w, h, glow), dtype=torch.uint8, device=dev)
+        glow_frame = torch.zeros(h * w * 4, dtype=torch.uint8, device=dev)
+
+    def render_glowed():
+        """the frame through _ss / _mb into glow_hdr, then the glow into glow_frame (bottom-up rows, not the tile layout)"""
+        prms[0].noise_table = state["table"]
+        if mb > 1:
+            rrt.launch_raymarch_mb(glow_frame, w, h, ss, state["times"], state["cams"], tex, fx, prms[0], hdr=glow_hdr)
+        else:
+            rrt.launch_raymarch_ss(glow_frame, w, h, ss, state["t"], state["cam"], tex, fx, prms[0], hdr=glow_hdr)
+        rrt.launch_glow(glow_frame, glow_hdr, w, h, glow, glow_scratch)
+        return glow_frame
 
     def render(buf, slot):
         prms[slot].noise_table = state["table"]
@@ -204,7 +236,7 @@ def main(argv=None):
             state["table"] = nwin.table_id(sim_t)
         if path is not None:
             state["cam"] = path.camera_at(path_t)
-        frame = fs.step()
+        frame = render_glowed() if glow is not None else fs.step()
         if sink and frame is not None:
             deliver(frame)
     for frame in fs.drain():                # the frames still in flight, in order
@@ -227,7 +259,8 @@ def main(argv=None):
                           "path_choice": chooser.stats() if chooser else None,
                           "noise_tables": nwin.summary(),
                           "tile_order": orders[0].info() if orders else None, "supersample": ss,
-                          "motion_blur": mb, "shutter": args.shutter}), flush=True)
+                          "motion_blur": mb, "shutter": args.shutter, "glow": glow.info() if glow is not None else None}),
+              flush=True)
     if world > 1:
         dist.destroy_process_group()
     nwin.close()
