@@ -467,6 +467,62 @@ int rrt_glow_scratch_bytes(int width, int height, const rrt_glow* g, size_t* byt
 int rrt_launch_glow(void* d_out_rgba8, const float* d_hdr_rgba32f, int width, int height, const rrt_glow* g, void* d_scratch,
                     size_t scratch_bytes, void* stream);
 
+/* ---- panoramas: 360-degree equirectangular and angular-fisheye (dome master) frames; no counterpart in the reference, whose one
+ *      camera is the pinhole of raymarcher.cu:20-34.  The frame is DEFINED as rrt_launch_raymarch_ss's: sub-sample (i, j) of output
+ *      pixel (x, y) is pixel (s*x + i, s*y + j) of the W x H = (s*width) x (s*height) panorama, the pixel's HDR is the same pairwise
+ *      sub-row / row-sum tree times 1/(s*s), tone-mapped once, bottom-up rows; d_hdr_rgba32f (may be NULL) receives the mean HDR.
+ *      The primary ray of virtual pixel (x, y), with fw, rt, up, pos from cam, every operation binary32, uncontracted, division and
+ *      square root correctly rounded, the same in all three arithmetic modes (the mode changes only the march):
+ *        - half-angles in radians, on the host: a_h = (float)((double)fov_deg * 3.14159265358979323846 / 360.0), a_v the same of
+ *          vfov_deg, a = a_h;
+ *        - EQUIRECT: lon = (((float)x + 0.5f) / (float)W * 2.0f - 1.0f) * a_h, lat = (((float)y + 0.5f) / (float)H * 2.0f - 1.0f) * a_v;
+ *          (s_lat, c_lat) and (s_lon, c_lon) from rrt_sincosf (csrc/rrt_math.h);
+ *          D = fw*(c_lat*c_lon) + (rt*(c_lat*s_lon) + up*s_lat), per component in that association.  The centre column looks
+ *          along fw, +x turns toward rt, +y toward up, as in the pinhole frame;
+ *        - FISHEYE (angular, equidistant): u = (2.0f*((float)x + 0.5f) - (float)W) / (float)H, v = (2.0f*((float)y + 0.5f) - (float)H)
+ *          / (float)H, r2 = u*u + v*v; r2 > 1.0f: the sub-sample is OUTSIDE the disc.  Otherwise r = sqrt(r2), (s_t, c_t) =
+ *          rrt_sincosf(r * a), k = r > 0 ? s_t / r : 0.0f, D = fw*c_t + (rt*(u*k) + up*(v*k));
+ *        - vel = normalize(D) (raymarcher.cu's: 1e-6f guard), then the nudge hash (rrt_params.nudge_ulps) on the virtual (x, y)
+ *          exactly as the pinhole's; the march starts at pos.
+ *      An outside sub-sample's post-FX HDR is exactly (0, 0, 0): no march, no sky, no bloom; it still enters its pixel's tree, which
+ *      antialiases the disc's rim.  Bloom and chromatic aberration act per ray and are honoured; use_lens_distortion and use_vignette
+ *      are IGNORED (both are defined on the pinhole's uv).  rrt_params honoured and ignored as in rrt_launch_raymarch_ss (noise table
+ *      included): a panorama is always the single kernel in the static order.  kind RRT_PROJ_PINHOLE makes the call
+ *      rrt_launch_raymarch_ss (same bytes; spans ignored).  RRT_ERR_INVALID_ARGUMENT, before any device call: everything
+ *      rrt_launch_raymarch_ss refuses, a NULL proj, an unknown kind, a span outside its range or not finite; RRT_ERR_ABI_MISMATCH for
+ *      another struct_size.  No memset, no synchronisation: a launch can be captured into a hipGraph. ---- */
+#define RRT_PROJ_PINHOLE 0      /* the reference's camera: the call IS rrt_launch_raymarch_ss, same bytes */
+#define RRT_PROJ_EQUIRECT 1
+#define RRT_PROJ_FISHEYE 2
+typedef struct rrt_projection {
+    uint32_t struct_size;   /* sizeof(rrt_projection): rrt_projection_default sets it; any other value is RRT_ERR_ABI_MISMATCH */
+    int32_t kind;           /* RRT_PROJ_* */
+    float fov_deg;          /* equirect: horizontal span, (0, 360], default 360; fisheye: aperture, (0, 360], default 180; pinhole: ignored (0) */
+    float vfov_deg;         /* equirect: vertical span, (0, 180], default 180; fisheye and pinhole: ignored (0) */
+} rrt_projection;
+int rrt_projection_default(int kind, rrt_projection* p);
+/* Host only: the unit direction vel of virtual pixel (x, y) of a width x height frame, before any nudge, from the same source the
+ * kernel runs; *inside_out (may be NULL) = 0 and a zero dir_out for a fisheye sub-sample outside the disc, 1 otherwise.
+ * RRT_PROJ_PINHOLE: raymarcher.cu:20-34's direction without the lens.  Maps a pixel to a sky direction (overlays).
+ * RRT_ERR_INVALID_ARGUMENT: the projection's refusals, NULL cam or dir_out, width or height <= 0, (x, y) outside the frame. */
+int rrt_projection_ray(const rrt_projection* p, int width, int height, int x, int y, const rrt_camera* cam,
+                       float dir_out[3], int* inside_out);
+int rrt_launch_raymarch_pano(void* d_out_rgba8, float* d_hdr_rgba32f /* may be NULL */, int width, int height,
+                             int samples_per_axis, const rrt_projection* proj, float time, const rrt_camera* cam,
+                             rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm, void* stream);
+/* The same primary rays on the device, for GPU-side overlays and compositing: every pixel (x, y) of a width x height frame as a
+ * float4 (vel before any nudge, 1 inside / 0 outside the fisheye disc) -- the bits rrt_projection_ray returns for it -- in the
+ * frame's layout (bottom-up rows: pixel (x, y) at index (height - 1 - y) * width + x).  A supersampled frame's sub-samples are the
+ * pixels of the (s*width) x (s*height) map.  RRT_ERR_INVALID_ARGUMENT, before any device call: the projection's refusals, NULL
+ * d_dir_rgba32f or cam, d_dir_rgba32f not 16-byte aligned, width or height <= 0, width*height >= 2^31.  Graph-capturable. */
+int rrt_launch_projection_map(void* d_dir_rgba32f, int width, int height, const rrt_projection* proj, const rrt_camera* cam,
+                              void* stream);
+/* The same frame's row tiles of `shard`, in the buffer layout of rrt_launch_raymarch_ss_tiles (rrt_assemble_(all_)tiles serve it). */
+int rrt_launch_raymarch_pano_tiles(void* d_out_tiles, int width, int height, int samples_per_axis, int tile_rows,
+                                   int shard, int n_shards, const rrt_projection* proj, float time,
+                                   const rrt_camera* cam, rrt_sky_t sky, const rrt_effects* fx,
+                                   const rrt_params* prm, void* stream);
+
 /* ---- which path a rank's share takes while several frames of a sequence are in flight (host only; no GPU call) ----
  * New in this repo (the reference renders one frame at a time on one GPU: src/main.cpp:505-529).  A launch of <= 1.5 M rays
  * with a pool can take the three-pass path (RRT_PATH_AUTO) or the single kernel (RRT_PATH_SINGLE); under frames in flight the

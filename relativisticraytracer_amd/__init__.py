@@ -19,13 +19,14 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import RRTError, rrt_camera, rrt_debug_outputs, rrt_effects, rrt_glow, rrt_params  # noqa: F401
+from ._lib import RRTError, rrt_camera, rrt_debug_outputs, rrt_effects, rrt_glow, rrt_params, rrt_projection  # noqa: F401
 
 __all__ = ["CameraState", "CameraEffects", "RenderParams", "SkyTexture", "Workspace", "NoiseTable", "launch_raymarch",
            "set_launch_defaults", "get_launch_defaults",
            "launch_raymarch_rows", "launch_raymarch_tiles", "assemble_tiles", "assemble_all_tiles",
            "launch_raymarch_ss", "launch_raymarch_ss_tiles", "launch_raymarch_mb", "launch_raymarch_mb_tiles",
            "GlowSettings", "glow_weights", "glow_scratch_bytes", "launch_glow",
+           "Projection", "projection_default", "projection_ray", "launch_projection_map", "launch_raymarch_pano", "launch_raymarch_pano_tiles",
            "tile_shard_rows",
            "launch_raymarch_debug", "RRTError", "device_count", "abi_version", "TileOrder", "TileMap",
            "probe_tile_costs", "balance_tiles", "launch_raymarch_tilemap", "assemble_all_tilemap", "clock_probe", "clock_probe_ghz"]
@@ -138,6 +139,48 @@ class GlowSettings(rrt_glow):
 
     def info(self):
         return {"radius": self.radius, "lobes": self.lobes, "threshold": self.threshold, "intensity": self.intensity}
+
+
+PROJ_PINHOLE, PROJ_EQUIRECT, PROJ_FISHEYE = 0, 1, 2          # include/rrt.h: RRT_PROJ_*
+PROJECTION_KINDS = {"pinhole": PROJ_PINHOLE, "equirect": PROJ_EQUIRECT, "fisheye": PROJ_FISHEYE}
+
+
+class Projection(rrt_projection):
+    """The camera of a panorama (include/rrt.h: rrt_projection): kind "pinhole" | "equirect" | "fisheye" (or RRT_PROJ_*), fov_deg
+    (equirect: horizontal span, default 360; fisheye: aperture, default 180) and vfov_deg (equirect: vertical span, default 180).
+    Defaults == rrt_projection_default(kind); the spans are checked by the calls that use them."""
+
+    def __init__(self, kind="equirect", fov_deg=None, vfov_deg=None):
+        super().__init__()
+        k = PROJECTION_KINDS.get(kind, kind)
+        if not isinstance(k, int):
+            raise ValueError(f"projection kind: one of {sorted(PROJECTION_KINDS)}, got {kind!r}")
+        _lib.check(_lib.load().rrt_projection_default(k, C.byref(self)), "rrt_projection_default")
+        if fov_deg is not None:
+            self.fov_deg = float(fov_deg)
+        if vfov_deg is not None:
+            self.vfov_deg = float(vfov_deg)
+
+    @property
+    def name(self):
+        return {v: k for k, v in PROJECTION_KINDS.items()}.get(self.kind, str(self.kind))
+
+    def info(self):
+        return {"kind": self.name, "fov_deg": self.fov_deg, "vfov_deg": self.vfov_deg}
+
+
+def projection_default(kind):
+    """rrt_projection_default: the documented defaults of a kind ("pinhole" | "equirect" | "fisheye" or RRT_PROJ_*)"""
+    return Projection(kind)
+
+
+def projection_ray(projection, w, h, x, y, cam):
+    """(unit direction as float32[3], inside) of virtual pixel (x, y) of a w x h frame (rrt_projection_ray, host only): the
+    primary ray before any nudge, from the source the panorama kernel runs; a fisheye pixel outside the disc is (0, 0, 0), False"""
+    d, inside = (C.c_float * 3)(), C.c_int(0)
+    _lib.check(_lib.load().rrt_projection_ray(C.byref(projection), w, h, x, y, C.byref(cam), C.byref(d), C.byref(inside)),
+               "rrt_projection_ray")
+    return np.array(d[:], np.float32), bool(inside.value)
 
 
 class SkyTexture:
@@ -521,6 +564,33 @@ def launch_raymarch_ss_tiles(d_out_tiles, w, h, samples, tile_rows, shard, n_sha
                                                         float(time), C.byref(cam), _sky_handle(skyboxTex), C.byref(effects),
                                                         C.byref(params) if params is not None else None,
                                                         _stream(stream)), "rrt_launch_raymarch_ss_tiles")
+
+
+def launch_raymarch_pano(d_out, w, h, samples, projection, time, cam, skyboxTex, effects, params=None, stream=None, hdr=None):
+    """samples x samples supersampled w x h panorama (include/rrt.h: rrt_launch_raymarch_pano): launch_raymarch_ss's frame with the
+    projection's primary ray (equirect or fisheye; "pinhole" is launch_raymarch_ss itself).  Lens distortion and vignette are
+    ignored; a fisheye pixel outside the disc is black.  `hdr` (optional): w*h*4 float32 that receives the mean HDR."""
+    _lib.check(_lib.load().rrt_launch_raymarch_pano(_ptr(d_out), _ptr(hdr), w, h, samples, C.byref(projection), float(time),
+                                                    C.byref(cam), _sky_handle(skyboxTex), C.byref(effects),
+                                                    C.byref(params) if params is not None else None,
+                                                    _stream(stream)), "rrt_launch_raymarch_pano")
+
+
+def launch_projection_map(d_dirs, w, h, projection, cam, stream=None):
+    """every pixel's primary ray on the device (rrt_launch_projection_map): d_dirs (w*h*4 float32, 16-byte aligned) receives
+    (dir, 1 inside / 0 outside the fisheye disc) per pixel in the frame's bottom-up layout -- projection_ray's bits"""
+    _lib.check(_lib.load().rrt_launch_projection_map(_ptr(d_dirs), w, h, C.byref(projection), C.byref(cam), _stream(stream)),
+               "rrt_launch_projection_map")
+
+
+def launch_raymarch_pano_tiles(d_out_tiles, w, h, samples, tile_rows, shard, n_shards, projection, time, cam, skyboxTex, effects,
+                               params=None, stream=None):
+    """The row tiles of `shard` of launch_raymarch_pano's frame, in launch_raymarch_tiles' buffer layout (assemble_tiles /
+    assemble_all_tiles serve it unchanged)."""
+    _lib.check(_lib.load().rrt_launch_raymarch_pano_tiles(_ptr(d_out_tiles), w, h, samples, tile_rows, shard, n_shards,
+                                                          C.byref(projection), float(time), C.byref(cam), _sky_handle(skyboxTex),
+                                                          C.byref(effects), C.byref(params) if params is not None else None,
+                                                          _stream(stream)), "rrt_launch_raymarch_pano_tiles")
 
 
 def _sub_frames(times, cams):

@@ -66,6 +66,10 @@ class rrt_glow(C.Structure):
                 ("intensity", C.c_float)]
 
 
+class rrt_projection(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_int32), ("fov_deg", C.c_float), ("vfov_deg", C.c_float)]
+
+
 # every symbol include/rrt.h declares: (name, restype, argtypes)
 _vp, _i, _f, _ull = C.c_void_p, C.c_int, C.c_float, C.c_ulonglong
 _cam, _fx, _prm = C.POINTER(rrt_camera), C.POINTER(rrt_effects), C.POINTER(rrt_params)
@@ -123,6 +127,11 @@ SYMBOLS = [
     ("rrt_glow_weights", _i, [C.POINTER(rrt_glow), _i, _i, C.POINTER(_f), _i, C.POINTER(_i)]),
     ("rrt_glow_scratch_bytes", _i, [_i, _i, C.POINTER(rrt_glow), C.POINTER(C.c_size_t)]),
     ("rrt_launch_glow", _i, [_vp, _vp, _i, _i, C.POINTER(rrt_glow), _vp, C.c_size_t, _vp]),
+    ("rrt_projection_default", _i, [_i, C.POINTER(rrt_projection)]),
+    ("rrt_projection_ray", _i, [C.POINTER(rrt_projection), _i, _i, _i, _i, _cam, C.POINTER(_f * 3), C.POINTER(_i)]),
+    ("rrt_launch_raymarch_pano", _i, [_vp, _vp, _i, _i, _i, C.POINTER(rrt_projection), _f, _cam, _ull, _fx, _prm, _vp]),
+    ("rrt_launch_projection_map", _i, [_vp, _i, _i, C.POINTER(rrt_projection), _cam, _vp]),
+    ("rrt_launch_raymarch_pano_tiles", _i, [_vp, _i, _i, _i, _i, _i, _i, C.POINTER(rrt_projection), _f, _cam, _ull, _fx, _prm, _vp]),
     ("rrt_tile_shard_rows", _i, [_i, _i, _i, _i, C.POINTER(_i)]),
     ("rrt_assemble_tiles", _i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     ("rrt_assemble_all_tiles", _i, [_vp, _vp, C.c_size_t, _i, _i, _i, _i, _vp]),

@@ -14,6 +14,9 @@
 //                [--glow INTENSITY [--glow-radius R] [--glow-threshold T] [--glow-lobes L]]   (HDR glow: the frame renders through
 //                                              rrt_launch_raymarch_ss / _mb into an HDR buffer, rrt_launch_glow writes its RGBA8;
 //                                              one GPU only, single kernel, no pool)
+//                [--projection pinhole|equirect|fisheye [--fov DEG] [--vfov DEG]]   (panoramas: rrt_launch_raymarch_pano*, single
+//                                              kernel, no pool; equirect --fov 360 --vfov 180, fisheye --fov 180 (aperture); not with
+//                                              --motion-blur > 1, equirect not with --glow)
 //
 // Noise tables: the reference's simTime runs without bound (main.cpp:515) and a table's size grows with the times
 // it covers, so each device keeps ONE table over a window of the clock that fits --noise-table-gib (default 2;
@@ -241,6 +244,8 @@ int main(int argc, char** argv) {
     rrt_glow glow;                 // --glow INTENSITY (+ --glow-radius / -threshold / -lobes): rrt_launch_glow on every frame
     rrt_glow_default(&glow);
     bool use_glow = false;
+    int projection = RRT_PROJ_PINHOLE;   // --projection: the camera (rrt_launch_raymarch_pano* for equirect / fisheye)
+    float fov = 0.0f, vfov = 0.0f;       // --fov / --vfov DEG (0: not given -- the kind's default, rrt_projection_default)
     int kSlots = 3;                // frames in flight: frame k renders on stream k mod kSlots while its predecessors are
                                    // gathered / assembled / copied out (a rank's share of a frame is only a few rounds of
                                    // wavefronts; 3 measured best at 8 shards of a 4K frame: profiles/r02_frames_in_flight.txt)
@@ -300,6 +305,20 @@ int main(int argc, char** argv) {
             else if (v == (float)(int)v) glow.lobes = (int)v;
             else { fprintf(stderr, "--glow-lobes 1 | 2 | 3 | 4\n"); return 2; }
         }
+        else if (a == "--projection") {
+            const std::string m = i + 1 < argc ? argv[++i] : "";
+            if (m == "pinhole") projection = RRT_PROJ_PINHOLE; else if (m == "equirect") projection = RRT_PROJ_EQUIRECT;
+            else if (m == "fisheye") projection = RRT_PROJ_FISHEYE;
+            else { fprintf(stderr, "--projection pinhole | equirect | fisheye\n"); return 2; }
+        }
+        else if (a == "--fov" || a == "--vfov") {
+            const char* m = i + 1 < argc ? argv[++i] : "";
+            char* end = nullptr;
+            const float v = strtof(m, &end);
+            if (end == m || *end != 0) { fprintf(stderr, "%s DEG: a number of degrees\n", a.c_str()); return 2; }
+            (a == "--fov" ? fov : vfov) = v;
+            if (v == 0.0f) { fprintf(stderr, "--fov DEG in (0, 360], --vfov DEG in (0, 180]\n"); return 2; }
+        }
         else if (a == "--arith" && i + 1 < argc) {
             const std::string m = argv[++i];
             if (m == "strict") arith = RRT_ARITH_STRICT; else if (m == "fmad") arith = RRT_ARITH_FMAD; else if (m == "fast") arith = RRT_ARITH_FAST;
@@ -320,8 +339,28 @@ int main(int argc, char** argv) {
             return 2;
         }
     }
+    // panoramas: the spans are checked by the host query (the launch's own refusals), the combinations the kernels lack up front
+    const bool pano = projection != RRT_PROJ_PINHOLE;
+    rrt_projection proj;
+    rrt_projection_default(projection, &proj);
+    if (!pano && (fov != 0.0f || vfov != 0.0f)) { fprintf(stderr, "--fov / --vfov need --projection equirect | fisheye\n"); return 2; }
+    if (projection == RRT_PROJ_FISHEYE && vfov != 0.0f) { fprintf(stderr, "--vfov: equirect only (a fisheye's aperture is --fov)\n"); return 2; }
+    if (fov != 0.0f) proj.fov_deg = fov;
+    if (vfov != 0.0f) proj.vfov_deg = vfov;
+    if (pano) {
+        const rrt_camera c0 = {};
+        float d[3];
+        if (rrt_projection_ray(&proj, 1, 1, 0, 0, &c0, d, nullptr) != RRT_OK) {
+            fprintf(stderr, "--fov DEG in (0, 360], --vfov DEG in (0, 180]\n"); return 2;
+        }
+        if (motion > 1) { fprintf(stderr, "rrt_headless: a panorama renders one instant per frame (--motion-blur 1)\n"); return 2; }
+        if (projection == RRT_PROJ_EQUIRECT && use_glow) {
+            fprintf(stderr, "rrt_headless: --glow clamps at the frame's edge and an equirect frame wraps: not with --projection equirect\n");
+            return 2;
+        }
+    }
     // a supersampled launch is always the single kernel in the static order (include/rrt.h): no pool, no path choice, no tile order
-    if (supersample > 1 || motion > 1 || use_glow) { workspace_gib = 0; path_window = -1; tile_order = 0; }
+    if (supersample > 1 || motion > 1 || use_glow || pano) { workspace_gib = 0; path_window = -1; tile_order = 0; }
     int n_dev = 0, rc;
     if ((rc = rrt_device_count(&n_dev)) != RRT_OK) return fail("no GPU", rc);
     if (gpus > n_dev) { fprintf(stderr, "rrt_headless: --gpus %d but %d device(s) visible\n", gpus, n_dev); return 2; }
@@ -547,8 +586,13 @@ int main(int argc, char** argv) {
             if (use_glow) {     // one device (checked above): the slot's HDR through _ss / _mb, then the glow on the same stream
                 float* lin = static_cast<float*>(hdr[slot]);
                 if (motion > 1) rc = rrt_launch_raymarch_mb(dst, lin, w, h, supersample, motion, sub_t, sub_cam, D.sky, &fx, &prm, D.stream[slot]);
+                else if (pano) rc = rrt_launch_raymarch_pano(dst, lin, w, h, supersample, &proj, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
                 else rc = rrt_launch_raymarch_ss(dst, lin, w, h, supersample, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
                 if (rc == RRT_OK) rc = rrt_launch_glow(dst, lin, w, h, &glow, glow_scratch[slot], glow_bytes, D.stream[slot]);
+            }
+            else if (pano) {
+                if (collective) rc = rrt_launch_raymarch_pano_tiles(dst, w, h, supersample, tile_rows, d, gpus, &proj, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
+                else rc = rrt_launch_raymarch_pano(dst, nullptr, w, h, supersample, &proj, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
             }
             else if (motion > 1) {
                 if (collective) rc = rrt_launch_raymarch_mb_tiles(dst, w, h, supersample, tile_rows, d, gpus, motion, sub_t, sub_cam, D.sky, &fx, &prm, D.stream[slot]);
@@ -617,14 +661,20 @@ int main(int argc, char** argv) {
                  glow.threshold, glow.intensity);
         glow_json = buf;
     }
+    const char* proj_name = projection == RRT_PROJ_EQUIRECT ? "equirect" : (projection == RRT_PROJ_FISHEYE ? "fisheye" : "pinhole");
+    char fov_json[32] = "null", vfov_json[32] = "null";
+    if (pano) snprintf(fov_json, sizeof(fov_json), "%g", proj.fov_deg);
+    if (projection == RRT_PROJ_EQUIRECT) snprintf(vfov_json, sizeof(vfov_json), "%g", proj.vfov_deg);
     printf("{\"frames\": %d, \"width\": %d, \"height\": %d, \"n_gpus\": %d, \"seconds\": %.4f, \"fps\": %.3f, \"Mrays_per_s\": %.3f, "
            "\"path\": \"%s\", \"spin\": %g, \"arith_mode\": \"%s\", \"noise_tables\": {\"builds\": %d, \"table_frames\": %d, "
            "\"arith_frames\": %d, \"coarsest_coverage\": %d, \"peak_bytes\": %zu, \"budget_bytes\": %zu}, \"tile_order\": %s, \"collective\": \"%s\", "
-           "\"path_choice\": %s, \"supersample\": %d, \"motion_blur\": %d, \"shutter\": %g, \"glow\": %s}\n",
+           "\"path_choice\": %s, \"supersample\": %d, \"motion_blur\": %d, \"shutter\": %g, \"glow\": %s, "
+           "\"projection\": \"%s\", \"fov_deg\": %s, \"vfov_deg\": %s}\n",
            frames, w, h, gpus, dt, frames / dt, (double)frames * w * h / dt / 1e6, path_name, spin,
            arith == RRT_ARITH_FAST ? "fast" : (arith == RRT_ARITH_FMAD ? "fmad" : "strict"),
            table_builds, table_frames, arith_frames, coarsest, table_peak, table_budget, dev[0].order[0] ? "true" : "false",
-           collective ? "rccl grouped send/recv gather" : "none", choice.c_str(), supersample, motion, shutter, glow_json.c_str());
+           collective ? "rccl grouped send/recv gather" : "none", choice.c_str(), supersample, motion, shutter, glow_json.c_str(),
+           proj_name, fov_json, vfov_json);
 
     for (int d = 0; d < gpus; ++d) {
         Device& D = dev[d];

@@ -647,6 +647,59 @@ int launch_mb(void* out, float4* hdr, int width, int height, int s, const RowMap
     return RRT_OK;
 }
 
+/* ---- panoramas (rrt_launch_raymarch_pano*, rrt_projection_ray): supersampled frames with the projection's primary ray */
+/* the projection's own refusals (include/rrt.h); a pinhole's spans are not looked at */
+int check_projection(const rrt_projection* p) {
+    if (!p) return RRT_ERR_INVALID_ARGUMENT;
+    if (p->struct_size != (uint32_t)sizeof(rrt_projection)) return RRT_ERR_ABI_MISMATCH;
+    const bool span_ok = std::isfinite(p->fov_deg) && p->fov_deg > 0.0f && p->fov_deg <= 360.0f;
+    if (p->kind == RRT_PROJ_PINHOLE) return RRT_OK;
+    if (p->kind == RRT_PROJ_FISHEYE) return span_ok ? RRT_OK : RRT_ERR_INVALID_ARGUMENT;
+    if (p->kind == RRT_PROJ_EQUIRECT)
+        return span_ok && std::isfinite(p->vfov_deg) && p->vfov_deg > 0.0f && p->vfov_deg <= 180.0f ? RRT_OK : RRT_ERR_INVALID_ARGUMENT;
+    return RRT_ERR_INVALID_ARGUMENT;
+}
+/* the kernel's constants: half-spans in radians, rounded once from double */
+ProjArgs proj_args(const rrt_projection& p) {
+    ProjArgs pj;
+    pj.kind = p.kind;
+    pj.a_h = (float)((double)p.fov_deg * 3.14159265358979323846 / 360.0);
+    pj.a_v = (float)((double)p.vfov_deg * 3.14159265358979323846 / 360.0);
+    return pj;
+}
+
+int check_pano(const void* out, int width, int height, int s, const rrt_projection* proj, const rrt_camera* cam, const rrt_effects* fx,
+               const rrt_params* prm) {
+    const int rc = check_projection(proj);
+    if (rc != RRT_OK) return rc;
+    return check_ss(out, width, height, s, cam, fx, prm);
+}
+
+/* launch_ss with projection_dir instead of primary_ray; the lens and the vignette are cleared (the contract ignores them) */
+int launch_pano(void* out, float4* hdr, int width, int height, int s, const RowMap& rows, const rrt_projection& proj, float time,
+                const rrt_camera* cam, rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm_in, hipStream_t st) {
+    if (proj.kind == RRT_PROJ_PINHOLE) return launch_ss(out, hdr, width, height, s, rows, time, cam, sky, fx, prm_in, st);
+    rrt_params prm;
+    load_params(prm_in, prm);
+    prm.workspace = 0; prm.path_policy = RRT_PATH_AUTO; prm.pool_rounds = 0; prm.pass_chains = 0; prm.tile_order = 0;
+    FrameArgs a;
+    LaunchOpts o;
+    const int rc = fill_args(a, o, out, s * width, s * height, time, cam, sky, fx, &prm);
+    if (rc) return rc;
+    a.use_lens = 0; a.use_vignette = 0;
+    a.rows = rows;
+    if (rows.n_local_rows == 0) return RRT_OK;
+    const ProjArgs pj = proj_args(proj);
+    const dim3 grid((a.width + kWGPixX - 1) / kWGPixX, (s * rows.n_local_rows + kWGPixY - 1) / kWGPixY), block(kWGThreads);
+    const bool spin = a.spin != 0.0f;
+    const int media = o.media, arith = o.arith;
+#define RRT_PANO3(S, M, F) hipLaunchKernelGGL((panorama_pixels<S, M, F>), grid, block, 0, st, a, s, hdr, pj)
+    RRT_SS_DISPATCH(RRT_PANO3);
+#undef RRT_PANO3
+    RRT_HIP(hipGetLastError());
+    return RRT_OK;
+}
+
 int shard_rows(int height, int tile_rows, int shard, int n_shards) {
     int n_tiles = (height + tile_rows - 1) / tile_rows;
     int rows = 0;
@@ -1680,6 +1733,58 @@ int rrt_launch_glow(void* d_out_rgba8, const float* d_hdr_rgba32f, int width, in
     if (scratch_bytes < glow_scratch(p, width, height)) return RRT_ERR_INVALID_ARGUMENT;
     return launch_glow(static_cast<uchar4*>(d_out_rgba8), reinterpret_cast<const float4*>(d_hdr_rgba32f), width, height, g, p,
                        d_scratch, static_cast<hipStream_t>(stream));
+}
+
+int rrt_projection_default(int kind, rrt_projection* p) {
+    if (!p || (kind != RRT_PROJ_PINHOLE && kind != RRT_PROJ_EQUIRECT && kind != RRT_PROJ_FISHEYE)) return RRT_ERR_INVALID_ARGUMENT;
+    p->struct_size = (uint32_t)sizeof(rrt_projection);
+    p->kind = kind;
+    p->fov_deg = kind == RRT_PROJ_EQUIRECT ? 360.0f : (kind == RRT_PROJ_FISHEYE ? 180.0f : 0.0f);
+    p->vfov_deg = kind == RRT_PROJ_EQUIRECT ? 180.0f : 0.0f;
+    return RRT_OK;
+}
+
+int rrt_projection_ray(const rrt_projection* p, int width, int height, int x, int y, const rrt_camera* cam, float dir_out[3],
+                       int* inside_out) {
+    const int rc = check_projection(p);
+    if (rc) return rc;
+    if (!cam || !dir_out || width <= 0 || height <= 0 || x < 0 || x >= width || y < 0 || y >= height) return RRT_ERR_INVALID_ARGUMENT;
+    const bool inside = projection_dir(proj_args(*p), width, height, x, y, *cam, dir_out);
+    if (inside_out) *inside_out = inside ? 1 : 0;
+    return RRT_OK;
+}
+
+int rrt_launch_projection_map(void* d_dir_rgba32f, int width, int height, const rrt_projection* proj, const rrt_camera* cam,
+                              void* stream) {
+    const int rc = check_projection(proj);
+    if (rc) return rc;
+    if (!d_dir_rgba32f || !cam || width <= 0 || height <= 0 || (long long)width * height >= (1ll << 31)) return RRT_ERR_INVALID_ARGUMENT;
+    if (reinterpret_cast<uintptr_t>(d_dir_rgba32f) & 15) return RRT_ERR_INVALID_ARGUMENT;
+    const long long n = (long long)width * height;
+    hipLaunchKernelGGL(projection_map, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<float4*>(d_dir_rgba32f), width, height, *cam, proj_args(*proj));
+    RRT_HIP(hipGetLastError());
+    return RRT_OK;
+}
+
+int rrt_launch_raymarch_pano(void* d_out_rgba8, float* d_hdr_rgba32f, int width, int height, int samples_per_axis,
+                             const rrt_projection* proj, float time, const rrt_camera* cam, rrt_sky_t sky, const rrt_effects* fx,
+                             const rrt_params* prm, void* stream) {
+    const int rc = check_pano(d_out_rgba8, width, height, samples_per_axis, proj, cam, fx, prm);
+    if (rc) return rc;
+    return launch_pano(d_out_rgba8, reinterpret_cast<float4*>(d_hdr_rgba32f), width, height, samples_per_axis,
+                       RowMap{height, 0, height, 0, 1, nullptr}, *proj, time, cam, sky, fx, prm, static_cast<hipStream_t>(stream));
+}
+
+int rrt_launch_raymarch_pano_tiles(void* d_out_tiles, int width, int height, int samples_per_axis, int tile_rows, int shard,
+                                   int n_shards, const rrt_projection* proj, float time, const rrt_camera* cam, rrt_sky_t sky,
+                                   const rrt_effects* fx, const rrt_params* prm, void* stream) {
+    const int rc = check_pano(d_out_tiles, width, height, samples_per_axis, proj, cam, fx, prm);
+    if (rc) return rc;
+    if (tile_rows <= 0 || n_shards <= 0 || shard < 0 || shard >= n_shards) return RRT_ERR_INVALID_ARGUMENT;
+    return launch_pano(d_out_tiles, nullptr, width, height, samples_per_axis,
+                       RowMap{shard_rows(height, tile_rows, shard, n_shards), 0, tile_rows, shard, n_shards, nullptr}, *proj, time,
+                       cam, sky, fx, prm, static_cast<hipStream_t>(stream));
 }
 
 #ifdef RRT_TEST_HOOKS

@@ -791,6 +791,61 @@ void motion_pixels(const MotionLaunch L) {
     if (hdr_out) hdr_out[oi] = make_float4(c.x, c.y, c.z, 1.0f);
 }
 
+/* Panorama (rrt_launch_raymarch_pano, include/rrt.h has the contract): supersample_pixels with the projection's primary ray
+ * (rrt_projection.h: projection_dir, the source the host query runs too) instead of primary_ray -- the same waves over the virtual
+ * grid, march, shading and pixel_sum butterfly.  The host clears use_lens and use_vignette (both are defined on the pinhole's uv).
+ * A fisheye sub-sample outside the disc stays in its lanes -- pixel_sum shuffles across all of a pixel's lanes -- but branches
+ * around the march and the shading with HDR exactly 0: its lane is masked off, so it adds no trips to the wave's vacuum loop and
+ * takes no part in its ballots. */
+#include "rrt_projection.h"
+template <bool SPIN, int MEDIA, int ARITH>
+__global__ __launch_bounds__(kWGThreads, (MEDIA != 0 ? RRT_MEDIA_WAVES : 1))      /* raymarch_pixels' register budget */
+void panorama_pixels(const FrameArgs a, const int s, float4* const hdr_out, const ProjArgs pj) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int vx = tile_column(a) * kWGPixX + (wave & 1) * kTileW + (lane & (kTileW - 1));      /* virtual column */
+    const int vlr = row_block(a) * kWGPixY + (wave >> 1) * kTileH + lane / kTileW;              /* virtual local row */
+    const int w = a.width / s, h = a.height / s;
+    const int x = vx / s;
+    int y, out_row;
+    if (x >= w || !map_row(a.rows, h, vlr / s, y, out_row)) return;
+    const int vy = s * y + (vlr - (vlr / s) * s);
+    float d[3];
+    v3 c = mk(0.f, 0.f, 0.f);
+    if (projection_dir(pj, a.width, a.height, vx, vy, a.cam, d)) {
+        v3 p = mk(a.cam.pos[0], a.cam.pos[1], a.cam.pos[2]);
+        v3 vel = mk(d[0], d[1], d[2]);
+        if (__builtin_expect(a.nudge_ulps != 0, 0)) {     /* as primary_ray, on the virtual pixel */
+            vel.x = nudge_component(vel.x, a.nudge_ulps, a.nudge_seed, vx, vy, 0u);
+            vel.y = nudge_component(vel.y, a.nudge_ulps, a.nudge_seed, vx, vy, 1u);
+            vel.z = nudge_component(vel.z, a.nudge_ulps, a.nudge_seed, vx, vy, 2u);
+        }
+        Radiance acc = {0.f, 0.f, 0.f, 1.0f};
+        bool hit = false;
+        int i = 0;
+        march_inline<SPIN, MEDIA, ARITH, true>(a, p, vel, acc, hit, i, nullptr);
+        c = shade_hdr(a, 0.f, 0.f, hit, vel, acc);
+    }
+    pixel_sum(c, s);
+    if (((vx | vlr) & (s - 1)) != 0) return;            /* the pixel's first lane stores */
+    const float inv = 1.0f / (float)(s * s);            /* a power of two: the mean is exact given the sum */
+    c = mk(c.x * inv, c.y * inv, c.z * inv);
+    float out_r, out_g, out_b;
+    tone_map(c, out_r, out_g, out_b);
+    const size_t oi = (size_t)out_row * w + x;
+    store_rgba8(a.out, oi, out_r, out_g, out_b);
+    if (hdr_out) hdr_out[oi] = make_float4(c.x, c.y, c.z, 1.0f);
+}
+
+/* rrt_launch_projection_map: projection_dir of every pixel, (dir, inside) in the frame's bottom-up layout */
+__global__ __launch_bounds__(256) void projection_map(float4* out, int W, int H, const rrt_camera cam, const ProjArgs pj) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)W * H) return;
+    const int y = (int)(i / W), x = (int)(i - (long long)y * W);
+    float d[3];
+    const bool inside = projection_dir(pj, W, H, x, y, cam, d);
+    out[(size_t)(H - 1 - y) * W + x] = make_float4(d[0], d[1], d[2], inside ? 1.0f : 0.0f);
+}
+
 /* ---- three-pass path, pass 1: geodesics only; sample points of in-medium steps go to the pool ---- */
 /* amdgpu_num_sgpr(80): gfx950 admits 8 waves per SIMD only up to 80 SGPRs (7 for 82-96); this loop needs
  * the occupancy (measured: 4 waves/SIMD is 15 % slower than 8).

@@ -3,6 +3,7 @@
     python -m relativisticraytracer_amd.headless --width 1920 --height 1080 --spin 0.9 \\
            --path 0 --frames 300 [--out frames.rgba | --out ppm_dir/] [--all-effects] [--supersample 2] [--motion-blur 4 --shutter 0.5]
            [--glow 0.25 [--glow-radius 0.004] [--glow-threshold 1.0] [--glow-lobes 4]]
+           [--projection pinhole|equirect|fisheye [--fov DEG] [--vfov DEG]]
     python -m torch.distributed.run --nproc-per-node 8 -m relativisticraytracer_amd.headless ...
 
 Per frame k = 1..N it does what `main()` does while recording: advance the fixed 1/24 s clock
@@ -65,6 +66,13 @@ def main(argv=None):
     ap.add_argument("--glow-radius", type=float, default=0.004, help="with --glow: the first lobe's sigma as a fraction of the height")
     ap.add_argument("--glow-threshold", type=float, default=1.0, help="with --glow: the bright pass' luma threshold (a soft knee)")
     ap.add_argument("--glow-lobes", type=int, choices=(1, 2, 3, 4), default=4, help="with --glow: Gaussian lobes, each twice as wide")
+    ap.add_argument("--projection", choices=("pinhole", "equirect", "fisheye"), default="pinhole",
+                    help="the camera: pinhole (the reference's), equirect (360-degree panorama) or fisheye (angular dome master), "
+                         "rrt_launch_raymarch_pano*.  A panorama always renders with the single kernel in the static order; not with "
+                         "--motion-blur > 1, and an equirect frame not with --glow (the glow does not wrap at the seam)")
+    ap.add_argument("--fov", type=float, default=None, metavar="DEG",
+                    help="equirect: horizontal span in (0, 360], default 360; fisheye: aperture in (0, 360], default 180")
+    ap.add_argument("--vfov", type=float, default=None, metavar="DEG", help="equirect: vertical span in (0, 180], default 180")
     ap.add_argument("--out", default=None, help="x.rgba (raw, bottom-up) | dir/ (PPM per frame) | x.mp4 (needs ffmpeg)")
     ap.add_argument("--init-timeout", type=float, default=300.0,
                     help="several ranks: seconds the process-group bring-up may take before the run exits non-zero with "
@@ -76,6 +84,15 @@ def main(argv=None):
     # the glow needs the whole frame's HDR on one GPU (no _tiles form); checked before any device is touched
     if args.glow is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         ap.error("--glow: one GPU only (WORLD_SIZE > 1)")
+    pano = args.projection != "pinhole"
+    if not pano and (args.fov is not None or args.vfov is not None):
+        ap.error("--fov / --vfov need --projection equirect | fisheye")
+    if args.projection == "fisheye" and args.vfov is not None:
+        ap.error("--vfov: equirect only (a fisheye's aperture is --fov)")
+    if pano and args.motion_blur > 1:
+        ap.error("a panorama renders one instant per frame (--motion-blur 1)")
+    if args.projection == "equirect" and args.glow is not None:
+        ap.error("--glow clamps at the frame's edge and an equirect frame wraps: not with --projection equirect")
 
     t_start = time.perf_counter()
 
@@ -95,6 +112,13 @@ def main(argv=None):
     import relativisticraytracer_amd as rrt
     from relativisticraytracer_amd import camera_paths, sharding, sinks
     from relativisticraytracer_amd.sky import load_sky, synthetic_sky
+    proj = None
+    if pano:                        # the spans' checks are the host query's (rrt_projection_ray): the launch's own refusals
+        proj = rrt.Projection(args.projection, args.fov, args.vfov)
+        try:
+            rrt.projection_ray(proj, 1, 1, 0, 0, rrt.CameraState())
+        except rrt.RRTError:
+            ap.error("--fov DEG in (0, 360], --vfov DEG in (0, 180]")
     glow = None
     if args.glow is not None:       # the settings' checks are host arithmetic (rrt_glow_scratch_bytes)
         glow = rrt.GlowSettings(radius=args.glow_radius, lobes=args.glow_lobes, threshold=args.glow_threshold, intensity=args.glow)
@@ -127,7 +151,7 @@ def main(argv=None):
     trace("process group ready" if world > 1 else "single rank")
     w, h = args.width, args.height
     ss, mb = args.supersample, args.motion_blur
-    single = ss > 1 or mb > 1 or glow is not None    # a supersampled, blurred or glowed launch: the single kernel, static order, no pool
+    single = ss > 1 or mb > 1 or glow is not None or pano   # supersampled, blurred, glowed, panorama: single kernel, static order, no pool
     tex = rrt.SkyTexture(load_sky(args.sky) if args.sky else synthetic_sky())
     fx = rrt.CameraEffects(useChromaticAberration=bool(args.all_effects))
     # with several ranks --frames-in-flight frames are in flight (FrameSharder pipeline mode), each with its own
@@ -172,7 +196,9 @@ def main(argv=None):
     def render_glowed():
         """the frame through _ss / _mb into glow_hdr, then the glow into glow_frame (bottom-up rows, not the tile layout)"""
         prms[0].noise_table = state["table"]
-        if mb > 1:
+        if pano:
+            rrt.launch_raymarch_pano(glow_frame, w, h, ss, proj, state["t"], state["cam"], tex, fx, prms[0], hdr=glow_hdr)
+        elif mb > 1:
             rrt.launch_raymarch_mb(glow_frame, w, h, ss, state["times"], state["cams"], tex, fx, prms[0], hdr=glow_hdr)
         else:
             rrt.launch_raymarch_ss(glow_frame, w, h, ss, state["t"], state["cam"], tex, fx, prms[0], hdr=glow_hdr)
@@ -184,7 +210,9 @@ def main(argv=None):
         k = state["k"]
         if chooser is not None:
             prms[slot].path_policy = chooser.policy(k)
-        if mb > 1:
+        if pano:
+            rrt.launch_raymarch_pano_tiles(buf, w, h, ss, args.tile_rows, rank, world, proj, state["t"], state["cam"], tex, fx, prms[slot])
+        elif mb > 1:
             rrt.launch_raymarch_mb_tiles(buf, w, h, ss, args.tile_rows, rank, world, state["times"], state["cams"], tex, fx, prms[slot])
         elif ss > 1:
             rrt.launch_raymarch_ss_tiles(buf, w, h, ss, args.tile_rows, rank, world, state["t"], state["cam"], tex, fx, prms[slot])
@@ -259,7 +287,9 @@ def main(argv=None):
                           "path_choice": chooser.stats() if chooser else None,
                           "noise_tables": nwin.summary(),
                           "tile_order": orders[0].info() if orders else None, "supersample": ss,
-                          "motion_blur": mb, "shutter": args.shutter, "glow": glow.info() if glow is not None else None}),
+                          "motion_blur": mb, "shutter": args.shutter, "glow": glow.info() if glow is not None else None,
+                          "projection": args.projection, "fov_deg": proj.fov_deg if pano else None,
+                          "vfov_deg": proj.vfov_deg if args.projection == "equirect" else None}),
               flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -1,0 +1,261 @@
+"""Panoramas (rrt_launch_raymarch_pano*, include/rrt.h) on the GPU against their definition.  The device's primary rays equal the
+host query's bit for bit; every panorama pixel's march is tied to the already-pinned pinhole path (a 2x2 pinhole frame whose centre
+pixel looks exactly along the panorama pixel's D gives its HDR bit for bit); the s x s frame is the documented tree over the 1x
+panorama of (s w) x (s h); the identities, tiles, streams, graphs and both drivers.  torch is only the device-memory plumbing."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import projection_ref as pr
+from conftest import same_bits
+from test_gpu_supersample import expected_mean, tone_map
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+FRAMES = [(pr.EQUIRECT, 360.0, 180.0, 64, 32), (pr.EQUIRECT, 180.0, 90.0, 64, 32), (pr.EQUIRECT, 360.0, 180.0, 37, 19),
+          (pr.FISHEYE, 180.0, 0.0, 48, 48), (pr.FISHEYE, 220.0, 0.0, 48, 48), (pr.FISHEYE, 180.0, 0.0, 33, 27),
+          (pr.PINHOLE, 0.0, 0.0, 40, 23)]
+
+
+@pytest.fixture(scope="module")
+def ctx(sky):
+    import torch
+    assert torch.cuda.is_available(), "the -m gpu tests need a GPU"
+    import relativisticraytracer_amd as rrt
+    tex = rrt.SkyTexture(sky)
+    yield rrt, tex
+    tex.destroy()
+
+
+def _zeros(n, dtype):
+    import torch
+    return torch.zeros(n, dtype=dtype, device="cuda")
+
+
+def _host(t, shape):
+    import torch
+    torch.cuda.synchronize()
+    return t.cpu().numpy().reshape(shape)
+
+
+def cameras(rrt):
+    from relativisticraytracer_amd import camera_paths as cp
+    return [rrt.CameraState.default(), rrt.CameraState.from_angles((12.0, -3.0, 40.0), 137.0, 21.5), cp.CameraPath(0).camera_at(3.7)]
+
+
+def all_fx(rrt, vignette_lens=True):
+    return rrt.CameraEffects(useBloom=True, useChromaticAberration=True, caAmount=0.004, useVignette=vignette_lens,
+                             useLensDistortion=vignette_lens)
+
+
+def render_pano(rrt, tex, w, h, s, proj, t, cam, fx, prm, stream=None):
+    """(rgba8, hdr), both (h, w, 4) bottom-up"""
+    import torch
+    out, hdr = _zeros(h * w * 4, torch.uint8), _zeros(h * w * 4, torch.float32)
+    rrt.launch_raymarch_pano(out, w, h, s, proj, t, cam, tex, fx, prm, stream=stream, hdr=hdr)
+    return _host(out, (h, w, 4)), _host(hdr, (h, w, 4))
+
+
+def test_device_directions_equal_the_host_query(ctx):
+    """rrt_launch_projection_map (projection_dir on the GPU, the kernel's source) == rrt_projection_ray on the host, every pixel, bit
+    for bit, in the frame's bottom-up layout"""
+    import torch
+    rrt, _ = ctx
+    for kind, fov, vfov, W, H in FRAMES:
+        p = rrt.Projection(kind, fov, vfov)
+        for cam in cameras(rrt):
+            d = torch.full((W * H * 4,), -7.0, dtype=torch.float32, device="cuda")
+            rrt.launch_projection_map(d, W, H, p, cam)
+            got = _host(d, (H, W, 4))[::-1]                              # stored rows are bottom-up
+            want = np.zeros((H, W, 4), np.float32)
+            for j in range(H):
+                for i in range(W):
+                    want[j, i, :3], inside = rrt.projection_ray(p, W, H, i, j, cam)
+                    want[j, i, 3] = 1.0 if inside else 0.0
+            assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (kind, fov, W, H, int((got != want).any(-1).sum()))
+            assert (kind != pr.FISHEYE) == bool(want[..., 3].all())
+
+
+def _probe_hdr(rrt, tex, t, pos, cam, forwards, fx, prm):
+    """the post-FX HDR of pixel (1, 1) of a 2x2 pinhole frame looking along each of `forwards` (from `pos`, cam's right and up):
+    u = v = 0 there, so its ray is exactly normalize(forward).  All launches first, one synchronisation."""
+    import torch
+    n = len(forwards)
+    out, hdr = _zeros(n * 16, torch.uint8), _zeros(n * 16, torch.float32)
+    a = cam.as_array()
+    for k, f in enumerate(forwards):
+        c = rrt.CameraState(pos, f, a[2], a[3])
+        rrt.launch_raymarch_debug(out.data_ptr() + 16 * k, 2, 2, t, c, tex, fx, prm, hdr=hdr.data_ptr() + 64 * k)
+    return _host(hdr, (n, 2, 2, 4))[:, 0, 1, :3]        # image row 1 is stored row 0 (bottom-up)
+
+
+def test_every_pixel_marches_the_pinned_pinhole_path(ctx, po):
+    """256 random inside pixels per configuration (both kinds) of 1x panoramas: their HDR == the pinhole probe's along the restated
+    D, bit for bit -- spin 0 and 0.9, volumetrics on, strict and FMAD, bloom and CA on (vignette and lens on in the panorama, where
+    they are ignored, off in the probe).  With a nudge, the probe looks along the restated nudged direction (pixels where the
+    pinhole's normalize leaves it unchanged)."""
+    rrt, tex = ctx
+    rng = np.random.default_rng(20261016)
+    cams = cameras(rrt)
+    views = [(rrt.Projection("equirect"), 96, 48, cams[0]), (rrt.Projection("fisheye", 220.0), 64, 64, cams[2])]
+    configs = [(0.0, 0, 0), (0.9, 0, 0), (0.0, 2, 0), (0.9, 2, 0), (0.9, 0, 3), (0.9, 2, 3)]      # (spin, arith, nudge_ulps)
+    t = 1.0
+    for spin, arith, nudge in configs:
+        prm = rrt.RenderParams(spin=spin, arith_mode=arith, nudge_ulps=nudge, nudge_seed=5)
+        probe_prm = rrt.RenderParams(spin=spin, arith_mode=arith)
+        for proj, W, H, cam in views:
+            _, hdr = render_pano(rrt, tex, W, H, 1, proj, t, cam, all_fx(rrt), prm)
+            D, inside = pr.d_vector(po, proj.kind, proj.fov_deg, proj.vfov_deg, W, H, *np.meshgrid(np.arange(W), np.arange(H)),
+                                    cam.as_array())
+            look = D
+            ok = inside & np.all(D != 0, axis=-1)
+            if nudge:
+                ys, xs = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
+                look = pr.nudge(pr.normalize(D), nudge, 5, xs, ys)
+                ok &= np.all(pr.normalize(look).view(np.uint32) == look.view(np.uint32), axis=-1) & np.all(look != 0, axis=-1)
+            cand = np.argwhere(ok)
+            assert len(cand) >= 128, (proj.info(), len(cand))
+            pick = cand[rng.choice(len(cand), 128, replace=False)]
+            want = _probe_hdr(rrt, tex, t, cam.as_array()[0], cam, [look[y, x] for y, x in pick], all_fx(rrt, False), probe_prm)
+            got = np.stack([hdr[H - 1 - y, x, :3] for y, x in pick])
+            bad = ~((got.view(np.uint32) == want.view(np.uint32)) | ((got == 0) & (want == 0))).all(-1)
+            assert not bad.any(), (proj.info(), spin, arith, nudge, int(bad.sum()), pick[bad][:4].tolist())
+            assert np.ptp(got) > 0.05, proj.info()                       # a real picture: disk, shadow and sky among the pixels
+
+
+@pytest.mark.parametrize("kind", ["equirect", "fisheye"])
+def test_supersampled_panorama_is_the_tree_over_the_big_panorama(ctx, po, kind):
+    """pano(w, h, s) HDR == the documented tree over pano(s w, s h, 1) HDR, its bytes the portable tone map of that; s = 2 and 4.
+    Fisheye sub-samples outside the disc are exactly 0 in the 1x frame."""
+    rrt, tex = ctx
+    proj = rrt.Projection(kind)
+    w, h = (33, 17) if kind == "equirect" else (25, 25)
+    cam = cameras(rrt)[2]
+    for s, arith in ((2, 0), (4, 2)):
+        prm = rrt.RenderParams(spin=0.9, arith_mode=arith)
+        _, big = render_pano(rrt, tex, s * w, s * h, 1, proj, 1.0, cam, all_fx(rrt), prm)
+        got8, got = render_pano(rrt, tex, w, h, s, proj, 1.0, cam, all_fx(rrt), prm)
+        if kind == "fisheye":
+            _, inside = pr.directions(po, pr.FISHEYE, 180.0, 0.0, s * w, s * h, cam.as_array())
+            outside = ~inside[::-1]                                       # stored rows are bottom-up
+            assert outside.any() and not big[outside][:, :3].any() and big[~outside][:, :3].any()
+        mean = expected_mean(big, w, h, s)
+        assert same_bits(got[..., :3], mean), (kind, s, int((got[..., :3] != mean).sum()))
+        assert np.all(got[..., 3] == 1.0)
+        assert np.array_equal(got8, tone_map(po, mean)), (kind, s)
+
+
+def test_identities(ctx):
+    """pinhole == rrt_launch_raymarch_ss; vignette and lens change nothing; a noise table gives the arithmetic hashing's bytes"""
+    import torch
+    rrt, tex = ctx
+    cam = rrt.CameraState.default()
+    for s in (1, 2):
+        prm = rrt.RenderParams(spin=0.9, arith_mode=2)
+        fx = all_fx(rrt)
+        out, hdr = _zeros(54 * 96 * 4, torch.uint8), _zeros(54 * 96 * 4, torch.float32)
+        rrt.launch_raymarch_ss(out, 96, 54, s, 1.0, cam, tex, fx, prm, hdr=hdr)
+        got8, got = render_pano(rrt, tex, 96, 54, s, rrt.Projection("pinhole"), 1.0, cam, fx, prm)
+        assert np.array_equal(got8, _host(out, (54, 96, 4))) and same_bits(got, _host(hdr, (54, 96, 4))), s
+    nt = rrt.NoiseTable(4.0)
+    try:
+        for kind, w, h in (("equirect", 96, 48), ("fisheye", 64, 64)):
+            proj = rrt.Projection(kind)
+            for arith in (0, 2):
+                prm = rrt.RenderParams(spin=0.9, arith_mode=arith)
+                ref8, ref = render_pano(rrt, tex, w, h, 2, proj, 1.0, cam, all_fx(rrt), prm)
+                assert ref8[..., :3].std() > 5.0, kind
+                for fx in (all_fx(rrt, False), rrt.CameraEffects(useBloom=True, useChromaticAberration=True, caAmount=0.004,
+                                                                 useVignette=True, vignetteIntensity=0.9, useLensDistortion=True,
+                                                                 distortionAmount=0.3)):
+                    got8, got = render_pano(rrt, tex, w, h, 2, proj, 1.0, cam, fx, prm)
+                    assert np.array_equal(got8, ref8) and same_bits(got, ref), (kind, arith)
+                tprm = rrt.RenderParams(spin=0.9, arith_mode=arith, noise_table=nt.id)
+                got8, got = render_pano(rrt, tex, w, h, 2, proj, 1.0, cam, all_fx(rrt), tprm)
+                assert np.array_equal(got8, ref8) and same_bits(got, ref), (kind, arith, "table")
+    finally:
+        nt.destroy()
+
+
+def test_tile_shards_assemble_to_the_full_panorama(ctx):
+    import torch
+    rrt, tex = ctx
+    cam = rrt.CameraState.default()
+    fx, prm = all_fx(rrt), rrt.RenderParams(spin=0.9)
+    for kind, w, h in (("equirect", 77, 39), ("fisheye", 45, 45)):
+        proj = rrt.Projection(kind)
+        for s, n, tr in ((1, 3, 16), (2, 3, 5)):
+            full, _ = render_pano(rrt, tex, w, h, s, proj, 1.0, cam, fx, prm)
+            rows = [rrt.tile_shard_rows(h, tr, k, n) for k in range(n)]
+            stride = ((max(rows) * w * 4) + 255) & ~255
+            tiles = _zeros(stride * n, torch.uint8)
+            for k in range(n):
+                rrt.launch_raymarch_pano_tiles(tiles.data_ptr() + k * stride, w, h, s, tr, k, n, proj, 1.0, cam, tex, fx, prm)
+            frame = _zeros(h * w * 4, torch.uint8)
+            rrt.assemble_all_tiles(frame, tiles, stride, w, h, tr, n)
+            assert np.array_equal(_host(frame, (h, w, 4)), full), (kind, s, n, tr)
+
+
+def test_graph_capture_and_side_stream(ctx):
+    """no memset, no synchronisation: a launch runs on a side stream and can be captured into a graph and replayed"""
+    import torch
+    rrt, tex = ctx
+    w, h = 64, 32
+    cam, fx, prm = rrt.CameraState.default(), all_fx(rrt), rrt.RenderParams(spin=0.9)
+    for kind in ("equirect", "fisheye"):
+        proj = rrt.Projection(kind)
+        ref8, ref = render_pano(rrt, tex, w, h, 2, proj, 1.0, cam, fx, prm)
+        side = torch.cuda.Stream()
+        got8, got = render_pano(rrt, tex, w, h, 2, proj, 1.0, cam, fx, prm, stream=side)
+        side.synchronize()
+        assert np.array_equal(got8, ref8) and same_bits(got, ref), kind
+        b, bh = _zeros(h * w * 4, torch.uint8), _zeros(h * w * 4, torch.float32)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            rrt.launch_raymarch_pano(b, w, h, 2, proj, 1.0, cam, tex, fx, prm, hdr=bh)
+        for _ in range(2):
+            b.zero_()
+            bh.zero_()
+            graph.replay()
+            assert np.array_equal(_host(b, (h, w, 4)), ref8) and same_bits(_host(bh, (h, w, 4)), ref), kind
+
+
+@pytest.mark.parametrize("extra", [["--projection", "equirect"], ["--projection", "fisheye", "--supersample", "2"],
+                                   ["--projection", "fisheye", "--fov", "200", "--glow", "0.25"]], ids=lambda e: "_".join(e))
+def test_drivers_write_the_panoramas(ctx, tmp_path, extra):
+    """rrt_headless and headless.py write the same file, whose frames are launch_raymarch_pano's with the driver's cameras and clock"""
+    import torch
+    from relativisticraytracer_amd import build
+    from relativisticraytracer_amd import camera_paths as cp
+    rrt, tex = ctx
+    exe = build.build_headless()
+    w, h = (96, 48) if extra[1] == "equirect" else (64, 64)
+    a, b = tmp_path / "cpp.rgba", tmp_path / "py.rgba"
+    args = ["--width", str(w), "--height", str(h), "--frames", "3", "--path", "0", "--spin", "0.9", "--all-effects"] + extra
+    r = subprocess.run([exe] + args + ["--out", str(a)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    meta_c = json.loads(r.stdout.strip().splitlines()[-1])
+    r = subprocess.run([sys.executable, "-m", "relativisticraytracer_amd.headless"] + args + ["--out", str(b)], cwd=ROOT,
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    meta_p = json.loads(r.stdout.strip().splitlines()[-1])
+    for m in (meta_c, meta_p):
+        assert m["projection"] == extra[1] and m["fov_deg"] == (200.0 if "--fov" in extra else rrt.Projection(extra[1]).fov_deg)
+        assert m["vfov_deg"] == (180.0 if extra[1] == "equirect" else None)
+    assert open(a, "rb").read() == open(b, "rb").read()
+    if "--glow" in extra:
+        return
+    data = np.fromfile(a, np.uint8).reshape(3, h, w, 4)
+    s = 2 if "--supersample" in extra else 1
+    path, proj = cp.CameraPath(0), rrt.Projection(extra[1])
+    fx = rrt.CameraEffects(useChromaticAberration=True)
+    for k in (1, 2, 3):
+        st, pt = cp.recording_clock(k)
+        buf = _zeros(h * w * 4, torch.uint8)
+        rrt.launch_raymarch_pano(buf, w, h, s, proj, st, path.camera_at(pt), tex, fx, rrt.RenderParams(spin=0.9))
+        assert np.array_equal(_host(buf, (h, w, 4)), data[k - 1]), k
