@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the geodesic ray-march hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A "step" is one full frame of the BASELINE.json workload: 3840x2160, Kerr a = 0.9,
 full volumetric disk + dust + Doppler/redshift, the reference's start-up camera
@@ -11,6 +11,9 @@ rank per GPU) the SAME frame is split into interleaved 16-row tiles across the r
 and assembled on rank 0 by one RCCL gather: strong scaling.
 
 Rank 0 prints one JSON line.  `value` = Mrays/s (= Mpixels/s) of the whole job, strict arithmetic.
+A plain run does only what that figure needs: set-up, warm-up, the K timed steps, --dump-outputs, the line
+(headline keys and `config`).  --full adds everything else the benchmark measures or checks, each in the
+same run after the timed steps, and the line carries it:
 `roofline` prices the dominant kernel (raymarch_pixels) against the FP32 vector-ALU
 issue rate, which is what bounds it, with every timed frame's kernel time,
 the clock the chip held, the PMC view (issue-slot utilisation, HBM traffic: only from records
@@ -18,7 +21,9 @@ measured on this build's sources); the HBM view that the north star asks for is 
 alongside.  `cpu_baseline` is the reference's own kernel body (OpenMP, all host cores; the
 oracle port beside it) on a strided sample of the same frame, on every N -- a reported
 baseline, not a target.  `within_tolerance_mode` = RRT_ARITH_FMAD (the arithmetic class of the
-reference's own build) with its account; never `value`.
+reference's own build) with its account; never `value`.  Also `headline_arithmetic_noise`,
+`projection_8_ranks`, `heavy_view` (one GPU) and `multi_gpu` (N > 1).  --no-fast, --no-heavy and
+--cpu-stride choose among these legs.
 
 --dump-outputs DIR writes the frame of the last timed step (rank 0's assembled RGBA8 frame) as a fixed
 seeded sample of its pixels (dump_frame), so that two builds can be compared output for output.
@@ -206,11 +211,15 @@ def main():
     ap.add_argument("--height", type=int, default=2160)
     ap.add_argument("--spin", type=float, default=0.9)
     ap.add_argument("--tile-rows", type=int, default=16)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other leg (roofline, CPU baseline, other arithmetic modes, noise "
+                         "without tables, heavy view, 8-rank projection; N > 1: phases, frames one at a time, single-GPU reference) "
+                         "and report them in the line")
     ap.add_argument("--cpu-stride", type=int, default=-1,
-                    help="CPU baseline sample stride: -1 (default) = sized so that the leg runs ~12 s on this host, 0 = skip")
-    ap.add_argument("--no-fast", action="store_true", help="skip the within-tolerance arithmetic modes (RRT_ARITH_FMAD / _FAST) and their account")
+                    help="--full: CPU baseline sample stride: -1 (default) = sized so that the leg runs ~12 s on this host, 0 = skip")
+    ap.add_argument("--no-fast", action="store_true", help="--full: skip the within-tolerance arithmetic modes (RRT_ARITH_FMAD / _FAST) and their account")
     ap.add_argument("--no-noise-table", action="store_true", help="hash every noise3D corner arithmetically (no lattice tables)")
-    ap.add_argument("--no-heavy", action="store_true", help="skip the informational heavy-view leg")
+    ap.add_argument("--no-heavy", action="store_true", help="--full: skip the informational heavy-view and projection legs")
     ap.add_argument("--frames-in-flight", type=int, default=3,
                     help="N > 1: frames rendered / gathered / assembled concurrently per rank (>= 2; 1 = no pipelining)")
     ap.add_argument("--workspace-gib", type=int, default=16,
@@ -388,7 +397,8 @@ def main():
     # reads the shader-clock counter (s_memtime) and the constant 100 MHz counter (s_memrealtime) at both ends -- runs on a
     # second stream BESIDE the timed frames, for about three quarters of their expected duration (from the warm-up frames'
     # kernel times, so that it has ended before they have; without warm-up frames it runs beside two extra frames afterwards).
-    # One sleeping wave of 8 192 slots does not move the measurement.
+    # One sleeping wave of 8 192 slots does not move the measurement.  It goes out in a plain run too, where nothing reads it, so
+    # that the K timed frames are the same launches with or without --full.
     clock_ghz, clock_when = None, None
     cbuf = torch.zeros(2, dtype=torch.int64, device=dev) if world == 1 else None
     side = torch.cuda.Stream() if world == 1 else None
@@ -417,7 +427,8 @@ def main():
     if args.dump_outputs and rank == 0:
         dump_frame(args.dump_outputs, fs.frame.cpu().numpy(), w, h)
 
-    if world == 1:
+    # Everything from here to the line is --full only: the headline needs none of it.
+    if world == 1 and args.full:
         if clock_when is None:                 # --warmup 0: beside two untimed frames of the same workload, afterwards
             est_ms = float(np.mean(kernel_ms)) if kernel_ms else 40.0
             side.wait_stream(torch.cuda.current_stream())
@@ -436,7 +447,7 @@ def main():
     #  - the same K frames ONE AT A TIME (no frames in flight): latency-bound strong scaling, reported next to the
     #    pipelined `value` (throughput with frames in flight, frames arrive n-1 steps late).
     phases, one_at_a_time = None, None
-    if world > 1:
+    if world > 1 and args.full:
         mine = fs.phase_times(skip=args.warmup) or {"render": 0.0, "gather": 0.0, "assemble": 0.0, "steps": 0}
         allp = [None] * world
         dist.all_gather_object(allp, {k: round(float(v), 4) for k, v in mine.items()})
@@ -482,7 +493,7 @@ def main():
     # be quoted against: rank 0 renders the whole frame alone with the single kernel, in the static order
     # and cost-ordered (rrt_tile_order), the other ranks wait at the barrier; best of the two is the reference.
     single_ref = None
-    if world > 1:
+    if world > 1 and args.full:
         if rank == 0:
             full = torch.zeros(h * w * 4, dtype=torch.uint8, device=dev)
             order = rrt.TileOrder()
@@ -510,7 +521,7 @@ def main():
     # by more than one LSB must be ILL-CONDITIONED -- a pixel the strict arithmetic itself moves out of the tolerance when its
     # primary direction is nudged by a few ulps.  `within_tolerance_mode` = the fastest mode whose account is clean.
     wtol = None
-    if world == 1 and not args.no_fast:
+    if world == 1 and args.full and not args.no_fast:
         from relativisticraytracer_amd import conditioning
         strict_frame = fs.frame.clone()
         buf = torch.zeros_like(strict_frame)
@@ -570,7 +581,7 @@ def main():
     # The headline frame WITHOUT the lattice-hash tables (every noise3D hashed arithmetically): the tables are a resident
     # input built outside the timed region, so the line carries the table-free time beside `value`.
     arith_noise = None
-    if world == 1 and ntab is not None:
+    if world == 1 and args.full and ntab is not None:
         prm_a = rrt.RenderParams(spin=args.spin, volumetrics=1)
         abuf = torch.zeros(h * w * 4, dtype=torch.uint8, device=dev)
         rrt.launch_raymarch(abuf, w, h, 1.0, cam, tex, fx, prm_a)
@@ -589,7 +600,7 @@ def main():
     # (camera_paths.cpp:62) from inside the disk, where media sampling is ~40 % of the work -- strict arithmetic,
     # with and without the noise tables.  The headline `value` is the BASELINE view above.
     heavy = None
-    if world == 1 and not args.no_heavy:
+    if world == 1 and args.full and not args.no_heavy:
         hcam = rrt.CameraState.from_angles((4.2, 0.6, 4.2), -90.0, -5.7)
         ht = 14.0
         hbuf = torch.zeros(h * w * 4, dtype=torch.uint8, device=dev)
@@ -641,7 +652,7 @@ def main():
     # three-pass path in one chain per launch, and the plain single kernel), sustained ms per frame; the slowest shard bounds the frame
     # rate.  Gather / assemble are not in it (4.15 MB per rank on another stream).  A projection, not a measurement of 8 GPUs.
     projection = None
-    if world == 1 and not args.no_heavy and ntab and h >= 8 * R:
+    if world == 1 and args.full and not args.no_heavy and ntab and h >= 8 * R:
         NP, slots = 8, 3
         p_pools = [rrt.Workspace(2 << 30) for _ in range(slots)]
         p_streams = [torch.cuda.Stream(dev) for _ in range(slots)]
@@ -678,99 +689,6 @@ def main():
         rays = w * h
         ms_per_step = dt / args.steps * 1e3
         value = rays * args.steps / dt / 1e6
-        k_ms = float(np.mean(kernel_ms))
-        k_note = "HIP-event kernel time"
-        # what the timed frames did, not only their mean: a slow box shows in min and median alike, a slow
-        # first frame in max / slowest_frame only.  No hidden warm-up: these are exactly the K timed frames.
-        k_stats = {"kernel_ms_min": round(float(np.min(kernel_ms)), 3), "kernel_ms_median": round(float(np.median(kernel_ms)), 3),
-                   "kernel_ms_max": round(float(np.max(kernel_ms)), 3), "kernel_ms_slowest_frame": int(np.argmax(kernel_ms)),
-                   "kernel_ms_per_frame": [round(float(v), 3) for v in kernel_ms]}
-        if fs.pipeline:
-            # several frames in flight: consecutive launches overlap on the device, so a launch's own start-to-end
-            # time is not its cost; price the rank's share against the whole step instead (gather included)
-            k_ms, k_note = ms_per_step, "step time (launches of consecutive frames overlap; gather included)"
-        my_rays = sharding.shard_rows(h, R, 0, world) * w
-
-        # The CPU leg runs on rank 0 for every N (north_star: "alongside a host-compiled OpenMP loop ... in the same run"); with
-        # N > 1 the other ranks wait at the barrier below, still under the RUN watchdog (not the 60 s shutdown one).
-        cpu, means = (None, None)
-        if args.cpu_stride != 0:
-            nthr = cpu_threads(world)
-            stride = args.cpu_stride if args.cpu_stride > 0 else cpu_sample_stride(w, h, args.spin, sky_np, nthr)
-            cpu, means = cpu_baseline(w, h, args.spin, stride, sky_np, nthreads=nthr)
-            if world > 1:
-                cpu["note"] = ("timed on rank 0 while the other %d ranks waited at a barrier; cores = the threads it actually ran on "
-                               "(all cores this process may use: the launcher's OMP_NUM_THREADS is per rank)" % (world - 1))
-        if means is None:   # per-ray work from a small oracle sample even when the baseline is skipped
-            _, means = cpu_baseline(w, h, args.spin, 48, sky_np)
-        opr = ops_per_ray(means["steps"], means["n_noise"], means["n_dens"], means["n_samples"])
-        tops = opr * my_rays / (k_ms * 1e-3) / 1e12
-        hbm_gbs = ALGO_BYTES_PER_RAY * my_rays / (k_ms * 1e-3) / 1e9
-        # HBM traffic per launch comes from rocprofv3 PMC passes (FETCH_SIZE / WRITE_SIZE, tools/profile_round.sh),
-        # which cannot run inside this process.  The record is only used when it was measured on THIS build
-        # (hash of the kernel sources) and workload; otherwise `traffic` is null rather than stale.
-        traffic, traffic_note = None, "not measured for this build: run tools/profile_round.sh + tools/summarize_profile.py"
-        tpath = os.path.join(ROOT, "profiles", "hbm_traffic.json")
-        if os.path.exists(tpath) and world == 1:
-            try:
-                tj = json.load(open(tpath))
-                if tj.get("workload") == f"{w}x{h}_a{args.spin:g}_vol" and tj.get("source_hash") == source_hash():
-                    traffic = tj.get("bytes_per_launch")
-                    traffic_note = "rocprofv3 PMC, " + str(tj.get("from", "profiles/"))
-                else:
-                    traffic_note = "profiles/hbm_traffic.json is from another build or workload; not used"
-            except Exception:
-                traffic = None
-        # The counter view of the same kernel (rocprofv3 PMC, tools/pass_counters.sh): SQ_INSTS_VALU x 2 clocks / (1024 SIMDs x busy
-        # clocks) -- the share of all VALU issue slots the kernel filled; quoted only if measured on THIS build's kernel sources.
-        issue_util, issue_note = None, "not measured for this build: run tools/final_set.sh + tools/summarize_pass_counters.py"
-        ppath0 = os.path.join(ROOT, "profiles", "pass_counters.json")
-        if os.path.exists(ppath0) and world == 1 and (w, h) == (3840, 2160):
-            try:
-                pj0 = json.load(open(ppath0))
-                if pj0.get("source_hash") == source_hash():
-                    k0 = pj0.get("runs", {}).get("default/single", {}).get("raymarch_pixels")
-                    if k0:
-                        issue_util = k0.get("issue_slot_util")
-                        issue_note = ("rocprofv3 PMC, " + str(pj0.get("from", "profiles/")) + ": SQ_INSTS_VALU %.4g per launch x 2 clocks / (1024 SIMDs x "
-                                      "GRBM_GUI_ACTIVE / 8), %.2f ms under the profiler" % (k0.get("valu_insts") or 0.0, k0.get("ms_per_frame") or 0.0))
-                else:
-                    issue_note = "profiles/pass_counters.json is from another build; not used"
-            except Exception:
-                issue_util = None
-        if heavy is not None and args.cpu_stride != 0:
-            # per-ray work of the heavy view from a small oracle sample (exact counts, like the headline's)
-            _, hm = cpu_baseline(w, h, args.spin, 96, sky_np, cam_arr=rrt.CameraState.from_angles((4.2, 0.6, 4.2), -90.0, -5.7).as_array(),
-                                 time_=14.0)
-            heavy["per_ray_means"] = {k: round(v, 2) for k, v in hm.items()}
-            heavy["ops_per_ray"] = round(ops_per_ray(hm["steps"], hm["n_noise"], hm["n_dens"], hm["n_samples"]), 1)
-            # counters of this view's kernels: issue-slot utilisation and HBM bytes from rocprofv3 PMC passes
-            # (tools/pass_counters.sh), quoted only if the record was measured on THIS build's kernel sources
-            pc_note = "not measured for this build: run tools/pass_counters.sh + tools/summarize_pass_counters.py"
-            pcs = {}
-            ppath = os.path.join(ROOT, "profiles", "pass_counters.json")
-            if os.path.exists(ppath):
-                try:
-                    pj = json.load(open(ppath))
-                    if pj.get("source_hash") == source_hash():
-                        pcs = pj.get("runs", {})
-                        pc_note = "rocprofv3 PMC, " + str(pj.get("from", "profiles/")) + "; " + str(pj.get("note", ""))
-                    else:
-                        pc_note = "profiles/pass_counters.json is from another build; not used"
-                except Exception:
-                    pcs = {}
-            for tag, run in (("arithmetic_noise", None), ("noise_table", "skimmer/single"), ("noise_table_cost_ordered", "skimmer/single_ordered"),
-                             ("noise_table_first_frame_probe_ordered", None)):
-                if tag in heavy:
-                    k = pcs.get(run, {}).get("raymarch_pixels") if run else None
-                    heavy[tag]["issue_slot_util"] = k.get("issue_slot_util") if k else None
-                    heavy[tag]["traffic_bytes"] = k.get("hbm_bytes_upper") if k else None
-                    heavy[tag]["source_ops_per_s_over_2p4ghz_peak"] = round(heavy["ops_per_ray"] * rays / (heavy[tag]["ms_per_step"] * 1e-3) / 1e12
-                                                                            / VALU_PEAK_TOPS, 4)
-            heavy["counters_note"] = pc_note + ("  (source_ops_per_s_over_2p4ghz_peak is a FORMULA -- SURVEY 8d's source operations, which price 223 per "
-                                                "noise3D that the tables replace by loads -- not a utilisation; it can exceed 1)")
-            if "skimmer/shard0of8" in pcs:
-                heavy["rank_share_three_pass_kernels"] = pcs["skimmer/shard0of8"]
         line = {
             "metric": "Mrays/s", "value": round(value, 3), "unit": "Mrays/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
@@ -787,43 +705,138 @@ def main():
                                        % (ntab.info()["bytes"] / 1e6, table_build_ms)) if ntab else "none (arithmetic hash)",
                        "dist_backend": (backend + (" (RCCL)" if backend == "nccl" else " (rehearsal: ranks share a card)")) if world > 1 else None,
                        "comm_ranks": dist.get_world_size() if world > 1 else 1},
-            "roofline": {"bound": "valu", "achieved": round(tops, 3), "peak": round(VALU_PEAK_TOPS, 2),
-                         "unit": "TFLOP/s", "frac": round(tops / VALU_PEAK_TOPS, 4), "traffic": traffic,
-                         "clock_ghz": round(clock_ghz, 4) if clock_ghz else None,
-                         "frac_at_held_clock": round(tops / (256 * 4 * 32 * clock_ghz * 1e9 / 1e12), 4) if clock_ghz else None,
-                         "clock_note": "shader clock held under this workload: s_memtime / s_memrealtime of a one-wave probe (rrt_clock_probe) "
-                                       "running " + str(clock_when) + "; `peak` prices 2.4 GHz, frac_at_held_clock the clock the chip actually ran at "
-                                       "(boxes of this pool hold 2.2-2.4 GHz); > 1 is possible: the peak counts one SOURCE operation per lane and clock "
-                                       "and the kernel needs 0.955 instructions per source operation",
-                         "traffic_note": traffic_note,
-                         "issue_slot_util": issue_util, "issue_slot_util_note": issue_note,
-                         "frac_of_fma_peak_157.3": round(tops / 157.3, 4),
-                         "kernel": "raymarch_pixels", "kernel_ms": round(k_ms, 3), **k_stats,
-                         "ops_per_ray": round(opr, 1), "per_ray_means": {k: round(v, 2) for k, v in means.items()},
-                         "note": "source-level unfused FP32 ops (SURVEY 8d formula) / " + k_note + "; "
-                                 "peak = 256CU x 4SIMD x 32 lanes x 2.4 GHz = one unfused FP32 op per lane per clock "
-                                 "(the datasheet's 157.3 TFLOP/s counts an FMA as two)",
-                         "hbm": {"bound": "hbm", "achieved": round(hbm_gbs, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                 "frac": round(hbm_gbs / HBM_PEAK_GBS, 6),
-                                 "note": "algorithmic 52 B/ray; the path is not HBM-bound"}},
-            "cpu_baseline": cpu,
-            "within_tolerance_mode": wtol,
-            "headline_arithmetic_noise": arith_noise,
-            "projection_8_ranks": projection,
-            "heavy_view": heavy,
         }
-        if world > 1:
-            best_single = min(single_ref["static_order_ms"], single_ref["cost_ordered_ms"])
-            line["multi_gpu"] = {"single_gpu_reference_ms": best_single, "single_gpu_reference": single_ref,
-                                 "speedup_vs_single_gpu_reference": round(best_single / ms_per_step, 3),
-                                 "single_gpu_reference_note": "the same frame on rank 0's GPU alone, single kernel, noise tables, best of static and "
-                                                              "cost-ordered dispatch, measured in this run while the other ranks waited",
-                                 "phases": phases, "one_frame_at_a_time": one_at_a_time,
-                                 "frames_in_flight": fs.n_slots,
-                                 "path_per_launch": path_tuning if fs.pipeline else "automatic (three-pass in two chains for a small share)",
-                                 "frames_in_flight_note": "default 3: chosen on ONE GPU rendering a single rank's share "
-                                                          "(profiles/r02_frames_in_flight.txt); provisional until a run on >= 2 GPUs"}
-        
+        if args.full:
+            k_ms = float(np.mean(kernel_ms))
+            k_note = "HIP-event kernel time"
+            # what the timed frames did, not only their mean: a slow GPU shows in min and median alike, a slow
+            # first frame in max / slowest_frame only.  No hidden warm-up: these are exactly the K timed frames.
+            k_stats = {"kernel_ms_min": round(float(np.min(kernel_ms)), 3), "kernel_ms_median": round(float(np.median(kernel_ms)), 3),
+                       "kernel_ms_max": round(float(np.max(kernel_ms)), 3), "kernel_ms_slowest_frame": int(np.argmax(kernel_ms)),
+                       "kernel_ms_per_frame": [round(float(v), 3) for v in kernel_ms]}
+            if fs.pipeline:
+                # several frames in flight: consecutive launches overlap on the device, so a launch's own start-to-end
+                # time is not its cost; price the rank's share against the whole step instead (gather included)
+                k_ms, k_note = ms_per_step, "step time (launches of consecutive frames overlap; gather included)"
+            my_rays = sharding.shard_rows(h, R, 0, world) * w
+
+            # The CPU leg runs on rank 0 for every N (north_star: "alongside a host-compiled OpenMP loop ... in the same run"); with
+            # N > 1 the other ranks wait at the barrier below, still under the RUN watchdog (not the 60 s shutdown one).
+            cpu, means = (None, None)
+            if args.cpu_stride != 0:
+                nthr = cpu_threads(world)
+                stride = args.cpu_stride if args.cpu_stride > 0 else cpu_sample_stride(w, h, args.spin, sky_np, nthr)
+                cpu, means = cpu_baseline(w, h, args.spin, stride, sky_np, nthreads=nthr)
+                if world > 1:
+                    cpu["note"] = ("timed on rank 0 while the other %d ranks waited at a barrier; cores = the threads it actually ran on "
+                                   "(all cores this process may use: the launcher's OMP_NUM_THREADS is per rank)" % (world - 1))
+            if means is None:   # per-ray work from a small oracle sample even when the baseline is skipped
+                _, means = cpu_baseline(w, h, args.spin, 48, sky_np)
+            opr = ops_per_ray(means["steps"], means["n_noise"], means["n_dens"], means["n_samples"])
+            tops = opr * my_rays / (k_ms * 1e-3) / 1e12
+            hbm_gbs = ALGO_BYTES_PER_RAY * my_rays / (k_ms * 1e-3) / 1e9
+            # HBM traffic per launch comes from rocprofv3 PMC passes (FETCH_SIZE / WRITE_SIZE, tools/profile_round.sh),
+            # which cannot run inside this process.  The record is only used when it was measured on THIS build
+            # (hash of the kernel sources) and workload; otherwise `traffic` is null rather than stale.
+            traffic, traffic_note = None, "not measured for this build: run tools/profile_round.sh + tools/summarize_profile.py"
+            tpath = os.path.join(ROOT, "profiles", "hbm_traffic.json")
+            if os.path.exists(tpath) and world == 1:
+                try:
+                    tj = json.load(open(tpath))
+                    if tj.get("workload") == f"{w}x{h}_a{args.spin:g}_vol" and tj.get("source_hash") == source_hash():
+                        traffic = tj.get("bytes_per_launch")
+                        traffic_note = "rocprofv3 PMC, " + str(tj.get("from", "profiles/"))
+                    else:
+                        traffic_note = "profiles/hbm_traffic.json is from another build or workload; not used"
+                except Exception:
+                    traffic = None
+            # The counter view of the same kernel (rocprofv3 PMC, tools/pass_counters.sh): SQ_INSTS_VALU x 2 clocks / (1024 SIMDs x busy
+            # clocks) -- the share of all VALU issue slots the kernel filled; quoted only if measured on THIS build's kernel sources.
+            issue_util, issue_note = None, "not measured for this build: run tools/final_set.sh + tools/summarize_pass_counters.py"
+            ppath0 = os.path.join(ROOT, "profiles", "pass_counters.json")
+            if os.path.exists(ppath0) and world == 1 and (w, h) == (3840, 2160):
+                try:
+                    pj0 = json.load(open(ppath0))
+                    if pj0.get("source_hash") == source_hash():
+                        k0 = pj0.get("runs", {}).get("default/single", {}).get("raymarch_pixels")
+                        if k0:
+                            issue_util = k0.get("issue_slot_util")
+                            issue_note = ("rocprofv3 PMC, " + str(pj0.get("from", "profiles/")) + ": SQ_INSTS_VALU %.4g per launch x 2 clocks / (1024 SIMDs x "
+                                          "GRBM_GUI_ACTIVE / 8), %.2f ms under the profiler" % (k0.get("valu_insts") or 0.0, k0.get("ms_per_frame") or 0.0))
+                    else:
+                        issue_note = "profiles/pass_counters.json is from another build; not used"
+                except Exception:
+                    issue_util = None
+            if heavy is not None and args.cpu_stride != 0:
+                # per-ray work of the heavy view from a small oracle sample (exact counts, like the headline's)
+                _, hm = cpu_baseline(w, h, args.spin, 96, sky_np, cam_arr=rrt.CameraState.from_angles((4.2, 0.6, 4.2), -90.0, -5.7).as_array(),
+                                     time_=14.0)
+                heavy["per_ray_means"] = {k: round(v, 2) for k, v in hm.items()}
+                heavy["ops_per_ray"] = round(ops_per_ray(hm["steps"], hm["n_noise"], hm["n_dens"], hm["n_samples"]), 1)
+                # counters of this view's kernels: issue-slot utilisation and HBM bytes from rocprofv3 PMC passes
+                # (tools/pass_counters.sh), quoted only if the record was measured on THIS build's kernel sources
+                pc_note = "not measured for this build: run tools/pass_counters.sh + tools/summarize_pass_counters.py"
+                pcs = {}
+                ppath = os.path.join(ROOT, "profiles", "pass_counters.json")
+                if os.path.exists(ppath):
+                    try:
+                        pj = json.load(open(ppath))
+                        if pj.get("source_hash") == source_hash():
+                            pcs = pj.get("runs", {})
+                            pc_note = "rocprofv3 PMC, " + str(pj.get("from", "profiles/")) + "; " + str(pj.get("note", ""))
+                        else:
+                            pc_note = "profiles/pass_counters.json is from another build; not used"
+                    except Exception:
+                        pcs = {}
+                for tag, run in (("arithmetic_noise", None), ("noise_table", "skimmer/single"), ("noise_table_cost_ordered", "skimmer/single_ordered"),
+                                 ("noise_table_first_frame_probe_ordered", None)):
+                    if tag in heavy:
+                        k = pcs.get(run, {}).get("raymarch_pixels") if run else None
+                        heavy[tag]["issue_slot_util"] = k.get("issue_slot_util") if k else None
+                        heavy[tag]["traffic_bytes"] = k.get("hbm_bytes_upper") if k else None
+                        heavy[tag]["source_ops_per_s_over_2p4ghz_peak"] = round(heavy["ops_per_ray"] * rays / (heavy[tag]["ms_per_step"] * 1e-3) / 1e12
+                                                                                / VALU_PEAK_TOPS, 4)
+                heavy["counters_note"] = pc_note + ("  (source_ops_per_s_over_2p4ghz_peak is a FORMULA -- SURVEY 8d's source operations, which price 223 per "
+                                                    "noise3D that the tables replace by loads -- not a utilisation; it can exceed 1)")
+                if "skimmer/shard0of8" in pcs:
+                    heavy["rank_share_three_pass_kernels"] = pcs["skimmer/shard0of8"]
+            line.update({
+                "roofline": {"bound": "valu", "achieved": round(tops, 3), "peak": round(VALU_PEAK_TOPS, 2),
+                             "unit": "TFLOP/s", "frac": round(tops / VALU_PEAK_TOPS, 4), "traffic": traffic,
+                             "clock_ghz": round(clock_ghz, 4) if clock_ghz else None,
+                             "frac_at_held_clock": round(tops / (256 * 4 * 32 * clock_ghz * 1e9 / 1e12), 4) if clock_ghz else None,
+                             "clock_note": "shader clock held under this workload: s_memtime / s_memrealtime of a one-wave probe (rrt_clock_probe) "
+                                           "running " + str(clock_when) + "; `peak` prices 2.4 GHz, frac_at_held_clock the clock the chip actually ran at "
+                                           "(MI355X boards have held 2.2-2.4 GHz under it); > 1 is possible: the peak counts one SOURCE operation per lane and clock "
+                                           "and the kernel needs 0.955 instructions per source operation",
+                             "traffic_note": traffic_note,
+                             "issue_slot_util": issue_util, "issue_slot_util_note": issue_note,
+                             "frac_of_fma_peak_157.3": round(tops / 157.3, 4),
+                             "kernel": "raymarch_pixels", "kernel_ms": round(k_ms, 3), **k_stats,
+                             "ops_per_ray": round(opr, 1), "per_ray_means": {k: round(v, 2) for k, v in means.items()},
+                             "note": "source-level unfused FP32 ops (SURVEY 8d formula) / " + k_note + "; "
+                                     "peak = 256CU x 4SIMD x 32 lanes x 2.4 GHz = one unfused FP32 op per lane per clock "
+                                     "(the datasheet's 157.3 TFLOP/s counts an FMA as two)",
+                             "hbm": {"bound": "hbm", "achieved": round(hbm_gbs, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                     "frac": round(hbm_gbs / HBM_PEAK_GBS, 6),
+                                     "note": "algorithmic 52 B/ray; the path is not HBM-bound"}},
+                "cpu_baseline": cpu,
+                "within_tolerance_mode": wtol,
+                "headline_arithmetic_noise": arith_noise,
+                "projection_8_ranks": projection,
+                "heavy_view": heavy,
+            })
+            if world > 1:
+                best_single = min(single_ref["static_order_ms"], single_ref["cost_ordered_ms"])
+                line["multi_gpu"] = {"single_gpu_reference_ms": best_single, "single_gpu_reference": single_ref,
+                                     "speedup_vs_single_gpu_reference": round(best_single / ms_per_step, 3),
+                                     "single_gpu_reference_note": "the same frame on rank 0's GPU alone, single kernel, noise tables, best of static and "
+                                                                  "cost-ordered dispatch, measured in this run while the other ranks waited",
+                                     "phases": phases, "one_frame_at_a_time": one_at_a_time,
+                                     "frames_in_flight": fs.n_slots,
+                                     "path_per_launch": path_tuning if fs.pipeline else "automatic (three-pass in two chains for a small share)",
+                                     "frames_in_flight_note": "default 3: chosen on ONE GPU rendering a single rank's share "
+                                                              "(profiles/r02_frames_in_flight.txt); provisional until a run on >= 2 GPUs"}
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()          # ranks > 0 wait here for rank 0's CPU leg and line, under the run watchdog

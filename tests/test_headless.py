@@ -188,7 +188,7 @@ def test_bench_self_launches_its_ranks():
     env = dict(os.environ, RRT_DIST_BACKEND="gloo")
     env.pop("WORLD_SIZE", None); env.pop("RANK", None)
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--width", "320", "--height", "180", "--steps", "2",
-                        "--warmup", "1", "--cpu-stride", "4", "--workspace-gib", "2"], cwd=ROOT, env=env, capture_output=True,
+                        "--warmup", "1", "--cpu-stride", "4", "--workspace-gib", "2", "--full"], cwd=ROOT, env=env, capture_output=True,
                        text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -332,9 +332,9 @@ def test_path_choice_changes_no_byte(tmp_path):
 
 @pytest.mark.gpu
 def test_bench_line_contract():
-    """bench.py at a reduced frame size: one JSON line with the driver's keys, the roofline and the CPU baseline."""
+    """bench.py --full at a reduced frame size: one JSON line with the driver's keys, the roofline and the CPU baseline."""
     r = subprocess.run([sys.executable, "bench.py", "--width", "320", "--height", "180", "--steps", "2", "--warmup", "1",
-                        "--cpu-stride", "4"], cwd=ROOT, capture_output=True, text=True, timeout=600)
+                        "--cpu-stride", "4", "--full"], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1
@@ -371,3 +371,34 @@ def test_bench_line_contract():
     assert cb["kind"] in ("port", "reference") and cb["cores"] >= 1 and cb["value"] > 0 and cb["unit"] == "Mrays/s" and cb["sample"]
     if cb["kind"] == "reference":       # oracle/_ref travelled with the tree: the reference's own kernel body was timed
         assert cb["step_counts_equal_port"] is True and cb["port"]["kind"] == "port" and cb["port"]["value"] > 0
+
+
+FULL_ONLY_KEYS = ("roofline", "cpu_baseline", "within_tolerance_mode", "headline_arithmetic_noise", "projection_8_ranks", "heavy_view",
+                  "multi_gpu")
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_is_the_headline_only(tmp_path):
+    """bench.py without --full: the same headline keys and config, none of the --full legs, and the timed frames write the same
+    bytes as those of a --full run."""
+    base = [sys.executable, "bench.py", "--width", "320", "--height", "180", "--steps", "2", "--warmup", "1"]
+    r = subprocess.run(base + ["--dump-outputs", str(tmp_path / "plain")], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config"):
+        assert k in d, k
+    assert not [k for k in FULL_ONLY_KEYS if k in d]
+    assert d["metric"] == "Mrays/s" and d["unit"] == "Mrays/s" and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and "workload" in d["config"]
+    assert abs(d["value"] - 320 * 180 / d["ms_per_step"] / 1e3) < 0.01 * d["value"]
+    r = subprocess.run(base + ["--full", "--cpu-stride", "0", "--no-fast", "--no-heavy", "--dump-outputs", str(tmp_path / "full")],
+                       cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    f = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
+    assert set(d) < set(f) and "roofline" in f and f["config"] == {**d["config"], "noise_table": f["config"]["noise_table"]}
+    for name in ("frame_rgba_sample.npy", "frame_pixel_index.npy"):
+        a, b = np.load(tmp_path / "plain" / name), np.load(tmp_path / "full" / name)
+        assert a.shape[0] == 320 * 180 and np.array_equal(a, b), name
