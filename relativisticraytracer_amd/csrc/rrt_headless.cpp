@@ -583,25 +583,21 @@ int main(int argc, char** argv) {
             if (D.chooser) { int pol = RRT_PATH_AUTO; rrt_path_chooser_policy(D.chooser, k, &pol); prm.path_policy = pol; }
             else if (path_policy >= 0) prm.path_policy = path_policy;
             void* dst = collective ? D.tiles[slot] : frame[slot];
-            if (use_glow) {     // one device (checked above): the slot's HDR through _ss / _mb, then the glow on the same stream
+            // the panorama / blurred / supersampled launch (_pano, _mb, _ss): this device's tiles, or the whole frame and its HDR (may be NULL)
+            auto launch_sampled = [&](bool tiles, float* lin) {
+                if (pano) return tiles ? rrt_launch_raymarch_pano_tiles(dst, w, h, supersample, tile_rows, d, gpus, &proj, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot])
+                                       : rrt_launch_raymarch_pano(dst, lin, w, h, supersample, &proj, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
+                if (motion > 1) return tiles ? rrt_launch_raymarch_mb_tiles(dst, w, h, supersample, tile_rows, d, gpus, motion, sub_t, sub_cam, D.sky, &fx, &prm, D.stream[slot])
+                                             : rrt_launch_raymarch_mb(dst, lin, w, h, supersample, motion, sub_t, sub_cam, D.sky, &fx, &prm, D.stream[slot]);
+                return tiles ? rrt_launch_raymarch_ss_tiles(dst, w, h, supersample, tile_rows, d, gpus, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot])
+                             : rrt_launch_raymarch_ss(dst, lin, w, h, supersample, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
+            };
+            if (use_glow) {     // one device (checked above): the slot's HDR through launch_sampled, then the glow on the same stream
                 float* lin = static_cast<float*>(hdr[slot]);
-                if (motion > 1) rc = rrt_launch_raymarch_mb(dst, lin, w, h, supersample, motion, sub_t, sub_cam, D.sky, &fx, &prm, D.stream[slot]);
-                else if (pano) rc = rrt_launch_raymarch_pano(dst, lin, w, h, supersample, &proj, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
-                else rc = rrt_launch_raymarch_ss(dst, lin, w, h, supersample, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
+                rc = launch_sampled(false, lin);
                 if (rc == RRT_OK) rc = rrt_launch_glow(dst, lin, w, h, &glow, glow_scratch[slot], glow_bytes, D.stream[slot]);
             }
-            else if (pano) {
-                if (collective) rc = rrt_launch_raymarch_pano_tiles(dst, w, h, supersample, tile_rows, d, gpus, &proj, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
-                else rc = rrt_launch_raymarch_pano(dst, nullptr, w, h, supersample, &proj, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
-            }
-            else if (motion > 1) {
-                if (collective) rc = rrt_launch_raymarch_mb_tiles(dst, w, h, supersample, tile_rows, d, gpus, motion, sub_t, sub_cam, D.sky, &fx, &prm, D.stream[slot]);
-                else rc = rrt_launch_raymarch_mb(dst, nullptr, w, h, supersample, motion, sub_t, sub_cam, D.sky, &fx, &prm, D.stream[slot]);
-            }
-            else if (supersample > 1) {
-                if (collective) rc = rrt_launch_raymarch_ss_tiles(dst, w, h, supersample, tile_rows, d, gpus, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
-                else rc = rrt_launch_raymarch_ss(dst, nullptr, w, h, supersample, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
-            }
+            else if (pano || motion > 1 || supersample > 1) rc = launch_sampled(collective, nullptr);
             else if (collective) rc = rrt_launch_raymarch_tiles(dst, w, h, tile_rows, d, gpus, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
             else rc = rrt_launch_raymarch(dst, w, h, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
             if (rc != RRT_OK) return fail("launch", rc);

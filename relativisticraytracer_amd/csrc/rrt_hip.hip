@@ -29,6 +29,7 @@
 #include <unordered_map>
 #include <vector>
 #include <algorithm>
+#include <type_traits>
 
 #include "../../include/rrt.h"
 #ifdef RRT_TEST_HOOKS
@@ -451,6 +452,23 @@ int enqueue_probe(const FrameArgs& a, ProbeArgs& q, unsigned* cells, int stride_
     return RRT_OK;
 }
 
+/* The template instance of a single-kernel launch: f(SPIN, MEDIA, ARITH) with the three as std::integral_constants */
+template <class F>
+void dispatch_kernel(bool spin, int media, int arith, F&& f) {
+    const auto by_arith = [&](auto S, auto M) {
+        if (arith == kArithFast) f(S, M, std::integral_constant<int, kArithFast>{});
+        else if (arith == kArithFmad) f(S, M, std::integral_constant<int, kArithFmad>{});
+        else f(S, M, std::integral_constant<int, kArithStrict>{});
+    };
+    const auto by_media = [&](auto S) {
+        if (media == 3) by_arith(S, std::integral_constant<int, 3>{});
+        else if (media == 2) by_arith(S, std::integral_constant<int, 2>{});
+        else if (media == 1) by_arith(S, std::integral_constant<int, 1>{});
+        else by_arith(S, std::integral_constant<int, 0>{});
+    };
+    if (spin) by_media(std::true_type{}); else by_media(std::false_type{});
+}
+
 int launch(const FrameArgs& a, const LaunchOpts& o, bool debug, hipStream_t st) {
     dim3 block(kWGThreads);
     if (a.rows.n_local_rows == 0) return RRT_OK;
@@ -522,18 +540,10 @@ int launch(const FrameArgs& a, const LaunchOpts& o, bool debug, hipStream_t st) 
         launched = rc == RRT_OK;
     }
     if (!launched) {
-        const int media = o.media;
-        const int arith = o.arith;
-#define RRT_LAUNCH4(S, M, D, F) hipLaunchKernelGGL((raymarch_pixels<S, M, D, F>), grid, block, 0, st, b)
-#define RRT_LAUNCH3(S, M, D) do { if (arith == kArithFast) RRT_LAUNCH4(S, M, D, kArithFast); else if (arith == kArithFmad) RRT_LAUNCH4(S, M, D, kArithFmad); \
-                                  else RRT_LAUNCH4(S, M, D, kArithStrict); } while (0)
-#define RRT_LAUNCH2(S, M) do { if (debug) RRT_LAUNCH3(S, M, true); else RRT_LAUNCH3(S, M, false); } while (0)
-#define RRT_LAUNCH1(S) do { if (media == 3) RRT_LAUNCH2(S, 3); else if (media == 2) RRT_LAUNCH2(S, 2); else if (media == 1) RRT_LAUNCH2(S, 1); else RRT_LAUNCH2(S, 0); } while (0)
-        if (spin) RRT_LAUNCH1(true); else RRT_LAUNCH1(false);
-#undef RRT_LAUNCH1
-#undef RRT_LAUNCH2
-#undef RRT_LAUNCH3
-#undef RRT_LAUNCH4
+        dispatch_kernel(spin, o.media, o.arith, [&](auto S, auto M, auto F) {
+            if (debug) hipLaunchKernelGGL((raymarch_pixels<S, M, true, F>), grid, block, 0, st, b);
+            else hipLaunchKernelGGL((raymarch_pixels<S, M, false, F>), grid, block, 0, st, b);
+        });
         RRT_HIP(hipGetLastError());
     }
     if (order) {
@@ -547,13 +557,7 @@ int launch(const FrameArgs& a, const LaunchOpts& o, bool debug, hipStream_t st) 
     return RRT_OK;
 }
 
-/* ---- s x s supersampled launches (rrt_launch_raymarch_ss*): one kernel, static order, nothing else */
-/* the template instance of a single-kernel launch: LAUNCH3(spin, media, arith) for the local `spin`, `media` and `arith` */
-#define RRT_SS_DISPATCH2(LAUNCH3, S, M) do { if (arith == kArithFast) LAUNCH3(S, M, kArithFast); \
-                                             else if (arith == kArithFmad) LAUNCH3(S, M, kArithFmad); else LAUNCH3(S, M, kArithStrict); } while (0)
-#define RRT_SS_DISPATCH1(LAUNCH3, S) do { if (media == 3) RRT_SS_DISPATCH2(LAUNCH3, S, 3); else if (media == 2) RRT_SS_DISPATCH2(LAUNCH3, S, 2); \
-                                          else if (media == 1) RRT_SS_DISPATCH2(LAUNCH3, S, 1); else RRT_SS_DISPATCH2(LAUNCH3, S, 0); } while (0)
-#define RRT_SS_DISPATCH(LAUNCH3) do { if (spin) RRT_SS_DISPATCH1(LAUNCH3, true); else RRT_SS_DISPATCH1(LAUNCH3, false); } while (0)
+/* ---- sampled launches (rrt_launch_raymarch_ss*, _mb*, _pano*): one kernel over the virtual (s w) x (s h) frame, static order */
 bool valid_samples(int s) { return s == 1 || s == 2 || s == 4 || s == 8; }
 
 /* the checks of check_common plus the virtual (s w) x (s h) frame's limits; all before any device call */
@@ -566,27 +570,30 @@ int check_ss(const void* out, int width, int height, int s, const rrt_camera* ca
     return RRT_OK;
 }
 
-/* `rows` in OUTPUT rows of the w x h frame.  The params that pick a path or an order (workspace, path_policy, pool_rounds,
- * pass_chains, tile_order) are dropped before fill_args looks at them: a supersampled launch neither takes the three-pass
- * path nor reads or records a tile order. */
-int launch_ss(void* out, float4* hdr, int width, int height, int s, const RowMap& rows, float time, const rrt_camera* cam,
-              rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm_in, hipStream_t st) {
+/* The arguments and grid of a sampled launch: the virtual frame at times [t_lo, t_hi], `rows` in OUTPUT rows of the w x h frame
+ * (grid.y == 0: nothing to launch).  The params that pick a path or an order (workspace, path_policy, pool_rounds, pass_chains,
+ * tile_order) are dropped before fill_args looks at them: a sampled launch neither takes the three-pass path nor reads or records
+ * a tile order.  The media mode is picked once for the interval: fill_args at both ends -- a table's window is an interval, so it
+ * holds every time iff it holds both -- and the arithmetic kernels unless both found the table. */
+int sampled_args(FrameArgs& a, LaunchOpts& o, dim3& grid, void* out, int width, int height, int s, const RowMap& rows, float t_lo,
+                 float t_hi, const rrt_camera* cam, rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm_in) {
     rrt_params prm;
     load_params(prm_in, prm);
     prm.workspace = 0; prm.path_policy = RRT_PATH_AUTO; prm.pool_rounds = 0; prm.pass_chains = 0; prm.tile_order = 0;
-    FrameArgs a;
-    LaunchOpts o;
-    const int rc = fill_args(a, o, out, s * width, s * height, time, cam, sky, fx, &prm);
+    int rc = fill_args(a, o, out, s * width, s * height, t_lo, cam, sky, fx, &prm);
     if (rc) return rc;
+    if (t_hi != t_lo) {
+        FrameArgs a_hi;
+        LaunchOpts o_hi;
+        rc = fill_args(a_hi, o_hi, out, s * width, s * height, t_hi, cam, sky, fx, &prm);
+        if (rc) return rc;
+        if (o.media != o_hi.media) {                /* some time outside the window: every sub-frame hashes arithmetically */
+            o.media = 1;
+            memset(&a.lut_acc, 0, sizeof(a.lut_acc)); memset(&a.lut_dust, 0, sizeof(a.lut_dust)); memset(&a.dust_bands, 0, sizeof(a.dust_bands));
+        }
+    }
     a.rows = rows;
-    if (rows.n_local_rows == 0) return RRT_OK;
-    const dim3 grid((a.width + kWGPixX - 1) / kWGPixX, (s * rows.n_local_rows + kWGPixY - 1) / kWGPixY), block(kWGThreads);
-    const bool spin = a.spin != 0.0f;
-    const int media = o.media, arith = o.arith;
-#define RRT_SS3(S, M, F) hipLaunchKernelGGL((supersample_pixels<S, M, F>), grid, block, 0, st, a, s, hdr)
-    RRT_SS_DISPATCH(RRT_SS3);
-#undef RRT_SS3
-    RRT_HIP(hipGetLastError());
+    grid = dim3((a.width + kWGPixX - 1) / kWGPixX, (s * rows.n_local_rows + kWGPixY - 1) / kWGPixY);
     return RRT_OK;
 }
 
@@ -605,14 +612,9 @@ int check_mb(const void* out, int width, int height, int s, int n_times, const f
     return RRT_OK;
 }
 
-/* launch_ss with n_times sub-frames.  The media mode is picked once for all of them: fill_args at the earliest and at the latest
- * time -- a table's window is an interval, so it holds every time iff it holds both -- and the arithmetic kernels unless both
- * found the table. */
+/* launch_ss with n_times sub-frames, over the span of their times */
 int launch_mb(void* out, float4* hdr, int width, int height, int s, const RowMap& rows, int n_times, const float* times,
               const rrt_camera* cams, rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm_in, hipStream_t st) {
-    rrt_params prm;
-    load_params(prm_in, prm);
-    prm.workspace = 0; prm.path_policy = RRT_PATH_AUTO; prm.pool_rounds = 0; prm.pass_chains = 0; prm.tile_order = 0;
     float t_lo = times[0], t_hi = times[0];
     MotionLaunch L;
     MotionArgs& m = L.m;
@@ -623,26 +625,14 @@ int launch_mb(void* out, float4* hdr, int width, int height, int s, const RowMap
         if (times[j] < t_lo) t_lo = times[j];
         if (times[j] > t_hi) t_hi = times[j];
     }
-    FrameArgs& a = L.a;
-    FrameArgs a_hi;
-    LaunchOpts o, o_hi;
-    int rc = fill_args(a, o, out, s * width, s * height, t_lo, &cams[0], sky, fx, &prm);
-    if (rc) return rc;
-    rc = fill_args(a_hi, o_hi, out, s * width, s * height, t_hi, &cams[0], sky, fx, &prm);
-    if (rc) return rc;
-    if (o.media != o_hi.media) {                    /* some time outside the window: every sub-frame hashes arithmetically */
-        o.media = 1;
-        memset(&a.lut_acc, 0, sizeof(a.lut_acc)); memset(&a.lut_dust, 0, sizeof(a.lut_dust)); memset(&a.dust_bands, 0, sizeof(a.dust_bands));
-    }
-    a.rows = rows;
+    LaunchOpts o;
+    dim3 grid;
+    const int rc = sampled_args(L.a, o, grid, out, width, height, s, rows, t_lo, t_hi, &cams[0], sky, fx, prm_in);
+    if (rc || grid.y == 0) return rc;
     L.s = s; L.n_times = n_times; L.hdr_out = hdr;
-    if (rows.n_local_rows == 0) return RRT_OK;
-    const dim3 grid((a.width + kWGPixX - 1) / kWGPixX, (s * rows.n_local_rows + kWGPixY - 1) / kWGPixY), block(kWGThreads);
-    const bool spin = a.spin != 0.0f;
-    const int media = o.media, arith = o.arith;
-#define RRT_MB3(S, M, F) hipLaunchKernelGGL((motion_pixels<S, M, F>), grid, block, 0, st, L)
-    RRT_SS_DISPATCH(RRT_MB3);
-#undef RRT_MB3
+    dispatch_kernel(L.a.spin != 0.0f, o.media, o.arith, [&](auto S, auto M, auto F) {
+        hipLaunchKernelGGL((motion_pixels<S, M, F>), grid, dim3(kWGThreads), 0, st, L);
+    });
     RRT_HIP(hipGetLastError());
     return RRT_OK;
 }
@@ -675,27 +665,22 @@ int check_pano(const void* out, int width, int height, int s, const rrt_projecti
     return check_ss(out, width, height, s, cam, fx, prm);
 }
 
-/* launch_ss with projection_dir instead of primary_ray; the lens and the vignette are cleared (the contract ignores them) */
-int launch_pano(void* out, float4* hdr, int width, int height, int s, const RowMap& rows, const rrt_projection& proj, float time,
-                const rrt_camera* cam, rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm_in, hipStream_t st) {
-    if (proj.kind == RRT_PROJ_PINHOLE) return launch_ss(out, hdr, width, height, s, rows, time, cam, sky, fx, prm_in, st);
-    rrt_params prm;
-    load_params(prm_in, prm);
-    prm.workspace = 0; prm.path_policy = RRT_PATH_AUTO; prm.pool_rounds = 0; prm.pass_chains = 0; prm.tile_order = 0;
+/* A supersampled frame (proj NULL or a pinhole: supersample_pixels), or a panorama (panorama_pixels: projection_dir instead of
+ * primary_ray; the lens and the vignette are cleared, the contract ignores them) */
+int launch_ss(void* out, float4* hdr, int width, int height, int s, const RowMap& rows, const rrt_projection* proj, float time,
+              const rrt_camera* cam, rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm_in, hipStream_t st) {
     FrameArgs a;
     LaunchOpts o;
-    const int rc = fill_args(a, o, out, s * width, s * height, time, cam, sky, fx, &prm);
-    if (rc) return rc;
-    a.use_lens = 0; a.use_vignette = 0;
-    a.rows = rows;
-    if (rows.n_local_rows == 0) return RRT_OK;
-    const ProjArgs pj = proj_args(proj);
-    const dim3 grid((a.width + kWGPixX - 1) / kWGPixX, (s * rows.n_local_rows + kWGPixY - 1) / kWGPixY), block(kWGThreads);
-    const bool spin = a.spin != 0.0f;
-    const int media = o.media, arith = o.arith;
-#define RRT_PANO3(S, M, F) hipLaunchKernelGGL((panorama_pixels<S, M, F>), grid, block, 0, st, a, s, hdr, pj)
-    RRT_SS_DISPATCH(RRT_PANO3);
-#undef RRT_PANO3
+    dim3 grid;
+    const int rc = sampled_args(a, o, grid, out, width, height, s, rows, time, time, cam, sky, fx, prm_in);
+    if (rc || grid.y == 0) return rc;
+    const bool pano = proj && proj->kind != RRT_PROJ_PINHOLE;
+    const ProjArgs pj = pano ? proj_args(*proj) : ProjArgs{};
+    if (pano) { a.use_lens = 0; a.use_vignette = 0; }
+    dispatch_kernel(a.spin != 0.0f, o.media, o.arith, [&](auto S, auto M, auto F) {
+        if (pano) hipLaunchKernelGGL((panorama_pixels<S, M, F>), grid, dim3(kWGThreads), 0, st, a, s, hdr, pj);
+        else hipLaunchKernelGGL((supersample_pixels<S, M, F>), grid, dim3(kWGThreads), 0, st, a, s, hdr);
+    });
     RRT_HIP(hipGetLastError());
     return RRT_OK;
 }
@@ -705,6 +690,14 @@ int shard_rows(int height, int tile_rows, int shard, int n_shards) {
     int rows = 0;
     for (int t = shard; t < n_tiles; t += n_shards) rows += (t * tile_rows + tile_rows <= height) ? tile_rows : (height - t * tile_rows);
     return rows;
+}
+/* the whole frame, bottom-up */
+RowMap frame_rows(int height) { return RowMap{height, 0, height, 0, 1, nullptr}; }
+/* shard `shard` of n_shards: tiles of tile_rows rows, dealt round-robin */
+int shard_map(int height, int tile_rows, int shard, int n_shards, RowMap& m) {
+    if (tile_rows <= 0 || n_shards <= 0 || shard < 0 || shard >= n_shards) return RRT_ERR_INVALID_ARGUMENT;
+    m = RowMap{shard_rows(height, tile_rows, shard, n_shards), 0, tile_rows, shard, n_shards, nullptr};
+    return RRT_OK;
 }
 
 /* ---- HDR glow (rrt_launch_glow): the lobes' taps in double, the checks, the three launches */
@@ -1421,7 +1414,7 @@ int rrt_launch_raymarch_ex(void* d_out_rgba8, int width, int height, float time,
     LaunchOpts o;
     rc = fill_args(a, o, d_out_rgba8, width, height, time, cam, sky, fx, prm);
     if (rc) return rc;
-    a.rows = RowMap{height, 0, height, 0, 1, nullptr};
+    a.rows = frame_rows(height);
     if (dbg) a.dbg = *dbg;
     return launch(a, o, dbg != nullptr, static_cast<hipStream_t>(stream));
 }
@@ -1438,12 +1431,13 @@ int rrt_launch_raymarch_tiles(void* d_out_tiles, int width, int height, int tile
                               const rrt_params* prm, void* stream) {
     int rc = check_common(d_out_tiles, width, height, cam, fx, prm);
     if (rc) return rc;
-    if (tile_rows <= 0 || n_shards <= 0 || shard < 0 || shard >= n_shards) return RRT_ERR_INVALID_ARGUMENT;
+    RowMap rows;
+    if ((rc = shard_map(height, tile_rows, shard, n_shards, rows))) return rc;
     FrameArgs a;
     LaunchOpts o;
     rc = fill_args(a, o, d_out_tiles, width, height, time, cam, sky, fx, prm);
     if (rc) return rc;
-    a.rows = RowMap{shard_rows(height, tile_rows, shard, n_shards), 0, tile_rows, shard, n_shards, nullptr};
+    a.rows = rows;
     return launch(a, o, false, static_cast<hipStream_t>(stream));
 }
 
@@ -1451,19 +1445,19 @@ int rrt_launch_raymarch_ss(void* d_out_rgba8, float* d_hdr_rgba32f, int width, i
                            const rrt_camera* cam, rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm, void* stream) {
     const int rc = check_ss(d_out_rgba8, width, height, samples_per_axis, cam, fx, prm);
     if (rc) return rc;
-    return launch_ss(d_out_rgba8, reinterpret_cast<float4*>(d_hdr_rgba32f), width, height, samples_per_axis,
-                     RowMap{height, 0, height, 0, 1, nullptr}, time, cam, sky, fx, prm, static_cast<hipStream_t>(stream));
+    return launch_ss(d_out_rgba8, reinterpret_cast<float4*>(d_hdr_rgba32f), width, height, samples_per_axis, frame_rows(height),
+                     nullptr, time, cam, sky, fx, prm, static_cast<hipStream_t>(stream));
 }
 
 int rrt_launch_raymarch_ss_tiles(void* d_out_tiles, int width, int height, int samples_per_axis, int tile_rows, int shard, int n_shards,
                                  float time, const rrt_camera* cam, rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm,
                                  void* stream) {
-    const int rc = check_ss(d_out_tiles, width, height, samples_per_axis, cam, fx, prm);
+    int rc = check_ss(d_out_tiles, width, height, samples_per_axis, cam, fx, prm);
     if (rc) return rc;
-    if (tile_rows <= 0 || n_shards <= 0 || shard < 0 || shard >= n_shards) return RRT_ERR_INVALID_ARGUMENT;
-    return launch_ss(d_out_tiles, nullptr, width, height, samples_per_axis,
-                     RowMap{shard_rows(height, tile_rows, shard, n_shards), 0, tile_rows, shard, n_shards, nullptr}, time, cam, sky,
-                     fx, prm, static_cast<hipStream_t>(stream));
+    RowMap rows;
+    if ((rc = shard_map(height, tile_rows, shard, n_shards, rows))) return rc;
+    return launch_ss(d_out_tiles, nullptr, width, height, samples_per_axis, rows, nullptr, time, cam, sky, fx, prm,
+                     static_cast<hipStream_t>(stream));
 }
 
 int rrt_launch_raymarch_mb(void* d_out_rgba8, float* d_hdr_rgba32f, int width, int height, int samples_per_axis, int n_times,
@@ -1471,28 +1465,27 @@ int rrt_launch_raymarch_mb(void* d_out_rgba8, float* d_hdr_rgba32f, int width, i
                            void* stream) {
     const int rc = check_mb(d_out_rgba8, width, height, samples_per_axis, n_times, times, cams, fx, prm);
     if (rc) return rc;
-    return launch_mb(d_out_rgba8, reinterpret_cast<float4*>(d_hdr_rgba32f), width, height, samples_per_axis,
-                     RowMap{height, 0, height, 0, 1, nullptr}, n_times, times, cams, sky, fx, prm, static_cast<hipStream_t>(stream));
+    return launch_mb(d_out_rgba8, reinterpret_cast<float4*>(d_hdr_rgba32f), width, height, samples_per_axis, frame_rows(height),
+                     n_times, times, cams, sky, fx, prm, static_cast<hipStream_t>(stream));
 }
 
 int rrt_launch_raymarch_mb_tiles(void* d_out_tiles, int width, int height, int samples_per_axis, int tile_rows, int shard, int n_shards,
                                  int n_times, const float* times, const rrt_camera* cams, rrt_sky_t sky, const rrt_effects* fx,
                                  const rrt_params* prm, void* stream) {
-    const int rc = check_mb(d_out_tiles, width, height, samples_per_axis, n_times, times, cams, fx, prm);
+    int rc = check_mb(d_out_tiles, width, height, samples_per_axis, n_times, times, cams, fx, prm);
     if (rc) return rc;
-    if (tile_rows <= 0 || n_shards <= 0 || shard < 0 || shard >= n_shards) return RRT_ERR_INVALID_ARGUMENT;
-    return launch_mb(d_out_tiles, nullptr, width, height, samples_per_axis,
-                     RowMap{shard_rows(height, tile_rows, shard, n_shards), 0, tile_rows, shard, n_shards, nullptr}, n_times, times,
-                     cams, sky, fx, prm, static_cast<hipStream_t>(stream));
+    RowMap rows;
+    if ((rc = shard_map(height, tile_rows, shard, n_shards, rows))) return rc;
+    return launch_mb(d_out_tiles, nullptr, width, height, samples_per_axis, rows, n_times, times, cams, sky, fx, prm,
+                     static_cast<hipStream_t>(stream));
 }
 
 int rrt_assemble_tiles(void* d_frame, const void* d_tiles, int width, int height, int tile_rows, int shard,
                        int n_shards, void* stream) {
-    if (!d_frame || !d_tiles || width <= 0 || height <= 0 || tile_rows <= 0 || n_shards <= 0 || shard < 0 ||
-        shard >= n_shards)
-        return RRT_ERR_INVALID_ARGUMENT;
-    RowMap m{shard_rows(height, tile_rows, shard, n_shards), 0, tile_rows, shard, n_shards, nullptr};
-    if (m.n_local_rows == 0) return RRT_OK;
+    if (!d_frame || !d_tiles || width <= 0 || height <= 0) return RRT_ERR_INVALID_ARGUMENT;
+    RowMap m;
+    const int rc = shard_map(height, tile_rows, shard, n_shards, m);
+    if (rc || m.n_local_rows == 0) return rc;
     dim3 grid((width + 255) / 256, m.n_local_rows < kMaxGridY ? m.n_local_rows : kMaxGridY);
     hipLaunchKernelGGL(assemble_tiles_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<uchar4*>(d_frame), static_cast<const uchar4*>(d_tiles), width, height, m);
@@ -1647,7 +1640,7 @@ int rrt_probe_tile_costs(int width, int height, int tile_rows, float time, const
     a.width = width; a.height = height; a.time = time; a.cam = *cam;
     a.use_lens = fx->use_lens_distortion != 0; a.distortion_amount = fx->distortion_amount;
     a.spin = p.spin; a.drag_c = (2.0f * p.spin) * 2.0f; a.max_steps = p.max_steps;
-    a.rows = RowMap{height, 0, height, 0, 1, nullptr};
+    a.rows = frame_rows(height);
     a.grid_row_stride = 1;
     const int sy = tile_rows < kProbeStride ? tile_rows : kProbeStride;
     ProbeArgs q;
@@ -1772,19 +1765,19 @@ int rrt_launch_raymarch_pano(void* d_out_rgba8, float* d_hdr_rgba32f, int width,
                              const rrt_params* prm, void* stream) {
     const int rc = check_pano(d_out_rgba8, width, height, samples_per_axis, proj, cam, fx, prm);
     if (rc) return rc;
-    return launch_pano(d_out_rgba8, reinterpret_cast<float4*>(d_hdr_rgba32f), width, height, samples_per_axis,
-                       RowMap{height, 0, height, 0, 1, nullptr}, *proj, time, cam, sky, fx, prm, static_cast<hipStream_t>(stream));
+    return launch_ss(d_out_rgba8, reinterpret_cast<float4*>(d_hdr_rgba32f), width, height, samples_per_axis, frame_rows(height),
+                     proj, time, cam, sky, fx, prm, static_cast<hipStream_t>(stream));
 }
 
 int rrt_launch_raymarch_pano_tiles(void* d_out_tiles, int width, int height, int samples_per_axis, int tile_rows, int shard,
                                    int n_shards, const rrt_projection* proj, float time, const rrt_camera* cam, rrt_sky_t sky,
                                    const rrt_effects* fx, const rrt_params* prm, void* stream) {
-    const int rc = check_pano(d_out_tiles, width, height, samples_per_axis, proj, cam, fx, prm);
+    int rc = check_pano(d_out_tiles, width, height, samples_per_axis, proj, cam, fx, prm);
     if (rc) return rc;
-    if (tile_rows <= 0 || n_shards <= 0 || shard < 0 || shard >= n_shards) return RRT_ERR_INVALID_ARGUMENT;
-    return launch_pano(d_out_tiles, nullptr, width, height, samples_per_axis,
-                       RowMap{shard_rows(height, tile_rows, shard, n_shards), 0, tile_rows, shard, n_shards, nullptr}, *proj, time,
-                       cam, sky, fx, prm, static_cast<hipStream_t>(stream));
+    RowMap rows;
+    if ((rc = shard_map(height, tile_rows, shard, n_shards, rows))) return rc;
+    return launch_ss(d_out_tiles, nullptr, width, height, samples_per_axis, rows, proj, time, cam, sky, fx, prm,
+                     static_cast<hipStream_t>(stream));
 }
 
 #ifdef RRT_TEST_HOOKS

@@ -669,34 +669,87 @@ __device__ __forceinline__ void pixel_sum(v3& c, const int s) {
 }
 
 static_assert(kTileW == 8 && kTileH == 8, "supersample_pixels maps a pixel's sub-samples into an 8x8 wave tile (s = 8: one pixel per wave)");
-template <bool SPIN, int MEDIA, int ARITH>
-__global__ __launch_bounds__(kWGThreads, (MEDIA != 0 ? RRT_MEDIA_WAVES : 1))      /* raymarch_pixels' register budget */
-void supersample_pixels(const FrameArgs a, const int s, float4* const hdr_out) {
+/* A lane of a sampled launch (the mapping above): its sub-sample's virtual pixel (vx, vy) and virtual local row vlr, its output
+ * pixel's column x and local output row out_row */
+struct SampleLane {
+    int vx, vy, vlr, x, out_row;
+    __device__ bool stores(int s) const { return ((vx | vlr) & (s - 1)) == 0; }   /* the pixel's first lane stores */
+};
+/* false: the lane is outside the frame (all of a pixel's lanes are) */
+__device__ __forceinline__ bool sample_lane(const FrameArgs& a, const int s, SampleLane& l) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int vx = tile_column(a) * kWGPixX + (wave & 1) * kTileW + (lane & (kTileW - 1));      /* virtual column */
-    const int vlr = row_block(a) * kWGPixY + (wave >> 1) * kTileH + lane / kTileW;              /* virtual local row */
+    l.vx = tile_column(a) * kWGPixX + (wave & 1) * kTileW + (lane & (kTileW - 1));
+    l.vlr = row_block(a) * kWGPixY + (wave >> 1) * kTileH + lane / kTileW;
     const int w = a.width / s, h = a.height / s;
-    const int x = vx / s;
-    int y, out_row;
-    if (x >= w || !map_row(a.rows, h, vlr / s, y, out_row)) return;
-    const int vy = s * y + (vlr - (vlr / s) * s);
-    float uvx, uvy;
-    v3 p, vel;
-    primary_ray(a, vx, vy, uvx, uvy, p, vel);
-    Radiance acc = {0.f, 0.f, 0.f, 1.0f};
-    bool hit = false;
-    int i = 0;
-    march_inline<SPIN, MEDIA, ARITH, true>(a, p, vel, acc, hit, i, nullptr);
-    v3 c = shade_hdr(a, uvx, uvy, hit, vel, acc);
-    pixel_sum(c, s);
-    if (((vx | vlr) & (s - 1)) != 0) return;            /* the pixel's first lane stores */
-    const float inv = 1.0f / (float)(s * s);            /* a power of two: the mean is exact given the sum */
+    l.x = l.vx / s;
+    int y;
+    if (l.x >= w || !map_row(a.rows, h, l.vlr / s, y, l.out_row)) return false;
+    l.vy = s * y + (l.vlr - (l.vlr / s) * s);
+    return true;
+}
+/* A sampled pixel's epilogue: the mean of its sum c (inv = 1 / (number of samples), a power of two: the mean is exact given the
+ * sum), tone-mapped and stored at oi; hdr_out (may be NULL): the mean HDR, alpha 1, indexed like the frame. */
+__device__ __forceinline__ void store_mean(v3 c, float inv, uchar4* out, float4* hdr_out, size_t oi) {
     c = mk(c.x * inv, c.y * inv, c.z * inv);
     float out_r, out_g, out_b;
     tone_map(c, out_r, out_g, out_b);
-    const size_t oi = (size_t)out_row * w + x;
-    store_rgba8(a.out, oi, out_r, out_g, out_b);
+    store_rgba8(out, oi, out_r, out_g, out_b);
     if (hdr_out) hdr_out[oi] = make_float4(c.x, c.y, c.z, 1.0f);
+}
+
+/* supersample_pixels (PROJ = false) and panorama_pixels (PROJ = true): the same waves, march, shading and butterfly; only the
+ * primary ray differs */
+#include "rrt_projection.h"
+template <bool SPIN, int MEDIA, int ARITH, bool PROJ>
+__device__ __forceinline__ void sampled_pixels(const FrameArgs& a, const int s, float4* const hdr_out, const ProjArgs& pj) {
+    SampleLane l;
+    if (!sample_lane(a, s, l)) return;
+    const auto march_shade = [&](v3 p, v3 vel, float uvx, float uvy) {
+        Radiance acc = {0.f, 0.f, 0.f, 1.0f};
+        bool hit = false;
+        int i = 0;
+        march_inline<SPIN, MEDIA, ARITH, true>(a, p, vel, acc, hit, i, nullptr);
+        return shade_hdr(a, uvx, uvy, hit, vel, acc);
+    };
+    v3 c = mk(0.f, 0.f, 0.f);
+    if constexpr (PROJ) {
+        float d[3];
+        if (projection_dir(pj, a.width, a.height, l.vx, l.vy, a.cam, d)) {     /* outside the disc: HDR exactly 0, no march */
+            v3 vel = mk(d[0], d[1], d[2]);
+            if (__builtin_expect(a.nudge_ulps != 0, 0)) {     /* as primary_ray, on the virtual pixel */
+                vel.x = nudge_component(vel.x, a.nudge_ulps, a.nudge_seed, l.vx, l.vy, 0u);
+                vel.y = nudge_component(vel.y, a.nudge_ulps, a.nudge_seed, l.vx, l.vy, 1u);
+                vel.z = nudge_component(vel.z, a.nudge_ulps, a.nudge_seed, l.vx, l.vy, 2u);
+            }
+            c = march_shade(mk(a.cam.pos[0], a.cam.pos[1], a.cam.pos[2]), vel, 0.f, 0.f);
+        }
+    } else {
+        float uvx, uvy;
+        v3 p, vel;
+        primary_ray(a, l.vx, l.vy, uvx, uvy, p, vel);
+        c = march_shade(p, vel, uvx, uvy);
+    }
+    pixel_sum(c, s);
+    if (!l.stores(s)) return;
+    store_mean(c, 1.0f / (float)(s * s), a.out, hdr_out, (size_t)l.out_row * (a.width / s) + l.x);
+}
+
+template <bool SPIN, int MEDIA, int ARITH>
+__global__ __launch_bounds__(kWGThreads, (MEDIA != 0 ? RRT_MEDIA_WAVES : 1))      /* raymarch_pixels' register budget */
+void supersample_pixels(const FrameArgs a, const int s, float4* const hdr_out) {
+    sampled_pixels<SPIN, MEDIA, ARITH, false>(a, s, hdr_out, ProjArgs{});
+}
+
+/* Panorama (rrt_launch_raymarch_pano, include/rrt.h has the contract): supersample_pixels with the projection's primary ray
+ * (rrt_projection.h: projection_dir, the source the host query runs too) instead of primary_ray -- the same waves over the virtual
+ * grid, march, shading and pixel_sum butterfly.  The host clears use_lens and use_vignette (both are defined on the pinhole's uv).
+ * A fisheye sub-sample outside the disc stays in its lanes -- pixel_sum shuffles across all of a pixel's lanes -- but branches
+ * around the march and the shading with HDR exactly 0: its lane is masked off, so it adds no trips to the wave's vacuum loop and
+ * takes no part in its ballots. */
+template <bool SPIN, int MEDIA, int ARITH>
+__global__ __launch_bounds__(kWGThreads, (MEDIA != 0 ? RRT_MEDIA_WAVES : 1))      /* raymarch_pixels' register budget */
+void panorama_pixels(const FrameArgs a, const int s, float4* const hdr_out, const ProjArgs pj) {
+    sampled_pixels<SPIN, MEDIA, ARITH, true>(a, s, hdr_out, pj);
 }
 
 /* Motion-blurred frame (rrt_launch_raymarch_mb, include/rrt.h has the contract): sub-frame k is supersample_pixels' frame at
@@ -740,18 +793,12 @@ void motion_pixels(const MotionLaunch L) {
     __shared__ volatile int where[3][kWGThreads];       /* vx, vy, the output index (-1: another lane of the pixel stores) */
     const int t = threadIdx.x;
     {
-        const FrameArgs& a = L.a;
         const int s = L.s;
-        const int lane = t & 63, wave = t >> 6;
-        const int vx = tile_column(a) * kWGPixX + (wave & 1) * kTileW + (lane & (kTileW - 1));      /* virtual column */
-        const int vlr = row_block(a) * kWGPixY + (wave >> 1) * kTileH + lane / kTileW;              /* virtual local row */
-        const int w = a.width / s, h = a.height / s;
-        const int x = vx / s;
-        int y, out_row;
-        if (x >= w || !map_row(a.rows, h, vlr / s, y, out_row)) return;
-        where[0][t] = vx;
-        where[1][t] = s * y + (vlr - (vlr / s) * s);
-        where[2][t] = ((vx | vlr) & (s - 1)) != 0 ? -1 : out_row * w + x;       /* the pixel's first lane stores */
+        SampleLane l;
+        if (!sample_lane(L.a, s, l)) return;
+        where[0][t] = l.vx;
+        where[1][t] = l.vy;
+        where[2][t] = l.stores(s) ? l.out_row * (L.a.width / s) + l.x : -1;
     }
     v3 c;
     for (int k = 0; k < L.n_times; ++k) {
@@ -782,58 +829,7 @@ void motion_pixels(const MotionLaunch L) {
     const int oi = where[2][t];
     if (oi < 0) return;
     const int s = RRT_MB_ARG(s);
-    const float inv = 1.0f / (float)(s * s * RRT_MB_ARG(n_times));  /* a power of two: the mean is exact given the sum */
-    c = mk(c.x * inv, c.y * inv, c.z * inv);
-    float out_r, out_g, out_b;
-    tone_map(c, out_r, out_g, out_b);
-    store_rgba8(RRT_MB_ARG(a.out), (size_t)oi, out_r, out_g, out_b);
-    float4* const hdr_out = RRT_MB_ARG(hdr_out);
-    if (hdr_out) hdr_out[oi] = make_float4(c.x, c.y, c.z, 1.0f);
-}
-
-/* Panorama (rrt_launch_raymarch_pano, include/rrt.h has the contract): supersample_pixels with the projection's primary ray
- * (rrt_projection.h: projection_dir, the source the host query runs too) instead of primary_ray -- the same waves over the virtual
- * grid, march, shading and pixel_sum butterfly.  The host clears use_lens and use_vignette (both are defined on the pinhole's uv).
- * A fisheye sub-sample outside the disc stays in its lanes -- pixel_sum shuffles across all of a pixel's lanes -- but branches
- * around the march and the shading with HDR exactly 0: its lane is masked off, so it adds no trips to the wave's vacuum loop and
- * takes no part in its ballots. */
-#include "rrt_projection.h"
-template <bool SPIN, int MEDIA, int ARITH>
-__global__ __launch_bounds__(kWGThreads, (MEDIA != 0 ? RRT_MEDIA_WAVES : 1))      /* raymarch_pixels' register budget */
-void panorama_pixels(const FrameArgs a, const int s, float4* const hdr_out, const ProjArgs pj) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int vx = tile_column(a) * kWGPixX + (wave & 1) * kTileW + (lane & (kTileW - 1));      /* virtual column */
-    const int vlr = row_block(a) * kWGPixY + (wave >> 1) * kTileH + lane / kTileW;              /* virtual local row */
-    const int w = a.width / s, h = a.height / s;
-    const int x = vx / s;
-    int y, out_row;
-    if (x >= w || !map_row(a.rows, h, vlr / s, y, out_row)) return;
-    const int vy = s * y + (vlr - (vlr / s) * s);
-    float d[3];
-    v3 c = mk(0.f, 0.f, 0.f);
-    if (projection_dir(pj, a.width, a.height, vx, vy, a.cam, d)) {
-        v3 p = mk(a.cam.pos[0], a.cam.pos[1], a.cam.pos[2]);
-        v3 vel = mk(d[0], d[1], d[2]);
-        if (__builtin_expect(a.nudge_ulps != 0, 0)) {     /* as primary_ray, on the virtual pixel */
-            vel.x = nudge_component(vel.x, a.nudge_ulps, a.nudge_seed, vx, vy, 0u);
-            vel.y = nudge_component(vel.y, a.nudge_ulps, a.nudge_seed, vx, vy, 1u);
-            vel.z = nudge_component(vel.z, a.nudge_ulps, a.nudge_seed, vx, vy, 2u);
-        }
-        Radiance acc = {0.f, 0.f, 0.f, 1.0f};
-        bool hit = false;
-        int i = 0;
-        march_inline<SPIN, MEDIA, ARITH, true>(a, p, vel, acc, hit, i, nullptr);
-        c = shade_hdr(a, 0.f, 0.f, hit, vel, acc);
-    }
-    pixel_sum(c, s);
-    if (((vx | vlr) & (s - 1)) != 0) return;            /* the pixel's first lane stores */
-    const float inv = 1.0f / (float)(s * s);            /* a power of two: the mean is exact given the sum */
-    c = mk(c.x * inv, c.y * inv, c.z * inv);
-    float out_r, out_g, out_b;
-    tone_map(c, out_r, out_g, out_b);
-    const size_t oi = (size_t)out_row * w + x;
-    store_rgba8(a.out, oi, out_r, out_g, out_b);
-    if (hdr_out) hdr_out[oi] = make_float4(c.x, c.y, c.z, 1.0f);
+    store_mean(c, 1.0f / (float)(s * s * RRT_MB_ARG(n_times)), RRT_MB_ARG(a.out), RRT_MB_ARG(hdr_out), (size_t)oi);
 }
 
 /* rrt_launch_projection_map: projection_dir of every pixel, (dir, inside) in the frame's bottom-up layout */

@@ -193,15 +193,23 @@ def main(argv=None):
         glow_scratch = torch.empty(rrt.glow_scratch_bytes(w, h, glow), dtype=torch.uint8, device=dev)
         glow_frame = torch.zeros(h * w * 4, dtype=torch.uint8, device=dev)
 
-    def render_glowed():
-        """the frame through _ss / _mb into glow_hdr, then the glow into glow_frame (bottom-up rows, not the tile layout)"""
-        prms[0].noise_table = state["table"]
+    def launch_sampled(buf, prm, hdr=None):
+        """the panorama / blurred / supersampled launch (_pano, _mb, _ss): the whole frame and its HDR when hdr is given, else
+        this rank's tiles"""
+        whole = hdr is not None
+        tiles = () if whole else (args.tile_rows, rank, world)
         if pano:
-            rrt.launch_raymarch_pano(glow_frame, w, h, ss, proj, state["t"], state["cam"], tex, fx, prms[0], hdr=glow_hdr)
+            launch, when = (rrt.launch_raymarch_pano if whole else rrt.launch_raymarch_pano_tiles), (proj, state["t"], state["cam"])
         elif mb > 1:
-            rrt.launch_raymarch_mb(glow_frame, w, h, ss, state["times"], state["cams"], tex, fx, prms[0], hdr=glow_hdr)
+            launch, when = (rrt.launch_raymarch_mb if whole else rrt.launch_raymarch_mb_tiles), (state["times"], state["cams"])
         else:
-            rrt.launch_raymarch_ss(glow_frame, w, h, ss, state["t"], state["cam"], tex, fx, prms[0], hdr=glow_hdr)
+            launch, when = (rrt.launch_raymarch_ss if whole else rrt.launch_raymarch_ss_tiles), (state["t"], state["cam"])
+        launch(buf, w, h, ss, *tiles, *when, tex, fx, prm, **({"hdr": hdr} if whole else {}))
+
+    def render_glowed():
+        """the frame through launch_sampled into glow_hdr, then the glow into glow_frame (bottom-up rows, not the tile layout)"""
+        prms[0].noise_table = state["table"]
+        launch_sampled(glow_frame, prms[0], hdr=glow_hdr)
         rrt.launch_glow(glow_frame, glow_hdr, w, h, glow, glow_scratch)
         return glow_frame
 
@@ -210,12 +218,8 @@ def main(argv=None):
         k = state["k"]
         if chooser is not None:
             prms[slot].path_policy = chooser.policy(k)
-        if pano:
-            rrt.launch_raymarch_pano_tiles(buf, w, h, ss, args.tile_rows, rank, world, proj, state["t"], state["cam"], tex, fx, prms[slot])
-        elif mb > 1:
-            rrt.launch_raymarch_mb_tiles(buf, w, h, ss, args.tile_rows, rank, world, state["times"], state["cams"], tex, fx, prms[slot])
-        elif ss > 1:
-            rrt.launch_raymarch_ss_tiles(buf, w, h, ss, args.tile_rows, rank, world, state["t"], state["cam"], tex, fx, prms[slot])
+        if pano or mb > 1 or ss > 1:
+            launch_sampled(buf, prms[slot])
         else:
             rrt.launch_raymarch_tiles(buf, w, h, args.tile_rows, rank, world, state["t"], state["cam"], tex, fx, prms[slot])
         if chooser is not None:
