@@ -523,6 +523,66 @@ int rrt_launch_raymarch_pano_tiles(void* d_out_tiles, int width, int height, int
                                    const rrt_camera* cam, rrt_sky_t sky, const rrt_effects* fx,
                                    const rrt_params* prm, void* stream);
 
+/* ---- stereo frames: omni-directional stereo (ODS) equirect pairs for headsets and off-axis pinhole pairs for 3D displays; no
+ *      counterpart in the reference.  width and height are PER EYE; the frame written is one RGBA8 composite of both eyes:
+ *        - RRT_STEREO_TOP_BOTTOM: width x 2 height; as displayed the left eye is on top, so with the usual bottom-up rows buffer
+ *          rows 0 ... height-1 hold the RIGHT eye and rows height ... 2 height-1 the left;
+ *        - RRT_STEREO_SIDE_BY_SIDE: 2 width x height, the left eye in columns 0 ... width-1.
+ *      Each eye's half is DEFINED as the mono frame of width x height -- rrt_launch_raymarch_ss's for RRT_PROJ_PINHOLE,
+ *      rrt_launch_raymarch_pano's for RRT_PROJ_EQUIRECT: the same virtual (s*width) x (s*height) grid, pairwise tree, 1/(s*s) and one
+ *      tone map; the EYE-LOCAL virtual pixel (x, y) feeds everything that depends on the pixel (projection, lens, vignette uv, the
+ *      nudge hash).  Only the primary ray changes: its origin and, for the pinhole, a shift of u.  Every operation binary32,
+ *      uncontracted, in the association written, the same in all three arithmetic modes; fw, rt, up, pos from cam:
+ *        - on the host: hb = (float)(0.5 * (double)base); e = -1 for the left eye, +1 for the right;
+ *        - EQUIRECT (ODS): the direction is rrt_launch_raymarch_pano's, bit for bit (lat, s_lon, c_lon its own values).  from and to
+ *          in radians, on the host: (float)((double)deg * 3.14159265358979323846 / 180.0).  a = fabsf(lat); f = 1 if a <= from, else
+ *          0 if a >= to, else (to - a) / (to - from); k = f * hb, negated for the left eye.  R_i = rt_i * c_lon - fw_i * s_lon (the
+ *          column's horizontal right-hand vector); origin_i = pos_i + R_i * k: every column looks from its own point on a circle of
+ *          radius hb, tangent to its viewing direction.  Lens and vignette are ignored, as in rrt_launch_raymarch_pano;
+ *        - PINHOLE (off-axis): origin_i = pos_i + rt_i * k with k = e*hb; the direction is the pinhole's primary ray on the eye's
+ *          frame (raymarcher.cu:20-34, the lens included) with u_coord = u_coord - c between u_coord *= aspect and forming D;
+ *          c = k / convergence, per eye on the host, 0 when convergence == 0 (parallel axes).  The eyes' rays cross convergence
+ *          units in front of the camera: the zero-parallax plane;
+ *        - zero rule: k == 0 (either sign) leaves the origin at pos with no addition, c == 0 leaves u_coord untouched.  So base = 0
+ *          gives each half the bytes of the mono frame, even for a signed-zero pos.
+ *      Bloom and chromatic aberration act per ray.  rrt_params honoured and ignored as in rrt_launch_raymarch_ss: a stereo launch is
+ *      always the single kernel in the static order.  d_hdr_rgba32f (may be NULL): the mean HDR in the composite's layout.
+ *      RRT_ERR_INVALID_ARGUMENT, before any device call: everything rrt_launch_raymarch_ss refuses for the COMPOSITE frame (its
+ *      virtual frame: (s*W)*(s*H) < 2^31, s*H <= 524 280 for W x H the composite), a NULL proj or st, the projection's refusals, a
+ *      fisheye (no stereo domes), an unknown layout, a negative or non-finite base or convergence, merge angles not
+ *      0 <= from <= to <= 90; RRT_ERR_ABI_MISMATCH for another struct_size of either struct.  No memset, no synchronisation: a
+ *      launch can be captured into a hipGraph. ---- */
+#define RRT_STEREO_TOP_BOTTOM 1     /* width x 2 height, left eye on top as displayed (buffer rows height ... 2 height-1) */
+#define RRT_STEREO_SIDE_BY_SIDE 2   /* 2 width x height, left eye on the left */
+#define RRT_EYE_LEFT 0
+#define RRT_EYE_RIGHT 1
+typedef struct rrt_stereo {
+    uint32_t struct_size;        /* sizeof(rrt_stereo): rrt_stereo_default sets it; any other value is RRT_ERR_ABI_MISMATCH */
+    int32_t layout;              /* RRT_STEREO_* */
+    float base;                  /* interaxial distance in scene units, >= 0 and finite */
+    float convergence;           /* pinhole: zero-parallax distance along forward, >= 0 (0 = parallel axes); equirect: finite >= 0, ignored */
+    float pole_merge_from_deg;   /* equirect: 0 <= from <= to <= 90; the eye separation fades linearly to 0 between the two */
+    float pole_merge_to_deg;     /*   latitudes (90, 90 = no fade); pinhole: checked, ignored */
+} rrt_stereo;
+/* base 1.0, convergence 0, pole merge 90 / 90: a look, not a measurement */
+int rrt_stereo_default(int layout, rrt_stereo* st);
+/* Host only: the primary ray of eye `eye`'s virtual pixel (x, y) of a width x height eye frame, before any nudge, from the source
+ * the kernel runs: origin_out, the unit direction dir_out, *inside_out (may be NULL) = 1.  The pinhole's direction is without the
+ * lens, as rrt_projection_ray's.  RRT_ERR_INVALID_ARGUMENT: the launch's refusals of proj and st, NULL cam, origin_out or dir_out,
+ * width or height <= 0, (x, y) outside the eye's frame, eye not RRT_EYE_*. */
+int rrt_stereo_ray(const rrt_projection* p, const rrt_stereo* st, int width, int height, int eye, int x, int y,
+                   const rrt_camera* cam, float origin_out[3], float dir_out[3], int* inside_out);
+int rrt_launch_raymarch_stereo(void* d_out_rgba8, float* d_hdr_rgba32f /* may be NULL */, int width, int height,
+                               int samples_per_axis, const rrt_projection* proj, const rrt_stereo* st, float time,
+                               const rrt_camera* cam, rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm, void* stream);
+/* The composite's row tiles of `shard` (tile t = the composite's OUTPUT rows [t*tile_rows, (t+1)*tile_rows)), in the buffer layout
+ * of rrt_launch_raymarch_ss_tiles: rrt_tile_shard_rows and rrt_assemble_(all_)tiles serve it unchanged, given the composite's
+ * width and height. */
+int rrt_launch_raymarch_stereo_tiles(void* d_out_tiles, int width, int height, int samples_per_axis, int tile_rows,
+                                     int shard, int n_shards, const rrt_projection* proj, const rrt_stereo* st, float time,
+                                     const rrt_camera* cam, rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm,
+                                     void* stream);
+
 /* ---- which path a rank's share takes while several frames of a sequence are in flight (host only; no GPU call) ----
  * New in this repo (the reference renders one frame at a time on one GPU: src/main.cpp:505-529).  A launch of <= 1.5 M rays
  * with a pool can take the three-pass path (RRT_PATH_AUTO) or the single kernel (RRT_PATH_SINGLE); under frames in flight the

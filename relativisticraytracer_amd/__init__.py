@@ -20,6 +20,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import RRTError, rrt_camera, rrt_debug_outputs, rrt_effects, rrt_glow, rrt_params, rrt_projection  # noqa: F401
+from ._lib import rrt_stereo  # noqa: F401
 
 __all__ = ["CameraState", "CameraEffects", "RenderParams", "SkyTexture", "Workspace", "NoiseTable", "launch_raymarch",
            "set_launch_defaults", "get_launch_defaults",
@@ -27,6 +28,7 @@ __all__ = ["CameraState", "CameraEffects", "RenderParams", "SkyTexture", "Worksp
            "launch_raymarch_ss", "launch_raymarch_ss_tiles", "launch_raymarch_mb", "launch_raymarch_mb_tiles",
            "GlowSettings", "glow_weights", "glow_scratch_bytes", "launch_glow",
            "Projection", "projection_default", "projection_ray", "launch_projection_map", "launch_raymarch_pano", "launch_raymarch_pano_tiles",
+           "Stereo", "stereo_default", "stereo_ray", "launch_raymarch_stereo", "launch_raymarch_stereo_tiles",
            "tile_shard_rows",
            "launch_raymarch_debug", "RRTError", "device_count", "abi_version", "TileOrder", "TileMap",
            "probe_tile_costs", "balance_tiles", "launch_raymarch_tilemap", "assemble_all_tilemap", "clock_probe", "clock_probe_ghz"]
@@ -181,6 +183,58 @@ def projection_ray(projection, w, h, x, y, cam):
     _lib.check(_lib.load().rrt_projection_ray(C.byref(projection), w, h, x, y, C.byref(cam), C.byref(d), C.byref(inside)),
                "rrt_projection_ray")
     return np.array(d[:], np.float32), bool(inside.value)
+
+
+STEREO_TOP_BOTTOM, STEREO_SIDE_BY_SIDE = 1, 2            # include/rrt.h: RRT_STEREO_*
+STEREO_LAYOUTS = {"top-bottom": STEREO_TOP_BOTTOM, "side-by-side": STEREO_SIDE_BY_SIDE}
+EYE_LEFT, EYE_RIGHT = 0, 1                                # RRT_EYE_*
+
+
+class Stereo(rrt_stereo):
+    """A stereo pair (include/rrt.h: rrt_stereo): layout "top-bottom" | "side-by-side" (or RRT_STEREO_*), base (interaxial
+    distance in scene units), convergence (pinhole: the zero-parallax distance, 0 = parallel axes) and pole_merge = (from, to) in
+    degrees of latitude (equirect: the eye separation fades to 0 between them; (90, 90) = no fade).  Defaults ==
+    rrt_stereo_default(layout); the values are checked by the calls that use them.  Width and height stay PER EYE everywhere."""
+
+    def __init__(self, layout="top-bottom", base=None, convergence=None, pole_merge=None):
+        super().__init__()
+        k = STEREO_LAYOUTS.get(layout, layout)
+        if not isinstance(k, int):
+            raise ValueError(f"stereo layout: one of {sorted(STEREO_LAYOUTS)}, got {layout!r}")
+        _lib.check(_lib.load().rrt_stereo_default(k, C.byref(self)), "rrt_stereo_default")
+        if base is not None:
+            self.base = float(base)
+        if convergence is not None:
+            self.convergence = float(convergence)
+        if pole_merge is not None:
+            self.pole_merge_from_deg, self.pole_merge_to_deg = (float(v) for v in pole_merge)
+
+    @property
+    def name(self):
+        return {v: k for k, v in STEREO_LAYOUTS.items()}.get(self.layout, str(self.layout))
+
+    def composite(self, w, h):
+        """(width, height) of the composite frame of w x h eyes"""
+        return (2 * w, h) if self.layout == STEREO_SIDE_BY_SIDE else (w, 2 * h)
+
+    def info(self):
+        return {"layout": self.name, "base": self.base, "convergence": self.convergence,
+                "pole_merge_deg": [self.pole_merge_from_deg, self.pole_merge_to_deg]}
+
+
+def stereo_default(layout):
+    """rrt_stereo_default: base 1, convergence 0, pole merge (90, 90) for a layout ("top-bottom" | "side-by-side" or RRT_STEREO_*)"""
+    return Stereo(layout)
+
+
+def stereo_ray(projection, stereo, w, h, eye, x, y, cam):
+    """(origin, unit direction, inside) as float32[3], float32[3], bool of eye `eye`'s (0 left, 1 right) virtual pixel (x, y) of a
+    w x h eye frame (rrt_stereo_ray, host only): the primary ray before any nudge, from the source the stereo kernel runs; the
+    pinhole's direction without the lens"""
+    o, d, inside = (C.c_float * 3)(), (C.c_float * 3)(), C.c_int(0)
+    _lib.check(_lib.load().rrt_stereo_ray(C.byref(projection), C.byref(stereo), w, h, eye, x, y, C.byref(cam), C.byref(o),
+                                          C.byref(d), C.byref(inside)), "rrt_stereo_ray")
+    return np.array(o[:], np.float32), np.array(d[:], np.float32), bool(inside.value)
 
 
 class SkyTexture:
@@ -591,6 +645,29 @@ def launch_raymarch_pano_tiles(d_out_tiles, w, h, samples, tile_rows, shard, n_s
                                                           C.byref(projection), float(time), C.byref(cam), _sky_handle(skyboxTex),
                                                           C.byref(effects), C.byref(params) if params is not None else None,
                                                           _stream(stream)), "rrt_launch_raymarch_pano_tiles")
+
+
+def launch_raymarch_stereo(d_out, w, h, samples, projection, stereo, time, cam, skyboxTex, effects, params=None, stream=None,
+                           hdr=None):
+    """samples x samples supersampled stereo composite of two w x h eyes (include/rrt.h: rrt_launch_raymarch_stereo): top-bottom
+    w x 2h (left eye on top as displayed: the upper stored rows) or side-by-side 2w x h (left eye on the left).  projection
+    "pinhole" (off-axis pair: launch_raymarch_ss's eyes) or "equirect" (omni-directional stereo: launch_raymarch_pano's eyes).
+    `hdr` (optional): the composite's mean HDR, 4 float32 per pixel."""
+    _lib.check(_lib.load().rrt_launch_raymarch_stereo(_ptr(d_out), _ptr(hdr), w, h, samples, C.byref(projection), C.byref(stereo),
+                                                      float(time), C.byref(cam), _sky_handle(skyboxTex), C.byref(effects),
+                                                      C.byref(params) if params is not None else None,
+                                                      _stream(stream)), "rrt_launch_raymarch_stereo")
+
+
+def launch_raymarch_stereo_tiles(d_out_tiles, w, h, samples, tile_rows, shard, n_shards, projection, stereo, time, cam, skyboxTex,
+                                 effects, params=None, stream=None):
+    """The row tiles of `shard` of launch_raymarch_stereo's composite (tiles of the COMPOSITE's rows), in launch_raymarch_tiles'
+    buffer layout: tile_shard_rows / assemble_tiles / assemble_all_tiles serve it given the composite's size."""
+    _lib.check(_lib.load().rrt_launch_raymarch_stereo_tiles(_ptr(d_out_tiles), w, h, samples, tile_rows, shard, n_shards,
+                                                            C.byref(projection), C.byref(stereo), float(time), C.byref(cam),
+                                                            _sky_handle(skyboxTex), C.byref(effects),
+                                                            C.byref(params) if params is not None else None,
+                                                            _stream(stream)), "rrt_launch_raymarch_stereo_tiles")
 
 
 def _sub_frames(times, cams):

@@ -70,6 +70,11 @@ class rrt_projection(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_int32), ("fov_deg", C.c_float), ("vfov_deg", C.c_float)]
 
 
+class rrt_stereo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("layout", C.c_int32), ("base", C.c_float), ("convergence", C.c_float),
+                ("pole_merge_from_deg", C.c_float), ("pole_merge_to_deg", C.c_float)]
+
+
 # every symbol include/rrt.h declares: (name, restype, argtypes)
 _vp, _i, _f, _ull = C.c_void_p, C.c_int, C.c_float, C.c_ulonglong
 _cam, _fx, _prm = C.POINTER(rrt_camera), C.POINTER(rrt_effects), C.POINTER(rrt_params)
@@ -132,6 +137,13 @@ SYMBOLS = [
     ("rrt_launch_raymarch_pano", _i, [_vp, _vp, _i, _i, _i, C.POINTER(rrt_projection), _f, _cam, _ull, _fx, _prm, _vp]),
     ("rrt_launch_projection_map", _i, [_vp, _i, _i, C.POINTER(rrt_projection), _cam, _vp]),
     ("rrt_launch_raymarch_pano_tiles", _i, [_vp, _i, _i, _i, _i, _i, _i, C.POINTER(rrt_projection), _f, _cam, _ull, _fx, _prm, _vp]),
+    ("rrt_stereo_default", _i, [_i, C.POINTER(rrt_stereo)]),
+    ("rrt_stereo_ray", _i, [C.POINTER(rrt_projection), C.POINTER(rrt_stereo), _i, _i, _i, _i, _i, _cam, C.POINTER(_f * 3),
+                            C.POINTER(_f * 3), C.POINTER(_i)]),
+    ("rrt_launch_raymarch_stereo", _i, [_vp, _vp, _i, _i, _i, C.POINTER(rrt_projection), C.POINTER(rrt_stereo), _f, _cam, _ull, _fx,
+                                        _prm, _vp]),
+    ("rrt_launch_raymarch_stereo_tiles", _i, [_vp, _i, _i, _i, _i, _i, _i, C.POINTER(rrt_projection), C.POINTER(rrt_stereo), _f,
+                                              _cam, _ull, _fx, _prm, _vp]),
     ("rrt_tile_shard_rows", _i, [_i, _i, _i, _i, C.POINTER(_i)]),
     ("rrt_assemble_tiles", _i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     ("rrt_assemble_all_tiles", _i, [_vp, _vp, C.c_size_t, _i, _i, _i, _i, _vp]),

@@ -17,6 +17,10 @@
 //                [--projection pinhole|equirect|fisheye [--fov DEG] [--vfov DEG]]   (panoramas: rrt_launch_raymarch_pano*, single
 //                                              kernel, no pool; equirect --fov 360 --vfov 180, fisheye --fov 180 (aperture); not with
 //                                              --motion-blur > 1, equirect not with --glow)
+//                [--stereo top-bottom|side-by-side [--stereo-base B] [--convergence Z] [--pole-merge FROM TO]]   (a stereo pair
+//                                              per frame: rrt_launch_raymarch_stereo*, single kernel, no pool; --width / --height per
+//                                              eye, the composite is written; pinhole (off-axis) or equirect (ODS); not with fisheye,
+//                                              --motion-blur > 1 or --glow; --convergence pinhole only, --pole-merge equirect only)
 //
 // Noise tables: the reference's simTime runs without bound (main.cpp:515) and a table's size grows with the times
 // it covers, so each device keeps ONE table over a window of the clock that fits --noise-table-gib (default 2;
@@ -246,6 +250,10 @@ int main(int argc, char** argv) {
     bool use_glow = false;
     int projection = RRT_PROJ_PINHOLE;   // --projection: the camera (rrt_launch_raymarch_pano* for equirect / fisheye)
     float fov = 0.0f, vfov = 0.0f;       // --fov / --vfov DEG (0: not given -- the kind's default, rrt_projection_default)
+    int stereo_layout = 0;               // --stereo: RRT_STEREO_* (0: mono); rrt_launch_raymarch_stereo*
+    bool stereo_base = false, stereo_conv = false, stereo_merge = false;   // which of the stereo options were given
+    rrt_stereo stereo;                   // --stereo-base / --convergence / --pole-merge over rrt_stereo_default
+    rrt_stereo_default(RRT_STEREO_TOP_BOTTOM, &stereo);
     int kSlots = 3;                // frames in flight: frame k renders on stream k mod kSlots while its predecessors are
                                    // gathered / assembled / copied out (a rank's share of a frame is only a few rounds of
                                    // wavefronts; 3 measured best at 8 shards of a 4K frame: profiles/r02_frames_in_flight.txt)
@@ -319,6 +327,24 @@ int main(int argc, char** argv) {
             (a == "--fov" ? fov : vfov) = v;
             if (v == 0.0f) { fprintf(stderr, "--fov DEG in (0, 360], --vfov DEG in (0, 180]\n"); return 2; }
         }
+        else if (a == "--stereo") {
+            const std::string m = i + 1 < argc ? argv[++i] : "";
+            if (m == "top-bottom") stereo_layout = RRT_STEREO_TOP_BOTTOM; else if (m == "side-by-side") stereo_layout = RRT_STEREO_SIDE_BY_SIDE;
+            else { fprintf(stderr, "usage: --stereo top-bottom | side-by-side\n"); return 2; }
+        }
+        else if (a == "--stereo-base" || a == "--convergence" || a == "--pole-merge") {
+            float v[2];
+            const int n = a == "--pole-merge" ? 2 : 1;
+            for (int j = 0; j < n; ++j) {
+                const char* m = i + 1 < argc ? argv[++i] : "";
+                char* end = nullptr;
+                v[j] = strtof(m, &end);
+                if (end == m || *end != 0) { fprintf(stderr, "usage: %s: a number\n", a.c_str()); return 2; }
+            }
+            if (a == "--stereo-base") { stereo.base = v[0]; stereo_base = true; }
+            else if (a == "--convergence") { stereo.convergence = v[0]; stereo_conv = true; }
+            else { stereo.pole_merge_from_deg = v[0]; stereo.pole_merge_to_deg = v[1]; stereo_merge = true; }
+        }
         else if (a == "--arith" && i + 1 < argc) {
             const std::string m = argv[++i];
             if (m == "strict") arith = RRT_ARITH_STRICT; else if (m == "fmad") arith = RRT_ARITH_FMAD; else if (m == "fast") arith = RRT_ARITH_FAST;
@@ -359,8 +385,29 @@ int main(int argc, char** argv) {
             return 2;
         }
     }
+    // stereo: the values are checked by the host query (the launch's own refusals), the combinations the kernel lacks up front;
+    // --width / --height stay per eye (ew x eh, what the launch takes), w x h becomes the composite that is sharded and written
+    const bool use_stereo = stereo_layout != 0;
+    const int ew = w, eh = h;
+    if (!use_stereo && (stereo_base || stereo_conv || stereo_merge)) {
+        fprintf(stderr, "usage: --stereo-base / --convergence / --pole-merge need --stereo top-bottom | side-by-side\n"); return 2;
+    }
+    if (use_stereo) {
+        stereo.layout = stereo_layout;
+        if (projection == RRT_PROJ_FISHEYE) { fprintf(stderr, "usage: --stereo: pinhole or equirect (no stereo fisheye domes)\n"); return 2; }
+        if (motion > 1) { fprintf(stderr, "usage: --stereo renders one instant per frame (--motion-blur 1)\n"); return 2; }
+        if (use_glow) { fprintf(stderr, "usage: --stereo: not with --glow\n"); return 2; }
+        if (stereo_conv && projection != RRT_PROJ_PINHOLE) { fprintf(stderr, "usage: --convergence: pinhole only\n"); return 2; }
+        if (stereo_merge && projection != RRT_PROJ_EQUIRECT) { fprintf(stderr, "usage: --pole-merge: equirect only\n"); return 2; }
+        const rrt_camera c0 = {};
+        float o[3], d[3];
+        if (rrt_stereo_ray(&proj, &stereo, 1, 1, RRT_EYE_LEFT, 0, 0, &c0, o, d, nullptr) != RRT_OK) {
+            fprintf(stderr, "usage: --stereo-base B >= 0, --convergence Z >= 0, --pole-merge FROM TO with 0 <= FROM <= TO <= 90\n"); return 2;
+        }
+        if (stereo_layout == RRT_STEREO_SIDE_BY_SIDE) w = 2 * ew; else h = 2 * eh;
+    }
     // a supersampled launch is always the single kernel in the static order (include/rrt.h): no pool, no path choice, no tile order
-    if (supersample > 1 || motion > 1 || use_glow || pano) { workspace_gib = 0; path_window = -1; tile_order = 0; }
+    if (supersample > 1 || motion > 1 || use_glow || pano || use_stereo) { workspace_gib = 0; path_window = -1; tile_order = 0; }
     int n_dev = 0, rc;
     if ((rc = rrt_device_count(&n_dev)) != RRT_OK) return fail("no GPU", rc);
     if (gpus > n_dev) { fprintf(stderr, "rrt_headless: --gpus %d but %d device(s) visible\n", gpus, n_dev); return 2; }
@@ -583,8 +630,11 @@ int main(int argc, char** argv) {
             if (D.chooser) { int pol = RRT_PATH_AUTO; rrt_path_chooser_policy(D.chooser, k, &pol); prm.path_policy = pol; }
             else if (path_policy >= 0) prm.path_policy = path_policy;
             void* dst = collective ? D.tiles[slot] : frame[slot];
-            // the panorama / blurred / supersampled launch (_pano, _mb, _ss): this device's tiles, or the whole frame and its HDR (may be NULL)
+            // the stereo / panorama / blurred / supersampled launch (_stereo, _pano, _mb, _ss): this device's tiles, or the whole frame and
+            // its HDR (may be NULL)
             auto launch_sampled = [&](bool tiles, float* lin) {
+                if (use_stereo) return tiles ? rrt_launch_raymarch_stereo_tiles(dst, ew, eh, supersample, tile_rows, d, gpus, &proj, &stereo, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot])
+                                             : rrt_launch_raymarch_stereo(dst, lin, ew, eh, supersample, &proj, &stereo, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
                 if (pano) return tiles ? rrt_launch_raymarch_pano_tiles(dst, w, h, supersample, tile_rows, d, gpus, &proj, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot])
                                        : rrt_launch_raymarch_pano(dst, lin, w, h, supersample, &proj, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
                 if (motion > 1) return tiles ? rrt_launch_raymarch_mb_tiles(dst, w, h, supersample, tile_rows, d, gpus, motion, sub_t, sub_cam, D.sky, &fx, &prm, D.stream[slot])
@@ -597,7 +647,7 @@ int main(int argc, char** argv) {
                 rc = launch_sampled(false, lin);
                 if (rc == RRT_OK) rc = rrt_launch_glow(dst, lin, w, h, &glow, glow_scratch[slot], glow_bytes, D.stream[slot]);
             }
-            else if (pano || motion > 1 || supersample > 1) rc = launch_sampled(collective, nullptr);
+            else if (use_stereo || pano || motion > 1 || supersample > 1) rc = launch_sampled(collective, nullptr);
             else if (collective) rc = rrt_launch_raymarch_tiles(dst, w, h, tile_rows, d, gpus, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
             else rc = rrt_launch_raymarch(dst, w, h, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
             if (rc != RRT_OK) return fail("launch", rc);
@@ -661,16 +711,24 @@ int main(int argc, char** argv) {
     char fov_json[32] = "null", vfov_json[32] = "null";
     if (pano) snprintf(fov_json, sizeof(fov_json), "%g", proj.fov_deg);
     if (projection == RRT_PROJ_EQUIRECT) snprintf(vfov_json, sizeof(vfov_json), "%g", proj.vfov_deg);
+    std::string stereo_json = "null";
+    if (use_stereo) {
+        char buf[200];
+        snprintf(buf, sizeof(buf), "{\"layout\": \"%s\", \"base\": %.17g, \"convergence\": %.17g, \"pole_merge_deg\": [%.17g, %.17g]}",
+                 stereo_layout == RRT_STEREO_TOP_BOTTOM ? "top-bottom" : "side-by-side", stereo.base, stereo.convergence,
+                 stereo.pole_merge_from_deg, stereo.pole_merge_to_deg);
+        stereo_json = buf;
+    }
     printf("{\"frames\": %d, \"width\": %d, \"height\": %d, \"n_gpus\": %d, \"seconds\": %.4f, \"fps\": %.3f, \"Mrays_per_s\": %.3f, "
            "\"path\": \"%s\", \"spin\": %g, \"arith_mode\": \"%s\", \"noise_tables\": {\"builds\": %d, \"table_frames\": %d, "
            "\"arith_frames\": %d, \"coarsest_coverage\": %d, \"peak_bytes\": %zu, \"budget_bytes\": %zu}, \"tile_order\": %s, \"collective\": \"%s\", "
            "\"path_choice\": %s, \"supersample\": %d, \"motion_blur\": %d, \"shutter\": %g, \"glow\": %s, "
-           "\"projection\": \"%s\", \"fov_deg\": %s, \"vfov_deg\": %s}\n",
+           "\"projection\": \"%s\", \"fov_deg\": %s, \"vfov_deg\": %s, \"stereo\": %s}\n",
            frames, w, h, gpus, dt, frames / dt, (double)frames * w * h / dt / 1e6, path_name, spin,
            arith == RRT_ARITH_FAST ? "fast" : (arith == RRT_ARITH_FMAD ? "fmad" : "strict"),
            table_builds, table_frames, arith_frames, coarsest, table_peak, table_budget, dev[0].order[0] ? "true" : "false",
            collective ? "rccl grouped send/recv gather" : "none", choice.c_str(), supersample, motion, shutter, glow_json.c_str(),
-           proj_name, fov_json, vfov_json);
+           proj_name, fov_json, vfov_json, stereo_json.c_str());
 
     for (int d = 0; d < gpus; ++d) {
         Device& D = dev[d];

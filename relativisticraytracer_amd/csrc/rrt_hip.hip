@@ -20,6 +20,7 @@
 
 #include <atomic>
 #include <memory>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -557,7 +558,7 @@ int launch(const FrameArgs& a, const LaunchOpts& o, bool debug, hipStream_t st) 
     return RRT_OK;
 }
 
-/* ---- sampled launches (rrt_launch_raymarch_ss*, _mb*, _pano*): one kernel over the virtual (s w) x (s h) frame, static order */
+/* ---- sampled launches (rrt_launch_raymarch_ss*, _mb*, _pano*, _stereo*): one kernel over the virtual (s w) x (s h) frame, static order */
 bool valid_samples(int s) { return s == 1 || s == 2 || s == 4 || s == 8; }
 
 /* the checks of check_common plus the virtual (s w) x (s h) frame's limits; all before any device call */
@@ -665,20 +666,74 @@ int check_pano(const void* out, int width, int height, int s, const rrt_projecti
     return check_ss(out, width, height, s, cam, fx, prm);
 }
 
-/* A supersampled frame (proj NULL or a pinhole: supersample_pixels), or a panorama (panorama_pixels: projection_dir instead of
- * primary_ray; the lens and the vignette are cleared, the contract ignores them) */
+/* ---- stereo frames (rrt_launch_raymarch_stereo*, rrt_stereo_ray): both eyes' supersampled frames in one composite */
+bool valid_layout(int layout) { return layout == RRT_STEREO_TOP_BOTTOM || layout == RRT_STEREO_SIDE_BY_SIDE; }
+
+/* the refusals of the projection (no fisheye) and of the stereo settings (include/rrt.h) */
+int check_stereo(const rrt_projection* p, const rrt_stereo* st) {
+    int rc = check_projection(p);
+    if (rc != RRT_OK) return rc;
+    if (p->kind == RRT_PROJ_FISHEYE || !st) return RRT_ERR_INVALID_ARGUMENT;
+    if (st->struct_size != (uint32_t)sizeof(rrt_stereo)) return RRT_ERR_ABI_MISMATCH;
+    if (!valid_layout(st->layout)) return RRT_ERR_INVALID_ARGUMENT;
+    if (!std::isfinite(st->base) || !(st->base >= 0.0f) || !std::isfinite(st->convergence) || !(st->convergence >= 0.0f))
+        return RRT_ERR_INVALID_ARGUMENT;
+    const float from = st->pole_merge_from_deg, to = st->pole_merge_to_deg;
+    if (!std::isfinite(from) || !std::isfinite(to) || !(from >= 0.0f) || !(from <= to) || !(to <= 90.0f)) return RRT_ERR_INVALID_ARGUMENT;
+    return RRT_OK;
+}
+/* the composite's output size of a width x height eye (false: it does not fit an int) */
+bool composite_size(const rrt_stereo& st, int width, int height, int& cw, int& ch) {
+    const long long w = (long long)width * (st.layout == RRT_STEREO_SIDE_BY_SIDE ? 2 : 1);
+    const long long h = (long long)height * (st.layout == RRT_STEREO_TOP_BOTTOM ? 2 : 1);
+    if (w > INT_MAX || h > INT_MAX) return false;
+    cw = (int)w; ch = (int)h;
+    return true;
+}
+/* the checks of check_stereo, then check_ss on the composite; all before any device call */
+int check_stereo_launch(const void* out, int width, int height, int s, const rrt_projection* proj, const rrt_stereo* st,
+                        const rrt_camera* cam, const rrt_effects* fx, const rrt_params* prm, int& cw, int& ch) {
+    const int rc = check_stereo(proj, st);
+    if (rc != RRT_OK) return rc;
+    if (width <= 0 || height <= 0 || !composite_size(*st, width, height, cw, ch)) return RRT_ERR_INVALID_ARGUMENT;
+    return check_ss(out, cw, ch, s, cam, fx, prm);
+}
+/* the kernel's constants of an eye's (s w) x (s h) virtual frame: hb, the merge latitudes and the pinhole's k and c per eye, all
+ * rounded on the host (include/rrt.h) */
+StereoArgs stereo_args(const rrt_stereo& st, int eye_w, int eye_h) {
+    StereoArgs sa;
+    sa.W = eye_w; sa.H = eye_h;
+    sa.right_x = st.layout == RRT_STEREO_SIDE_BY_SIDE ? eye_w : 0;
+    sa.right_y = st.layout == RRT_STEREO_TOP_BOTTOM ? eye_h : 0;
+    sa.hb = (float)(0.5 * (double)st.base);
+    sa.from = (float)((double)st.pole_merge_from_deg * 3.14159265358979323846 / 180.0);
+    sa.to = (float)((double)st.pole_merge_to_deg * 3.14159265358979323846 / 180.0);
+    sa.k_left = -sa.hb; sa.k_right = sa.hb;
+    sa.c_left = st.convergence != 0.0f ? sa.k_left / st.convergence : 0.0f;
+    sa.c_right = st.convergence != 0.0f ? sa.k_right / st.convergence : 0.0f;
+    return sa;
+}
+
+/* A supersampled frame (proj NULL or a pinhole: supersample_pixels), a panorama (panorama_pixels: projection_dir instead of
+ * primary_ray; the lens and the vignette are cleared, the contract ignores them), or -- stereo not NULL -- a stereo composite of
+ * width x height eyes (stereo_pixels; `rows` in the composite's output rows; equirect clears the lens and the vignette too) */
 int launch_ss(void* out, float4* hdr, int width, int height, int s, const RowMap& rows, const rrt_projection* proj, float time,
-              const rrt_camera* cam, rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm_in, hipStream_t st) {
+              const rrt_camera* cam, rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm_in, hipStream_t st,
+              const rrt_stereo* stereo = nullptr) {
     FrameArgs a;
     LaunchOpts o;
     dim3 grid;
-    const int rc = sampled_args(a, o, grid, out, width, height, s, rows, time, time, cam, sky, fx, prm_in);
+    int cw = width, ch = height;
+    if (stereo && !composite_size(*stereo, width, height, cw, ch)) return RRT_ERR_INVALID_ARGUMENT;
+    const int rc = sampled_args(a, o, grid, out, cw, ch, s, rows, time, time, cam, sky, fx, prm_in);
     if (rc || grid.y == 0) return rc;
     const bool pano = proj && proj->kind != RRT_PROJ_PINHOLE;
-    const ProjArgs pj = pano ? proj_args(*proj) : ProjArgs{};
+    const ProjArgs pj = pano || stereo ? proj_args(*proj) : ProjArgs{};
+    const StereoArgs sa = stereo ? stereo_args(*stereo, s * width, s * height) : StereoArgs{};
     if (pano) { a.use_lens = 0; a.use_vignette = 0; }
     dispatch_kernel(a.spin != 0.0f, o.media, o.arith, [&](auto S, auto M, auto F) {
-        if (pano) hipLaunchKernelGGL((panorama_pixels<S, M, F>), grid, dim3(kWGThreads), 0, st, a, s, hdr, pj);
+        if (stereo) hipLaunchKernelGGL((stereo_pixels<S, M, F>), grid, dim3(kWGThreads), 0, st, a, s, hdr, pj, sa);
+        else if (pano) hipLaunchKernelGGL((panorama_pixels<S, M, F>), grid, dim3(kWGThreads), 0, st, a, s, hdr, pj);
         else hipLaunchKernelGGL((supersample_pixels<S, M, F>), grid, dim3(kWGThreads), 0, st, a, s, hdr);
     });
     RRT_HIP(hipGetLastError());
@@ -1778,6 +1833,53 @@ int rrt_launch_raymarch_pano_tiles(void* d_out_tiles, int width, int height, int
     if ((rc = shard_map(height, tile_rows, shard, n_shards, rows))) return rc;
     return launch_ss(d_out_tiles, nullptr, width, height, samples_per_axis, rows, proj, time, cam, sky, fx, prm,
                      static_cast<hipStream_t>(stream));
+}
+
+int rrt_stereo_default(int layout, rrt_stereo* st) {
+    if (!st || !valid_layout(layout)) return RRT_ERR_INVALID_ARGUMENT;
+    st->struct_size = (uint32_t)sizeof(rrt_stereo);
+    st->layout = layout;
+    st->base = 1.0f;
+    st->convergence = 0.0f;
+    st->pole_merge_from_deg = 90.0f;
+    st->pole_merge_to_deg = 90.0f;
+    return RRT_OK;
+}
+
+int rrt_stereo_ray(const rrt_projection* p, const rrt_stereo* st, int width, int height, int eye, int x, int y,
+                   const rrt_camera* cam, float origin_out[3], float dir_out[3], int* inside_out) {
+    const int rc = check_stereo(p, st);
+    if (rc) return rc;
+    if (!cam || !origin_out || !dir_out || width <= 0 || height <= 0 || x < 0 || x >= width || y < 0 || y >= height ||
+        (eye != RRT_EYE_LEFT && eye != RRT_EYE_RIGHT))
+        return RRT_ERR_INVALID_ARGUMENT;
+    float uvx, uvy;
+    stereo_ray(proj_args(*p), stereo_args(*st, width, height), eye, x, y, *cam, 0, 0.0f, origin_out, dir_out, uvx, uvy);
+    if (inside_out) *inside_out = 1;
+    return RRT_OK;
+}
+
+int rrt_launch_raymarch_stereo(void* d_out_rgba8, float* d_hdr_rgba32f, int width, int height, int samples_per_axis,
+                               const rrt_projection* proj, const rrt_stereo* st, float time, const rrt_camera* cam, rrt_sky_t sky,
+                               const rrt_effects* fx, const rrt_params* prm, void* stream) {
+    int cw, ch;
+    const int rc = check_stereo_launch(d_out_rgba8, width, height, samples_per_axis, proj, st, cam, fx, prm, cw, ch);
+    if (rc) return rc;
+    return launch_ss(d_out_rgba8, reinterpret_cast<float4*>(d_hdr_rgba32f), width, height, samples_per_axis, frame_rows(ch),
+                     proj, time, cam, sky, fx, prm, static_cast<hipStream_t>(stream), st);
+}
+
+int rrt_launch_raymarch_stereo_tiles(void* d_out_tiles, int width, int height, int samples_per_axis, int tile_rows, int shard,
+                                     int n_shards, const rrt_projection* proj, const rrt_stereo* st, float time,
+                                     const rrt_camera* cam, rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm,
+                                     void* stream) {
+    int cw, ch;
+    int rc = check_stereo_launch(d_out_tiles, width, height, samples_per_axis, proj, st, cam, fx, prm, cw, ch);
+    if (rc) return rc;
+    RowMap rows;
+    if ((rc = shard_map(ch, tile_rows, shard, n_shards, rows))) return rc;
+    return launch_ss(d_out_tiles, nullptr, width, height, samples_per_axis, rows, proj, time, cam, sky, fx, prm,
+                     static_cast<hipStream_t>(stream), st);
 }
 
 #ifdef RRT_TEST_HOOKS

@@ -697,11 +697,13 @@ __device__ __forceinline__ void store_mean(v3 c, float inv, uchar4* out, float4*
     if (hdr_out) hdr_out[oi] = make_float4(c.x, c.y, c.z, 1.0f);
 }
 
-/* supersample_pixels (PROJ = false) and panorama_pixels (PROJ = true): the same waves, march, shading and butterfly; only the
- * primary ray differs */
+/* supersample_pixels (kRayPinhole), panorama_pixels (kRayProjection) and stereo_pixels (kRayStereo): the same waves, march,
+ * shading and butterfly; only the primary ray differs */
 #include "rrt_projection.h"
-template <bool SPIN, int MEDIA, int ARITH, bool PROJ>
-__device__ __forceinline__ void sampled_pixels(const FrameArgs& a, const int s, float4* const hdr_out, const ProjArgs& pj) {
+enum SampledRay { kRayPinhole, kRayProjection, kRayStereo };
+template <bool SPIN, int MEDIA, int ARITH, SampledRay RAY>
+__device__ __forceinline__ void sampled_pixels(const FrameArgs& a, const int s, float4* const hdr_out, const ProjArgs& pj,
+                                               const StereoArgs& sa) {
     SampleLane l;
     if (!sample_lane(a, s, l)) return;
     const auto march_shade = [&](v3 p, v3 vel, float uvx, float uvy) {
@@ -712,7 +714,20 @@ __device__ __forceinline__ void sampled_pixels(const FrameArgs& a, const int s, 
         return shade_hdr(a, uvx, uvy, hit, vel, acc);
     };
     v3 c = mk(0.f, 0.f, 0.f);
-    if constexpr (PROJ) {
+    if constexpr (RAY == kRayStereo) {
+        /* the lane's eye from its composite virtual pixel, then the eye-local pixel every pixel-dependent term sees */
+        const bool right = l.vx >= sa.right_x && l.vy >= sa.right_y;
+        const int x = right ? l.vx - sa.right_x : l.vx, y = right ? l.vy - sa.right_y : l.vy;
+        float o[3], d[3], uvx, uvy;
+        stereo_ray(pj, sa, right ? RRT_EYE_RIGHT : RRT_EYE_LEFT, x, y, a.cam, a.use_lens, a.distortion_amount, o, d, uvx, uvy);
+        v3 vel = mk(d[0], d[1], d[2]);
+        if (__builtin_expect(a.nudge_ulps != 0, 0)) {         /* as primary_ray, on the eye-local virtual pixel */
+            vel.x = nudge_component(vel.x, a.nudge_ulps, a.nudge_seed, x, y, 0u);
+            vel.y = nudge_component(vel.y, a.nudge_ulps, a.nudge_seed, x, y, 1u);
+            vel.z = nudge_component(vel.z, a.nudge_ulps, a.nudge_seed, x, y, 2u);
+        }
+        c = march_shade(mk(o[0], o[1], o[2]), vel, uvx, uvy);
+    } else if constexpr (RAY == kRayProjection) {
         float d[3];
         if (projection_dir(pj, a.width, a.height, l.vx, l.vy, a.cam, d)) {     /* outside the disc: HDR exactly 0, no march */
             v3 vel = mk(d[0], d[1], d[2]);
@@ -737,7 +752,7 @@ __device__ __forceinline__ void sampled_pixels(const FrameArgs& a, const int s, 
 template <bool SPIN, int MEDIA, int ARITH>
 __global__ __launch_bounds__(kWGThreads, (MEDIA != 0 ? RRT_MEDIA_WAVES : 1))      /* raymarch_pixels' register budget */
 void supersample_pixels(const FrameArgs a, const int s, float4* const hdr_out) {
-    sampled_pixels<SPIN, MEDIA, ARITH, false>(a, s, hdr_out, ProjArgs{});
+    sampled_pixels<SPIN, MEDIA, ARITH, kRayPinhole>(a, s, hdr_out, ProjArgs{}, StereoArgs{});
 }
 
 /* Panorama (rrt_launch_raymarch_pano, include/rrt.h has the contract): supersample_pixels with the projection's primary ray
@@ -749,7 +764,19 @@ void supersample_pixels(const FrameArgs a, const int s, float4* const hdr_out) {
 template <bool SPIN, int MEDIA, int ARITH>
 __global__ __launch_bounds__(kWGThreads, (MEDIA != 0 ? RRT_MEDIA_WAVES : 1))      /* raymarch_pixels' register budget */
 void panorama_pixels(const FrameArgs a, const int s, float4* const hdr_out, const ProjArgs pj) {
-    sampled_pixels<SPIN, MEDIA, ARITH, true>(a, s, hdr_out, pj);
+    sampled_pixels<SPIN, MEDIA, ARITH, kRayProjection>(a, s, hdr_out, pj, StereoArgs{});
+}
+
+/* Stereo (rrt_launch_raymarch_stereo, include/rrt.h has the contract): supersample_pixels over the COMPOSITE virtual frame (a.width
+ * x a.height: both eyes; a.rows maps the composite's output rows), each lane's ray from stereo_ray (rrt_projection.h, the source
+ * the host query runs too) on its eye-local pixel.  A pixel's s x s sub-samples lie in one eye (the eye boundary is a whole output
+ * pixel), so the butterfly is unchanged.  The eye is uniform across a wave when the boundary (s*height rows, or s*width columns)
+ * is a multiple of 8 virtual pixels; otherwise the wave that straddles it is split per lane -- coherence, not correctness.  For
+ * equirect the host clears use_lens and use_vignette, as for panorama_pixels. */
+template <bool SPIN, int MEDIA, int ARITH>
+__global__ __launch_bounds__(kWGThreads, (MEDIA != 0 ? RRT_MEDIA_WAVES : 1))      /* raymarch_pixels' register budget */
+void stereo_pixels(const FrameArgs a, const int s, float4* const hdr_out, const ProjArgs pj, const StereoArgs sa) {
+    sampled_pixels<SPIN, MEDIA, ARITH, kRayStereo>(a, s, hdr_out, pj, sa);
 }
 
 /* Motion-blurred frame (rrt_launch_raymarch_mb, include/rrt.h has the contract): sub-frame k is supersample_pixels' frame at

@@ -4,6 +4,7 @@
            --path 0 --frames 300 [--out frames.rgba | --out ppm_dir/] [--all-effects] [--supersample 2] [--motion-blur 4 --shutter 0.5]
            [--glow 0.25 [--glow-radius 0.004] [--glow-threshold 1.0] [--glow-lobes 4]]
            [--projection pinhole|equirect|fisheye [--fov DEG] [--vfov DEG]]
+           [--stereo top-bottom|side-by-side [--stereo-base B] [--convergence Z] [--pole-merge FROM TO]]
     python -m torch.distributed.run --nproc-per-node 8 -m relativisticraytracer_amd.headless ...
 
 Per frame k = 1..N it does what `main()` does while recording: advance the fixed 1/24 s clock
@@ -73,6 +74,18 @@ def main(argv=None):
     ap.add_argument("--fov", type=float, default=None, metavar="DEG",
                     help="equirect: horizontal span in (0, 360], default 360; fisheye: aperture in (0, 360], default 180")
     ap.add_argument("--vfov", type=float, default=None, metavar="DEG", help="equirect: vertical span in (0, 180], default 180")
+    ap.add_argument("--stereo", choices=("top-bottom", "side-by-side"), default=None,
+                    help="a stereo pair per frame (rrt_launch_raymarch_stereo*): --width / --height per eye, written as one composite "
+                         "(top-bottom: width x 2 height, left eye on top; side-by-side: 2 width x height, left eye on the left).  "
+                         "pinhole: off-axis pair; equirect: omni-directional stereo.  Single kernel, static order; not with fisheye, "
+                         "--motion-blur > 1 or --glow")
+    ap.add_argument("--stereo-base", type=float, default=None, metavar="B",
+                    help="with --stereo: the interaxial distance in scene units, >= 0 (default 1)")
+    ap.add_argument("--convergence", type=float, default=None, metavar="Z",
+                    help="with --stereo, pinhole only: the zero-parallax distance along forward, >= 0 (default 0: parallel axes)")
+    ap.add_argument("--pole-merge", type=float, nargs=2, default=None, metavar=("FROM", "TO"),
+                    help="with --stereo, equirect only: the eye separation fades to 0 between these latitudes in degrees, "
+                         "0 <= FROM <= TO <= 90 (default 90 90: no fade)")
     ap.add_argument("--out", default=None, help="x.rgba (raw, bottom-up) | dir/ (PPM per frame) | x.mp4 (needs ffmpeg)")
     ap.add_argument("--init-timeout", type=float, default=300.0,
                     help="several ranks: seconds the process-group bring-up may take before the run exits non-zero with "
@@ -93,6 +106,20 @@ def main(argv=None):
         ap.error("a panorama renders one instant per frame (--motion-blur 1)")
     if args.projection == "equirect" and args.glow is not None:
         ap.error("--glow clamps at the frame's edge and an equirect frame wraps: not with --projection equirect")
+    stereo_opts = args.stereo_base is not None or args.convergence is not None or args.pole_merge is not None
+    if args.stereo is None and stereo_opts:
+        ap.error("--stereo-base / --convergence / --pole-merge need --stereo top-bottom | side-by-side")
+    if args.stereo is not None:
+        if args.projection == "fisheye":
+            ap.error("--stereo: pinhole or equirect (no stereo fisheye domes)")
+        if args.motion_blur > 1:
+            ap.error("--stereo renders one instant per frame (--motion-blur 1)")
+        if args.glow is not None:
+            ap.error("--stereo: not with --glow")
+        if args.convergence is not None and args.projection != "pinhole":
+            ap.error("--convergence: pinhole only")
+        if args.pole_merge is not None and args.projection != "equirect":
+            ap.error("--pole-merge: equirect only")
 
     t_start = time.perf_counter()
 
@@ -119,6 +146,13 @@ def main(argv=None):
             rrt.projection_ray(proj, 1, 1, 0, 0, rrt.CameraState())
         except rrt.RRTError:
             ap.error("--fov DEG in (0, 360], --vfov DEG in (0, 180]")
+    stereo = None
+    if args.stereo is not None:     # the values' checks are the host query's (rrt_stereo_ray): the launch's own refusals
+        stereo = rrt.Stereo(args.stereo, args.stereo_base, args.convergence, args.pole_merge)
+        try:
+            rrt.stereo_ray(proj if proj is not None else rrt.Projection("pinhole"), stereo, 1, 1, 0, 0, 0, rrt.CameraState())
+        except rrt.RRTError:
+            ap.error("--stereo-base B >= 0, --convergence Z >= 0, --pole-merge FROM TO with 0 <= FROM <= TO <= 90")
     glow = None
     if args.glow is not None:       # the settings' checks are host arithmetic (rrt_glow_scratch_bytes)
         glow = rrt.GlowSettings(radius=args.glow_radius, lobes=args.glow_lobes, threshold=args.glow_threshold, intensity=args.glow)
@@ -149,9 +183,11 @@ def main(argv=None):
             warm.join()
 
     trace("process group ready" if world > 1 else "single rank")
-    w, h = args.width, args.height
+    ew, eh = args.width, args.height                        # the launch's frame: one eye's with --stereo
+    w, h = stereo.composite(ew, eh) if stereo is not None else (ew, eh)       # the frame that is sharded, gathered and written
     ss, mb = args.supersample, args.motion_blur
-    single = ss > 1 or mb > 1 or glow is not None or pano   # supersampled, blurred, glowed, panorama: single kernel, static order, no pool
+    # supersampled, blurred, glowed, panorama, stereo: single kernel, static order, no pool
+    single = ss > 1 or mb > 1 or glow is not None or pano or stereo is not None
     tex = rrt.SkyTexture(load_sky(args.sky) if args.sky else synthetic_sky())
     fx = rrt.CameraEffects(useChromaticAberration=bool(args.all_effects))
     # with several ranks --frames-in-flight frames are in flight (FrameSharder pipeline mode), each with its own
@@ -194,10 +230,15 @@ def main(argv=None):
         glow_frame = torch.zeros(h * w * 4, dtype=torch.uint8, device=dev)
 
     def launch_sampled(buf, prm, hdr=None):
-        """the panorama / blurred / supersampled launch (_pano, _mb, _ss): the whole frame and its HDR when hdr is given, else
-        this rank's tiles"""
+        """the stereo / panorama / blurred / supersampled launch (_stereo, _pano, _mb, _ss): the whole frame and its HDR when hdr
+        is given, else this rank's tiles"""
         whole = hdr is not None
         tiles = () if whole else (args.tile_rows, rank, world)
+        if stereo is not None:
+            launch = rrt.launch_raymarch_stereo if whole else rrt.launch_raymarch_stereo_tiles
+            when = (proj if proj is not None else rrt.Projection("pinhole"), stereo, state["t"], state["cam"])
+            launch(buf, ew, eh, ss, *tiles, *when, tex, fx, prm, **({"hdr": hdr} if whole else {}))
+            return
         if pano:
             launch, when = (rrt.launch_raymarch_pano if whole else rrt.launch_raymarch_pano_tiles), (proj, state["t"], state["cam"])
         elif mb > 1:
@@ -218,7 +259,7 @@ def main(argv=None):
         k = state["k"]
         if chooser is not None:
             prms[slot].path_policy = chooser.policy(k)
-        if pano or mb > 1 or ss > 1:
+        if pano or mb > 1 or ss > 1 or stereo is not None:
             launch_sampled(buf, prms[slot])
         else:
             rrt.launch_raymarch_tiles(buf, w, h, args.tile_rows, rank, world, state["t"], state["cam"], tex, fx, prms[slot])
@@ -293,7 +334,8 @@ def main(argv=None):
                           "tile_order": orders[0].info() if orders else None, "supersample": ss,
                           "motion_blur": mb, "shutter": args.shutter, "glow": glow.info() if glow is not None else None,
                           "projection": args.projection, "fov_deg": proj.fov_deg if pano else None,
-                          "vfov_deg": proj.vfov_deg if args.projection == "equirect" else None}),
+                          "vfov_deg": proj.vfov_deg if args.projection == "equirect" else None,
+                          "stereo": stereo.info() if stereo is not None else None}),
               flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -1,0 +1,287 @@
+"""Stereo frames (rrt_launch_raymarch_stereo*, include/rrt.h) on the GPU against their definition.  base 0 gives each half the mono
+frame's bytes; every stereo pixel's march is tied to the already-pinned pinhole path (a 2x2 pinhole frame at the restated origin
+whose centre pixel looks exactly along the restated D gives its HDR bit for bit); the s x s composite is the documented tree over
+the 1x composite of (s w) x (s h) eyes; the eyes differ where they should; tiles, streams, graphs and both drivers.  torch is only
+the device-memory plumbing."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import projection_ref as pr
+import stereo_ref as sr
+from conftest import same_bits
+from test_gpu_supersample import expected_mean, tone_map
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+LAYOUTS = ("top-bottom", "side-by-side")
+
+
+@pytest.fixture(scope="module")
+def ctx(sky):
+    import torch
+    assert torch.cuda.is_available(), "the -m gpu tests need a GPU"
+    import relativisticraytracer_amd as rrt
+    tex = rrt.SkyTexture(sky)
+    yield rrt, tex
+    tex.destroy()
+
+
+def _zeros(n, dtype):
+    import torch
+    return torch.zeros(n, dtype=dtype, device="cuda")
+
+
+def _host(t, shape):
+    import torch
+    torch.cuda.synchronize()
+    return t.cpu().numpy().reshape(shape)
+
+
+def all_fx(rrt, vignette_lens=True):
+    return rrt.CameraEffects(useBloom=True, useChromaticAberration=True, caAmount=0.004, useVignette=vignette_lens,
+                             vignetteIntensity=0.6, useLensDistortion=vignette_lens, distortionAmount=0.2)
+
+
+def render_stereo(rrt, tex, w, h, s, proj, st, t, cam, fx, prm, stream=None):
+    """(rgba8, hdr) of the composite, both (rows, cols, 4) bottom-up"""
+    import torch
+    cw, ch = st.composite(w, h)
+    out, hdr = _zeros(ch * cw * 4, torch.uint8), _zeros(ch * cw * 4, torch.float32)
+    rrt.launch_raymarch_stereo(out, w, h, s, proj, st, t, cam, tex, fx, prm, stream=stream, hdr=hdr)
+    return _host(out, (ch, cw, 4)), _host(hdr, (ch, cw, 4))
+
+
+def render_mono(rrt, tex, w, h, s, proj, t, cam, fx, prm):
+    """the mono frame an eye's half is defined by: _ss for a pinhole, _pano for equirect"""
+    import torch
+    out, hdr = _zeros(h * w * 4, torch.uint8), _zeros(h * w * 4, torch.float32)
+    if proj.kind == pr.PINHOLE:
+        rrt.launch_raymarch_ss(out, w, h, s, t, cam, tex, fx, prm, hdr=hdr)
+    else:
+        rrt.launch_raymarch_pano(out, w, h, s, proj, t, cam, tex, fx, prm, hdr=hdr)
+    return _host(out, (h, w, 4)), _host(hdr, (h, w, 4))
+
+
+def _layout(st):
+    return sr.TOP_BOTTOM if st.layout == 1 else sr.SIDE_BY_SIDE
+
+
+@pytest.mark.parametrize("kind", ["pinhole", "equirect"])
+def test_base_zero_halves_are_the_mono_frame(ctx, kind):
+    """base 0 (any convergence and merge): each half of the composite == the mono frame, bytes and HDR, s = 1 and 2, every effect
+    on (lens and vignette honoured by the pinhole, ignored by equirect), strict and FMAD, nudged rays"""
+    rrt, tex = ctx
+    proj = rrt.Projection(kind)
+    w, h = (48, 27) if kind == "pinhole" else (64, 32)
+    cam = rrt.CameraState.from_angles((12.0, -3.0, 40.0), 137.0, 21.5) if kind == "equirect" else rrt.CameraState.default()
+    for layout in LAYOUTS:
+        st = rrt.Stereo(layout, 0.0, 9.0, (30.0, 60.0))
+        for s, arith, nudge in ((1, 0, 0), (2, 2, 0), (2, 0, 3)):
+            prm = rrt.RenderParams(spin=0.9, arith_mode=arith, nudge_ulps=nudge, nudge_seed=7)
+            ref8, ref = render_mono(rrt, tex, w, h, s, proj, 1.0, cam, all_fx(rrt), prm)
+            assert ref8[..., :3].std() > 5.0
+            got8, got = render_stereo(rrt, tex, w, h, s, proj, st, 1.0, cam, all_fx(rrt), prm)
+            for eye in (sr.LEFT, sr.RIGHT):
+                g8, g = sr.eye_half(_layout(st), got8, eye, w, h), sr.eye_half(_layout(st), got, eye, w, h)
+                assert np.array_equal(g8, ref8) and same_bits(g, ref), (kind, layout, s, arith, nudge, eye)
+
+
+def _probe_hdr(rrt, tex, t, cam, rays, fx, prm):
+    """the post-FX HDR of pixel (1, 1) of a 2x2 pinhole frame from each (origin, forward) of `rays` (cam's right and up): u = v = 0
+    there, so its ray starts at origin and is exactly normalize(forward).  All launches first, one synchronisation."""
+    import torch
+    n = len(rays)
+    out, hdr = _zeros(n * 16, torch.uint8), _zeros(n * 16, torch.float32)
+    a = cam.as_array()
+    for k, (o, f) in enumerate(rays):
+        c = rrt.CameraState(o, f, a[2], a[3])
+        rrt.launch_raymarch_debug(out.data_ptr() + 16 * k, 2, 2, t, c, tex, fx, prm, hdr=hdr.data_ptr() + 64 * k)
+    return _host(hdr, (n, 2, 2, 4))[:, 0, 1, :3]        # image row 1 is stored row 0 (bottom-up)
+
+
+def test_every_pixel_marches_the_pinned_pinhole_path(ctx, po):
+    """128 random pixels per eye per configuration of 1x composites: their HDR == the pinhole probe's from the restated origin along
+    the restated D, bit for bit -- spin 0 and 0.9, strict and FMAD, nudged rays; ODS with a pole merge, an off-axis pinhole pair
+    (lens and vignette off), both layouts; bloom and CA on"""
+    rrt, tex = ctx
+    rng = np.random.default_rng(20261016)
+    cam = rrt.CameraState.default()
+    views = [(rrt.Projection("equirect"), rrt.Stereo("top-bottom", 1.5, 0.0, (45.0, 80.0)), 96, 48),
+             (rrt.Projection("pinhole"), rrt.Stereo("side-by-side", 0.8, 12.0), 64, 36)]
+    configs = [(0.0, 0, 0), (0.9, 0, 0), (0.9, 2, 0), (0.9, 0, 3), (0.9, 2, 3)]      # (spin, arith, nudge_ulps)
+    t = 1.0
+    for spin, arith, nudge in configs:
+        prm = rrt.RenderParams(spin=spin, arith_mode=arith, nudge_ulps=nudge, nudge_seed=5)
+        probe_prm = rrt.RenderParams(spin=spin, arith_mode=arith)
+        for proj, st, W, H in views:
+            fx = all_fx(rrt, proj.kind == pr.EQUIRECT)       # equirect ignores lens and vignette; the pinhole pair runs without
+            _, hdr = render_stereo(rrt, tex, W, H, 1, proj, st, t, cam, fx, prm)
+            for eye in (sr.LEFT, sr.RIGHT):
+                o, D = sr.ray(po, proj.kind, proj.fov_deg, proj.vfov_deg, st.base, st.convergence,
+                              (st.pole_merge_from_deg, st.pole_merge_to_deg), W, H, eye, cam.as_array())
+                look = D
+                ok = np.all(D != 0, axis=-1)
+                if nudge:
+                    ys, xs = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
+                    look = pr.nudge(pr.normalize(D), nudge, 5, xs, ys)           # the eye-local pixel feeds the hash
+                    ok &= np.all(pr.normalize(look).view(np.uint32) == look.view(np.uint32), axis=-1) & np.all(look != 0, axis=-1)
+                cand = np.argwhere(ok)
+                assert len(cand) >= 128, (proj.info(), len(cand))
+                pick = cand[rng.choice(len(cand), 128, replace=False)]
+                want = _probe_hdr(rrt, tex, t, cam, [(o[y, x], look[y, x]) for y, x in pick], all_fx(rrt, False), probe_prm)
+                half = sr.eye_half(_layout(st), hdr, eye, W, H)
+                got = np.stack([half[H - 1 - y, x, :3] for y, x in pick])
+                bad = ~((got.view(np.uint32) == want.view(np.uint32)) | ((got == 0) & (want == 0))).all(-1)
+                assert not bad.any(), (proj.info(), st.info(), eye, spin, arith, nudge, int(bad.sum()), pick[bad][:4].tolist())
+                assert np.ptp(got) > 0.05, proj.info()                   # a real picture: disk, shadow and sky among the pixels
+
+
+@pytest.mark.parametrize("kind", ["pinhole", "equirect"])
+def test_supersampled_stereo_is_the_tree_over_the_big_stereo(ctx, po, kind):
+    """stereo(w, h, s) HDR == the documented tree over stereo(s w, s h, 1) HDR, its bytes the portable tone map of that; s = 2, 4"""
+    rrt, tex = ctx
+    proj = rrt.Projection(kind)
+    w, h = (33, 17) if kind == "equirect" else (30, 17)
+    cam = rrt.CameraState.from_angles((12.0, -3.0, 40.0), 137.0, 21.5)
+    for layout, s, arith in (("top-bottom", 2, 0), ("side-by-side", 4, 2), ("side-by-side", 2, 0), ("top-bottom", 4, 2)):
+        st = rrt.Stereo(layout, 1.2, 15.0 if kind == "pinhole" else 0.0, (90, 90) if kind == "pinhole" else (50, 70))
+        prm = rrt.RenderParams(spin=0.9, arith_mode=arith)
+        _, big = render_stereo(rrt, tex, s * w, s * h, 1, proj, st, 1.0, cam, all_fx(rrt), prm)
+        got8, got = render_stereo(rrt, tex, w, h, s, proj, st, 1.0, cam, all_fx(rrt), prm)
+        cw, ch = st.composite(w, h)
+        mean = expected_mean(big, cw, ch, s)
+        assert same_bits(got[..., :3], mean), (kind, layout, s, int((got[..., :3] != mean).sum()))
+        assert np.all(got[..., 3] == 1.0)
+        assert np.array_equal(got8, tone_map(po, mean)), (kind, layout, s)
+
+
+@pytest.mark.parametrize("kind", ["pinhole", "equirect"])
+def test_parallax_grows_with_the_base(ctx, kind):
+    """base > 0: the eyes differ, most where the lensing is strongest (disk and photon ring), and more for a wider base"""
+    rrt, tex = ctx
+    proj = rrt.Projection(kind)
+    w, h = (96, 54) if kind == "pinhole" else (128, 64)
+    cam, prm = rrt.CameraState.default(), rrt.RenderParams(spin=0.9)
+    diffs = []
+    for base in (0.0, 0.5, 2.0):
+        _, hdr = render_stereo(rrt, tex, w, h, 1, proj, rrt.Stereo("side-by-side", base), 1.0, cam, all_fx(rrt, False), prm)
+        left, right = hdr[:, :w, :3], hdr[:, w:, :3]
+        diffs.append(np.abs(left.astype(np.float64) - right).sum(-1))
+    assert not diffs[0].any()
+    assert 0 < diffs[1].mean() < diffs[2].mean(), [d.mean() for d in diffs]
+    # the difference concentrates near the hole: the central third of the rows and columns against the rest
+    rows, cols = slice(h // 3, 2 * h // 3), slice(w // 3, 2 * w // 3)
+    centre = diffs[2][rows, cols].mean()
+    mask = np.ones_like(diffs[2], bool)
+    mask[rows, cols] = False
+    assert centre > diffs[2][mask].mean(), (centre, diffs[2][mask].mean())
+
+
+def test_tile_shards_assemble_to_the_full_composite(ctx):
+    import torch
+    rrt, tex = ctx
+    cam = rrt.CameraState.default()
+    fx, prm = all_fx(rrt), rrt.RenderParams(spin=0.9)
+    for kind, w, h in (("equirect", 45, 23), ("pinhole", 41, 19)):
+        proj = rrt.Projection(kind)
+        for layout in LAYOUTS:
+            st = rrt.Stereo(layout, 0.9, 6.0 if kind == "pinhole" else 0.0)
+            cw, ch = st.composite(w, h)
+            for s, n, tr in ((1, 1, 16), (1, 3, 16), (2, 3, 5), (2, 4, 7)):
+                full, _ = render_stereo(rrt, tex, w, h, s, proj, st, 1.0, cam, fx, prm)
+                rows = [rrt.tile_shard_rows(ch, tr, k, n) for k in range(n)]
+                stride = ((max(rows) * cw * 4) + 255) & ~255
+                tiles = _zeros(stride * n, torch.uint8)
+                for k in range(n):
+                    rrt.launch_raymarch_stereo_tiles(tiles.data_ptr() + k * stride, w, h, s, tr, k, n, proj, st, 1.0, cam, tex, fx, prm)
+                frame = _zeros(ch * cw * 4, torch.uint8)
+                rrt.assemble_all_tiles(frame, tiles, stride, cw, ch, tr, n)
+                assert np.array_equal(_host(frame, (ch, cw, 4)), full), (kind, layout, s, n, tr)
+
+
+def test_graph_capture_and_side_stream(ctx):
+    """no memset, no synchronisation: a launch runs on a side stream and can be captured into a graph and replayed"""
+    import torch
+    rrt, tex = ctx
+    w, h = 48, 24
+    cam, fx, prm = rrt.CameraState.default(), all_fx(rrt), rrt.RenderParams(spin=0.9)
+    for kind, layout in (("equirect", "top-bottom"), ("pinhole", "side-by-side")):
+        proj, st = rrt.Projection(kind), rrt.Stereo(layout, 0.7, 5.0 if kind == "pinhole" else 0.0)
+        cw, ch = st.composite(w, h)
+        ref8, ref = render_stereo(rrt, tex, w, h, 2, proj, st, 1.0, cam, fx, prm)
+        side = torch.cuda.Stream()
+        got8, got = render_stereo(rrt, tex, w, h, 2, proj, st, 1.0, cam, fx, prm, stream=side)
+        side.synchronize()
+        assert np.array_equal(got8, ref8) and same_bits(got, ref), kind
+        b, bh = _zeros(ch * cw * 4, torch.uint8), _zeros(ch * cw * 4, torch.float32)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            rrt.launch_raymarch_stereo(b, w, h, 2, proj, st, 1.0, cam, tex, fx, prm, hdr=bh)
+        for _ in range(2):
+            b.zero_()
+            bh.zero_()
+            graph.replay()
+            assert np.array_equal(_host(b, (ch, cw, 4)), ref8) and same_bits(_host(bh, (ch, cw, 4)), ref), kind
+
+
+@pytest.mark.parametrize("extra", [["--stereo", "top-bottom", "--projection", "equirect", "--stereo-base", "0.8", "--pole-merge", "60", "85"],
+                                   ["--stereo", "side-by-side", "--supersample", "2", "--convergence", "12"]],
+                         ids=lambda e: "_".join(e[1:4:2]))
+def test_drivers_write_the_stereo_composite(ctx, tmp_path, extra):
+    """rrt_headless and headless.py write the same file, whose frames are launch_raymarch_stereo's with the driver's cameras and
+    clock at the composite's size; rrt_headless --force-collective (the tile path through a one-GPU RCCL exchange) writes the same"""
+    import torch
+    from relativisticraytracer_amd import build
+    from relativisticraytracer_amd import camera_paths as cp
+    rrt, tex = ctx
+    exe = build.build_headless()
+    w, h = (64, 32) if "equirect" in extra else (48, 27)
+    a, b, c = tmp_path / "cpp.rgba", tmp_path / "py.rgba", tmp_path / "coll.rgba"
+    args = ["--width", str(w), "--height", str(h), "--frames", "3", "--path", "0", "--spin", "0.9", "--all-effects",
+            "--tile-rows", "7"] + extra
+    r = subprocess.run([exe] + args + ["--out", str(a)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    meta_c = json.loads(r.stdout.strip().splitlines()[-1])
+    r = subprocess.run([sys.executable, "-m", "relativisticraytracer_amd.headless"] + args + ["--out", str(b)], cwd=ROOT,
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    meta_p = json.loads(r.stdout.strip().splitlines()[-1])
+    r = subprocess.run([exe] + args + ["--force-collective", "--out", str(c)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "rccl" in json.loads(r.stdout.strip().splitlines()[-1])["collective"]
+    proj = rrt.Projection("equirect" if "equirect" in extra else "pinhole")
+    st = (rrt.Stereo("top-bottom", 0.8, None, (60, 85)) if "equirect" in extra else rrt.Stereo("side-by-side", None, 12.0))
+    cw, ch = st.composite(w, h)
+    for m in (meta_c, meta_p):
+        assert (m["width"], m["height"]) == (cw, ch) and m["stereo"] == st.info(), m
+    assert open(a, "rb").read() == open(b, "rb").read() == open(c, "rb").read()
+    data = np.fromfile(a, np.uint8).reshape(3, ch, cw, 4)
+    s = 2 if "--supersample" in extra else 1
+    path = cp.CameraPath(0)
+    fx = rrt.CameraEffects(useChromaticAberration=True)
+    for k in (1, 2, 3):
+        t, pt = cp.recording_clock(k)
+        buf = _zeros(ch * cw * 4, torch.uint8)
+        rrt.launch_raymarch_stereo(buf, w, h, s, proj, st, t, path.camera_at(pt), tex, fx, rrt.RenderParams(spin=0.9))
+        assert np.array_equal(_host(buf, (ch, cw, 4)), data[k - 1]), k
+
+
+def test_two_gpus_write_the_one_gpu_composite(tmp_path):
+    """Needs >= 2 GPUs (skipped on a one-GPU box): rrt_headless --gpus 2 --stereo writes the frames of the one-GPU run"""
+    import torch
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two GPUs")
+    from relativisticraytracer_amd import build
+    exe = build.build_headless()
+    base = ["--width", "160", "--height", "90", "--frames", "3", "--path", "0", "--spin", "0.9", "--stereo", "top-bottom"]
+    one, two = tmp_path / "one.rgba", tmp_path / "two.rgba"
+    subprocess.run([exe] + base + ["--out", str(one)], check=True, capture_output=True, timeout=600)
+    r = subprocess.run([exe] + base + ["--gpus", "2", "--out", str(two)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert open(two, "rb").read() == open(one, "rb").read()
