@@ -33,6 +33,14 @@ int rrt_unit_rk4(int n, float* d_p, float* d_v, const float* d_h, float spin, vo
  * seeded with seed_scale / r (0: no seed, like a ray's first step). */
 int rrt_unit_rk4_lean(int n, float* d_p, float* d_v, const float* d_h, float spin, int n_steps, float seed_scale,
                       int32_t* d_steps, void* stream);
+/* the PRODUCTION march loop (csrc/rrt_kernels.h: march_inline and, inside it, vacuum_run -- the very instances the render
+ * kernels call, not a copy) on rays the caller chose: one ray per element, 64 consecutive elements one wavefront, no media
+ * (the zone rule still sets the step size).  d_p / d_v: position and velocity, in/out.  d_first_step == NULL: every ray
+ * starts at step 0 (the instance of the single kernel, whose step counter is one scalar per wave); otherwise ray i starts
+ * at step d_first_step[i] (the instance a ray resumed after a pool overflow runs).  d_steps / d_hit (may be NULL): steps
+ * taken (counted from 0, the first step included) and whether the horizon test ended the ray.  arith_mode: RRT_ARITH_*. */
+int rrt_unit_march(int n, float* d_p, float* d_v, float spin, int arith_mode, int max_steps, const int32_t* d_first_step,
+                   int32_t* d_steps, int32_t* d_hit, void* stream);
 /* the march's divide (csrc/rrt_device.h: div_seeded, one Markstein correction) on explicit operands and seeds */
 int rrt_unit_div_seeded(int n, const float* d_a, const float* d_b, const float* d_seed, float* d_out, void* stream);
 int rrt_unit_hash31(int n, const float* d_p, float* d_out, void* stream);

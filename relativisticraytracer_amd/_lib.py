@@ -171,6 +171,7 @@ TEST_SYMBOLS = [
     ("rrt_unit_geodesic_acc", _i, [_i, _vp, _vp, _f, _vp, _vp]),
     ("rrt_unit_rk4", _i, [_i, _vp, _vp, _vp, _f, _vp]),
     ("rrt_unit_rk4_lean", _i, [_i, _vp, _vp, _vp, _f, _i, _f, _vp, _vp]),
+    ("rrt_unit_march", _i, [_i, _vp, _vp, _f, _i, _i, _vp, _vp, _vp, _vp]),
     ("rrt_unit_div_seeded", _i, [_i, _vp, _vp, _vp, _vp, _vp]),
     ("rrt_unit_hash31", _i, [_i, _vp, _vp, _vp]),
     ("rrt_unit_noise3d", _i, [_i, _vp, _vp, _vp]),

@@ -77,6 +77,32 @@ __global__ __launch_bounds__(64) void k_rk4_lean(int n, float* p, float* v, cons
     }
     if (valid) { st3(p, i, pp); st3(v, i, vv); if (steps_out) steps_out[i] = k; }
 }
+/* The PRODUCTION march loop itself -- march_inline (rrt_kernels.h), and through it vacuum_run -- on rays the caller chose: one
+ * ray per element, 64 consecutive elements one wavefront, so a test decides who shares a wave with whom.  No copy of the loop
+ * lives here: the kernel builds the ray state of raymarch_pixels and calls the instance the render kernels call, with no media
+ * (MEDIA = 0: the zone rule still sets the step size).  Elements past n leave before the loop, as lane_pixel's false does in
+ * raymarch_pixels.  UK = true: every ray starts at step 0 (the single kernel's instance, scalar step counter); UK = false: ray i
+ * starts at first_step[i] (the instance a ray resumed after a pool overflow runs: composite_and_shade). */
+template <bool SPIN, int ARITH, bool UK>
+__global__ __launch_bounds__(64) void k_march(int n, float* p, float* v, const FrameArgs a, const int* first_step, int* steps_out,
+                                              int* hit_out) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    v3 pp = ld3(p, i), vv = ld3(v, i);
+    Radiance acc = {0.f, 0.f, 0.f, 1.0f};
+    bool hit = false;
+    int k = UK ? 0 : first_step[i];
+    march_inline<SPIN, 0, ARITH, UK>(a, pp, vv, acc, hit, k, nullptr);
+    st3(p, i, pp); st3(v, i, vv);
+    if (steps_out) steps_out[i] = k;
+    if (hit_out) hit_out[i] = hit ? 1 : 0;
+}
+template <bool SPIN, int ARITH>
+void launch_k_march(int n, float* p, float* v, const FrameArgs& a, const int* first_step, int* steps, int* hit, hipStream_t st) {
+    const dim3 g((n + 63) / 64), b(64);                     /* one wavefront per workgroup, like the render kernels */
+    if (first_step) hipLaunchKernelGGL((k_march<SPIN, ARITH, false>), g, b, 0, st, n, p, v, a, first_step, steps, hit);
+    else hipLaunchKernelGGL((k_march<SPIN, ARITH, true>), g, b, 0, st, n, p, v, a, first_step, steps, hit);
+}
 /* the march's divide on explicit operands: out = div_seeded(a, b, seed) */
 __global__ void k_div_seeded(int n, const float* a, const float* b, const float* seed, float* out) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -451,6 +477,22 @@ int rrt_unit_rk4_lean(int n, float* p, float* v, const float* h, float spin, int
     const dim3 g((n + 63) / 64), b(64);                     /* one wavefront per workgroup, like the render kernels */
     if (spin != 0.0f) hipLaunchKernelGGL((k_rk4_lean<true>), g, b, 0, static_cast<hipStream_t>(st), n, p, v, h, drag_c, n_steps, seed_scale, steps);
     else hipLaunchKernelGGL((k_rk4_lean<false>), g, b, 0, static_cast<hipStream_t>(st), n, p, v, h, drag_c, n_steps, seed_scale, steps);
+    RRT_HIP(hipGetLastError());
+    return RRT_OK;
+}
+int rrt_unit_march(int n, float* p, float* v, float spin, int arith_mode, int max_steps, const int32_t* first_step, int32_t* steps,
+                   int32_t* hit, void* st) {
+    if (n < 0 || max_steps < 0 || (n > 0 && (!p || !v))) return RRT_ERR_INVALID_ARGUMENT;
+    if (arith_mode != RRT_ARITH_STRICT && arith_mode != RRT_ARITH_FAST && arith_mode != RRT_ARITH_FMAD) return RRT_ERR_INVALID_ARGUMENT;
+    if (n == 0) return RRT_OK;
+    FrameArgs a;
+    memset(&a, 0, sizeof(a));
+    a.spin = spin; a.drag_c = (2.0f * spin) * 2.0f; a.max_steps = max_steps;
+    const hipStream_t s = static_cast<hipStream_t>(st);
+    const bool sp = spin != 0.0f;
+    if (arith_mode == RRT_ARITH_STRICT) sp ? launch_k_march<true, kArithStrict>(n, p, v, a, first_step, steps, hit, s) : launch_k_march<false, kArithStrict>(n, p, v, a, first_step, steps, hit, s);
+    else if (arith_mode == RRT_ARITH_FMAD) sp ? launch_k_march<true, kArithFmad>(n, p, v, a, first_step, steps, hit, s) : launch_k_march<false, kArithFmad>(n, p, v, a, first_step, steps, hit, s);
+    else sp ? launch_k_march<true, kArithFast>(n, p, v, a, first_step, steps, hit, s) : launch_k_march<false, kArithFast>(n, p, v, a, first_step, steps, hit, s);
     RRT_HIP(hipGetLastError());
     return RRT_OK;
 }

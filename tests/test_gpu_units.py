@@ -499,3 +499,13 @@ def test_unit_kernels_empty_and_bad_args(g):
     g.unit("hash31", 0, z, z)                         # n = 0 is a no-op
     assert _lib.load_test().rrt_unit_hash31(4, None, None, None) == 1        # RRT_ERR_INVALID_ARGUMENT
     assert _lib.load_test().rrt_unit_fbm(4, z.data_ptr(), 99, z.data_ptr(), None) == 1
+    g.unit("march", 0, z, z, 0.9, 0, 10, None, None, None)                  # n = 0 is a no-op
+    q = torch.ones(3, device="cuda")
+    march = _lib.load_test().rrt_unit_march
+    assert march(1, q.data_ptr(), q.data_ptr(), 0.9, 3, 10, None, None, None, None) == 1        # no such arith_mode
+    assert march(1, q.data_ptr(), q.data_ptr(), 0.9, -1, 10, None, None, None, None) == 1
+    assert march(1, q.data_ptr(), q.data_ptr(), 0.9, 0, -1, None, None, None, None) == 1        # a negative max_steps
+    assert march(-1, q.data_ptr(), q.data_ptr(), 0.9, 0, 10, None, None, None, None) == 1
+    assert march(1, None, q.data_ptr(), 0.9, 0, 10, None, None, None, None) == 1
+    torch.cuda.synchronize()
+    assert (q == 1).all()                                                   # nothing was launched
