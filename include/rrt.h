@@ -606,6 +606,35 @@ int rrt_path_chooser_report(int id, int frame, float sustained_ms);
 int rrt_path_chooser_get_stats(int id, rrt_path_chooser_stats* out);
 
 
+/* ---- march cache: retained geodesics of a still camera ("Retained geodesics") ----
+ * rrt_launch_raymarch, _rows and _tiles WITHOUT an rrt_params.workspace keep state per device: about 90 % of a frame is the
+ * march of the geodesics, and the march does not depend on `time`, the sky, the noise table or the effects applied after it.
+ * The library remembers the last launch's key per device (camera block, size, row selection, spin, volumetrics, max_steps,
+ * nudge, arith_mode, the lens distortion).  A launch with another key runs exactly as before.  The second
+ * consecutive launch of a key runs the three passes and keeps pass 1's output (a "fill"); the third and later ones run only the
+ * media evaluation and the composite on the retained rows (a "hit") -- same bytes as the uncached launch, always.  Not cached:
+ * launches with a workspace, an rrt_tile_order or an rrt_tile_map, with path_policy RRT_PATH_SINGLE, without volumetrics, with
+ * debug outputs, launches being captured into a graph, and the _ss / _mb / _pano / _stereo launches.
+ * Memory: allocated at the first fill, kept until released; bounded by max_bytes -- default the smaller of 8 GiB and a quarter of
+ * the device memory free at the first use.  A frame that does not fit stays on the uncached path (no error; `why` says so).
+ * RRT_MARCH_CACHE=0 in the environment switches it off for every device. */
+typedef struct rrt_march_cache_info {
+    uint64_t fills, hits;              /* launches that filled the cache / were served from it */
+    uint64_t drops;                    /* keys given up after a fill had been made or started for them */
+    uint64_t misses;                   /* launches whose key differed from the previous one's (uncached path, key remembered) */
+    uint64_t uncacheable;              /* launches of a repeated key that stayed on the uncached path */
+    uint64_t bytes, max_bytes;         /* device memory held / the budget (0: off) */
+    uint64_t blocks_used, blocks_capacity;   /* of the current key's fill, in pool blocks */
+    int32_t state;                     /* 0 none, 1 key seen once, 2 fill not yet verified, 3 refill at a larger capacity next, 4 ready, 5 uncacheable */
+    int32_t why;                       /* state 5: 1 the budget is too small, 2 the pool overflowed twice, 3 allocation failed */
+} rrt_march_cache_info;
+/* device < 0: the calling thread's current device.  configure: max_bytes 0 = off; forgets the key, frees memory above the budget */
+int rrt_march_cache_configure(int device, size_t max_bytes);
+int rrt_march_cache_stats(int device, rrt_march_cache_info* out);
+/* waits for the launches through the cache, frees everything, forgets the key; counters and budget stay.  Nothing is freed
+ * at process exit or library unload: call this first if that matters */
+int rrt_march_cache_release(int device);
+
 /* ---- host-side camera helpers (host C++ in the reference too) ---- */
 /* CameraController::getCUDAStateFrom, src/main.cpp:141-167 (degrees; note its 3.14159f) */
 int rrt_camera_from_angles(const float pos[3], float yaw_deg, float pitch_deg, rrt_camera* out);

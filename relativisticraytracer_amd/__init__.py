@@ -31,7 +31,8 @@ __all__ = ["CameraState", "CameraEffects", "RenderParams", "SkyTexture", "Worksp
            "Stereo", "stereo_default", "stereo_ray", "launch_raymarch_stereo", "launch_raymarch_stereo_tiles",
            "tile_shard_rows",
            "launch_raymarch_debug", "RRTError", "device_count", "abi_version", "TileOrder", "TileMap",
-           "probe_tile_costs", "balance_tiles", "launch_raymarch_tilemap", "assemble_all_tilemap", "clock_probe", "clock_probe_ghz"]
+           "probe_tile_costs", "balance_tiles", "launch_raymarch_tilemap", "assemble_all_tilemap", "clock_probe", "clock_probe_ghz",
+           "march_cache_configure", "march_cache_stats", "march_cache_release"]
 
 
 def _ptr(x):
@@ -558,6 +559,31 @@ def get_launch_defaults():
     out = RenderParams()
     _lib.check(_lib.load().rrt_get_launch_defaults_sized(C.byref(out), C.sizeof(rrt_params)), "rrt_get_launch_defaults")
     return out
+
+
+def march_cache_configure(max_bytes, device=-1):
+    """Byte budget of a device's march cache (retained geodesics of a still camera, include/rrt.h); 0 switches it off.
+    device -1: the current one."""
+    _lib.check(_lib.load().rrt_march_cache_configure(int(device), int(max_bytes)), "rrt_march_cache_configure")
+
+
+_MARCH_CACHE_STATES = ("none", "seen", "fill-pending", "refill", "ready", "uncacheable")
+_MARCH_CACHE_WHY = ("", "budget", "overflow", "allocation")
+
+
+def march_cache_stats(device=-1):
+    """Counters of a device's march cache: which path its launches took (fills / hits / drops / misses / uncacheable), memory."""
+    info = _lib.rrt_march_cache_info()
+    _lib.check(_lib.load().rrt_march_cache_stats(int(device), C.byref(info)), "rrt_march_cache_stats")
+    d = {k: int(getattr(info, k)) for k, _ in info._fields_}
+    d["state"] = _MARCH_CACHE_STATES[info.state] if 0 <= info.state < len(_MARCH_CACHE_STATES) else str(info.state)
+    d["why"] = _MARCH_CACHE_WHY[info.why] if 0 <= info.why < len(_MARCH_CACHE_WHY) else str(info.why)
+    return d
+
+
+def march_cache_release(device=-1):
+    """Free a device's march cache and forget its key (counters and budget stay)."""
+    _lib.check(_lib.load().rrt_march_cache_release(int(device)), "rrt_march_cache_release")
 
 
 def _sky_handle(sky):

@@ -61,6 +61,12 @@ class rrt_path_chooser_stats(C.Structure):
                 ("switches", C.c_int32), ("outliers", C.c_int32), ("frames", C.c_int32 * 2), ("last_three_pass_mean_ms", C.c_float)]
 
 
+class rrt_march_cache_info(C.Structure):
+    _fields_ = [("fills", C.c_uint64), ("hits", C.c_uint64), ("drops", C.c_uint64), ("misses", C.c_uint64),
+                ("uncacheable", C.c_uint64), ("bytes", C.c_uint64), ("max_bytes", C.c_uint64),
+                ("blocks_used", C.c_uint64), ("blocks_capacity", C.c_uint64), ("state", C.c_int32), ("why", C.c_int32)]
+
+
 class rrt_glow(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("radius", C.c_float), ("lobes", C.c_int32), ("threshold", C.c_float),
                 ("intensity", C.c_float)]
@@ -163,6 +169,9 @@ SYMBOLS = [
     ("rrt_path_chooser_policy", _i, [_i, _i, C.POINTER(_i)]),
     ("rrt_path_chooser_report", _i, [_i, _i, _f]),
     ("rrt_path_chooser_get_stats", _i, [_i, _vp]),
+    ("rrt_march_cache_configure", _i, [_i, C.c_size_t]),
+    ("rrt_march_cache_stats", _i, [_i, C.POINTER(rrt_march_cache_info)]),
+    ("rrt_march_cache_release", _i, [_i]),
 ]
 
 # include/rrt_test.h: librrt_hip_test.so only

@@ -719,16 +719,29 @@ int main(int argc, char** argv) {
                  stereo.pole_merge_from_deg, stereo.pole_merge_to_deg);
         stereo_json = buf;
     }
+    /* which path the frames took through each device's march cache (launches without a workspace: one GPU, or --workspace-gib 0) */
+    std::string cache_json = "[";
+    for (int d = 0; d < gpus; ++d) {
+        rrt_march_cache_info mc = {};
+        (void)rrt_march_cache_stats(d, &mc);
+        char buf[256];
+        snprintf(buf, sizeof(buf), "%s{\"device\": %d, \"fills\": %llu, \"hits\": %llu, \"drops\": %llu, \"misses\": %llu, \"uncacheable\": %llu, "
+                 "\"bytes\": %llu, \"max_bytes\": %llu}", d ? ", " : "", d, (unsigned long long)mc.fills, (unsigned long long)mc.hits,
+                 (unsigned long long)mc.drops, (unsigned long long)mc.misses, (unsigned long long)mc.uncacheable, (unsigned long long)mc.bytes,
+                 (unsigned long long)mc.max_bytes);
+        cache_json += buf;
+    }
+    cache_json += "]";
     printf("{\"frames\": %d, \"width\": %d, \"height\": %d, \"n_gpus\": %d, \"seconds\": %.4f, \"fps\": %.3f, \"Mrays_per_s\": %.3f, "
            "\"path\": \"%s\", \"spin\": %g, \"arith_mode\": \"%s\", \"noise_tables\": {\"builds\": %d, \"table_frames\": %d, "
            "\"arith_frames\": %d, \"coarsest_coverage\": %d, \"peak_bytes\": %zu, \"budget_bytes\": %zu}, \"tile_order\": %s, \"collective\": \"%s\", "
            "\"path_choice\": %s, \"supersample\": %d, \"motion_blur\": %d, \"shutter\": %g, \"glow\": %s, "
-           "\"projection\": \"%s\", \"fov_deg\": %s, \"vfov_deg\": %s, \"stereo\": %s}\n",
+           "\"projection\": \"%s\", \"fov_deg\": %s, \"vfov_deg\": %s, \"stereo\": %s, \"march_cache\": %s}\n",
            frames, w, h, gpus, dt, frames / dt, (double)frames * w * h / dt / 1e6, path_name, spin,
            arith == RRT_ARITH_FAST ? "fast" : (arith == RRT_ARITH_FMAD ? "fmad" : "strict"),
            table_builds, table_frames, arith_frames, coarsest, table_peak, table_budget, dev[0].order[0] ? "true" : "false",
            collective ? "rccl grouped send/recv gather" : "none", choice.c_str(), supersample, motion, shutter, glow_json.c_str(),
-           proj_name, fov_json, vfov_json, stereo_json.c_str());
+           proj_name, fov_json, vfov_json, stereo_json.c_str(), cache_json.c_str());
 
     for (int d = 0; d < gpus; ++d) {
         Device& D = dev[d];

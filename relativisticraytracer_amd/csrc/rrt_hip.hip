@@ -11,7 +11,8 @@
  *   rrt_kernels.h      the kernels and the structures they share with the host (included below: a kernel and its launch
  *                      site share a translation unit)
  *   this file          handle registries (sky, workspace, noise table, tile map, tile order), noise-table planning, path choice
- *                      and launch logic, the C ABI
+ *                      and launch logic, the march cache's device object, the C ABI
+ *   rrt_march_cache.h  the march cache's key, policy state machine and capacity rule (host only, no HIP)
  *   rrt_camera.cpp     camera basis / path playback / recording clock (plain C++)
  *   rrt_test_hooks.h   rrt_unit_*, rrt_selfcheck_*, rrt_debug_fake_device -- compiled only with -DRRT_TEST_HOOKS, i.e. into
  *                      librrt_hip_test.so; the product library exports none of them
@@ -38,6 +39,7 @@
 #endif
 #include "rrt_device.h"
 #include "rrt_tile_sort.h"              /* the native radix sort behind rrt_tile_order */
+#include "rrt_march_cache.h"            /* the march cache's key, policy and capacity rule (host only) */
 
 namespace {
 
@@ -271,28 +273,36 @@ int auto_pool_rounds(const volatile DeferCounters* h, unsigned capacity) {
     return r > kMaxPoolRounds ? kMaxPoolRounds : r;
 }
 
-/* the kernels of one arithmetic mode, instantiated per (spin, tables) */
-template <int ARITH>
-int enqueue_chain_arith(const FrameArgs& a, int media, dim3 grid, dim3 block, int rounds, hipStream_t st) {
+/* the kernels of one arithmetic mode, instantiated per (spin, tables).  KEEP: the march cache's chain (rrt_march_cache.h) -- one
+ * round, pass 2's results in planes of their own (kp); with kp.replay pass 1 and the round's close are left out */
+/* (the kernels of passes 2 and 3 take a KeepArgs whether or not they are KEEP instances: one signature per kernel; the
+ * workspace path passes an empty one, which its instances never read) */
+template <int ARITH, bool KEEP = false>
+int enqueue_chain_arith(const FrameArgs& a, int media, dim3 grid, dim3 block, int rounds, hipStream_t st, const KeepArgs kp = KeepArgs{nullptr, 0u, 0}) {
     const bool spin = a.spin != 0.0f;
+    const bool replay = KEEP && kp.replay != 0;
+    if (KEEP) rounds = 1;
     for (int r = 0; r < rounds; ++r) {
         const bool last = r == rounds - 1;
 #define RRT_MARCH(S) do { if (r == 0) hipLaunchKernelGGL((march_defer<S, ARITH, false>), grid, block, 0, st, a); \
                           else hipLaunchKernelGGL((march_defer<S, ARITH, true>), grid, block, 0, st, a); } while (0)
-        if (spin) RRT_MARCH(true); else RRT_MARCH(false);
+        if (!replay) { if (spin) RRT_MARCH(true); else RRT_MARCH(false); }
 #undef RRT_MARCH
         RRT_HIP(hipGetLastError());
-        if (media == 3) hipLaunchKernelGGL((eval_sample_rows<ARITH, 3>), dim3(2048), dim3(256), 0, st, a);
-        else if (media == 2) hipLaunchKernelGGL((eval_sample_rows<ARITH, 2>), dim3(2048), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((eval_sample_rows<ARITH, 1>), dim3(2048), dim3(256), 0, st, a);
+        if (media == 3) hipLaunchKernelGGL((eval_sample_rows<ARITH, 3, KEEP>), dim3(2048), dim3(256), 0, st, a, kp);
+        else if (media == 2) hipLaunchKernelGGL((eval_sample_rows<ARITH, 2, KEEP>), dim3(2048), dim3(256), 0, st, a, kp);
+        else hipLaunchKernelGGL((eval_sample_rows<ARITH, 1, KEEP>), dim3(2048), dim3(256), 0, st, a, kp);
         RRT_HIP(hipGetLastError());
-#define RRT_COMP3(S, L) do { if (last) hipLaunchKernelGGL((composite_and_shade<S, ARITH, L, true>), grid, block, 0, st, a); \
-                             else hipLaunchKernelGGL((composite_and_shade<S, ARITH, L, false>), grid, block, 0, st, a); } while (0)
+        /* LAST = true for the last round enqueued; the cache's chain (KEEP) has one round, so only <LAST, KEEP> = <true, true> exists */
+#define RRT_COMP3(S, L) do { if constexpr (KEEP) hipLaunchKernelGGL((composite_and_shade<S, ARITH, L, true, true>), grid, block, 0, st, a, kp); \
+                             else if (last) hipLaunchKernelGGL((composite_and_shade<S, ARITH, L, true, false>), grid, block, 0, st, a, kp); \
+                             else hipLaunchKernelGGL((composite_and_shade<S, ARITH, L, false, false>), grid, block, 0, st, a, kp); } while (0)
 #define RRT_COMP(S) do { if (media == 3) RRT_COMP3(S, 3); else if (media == 2) RRT_COMP3(S, 2); else RRT_COMP3(S, 1); } while (0)
         if (spin) RRT_COMP(true); else RRT_COMP(false);
 #undef RRT_COMP
 #undef RRT_COMP3
         RRT_HIP(hipGetLastError());
+        if (replay) break;
         hipLaunchKernelGGL(pool_next_round, dim3(1), dim3(1), 0, st, a.ctr, a.block_capacity, last ? 1 : 0);
         RRT_HIP(hipGetLastError());
     }
@@ -301,10 +311,16 @@ int enqueue_chain_arith(const FrameArgs& a, int media, dim3 grid, dim3 block, in
 
 /* one chain = march -> evaluate -> composite (in rounds) over dispatch rows [row0, row1) of the launch, in its own slice
  * of the pool, on its own stream */
-int enqueue_chain(FrameArgs a, int arith, int media, dim3 full_grid, int row0, int row_stride, int n_rows, int rounds, hipStream_t st) {
+int enqueue_chain(FrameArgs a, int arith, int media, dim3 full_grid, int row0, int row_stride, int n_rows, int rounds, hipStream_t st,
+                  const KeepArgs* keep = nullptr) {
     if (n_rows <= 0) return RRT_OK;
     const dim3 block(kWGThreads), grid(full_grid.x, (unsigned)n_rows);
     a.grid_rows = (int)full_grid.y; a.grid_row_base = row0; a.grid_row_stride = row_stride;
+    if (keep) {
+        if (arith == kArithFast) return enqueue_chain_arith<kArithFast, true>(a, media, grid, block, 1, st, *keep);
+        if (arith == kArithFmad) return enqueue_chain_arith<kArithFmad, true>(a, media, grid, block, 1, st, *keep);
+        return enqueue_chain_arith<kArithStrict, true>(a, media, grid, block, 1, st, *keep);
+    }
     if (arith == kArithFast) return enqueue_chain_arith<kArithFast>(a, media, grid, block, rounds, st);
     if (arith == kArithFmad) return enqueue_chain_arith<kArithFmad>(a, media, grid, block, rounds, st);
     return enqueue_chain_arith<kArithStrict>(a, media, grid, block, rounds, st);
@@ -410,6 +426,211 @@ int launch_deferred(FrameArgs a, int arith, int media, const WorkspaceObject& ws
  * frame (profiles/README.md): 1/4 of the frame (2.07 M rays) 11.8 ms in line vs 12.6 ms three-pass;
  * 1/8 (1.04 M rays) 11.7 ms vs 6.8 ms. */
 constexpr long long kThreePassMaxRays = 1500000;
+
+
+/* ------------------------------------------------------------------ march cache: retained geodesics
+ * One object per device, made at the first launch that could use it.  It owns the pool pass 1 fills for the most recent launch
+ * key (rrt_march_cache.h: key, policy, capacity) and follows rrt_tile_order's rules for hidden state: one mutex per object held
+ * while a launch is enqueued, launches through the object chained by an event (a replay on another stream never reads a
+ * half-written fill), a launch that is being captured into a graph ignores it entirely, and so do debug launches. */
+struct MarchCacheObject {
+    std::mutex mu;
+    int device = -1;
+    rrt_mc::Policy pol;
+    bool budget_known = false, configured = false;
+    size_t max_bytes = 0;                  /* 0: off */
+    uint8_t* d_base = nullptr; size_t bytes = 0;
+    DeferCounters* h_stats = nullptr;      /* pinned: what the fill used, copied behind it */
+    hipEvent_t chained = nullptr;
+    unsigned long long launches = 0;
+    /* layout of the current key's fill */
+    size_t off_fin = 0, off_rows = 0, off_out = 0, n_lanes = 0;
+    unsigned cap_blocks = 0, used_blocks = 0;
+};
+struct MarchCacheRegistry {
+    std::mutex mu;
+    std::unordered_map<int, std::unique_ptr<MarchCacheObject>> by_device;
+    static void free_device_memory(MarchCacheObject& c) {
+        if (c.launches > 0 && c.chained) (void)hipEventSynchronize(c.chained);
+        if (c.d_base) (void)hipFree(c.d_base);
+        c.d_base = nullptr; c.bytes = 0; c.cap_blocks = 0;
+        (void)hipGetLastError();
+    }
+    static void destroy(MarchCacheObject& c) {
+        free_device_memory(c);
+        if (c.h_stats) (void)hipHostFree(c.h_stats);
+        if (c.chained) (void)hipEventDestroy(c.chained);
+        c.h_stats = nullptr; c.chained = nullptr; c.launches = 0;
+        (void)hipGetLastError();
+    }
+};
+/* Never destroyed, like the other registries of this file: a static destructor would call into the HIP runtime at process exit
+ * or library unload, when the runtime may already be gone.  rrt_march_cache_release() is the way to give the memory back; what
+ * is still held at exit goes with the process. */
+MarchCacheRegistry& march_caches() { static MarchCacheRegistry* const r = new MarchCacheRegistry; return *r; }
+MarchCacheObject* march_cache_of(int device, bool create) {
+    MarchCacheRegistry& r = march_caches();
+    std::lock_guard<std::mutex> lk(r.mu);
+    auto it = r.by_device.find(device);
+    if (it != r.by_device.end()) return it->second.get();
+    if (!create) return nullptr;
+    auto c = std::make_unique<MarchCacheObject>();
+    c->device = device;
+    MarchCacheObject* p = c.get();
+    r.by_device.emplace(device, std::move(c));
+    return p;
+}
+/* RRT_MARCH_CACHE=0 in the environment switches every device's cache off, whatever rrt_march_cache_configure says */
+bool march_cache_env_off() {
+    static const bool off = [] { const char* e = getenv("RRT_MARCH_CACHE"); return e && e[0] == '0' && e[1] == 0; }();
+    return off;
+}
+/* the byte budget, decided at first use: the smaller of 8 GiB and a quarter of the device memory free then */
+size_t march_cache_budget(MarchCacheObject& c) {
+    if (march_cache_env_off()) return 0;
+    if (!c.budget_known) {
+        if (!c.configured) {
+            size_t free_b = 0, total_b = 0;
+            if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); free_b = 0; }
+            c.max_bytes = std::min<size_t>((size_t)8 << 30, free_b / 4);
+        }
+        c.budget_known = true;
+    }
+    return c.max_bytes;
+}
+
+/* THE KEY.  What pass 1 (march_defer) and the row bookkeeping read of a launch, proven from the source:
+ *   lane_pixel / map_row / wave_slot / row_block   width, height, rows.{n_local_rows, y_base, tile_rows, shard, n_shards,
+ *                                                  tile_of_local}, tile_perm, grid_rows / grid_row_base / grid_row_stride
+ *   primary_ray                                    width, height, cam, use_lens, distortion_amount, nudge_ulps, nudge_seed
+ *   the march loop                                 max_steps, drag_c (= 4 spin), SPIN = (spin != 0), ARITH
+ *   pool bookkeeping                               ctr, hdr, finals, n_lanes, sample_blocks, block_capacity (the cache's own)
+ *   tile_cost                                      written only (rrt_tile_order)
+ * and nothing else: not `time` (media_densities is called by passes 2 and 3 only), not the sky, not the noise tables (MEDIA is
+ * no template parameter of march_defer), not bloom / vignette / chromatic aberration.  Launches with an rrt_tile_map
+ * (tile_of_local), an rrt_tile_order (tile_perm, tile_cost) or without volumetrics (no pass 1 exists) are not cached, so those
+ * fields are not in the key; the cache runs ONE chain over the whole grid (grid_rows = 0), so the grid_row_* triple is constant.
+ * max_steps above the three-pass bookkeeping's limit is not cached either.
+ * A field added to FrameArgs trips the assertion below: decide whether pass 1 reads it BEFORE changing the number. */
+static_assert(sizeof(FrameArgs) == 416, "FrameArgs changed: does march_defer read the new field?  Then it belongs in rrt_mc::MarchKey (march_key)");
+rrt_mc::MarchKey march_key(const FrameArgs& a, const LaunchOpts& o) {
+    rrt_mc::MarchKey k;
+    memset(&k, 0, sizeof(k));
+    static_assert(sizeof(k.cam) == sizeof(a.cam), "rrt_camera is twelve floats");
+    memcpy(k.cam, &a.cam, sizeof(k.cam));
+    k.width = a.width; k.height = a.height;
+    k.n_local_rows = a.rows.n_local_rows; k.y_base = a.rows.y_base; k.tile_rows = a.rows.tile_rows;
+    k.shard = a.rows.shard; k.n_shards = a.rows.n_shards;
+    memcpy(&k.spin, &a.spin, 4);
+    k.max_steps = a.max_steps;
+    k.nudge_ulps = a.nudge_ulps; k.nudge_seed = a.nudge_seed;
+    k.arith_mode = o.arith;
+    k.volumetrics = o.media != 0;
+    k.use_lens = a.use_lens; memcpy(&k.distortion_amount, &a.distortion_amount, 4);
+    rrt_mc::canonicalize(k);
+    return k;
+}
+
+constexpr int kCacheFinalPlanes = 7;       /* vel xyz, code, pos xyz: one round, so no radiance is ever saved between rounds */
+constexpr size_t kCacheBlockBytes = (size_t)kBlockBytes + kOutBlockBytes;
+
+/* memory and layout for a fill of `grid` with (at least) the capacity rule's blocks; rrt_mc::kWhy* if there is none to be had */
+int march_cache_reserve(MarchCacheObject& c, const FrameArgs& a, dim3 grid, bool grown) {
+    auto align = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t n_waves = (size_t)grid.x * grid.y * kWGWaves, n_lanes = n_waves * 64;
+    const size_t off_fin = align(256 + n_waves * sizeof(WaveHdr));
+    const size_t off_rows = align(off_fin + n_lanes * 4 * kCacheFinalPlanes);
+    const size_t fixed = off_rows + 256;
+    const uint64_t rays = (uint64_t)a.width * (uint64_t)a.rows.n_local_rows;
+    uint64_t blocks = rrt_mc::blocks_in_budget(rrt_mc::wanted_blocks(rays, kBlockBytes, grown), march_cache_budget(c), fixed, kCacheBlockBytes);
+    if (blocks == 0) return rrt_mc::kWhyBudget;
+    if (c.bytes > fixed) {                           /* memory an earlier key left: use all of it */
+        uint64_t have = (c.bytes - fixed) / kCacheBlockBytes;
+        if (have > 0x0fffffffull) have = 0x0fffffffull;
+        if (have > blocks) blocks = have;
+    }
+    if (grown && blocks <= c.cap_blocks) return rrt_mc::kWhyOverflow;       /* the budget leaves nothing to grow into */
+    const size_t need = fixed + (size_t)blocks * kCacheBlockBytes;
+    if (!c.chained) {
+        if (hipEventCreateWithFlags(&c.chained, hipEventDisableTiming) != hipSuccess ||
+            hipHostMalloc(reinterpret_cast<void**>(&c.h_stats), sizeof(DeferCounters), hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            MarchCacheRegistry::destroy(c);
+            return rrt_mc::kWhyAlloc;
+        }
+        memset(c.h_stats, 0, sizeof(DeferCounters));
+    }
+    if (need > c.bytes) {
+        MarchCacheRegistry::free_device_memory(c);          /* waits for the launches that still read it */
+        if (hipMalloc(reinterpret_cast<void**>(&c.d_base), need) != hipSuccess) { (void)hipGetLastError(); c.d_base = nullptr; return rrt_mc::kWhyAlloc; }
+        c.bytes = need;
+    }
+    c.off_fin = off_fin; c.off_rows = off_rows; c.n_lanes = n_lanes;
+    c.cap_blocks = (unsigned)blocks;
+    c.off_out = align(off_rows + (size_t)blocks * kBlockBytes);
+    c.used_blocks = 0;
+    return rrt_mc::kWhyNone;
+}
+
+/* a fill (march -> evaluate -> composite, pass 1 writing the cache) or a replay (evaluate -> composite on the retained rows):
+ * one chain on the caller's stream.  Two chains were measured for a whole-frame replay and bought nothing (3.78 against 3.78 ms,
+ * profiles/r07_march_cache_ab.txt): no second stream, no pool split. */
+int march_cache_enqueue(MarchCacheObject& c, FrameArgs a, int arith, int media, dim3 grid, bool fill, hipStream_t st) {
+    a.hdr = reinterpret_cast<WaveHdr*>(c.d_base + 256);
+    a.finals = reinterpret_cast<float*>(c.d_base + c.off_fin);
+    a.n_lanes = c.n_lanes;
+    if (c.launches > 0) RRT_HIP(hipStreamWaitEvent(st, c.chained, 0));
+    if (fill) {
+        hipLaunchKernelGGL(zero_words, dim3((unsigned)((c.off_fin / 16 + 255) / 256)), dim3(256), 0, st,
+                           reinterpret_cast<uint4*>(c.d_base), c.off_fin / 16);
+        RRT_HIP(hipGetLastError());
+    }
+    a.ctr = reinterpret_cast<DeferCounters*>(c.d_base);
+    a.sample_blocks = c.d_base + c.off_rows;
+    a.block_capacity = c.cap_blocks;
+    const KeepArgs kp{c.d_base + c.off_out, fill ? 0u : c.used_blocks, fill ? 0 : 1};
+    const int rc = enqueue_chain(a, arith, media, grid, 0, 1, (int)grid.y, 1, st, &kp);
+    if (rc != RRT_OK) return rc;
+    if (fill) RRT_HIP(hipMemcpyAsync(c.h_stats, a.ctr, sizeof(DeferCounters), hipMemcpyDeviceToHost, st));
+    RRT_HIP(hipEventRecord(c.chained, st));
+    ++c.launches;
+    return RRT_OK;
+}
+
+/* A launch without a workspace of its own asks its device's cache.  `launched`: the frame has been enqueued here; otherwise the
+ * caller runs today's code, whether the key was only remembered, cannot be cached, or the cache is off. */
+int march_cache_launch(const FrameArgs& a, const LaunchOpts& o, dim3 grid, hipStream_t st, bool& launched) {
+    launched = false;
+    if (march_cache_env_off() || faked_device() >= 0) return RRT_OK;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (st != nullptr && hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
+    if (cap != hipStreamCaptureStatusNone) return RRT_OK;             /* a replayed graph must not read what a later launch rewrites */
+    const int dev = current_device();
+    if (dev < 0) return RRT_OK;
+    MarchCacheObject* cp = march_cache_of(dev, true);
+    std::lock_guard<std::mutex> lk(cp->mu);
+    MarchCacheObject& c = *cp;
+    if (march_cache_budget(c) == 0) return RRT_OK;
+    const rrt_mc::MarchKey k = march_key(a, o);
+    if (c.pol.pending_for(k)) {                   /* the third launch of a key: what did its fill use, did everything fit? */
+        RRT_HIP(hipEventSynchronize(c.chained));
+        const volatile DeferCounters* h = c.h_stats;
+        c.used_blocks = h->peak_blocks;
+        c.pol.fill_verified(h->rounds_run == 1u && h->suspended_left == 0u);
+    }
+    const rrt_mc::Action act = c.pol.next(k);
+    if (act == rrt_mc::kFill) {
+        const int why = march_cache_reserve(c, a, grid, c.pol.grown);
+        if (why != rrt_mc::kWhyNone) c.pol.fill_failed(why);
+    }
+    /* a key that has been given up serves nothing: its memory goes back now, not when another key arrives */
+    if (c.pol.state == rrt_mc::kOff && c.d_base) MarchCacheRegistry::free_device_memory(c);
+    if (act == rrt_mc::kToday || c.pol.state == rrt_mc::kOff) return RRT_OK;
+    const int rc = march_cache_enqueue(c, a, o.arith, o.media, grid, act == rrt_mc::kFill, st);
+    if (rc != RRT_OK) { c.pol.reset(); return rc; }
+    launched = true;
+    return RRT_OK;
+}
 
 /* room for n tiles in a tile-order object (grows only; growing forgets the order) */
 int tile_order_reserve(TileOrderObject& o, size_t n) {
@@ -539,6 +760,12 @@ int launch(const FrameArgs& a, const LaunchOpts& o, bool debug, hipStream_t st) 
         const int rc = launch_deferred(b, o.arith, o.media, ws, o.pool_rounds, o.pass_chains, st);
         if (rc > 0) return rc;
         launched = rc == RRT_OK;
+    }
+    /* a launch that brings no workspace: its device's march cache may hold this key's geodesics (a still camera) */
+    if (o.workspace == 0 && !debug && o.media != 0 && o.policy != RRT_PATH_SINGLE && a.tile_order_id == 0 &&
+        a.rows.tile_of_local == nullptr && a.max_steps <= kThreePassMaxSteps) {
+        const int rc = march_cache_launch(b, o, grid, st, launched);
+        if (rc != RRT_OK) return rc;
     }
     if (!launched) {
         dispatch_kernel(spin, o.media, o.arith, [&](auto S, auto M, auto F) {
@@ -1439,6 +1666,64 @@ int rrt_noise_table_fit_window(float t_from, float t_until, size_t budget_bytes,
         }
     }
     return RRT_OK;
+}
+
+/* ---- march cache (include/rrt.h) ---- */
+}  // extern "C"
+namespace {
+int march_cache_device(int device) { return device >= 0 ? device : current_device(); }
+/* runs f with `device` current (the cache's memory is freed and allocated there) */
+template <class F>
+int on_device(int device, F&& f) {
+    int prev = -1;
+    if (faked_device() >= 0) return f();
+    RRT_HIP(hipGetDevice(&prev));
+    if (prev != device) RRT_HIP(hipSetDevice(device));
+    const int rc = f();
+    if (prev != device) (void)hipSetDevice(prev);
+    return rc;
+}
+}  // namespace
+extern "C" {
+int rrt_march_cache_configure(int device, size_t max_bytes) {
+    const int dev = march_cache_device(device);
+    if (dev < 0) return RRT_ERR_NO_DEVICE;
+    MarchCacheObject* c = march_cache_of(dev, true);
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->pol.reset();
+    c->configured = true; c->budget_known = true; c->max_bytes = max_bytes;
+    if (c->bytes > max_bytes) return on_device(dev, [&] { MarchCacheRegistry::free_device_memory(*c); return RRT_OK; });
+    return RRT_OK;
+}
+
+int rrt_march_cache_stats(int device, rrt_march_cache_info* out) {
+    if (!out) return RRT_ERR_INVALID_ARGUMENT;
+    memset(out, 0, sizeof(*out));
+    const int dev = march_cache_device(device);
+    if (dev < 0) return RRT_ERR_NO_DEVICE;
+    MarchCacheObject* c = march_cache_of(dev, false);
+    if (!c) return RRT_OK;
+    std::lock_guard<std::mutex> lk(c->mu);
+    out->fills = c->pol.st.fills; out->hits = c->pol.st.hits; out->drops = c->pol.st.drops;
+    out->misses = c->pol.st.misses; out->uncacheable = c->pol.st.uncacheable;
+    out->bytes = c->bytes;
+    out->max_bytes = march_cache_env_off() ? 0 : (c->budget_known ? c->max_bytes : 0);
+    out->state = c->pol.state; out->why = c->pol.why;
+    if (c->pol.state == rrt_mc::kReady || c->pol.state == rrt_mc::kPending) {
+        out->blocks_capacity = c->cap_blocks;
+        if (c->pol.state == rrt_mc::kReady) out->blocks_used = c->used_blocks;
+    }
+    return RRT_OK;
+}
+
+int rrt_march_cache_release(int device) {
+    const int dev = march_cache_device(device);
+    if (dev < 0) return RRT_ERR_NO_DEVICE;
+    MarchCacheObject* c = march_cache_of(dev, false);
+    if (!c) return RRT_OK;
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->pol.reset();
+    return on_device(dev, [&] { MarchCacheRegistry::destroy(*c); return RRT_OK; });
 }
 
 int rrt_launch_raymarch_rows(void* d_out_rows, int width, int height, int y0, int y1, float time,

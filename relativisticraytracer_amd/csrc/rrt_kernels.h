@@ -8,7 +8,8 @@
  * Replaces the reference's only kernel, raymarch_kernel (src/raymarcher.cu:15-174):
  *   raymarch_pixels<SPIN,MEDIA,DEBUG,ARITH>   single-kernel path: one ray per lane, media sampled in line
  *   march_defer / eval_sample_rows / composite_and_shade (/ pool_next_round, zero_words)
- *                                             three-pass path through a caller-owned workspace, in rounds, as two chains
+ *                                             three-pass path through a caller-owned workspace, in rounds, as two chains;
+ *                                             with KEEP: passes 2 and 3 over the march cache's retained rows (KeepArgs)
  *   probe_costs / probe_to_tiles              coarse march-only probe of a view: first-frame dispatch order, row-tile costs
  *   clock_probe_kernel                        the shader clock the chip holds
  *   assemble_tiles_kernel / assemble_all_kernel / assemble_map_kernel   scatter gathered row-tile shards into the frame
@@ -69,6 +70,19 @@ constexpr unsigned kNoBlock = 0xffffffffu;
 constexpr int kMaxChains = 2;
 constexpr size_t kCounterStride = 64;      /* bytes between the chains' DeferCounters at the head of the workspace */
 static_assert(sizeof(DeferCounters) <= kCounterStride, "one counter block per chain");
+/* Retained geodesics (the march cache): passes 2 and 3 instantiated with KEEP leave a row's inputs alone --
+ * pass 2 writes (ex, ey, ez, transmittance) and the row's live mask to planes of their own, block b of the pool's slice at
+ * out_blocks + b * kOutBlockBytes: kBlockRows x four float[64] planes, then the kBlockRows masks -- and pass 3 reads them there
+ * (the links between a wave's runs stay in the input blocks).  `replay`: the rows are those an earlier launch's pass 1 left;
+ * n_blocks of the slice are in use, every wave has marched to its end, the headers and counters are not written. */
+struct KeepArgs {
+    uint8_t* out_blocks;
+    unsigned n_blocks;
+    int replay;
+};
+constexpr unsigned kOutRowData = 4 * 256;
+constexpr unsigned kOutBlockMasks = kBlockRows * kOutRowData;
+constexpr unsigned kOutBlockBytes = kOutBlockMasks + kBlockRows * 8;
 /* ------------------------------------------------------------------ lattice-hash tables: box of lattice points, fill kernel */
 struct LutBox { int x0, y0, z0, nx, ny, nz; };
 
@@ -378,7 +392,7 @@ __device__ __forceinline__ void march_inline_v1(const FrameArgs& a, v3& p, v3& v
  * the register copies of that meeting (FMAD: 14 v_mov on 221 arithmetic instructions; strict: 5 on 278).  Here the
  * loop-carried state has one producer; with the body written out twice a step can write its results into the registers of
  * the state before last, which the escape test (pre-step position, post-step velocity: raymarcher.cu:120) has released by
- * then: 220 VALU per FMAD vacuum step, 281 strict, no copy left (tools/isa_histogram.py; 4K bench frame 32.2 -> 30.3 ms
+ * then: 216 VALU per FMAD vacuum step, 276 strict, no copy left (tools/isa_histogram.py; 4K bench frame 32.2 -> 30.3 ms
  * FMAD, 37.2 -> 35.9 strict, same bytes: profiles/r06_vac_inner_ab.txt).  A lane that escapes does not leave by itself -- a
  * divergent exit would make the step counter a per-lane value: the WAVE leaves (1), the escaped lanes end their march at the
  * caller, the others come back in.
@@ -1102,10 +1116,10 @@ __global__ void pool_next_round(DeferCounters* c, unsigned capacity, int last) {
 #ifndef RRT_EVAL_WAVES
 #define RRT_EVAL_WAVES 8
 #endif
-template <int ARITH, int MEDIA>
-__global__ __launch_bounds__(256, RRT_EVAL_WAVES) void eval_sample_rows(const FrameArgs a) {
+template <int ARITH, int MEDIA, bool KEEP = false>
+__global__ __launch_bounds__(256, RRT_EVAL_WAVES) void eval_sample_rows(const FrameArgs a, const KeepArgs kp) {
     const int lane = threadIdx.x & 63;
-    const unsigned n_blk = min(a.ctr->next_block, a.block_capacity);
+    const unsigned n_blk = KEEP && kp.replay ? min(kp.n_blocks, a.block_capacity) : min(a.ctr->next_block, a.block_capacity);
     const unsigned total = n_blk * kBlockRows;
     const unsigned n_waves = gridDim.x * 4u;
     /* (Round 5 also tried this loop software-pipelined by hand -- the next row's planes and the mask after it in flight while a
@@ -1116,7 +1130,12 @@ __global__ __launch_bounds__(256, RRT_EVAL_WAVES) void eval_sample_rows(const Fr
         const unsigned k = row % kBlockRows;
         unsigned long long* mask_p = reinterpret_cast<unsigned long long*>(blk + kBlockTrailer) + k;
         const unsigned long long mask = *mask_p;
-        if (mask == 0ull) continue;                                   /* wave-uniform */
+        uint8_t* const oblk = KEEP ? kp.out_blocks + (size_t)(row / kBlockRows) * kOutBlockBytes : nullptr;
+        unsigned long long* const omask_p = KEEP ? reinterpret_cast<unsigned long long*>(oblk + kOutBlockMasks) + k : nullptr;
+        if (mask == 0ull) {                                           /* wave-uniform */
+            if (KEEP && lane == 0) *omask_p = 0ull;                   /* the planes hold another frame's masks */
+            continue;
+        }
         const bool mine = (mask >> lane) & 1ull;
         float* f = reinterpret_cast<float*>(blk + k * kRowData) + lane;
         bool has = false;
@@ -1138,22 +1157,29 @@ __global__ __launch_bounds__(256, RRT_EVAL_WAVES) void eval_sample_rows(const Fr
          * and so does pass 3 now: such lanes leave the row's mask instead of storing (0, 0, 0, 1) (the march pools every sample
          * inside the radial gate and the slab: from inside the disk most of them are real, on the bench view most are not). */
         const unsigned long long live = __ballot(has);
-        if (has) { f[0] = ex; f[64] = ey; f[128] = ez; f[192] = s; }
-        if (live != mask && lane == (int)(__ffsll((long long)mask) - 1)) *mask_p = live;
+        if (KEEP) {                                                    /* the row keeps its inputs and its mask */
+            float* g = reinterpret_cast<float*>(oblk + k * kOutRowData) + lane;
+            if (has) { g[0] = ex; g[64] = ey; g[128] = ez; g[192] = s; }
+            if (lane == (int)(__ffsll((long long)mask) - 1)) *omask_p = live;
+        } else {
+            if (has) { f[0] = ex; f[64] = ey; f[128] = ez; f[192] = s; }
+            if (live != mask && lane == (int)(__ffsll((long long)mask) - 1)) *mask_p = live;
+        }
     }
 }
 
 /* ---- pass 3: composite each ray's samples in march order; shade the rays of wavefronts that have reached their end;
  *      LAST (the last round the host enqueued): rays still suspended are finished with the media sampled in line ---- */
-template <bool SPIN, int ARITH, int MEDIA, bool LAST>
-__global__ __launch_bounds__(kWGThreads) void composite_and_shade(const FrameArgs a) {
-    if (a.ctr->rounds_run != 0u && a.ctr->last_overflow == 0u) return;      /* a later round with nothing left: all leave */
+template <bool SPIN, int ARITH, int MEDIA, bool LAST, bool KEEP = false>
+__global__ __launch_bounds__(kWGThreads) void composite_and_shade(const FrameArgs a, const KeepArgs kp) {
+    const bool replay = KEEP && kp.replay != 0;                             /* retained rows: one round, long finished */
+    if (!replay && a.ctr->rounds_run != 0u && a.ctr->last_overflow == 0u) return;      /* a later round with nothing left: all leave */
     const unsigned long long t_start = a.tile_cost ? __builtin_readcyclecounter() : 0ull;
     int x, y, out_row;
     if (!lane_pixel(a, x, y, out_row)) return;
     const int lane = threadIdx.x & 63;
     const unsigned wid = wave_slot(a);
-    const unsigned state = a.hdr[wid].state;
+    const unsigned state = replay ? 1u : a.hdr[wid].state;
     if (state != 1u && state != 2u) return;                        /* shaded in an earlier round */
     const size_t li = (size_t)wid * 64 + lane;
     Radiance acc = {0.f, 0.f, 0.f, 1.0f};
@@ -1180,12 +1206,13 @@ __global__ __launch_bounds__(kWGThreads) void composite_and_shade(const FrameArg
              * mask pass 2 has emptied cost this pass 30-150 % (round 5, profiles/r05_pass_counters.txt) for 25 % fewer bytes */
 #pragma unroll
             for (unsigned j = 0; j < kNB; ++j) {
-                const uint8_t* blk = a.sample_blocks + (size_t)(run_start + (b + j < run_len ? b + j : b)) * kBlockBytes;
-                const unsigned long long* masks = reinterpret_cast<const unsigned long long*>(blk + kBlockTrailer);
+                const size_t bi = run_start + (b + j < run_len ? b + j : b);
+                const uint8_t* blk = KEEP ? kp.out_blocks + bi * kOutBlockBytes : a.sample_blocks + bi * kBlockBytes;
+                const unsigned long long* masks = reinterpret_cast<const unsigned long long*>(blk + (KEEP ? kOutBlockMasks : kBlockTrailer));
 #pragma unroll
                 for (unsigned k = 0; k < kBlockRows; ++k) {
                     m[j][k] = masks[k];
-                    const float* f = reinterpret_cast<const float*>(blk + k * kRowData) + lane;
+                    const float* f = reinterpret_cast<const float*>(blk + k * (KEEP ? kOutRowData : kRowData)) + lane;
                     e[j][k][0] = f[0]; e[j][k][1] = f[64]; e[j][k][2] = f[128]; e[j][k][3] = f[192];
                 }
             }
@@ -1224,7 +1251,7 @@ __global__ __launch_bounds__(kWGThreads) void composite_and_shade(const FrameArg
     }
     if (hit) acc.t = 0.0f;                                         /* raymarcher.cu:49 */
     shade_and_store<false>(a, x, y, out_row, uvx, uvy, hit, p, vel, acc, steps);
-    if (lane == leader) a.hdr[wid].state = 3u;
+    if (!replay && lane == leader) a.hdr[wid].state = 3u;
 #ifndef RRT_WAVE_TIMELINE
     if (a.tile_cost) add_tile_cost(a, t_start);
 #endif

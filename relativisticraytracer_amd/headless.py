@@ -335,7 +335,8 @@ def main(argv=None):
                           "motion_blur": mb, "shutter": args.shutter, "glow": glow.info() if glow is not None else None,
                           "projection": args.projection, "fov_deg": proj.fov_deg if pano else None,
                           "vfov_deg": proj.vfov_deg if args.projection == "equirect" else None,
-                          "stereo": stereo.info() if stereo is not None else None}),
+                          "stereo": stereo.info() if stereo is not None else None,
+                          "march_cache": rrt.march_cache_stats()}),
               flush=True)
     if world > 1:
         dist.destroy_process_group()
