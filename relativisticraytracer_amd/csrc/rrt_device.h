@@ -461,8 +461,9 @@ RRT_DEV void integrate_rk4(v3& p, v3& v, float h, float drag_c) {
  * an estimate to rounding level, then the same residual correction as sqrt_rsq.  The residual r of the LAST
  * iteration measures the error that iteration started from; the result is used only if |r| <= kSeedTol, i.e. if
  * that error was small enough for the iteration to converge to rounding level -- otherwise (first step of a ray,
- * a huge jump) the caller falls back to sqrt_rsq.  Checked against sqrtf over two full binades x seed errors up to
- * the tolerance on the GPU (rrt_selfcheck_sqrt_seeded).
+ * a huge jump) the caller falls back to sqrt_rsq.  This is the plain form of the idea; the march runs sqrt_seeded_yh
+ * below (the same iteration, acceptance on the first residual), which is the one checked against sqrtf over two full
+ * binades x seed errors up to the tolerance on the GPU (rrt_selfcheck_sqrt_seeded).
  */
 constexpr float kSeedTol = 1.5e-4f;         /* 1.5 * tol^2 = 3.4e-8 < 2^-24.8 */
 template <int ITERS>
@@ -482,59 +483,10 @@ RRT_DEV bool sqrt_seeded(float x, float y0, float& root, float& inv_root) {
     return fabsf(r) <= kSeedTol;
 }
 
-/* radius of a stage position: seeded sqrt, rsq-based one where the seed was not good enough, and the
- * `r < 1` special case of geodesic_acc() */
-template <int ITERS>
-RRT_DEV void stage_radius(float r2, float seed, float& r, float& y) {
-    const bool ok = sqrt_seeded<ITERS>(r2, seed, r, y);
-    /* An accepted result is the correctly rounded root whatever the magnitude of r2 (the iteration is invariant
-     * under scaling by 4^k), so the `r2 < 1` special case -- there to keep r and the reciprocal finite when r2 is 0,
-     * tiny or NaN, none of which a finite estimate can "converge" to -- only needs looking at when it is rejected. */
-    if (__builtin_expect(__any(!ok), 0)) {
-        if (!ok) {
-            sqrt_rsq(r2, r, y);
-            if (!(r2 >= 1.0f)) { r = sqrtf(r2); y = 1.0f; }
-        }
-    }
-}
-
-/* integrate_rk4_r with the stage radii from seeded square roots; y_next = 1/|p4|, the estimate for the
- * radius of the position this step ends at (it differs from p4 by O(h^2)) */
-template <bool SPIN>
-RRT_DEV void integrate_rk4_seeded(v3& p, v3& v, float h, float hh, float h6, float drag_c,
-                                  float r2, float r, float y, float& y_next) {
-    v3 p0 = p, v0 = v;
-    v3 kv1 = geodesic_acc_r<SPIN>(p0, v0, drag_c, r2, r, y);
-    v3 v2 = add(v0, mul(kv1, hh));
-    v3 p2 = add(p0, mul(v0, hh));
-    float r2b = dot(p2, p2), rb, yb;
-    stage_radius<2>(r2b, y, rb, yb);
-    v3 kv2 = geodesic_acc_r<SPIN>(p2, v2, drag_c, r2b, rb, yb);
-    v3 v3_ = add(v0, mul(kv2, hh));
-    v3 p3 = add(p0, mul(v2, hh));
-    float r2c = dot(p3, p3), rc, yc;
-    stage_radius<1>(r2c, yb, rc, yc);
-    v3 kv3 = geodesic_acc_r<SPIN>(p3, v3_, drag_c, r2c, rc, yc);
-    v3 v4 = add(v0, mul(kv3, h));
-    v3 p4 = add(p0, mul(v3_, h));
-    float r2d = dot(p4, p4), rd, yd;
-    stage_radius<2>(r2d, yc, rd, yd);
-    v3 kv4 = geodesic_acc_r<SPIN>(p4, v4, drag_c, r2d, rd, yd);
-    v3 kv_sum, kp_sum;
-    kv_sum.x = kv1.x + __builtin_fmaf(2.0f, kv2.x, __builtin_fmaf(2.0f, kv3.x, kv4.x));
-    kv_sum.y = kv1.y + __builtin_fmaf(2.0f, kv2.y, __builtin_fmaf(2.0f, kv3.y, kv4.y));
-    kv_sum.z = kv1.z + __builtin_fmaf(2.0f, kv2.z, __builtin_fmaf(2.0f, kv3.z, kv4.z));
-    kp_sum.x = v0.x + __builtin_fmaf(2.0f, v2.x, __builtin_fmaf(2.0f, v3_.x, v4.x));
-    kp_sum.y = v0.y + __builtin_fmaf(2.0f, v2.y, __builtin_fmaf(2.0f, v3_.y, v4.y));
-    kp_sum.z = v0.z + __builtin_fmaf(2.0f, v2.z, __builtin_fmaf(2.0f, v3_.z, v4.z));
-    v = add(v0, mul(kv_sum, h6));
-    p = add(p0, mul(kp_sum, h6));
-    y_next = yd;
-}
-
 /*
- * Round 3: the same step with fewer instructions (`integrate_rk4_lean`).  The loop is VALU-issue bound at ~95 % of
- * all issue slots, so only the instruction COUNT moves it; what was still in the step beyond the arithmetic:
+ * The march's step (`integrate_rk4_lean`): integrate_rk4_r with every stage radius a seeded square root, in as few
+ * instructions as that takes.  The loop is VALU-issue bound at ~95 % of all issue slots, so only the instruction COUNT moves
+ * it; what a straightforward seeded step (sqrt_seeded per stage, round 2) carries beyond the arithmetic, and this one does not:
  *   - `h = 0.5f * y0` at the head of every seeded square root: each root already produces h = y/2 (the Goldschmidt
  *     half-reciprocal) next to y = h + h, so the pair (y, h) is handed on instead of y alone (-1 per root);
  *   - the acceptance test moves from the LAST to the FIRST residual, r1 = 1/2 - h0*g0 = (1 - x*y0^2)/2, which measures
@@ -547,7 +499,7 @@ RRT_DEV void integrate_rk4_seeded(v3& p, v3& v, float h, float hh, float h6, flo
  *     radius its seed came from, and the chain of seeds starts at the loop-top radius, which has passed the horizon
  *     test r >= 2.02 (or, for the loop-top root itself, at the previous step's last stage): every accepted radius
  *     is > 1.9, so the guard can only fire on lanes that took the v_rsq fall-back, and is evaluated there (-4 compares);
- *   - VAC (a compile-time flag for the wave-uniform vacuum step, rrt_hip.hip): h, h/2 and h/6 are literals.
+ *   - VAC (a compile-time flag for the wave-uniform vacuum step, rrt_kernels.h: vacuum_run): h, h/2 and h/6 are literals.
  * Bits are unchanged: every root is still the correctly rounded one (or the fall-back's), y and h only seed the
  * Markstein divides, which deliver the correctly rounded quotient from any seed of that quality.
  */

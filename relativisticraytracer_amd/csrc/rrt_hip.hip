@@ -57,6 +57,13 @@ int hip_fail(hipError_t e, const char* what) {
         if (e_ != hipSuccess) return hip_fail(e_, #call);   \
     } while (0)
 
+/* is `st` being captured into a graph?  The null stream never is; an error from the query reads as "no" and is cleared */
+bool stream_is_capturing(hipStream_t st) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (st != nullptr && hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
+    return cap != hipStreamCaptureStatusNone;
+}
+
 /* ------------------------------------------------------------------ sky handles
  * A handle is an id into a process-wide registry, never a raw pointer: a stale or made-up handle is
  * reported as RRT_ERR_BAD_HANDLE instead of being dereferenced. */
@@ -252,6 +259,25 @@ static_assert(kThreePassMaxSteps < (1ll << 30), "step count must fit beside the 
 constexpr int kFinalPlanes = 11;      /* per ray: vel xyz, code, pos xyz, radiance rgbt */
 constexpr int kMaxPoolRounds = 64;
 
+/* Where the three-pass bookkeeping of a launch over `grid` sits in its memory: the chains' counters at byte 0, the wave headers
+ * at off_hdr, `final_planes` float planes of n_lanes rays at off_fin, the sample blocks from off_rows on (all multiples of 256) */
+struct PoolLayout {
+    size_t n_waves, n_lanes, off_hdr, off_fin, off_rows;
+    static size_t align(size_t v) { return (v + 255) & ~(size_t)255; }
+    /* how many blocks of `block_bytes` fit in `bytes` (the block index shares its word with flags) */
+    static size_t blocks_in(size_t bytes, size_t block_bytes) { return std::min<size_t>(bytes / block_bytes, 0x0fffffffu); }
+};
+PoolLayout pool_layout(dim3 grid, int final_planes) {
+    static_assert(kMaxChains * kCounterStride <= 256, "the chains' counters sit in front of the wave headers");
+    PoolLayout l;
+    l.n_waves = (size_t)grid.x * grid.y * kWGWaves;
+    l.n_lanes = l.n_waves * 64;
+    l.off_hdr = 256;
+    l.off_fin = PoolLayout::align(l.off_hdr + l.n_waves * sizeof(WaveHdr));
+    l.off_rows = PoolLayout::align(l.off_fin + l.n_lanes * 4 * final_planes);
+    return l;
+}
+
 /* How many rounds to enqueue (rrt_params.pool_rounds == 0).  The host cannot ask the device without stalling the
  * stream, so it reads the statistics the workspace's PREVIOUS launch left in pinned host memory (an asynchronous copy
  * behind its last kernel; possibly a frame stale, which is all an animation needs): as many rounds as that launch had
@@ -273,34 +299,46 @@ int auto_pool_rounds(const volatile DeferCounters* h, unsigned capacity) {
     return r > kMaxPoolRounds ? kMaxPoolRounds : r;
 }
 
-/* the kernels of one arithmetic mode, instantiated per (spin, tables).  KEEP: the march cache's chain (rrt_march_cache.h) -- one
- * round, pass 2's results in planes of their own (kp); with kp.replay pass 1 and the round's close are left out */
-/* (the kernels of passes 2 and 3 take a KeepArgs whether or not they are KEEP instances: one signature per kernel; the
- * workspace path passes an empty one, which its instances never read) */
-template <int ARITH, bool KEEP = false>
-int enqueue_chain_arith(const FrameArgs& a, int media, dim3 grid, dim3 block, int rounds, hipStream_t st, const KeepArgs kp = KeepArgs{nullptr, 0u, 0}) {
-    const bool spin = a.spin != 0.0f;
+/* The template instances of a launch: f(SPIN, MEDIA, ARITH) with the three as std::integral_constants.  MEDIA0: `media == 0`
+ * (no volumetrics) is an instance of its own -- the single kernels; the three-pass chain has no such instance (a launch
+ * without volumetrics never takes it) and dispatches with MEDIA0 = false */
+template <bool MEDIA0 = true, class F>
+void dispatch_kernel(bool spin, int media, int arith, F&& f) {
+    const auto by_arith = [&](auto S, auto M) {
+        if (arith == kArithFast) f(S, M, std::integral_constant<int, kArithFast>{});
+        else if (arith == kArithFmad) f(S, M, std::integral_constant<int, kArithFmad>{});
+        else f(S, M, std::integral_constant<int, kArithStrict>{});
+    };
+    const auto by_media = [&](auto S) {
+        if (media == 3) by_arith(S, std::integral_constant<int, 3>{});
+        else if (media == 2) by_arith(S, std::integral_constant<int, 2>{});
+        else if (!MEDIA0 || media == 1) by_arith(S, std::integral_constant<int, 1>{});
+        else if constexpr (MEDIA0) by_arith(S, std::integral_constant<int, 0>{});
+    };
+    if (spin) by_media(std::true_type{}); else by_media(std::false_type{});
+}
+
+/* the rounds of one chain.  KEEP: the march cache's chain (rrt_march_cache.h) -- one round, pass 2's results in planes of their
+ * own (kp); with kp.replay pass 1 and the round's close are left out.  (The kernels of passes 2 and 3 take a KeepArgs whether
+ * or not they are KEEP instances: one signature per kernel; the workspace path passes an empty one, which its instances never
+ * read.  march_defer has no MEDIA parameter: every MEDIA launches the same instance.) */
+template <bool SPIN, int MEDIA, int ARITH, bool KEEP>
+int enqueue_rounds(const FrameArgs& a, dim3 grid, dim3 block, int rounds, hipStream_t st, const KeepArgs kp) {
     const bool replay = KEEP && kp.replay != 0;
     if (KEEP) rounds = 1;
     for (int r = 0; r < rounds; ++r) {
         const bool last = r == rounds - 1;
-#define RRT_MARCH(S) do { if (r == 0) hipLaunchKernelGGL((march_defer<S, ARITH, false>), grid, block, 0, st, a); \
-                          else hipLaunchKernelGGL((march_defer<S, ARITH, true>), grid, block, 0, st, a); } while (0)
-        if (!replay) { if (spin) RRT_MARCH(true); else RRT_MARCH(false); }
-#undef RRT_MARCH
+        if (!replay) {
+            if (r == 0) hipLaunchKernelGGL((march_defer<SPIN, ARITH, false>), grid, block, 0, st, a);
+            else hipLaunchKernelGGL((march_defer<SPIN, ARITH, true>), grid, block, 0, st, a);
+        }
         RRT_HIP(hipGetLastError());
-        if (media == 3) hipLaunchKernelGGL((eval_sample_rows<ARITH, 3, KEEP>), dim3(2048), dim3(256), 0, st, a, kp);
-        else if (media == 2) hipLaunchKernelGGL((eval_sample_rows<ARITH, 2, KEEP>), dim3(2048), dim3(256), 0, st, a, kp);
-        else hipLaunchKernelGGL((eval_sample_rows<ARITH, 1, KEEP>), dim3(2048), dim3(256), 0, st, a, kp);
+        hipLaunchKernelGGL((eval_sample_rows<ARITH, MEDIA, KEEP>), dim3(2048), dim3(256), 0, st, a, kp);
         RRT_HIP(hipGetLastError());
         /* LAST = true for the last round enqueued; the cache's chain (KEEP) has one round, so only <LAST, KEEP> = <true, true> exists */
-#define RRT_COMP3(S, L) do { if constexpr (KEEP) hipLaunchKernelGGL((composite_and_shade<S, ARITH, L, true, true>), grid, block, 0, st, a, kp); \
-                             else if (last) hipLaunchKernelGGL((composite_and_shade<S, ARITH, L, true, false>), grid, block, 0, st, a, kp); \
-                             else hipLaunchKernelGGL((composite_and_shade<S, ARITH, L, false, false>), grid, block, 0, st, a, kp); } while (0)
-#define RRT_COMP(S) do { if (media == 3) RRT_COMP3(S, 3); else if (media == 2) RRT_COMP3(S, 2); else RRT_COMP3(S, 1); } while (0)
-        if (spin) RRT_COMP(true); else RRT_COMP(false);
-#undef RRT_COMP
-#undef RRT_COMP3
+        if constexpr (KEEP) hipLaunchKernelGGL((composite_and_shade<SPIN, ARITH, MEDIA, true, true>), grid, block, 0, st, a, kp);
+        else if (last) hipLaunchKernelGGL((composite_and_shade<SPIN, ARITH, MEDIA, true, false>), grid, block, 0, st, a, kp);
+        else hipLaunchKernelGGL((composite_and_shade<SPIN, ARITH, MEDIA, false, false>), grid, block, 0, st, a, kp);
         RRT_HIP(hipGetLastError());
         if (replay) break;
         hipLaunchKernelGGL(pool_next_round, dim3(1), dim3(1), 0, st, a.ctr, a.block_capacity, last ? 1 : 0);
@@ -310,20 +348,18 @@ int enqueue_chain_arith(const FrameArgs& a, int media, dim3 grid, dim3 block, in
 }
 
 /* one chain = march -> evaluate -> composite (in rounds) over dispatch rows [row0, row1) of the launch, in its own slice
- * of the pool, on its own stream */
+ * of the pool, on its own stream; `keep`: the march cache's chain */
 int enqueue_chain(FrameArgs a, int arith, int media, dim3 full_grid, int row0, int row_stride, int n_rows, int rounds, hipStream_t st,
                   const KeepArgs* keep = nullptr) {
     if (n_rows <= 0) return RRT_OK;
     const dim3 block(kWGThreads), grid(full_grid.x, (unsigned)n_rows);
     a.grid_rows = (int)full_grid.y; a.grid_row_base = row0; a.grid_row_stride = row_stride;
-    if (keep) {
-        if (arith == kArithFast) return enqueue_chain_arith<kArithFast, true>(a, media, grid, block, 1, st, *keep);
-        if (arith == kArithFmad) return enqueue_chain_arith<kArithFmad, true>(a, media, grid, block, 1, st, *keep);
-        return enqueue_chain_arith<kArithStrict, true>(a, media, grid, block, 1, st, *keep);
-    }
-    if (arith == kArithFast) return enqueue_chain_arith<kArithFast>(a, media, grid, block, rounds, st);
-    if (arith == kArithFmad) return enqueue_chain_arith<kArithFmad>(a, media, grid, block, rounds, st);
-    return enqueue_chain_arith<kArithStrict>(a, media, grid, block, rounds, st);
+    int rc = RRT_OK;
+    dispatch_kernel<false>(a.spin != 0.0f, media, arith, [&](auto S, auto M, auto A) {
+        rc = keep ? enqueue_rounds<S, M, A, true>(a, grid, block, 1, st, *keep)
+                  : enqueue_rounds<S, M, A, false>(a, grid, block, rounds, st, KeepArgs{nullptr, 0u, 0});
+    });
+    return rc;
 }
 
 /* Three-pass launch through a workspace.  Returns RRT_OK after enqueuing, or -1 if the workspace cannot
@@ -341,33 +377,21 @@ int enqueue_chain(FrameArgs a, int arith, int media, dim3 full_grid, int row0, i
  * a launch that is being captured into a graph, or a small one, runs one chain. */
 int launch_deferred(FrameArgs a, int arith, int media, const WorkspaceObject& ws, int pool_rounds, int chains_wanted, hipStream_t st) {
     dim3 grid((a.width + kWGPixX - 1) / kWGPixX, (a.rows.n_local_rows + kWGPixY - 1) / kWGPixY);
-    const size_t n_waves = (size_t)grid.x * grid.y * kWGWaves;
-    const size_t n_lanes = n_waves * 64;
-    auto align = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t off_hdr = 256;
-    static_assert(kMaxChains * kCounterStride <= 256, "the chains' counters sit in front of the wave headers");
-    const size_t off_fin = align(off_hdr + n_waves * sizeof(WaveHdr));
-    const size_t off_rows = align(off_fin + n_lanes * 4 * kFinalPlanes);
+    const PoolLayout lay = pool_layout(grid, kFinalPlanes);
+    const size_t n_waves = lay.n_waves, off_fin = lay.off_fin, off_rows = lay.off_rows;
     if (ws.bytes < off_rows + (size_t)1024 * kBlockBytes) return -1;
-    size_t cap = (ws.bytes - off_rows) / kBlockBytes;
-    if (cap > 0x0fffffffu) cap = 0x0fffffffu;
-    a.hdr = reinterpret_cast<WaveHdr*>(ws.d_base + off_hdr);
+    const size_t cap = PoolLayout::blocks_in(ws.bytes - off_rows, kBlockBytes);
+    a.hdr = reinterpret_cast<WaveHdr*>(ws.d_base + lay.off_hdr);
     a.finals = reinterpret_cast<float*>(ws.d_base + off_fin);
-    a.n_lanes = n_lanes;
+    a.n_lanes = lay.n_lanes;
     /* one chain or two */
     int chains = 1;
-    if (chains_wanted != 1 && ws.side != nullptr && grid.y >= 8 && cap >= 4096 && n_waves >= (chains_wanted == 2 ? 2u : 2048u)) {
-        hipStreamCaptureStatus capst = hipStreamCaptureStatusNone;
-        if (st != nullptr && hipStreamIsCapturing(st, &capst) != hipSuccess) { (void)hipGetLastError(); capst = hipStreamCaptureStatusNone; }
-        if (capst == hipStreamCaptureStatusNone) chains = 2;
-    }
-#ifdef RRT_WS_MEMSET      /* dev builds only: rounds 1-3's hipMemsetAsync, to re-examine round 4's capture failure (LABNOTES.md, round 5) */
-    RRT_HIP(hipMemsetAsync(ws.d_base, 0, off_fin, st));
-#else
+    if (chains_wanted != 1 && ws.side != nullptr && grid.y >= 8 && cap >= 4096 && n_waves >= (chains_wanted == 2 ? 2u : 2048u) &&
+        !stream_is_capturing(st))
+        chains = 2;
     hipLaunchKernelGGL(zero_words, dim3((unsigned)((off_fin / 16 + 255) / 256)), dim3(256), 0, st,
                        reinterpret_cast<uint4*>(ws.d_base), off_fin / 16);        /* counters + wave headers (off_fin is a multiple of 256) */
     RRT_HIP(hipGetLastError());
-#endif
     /* the pool's split: by what each chain pooled last time (the heavy half holds most of the media), 65 : 35 without history */
     size_t cap_of[kMaxChains] = {cap, 0};
     /* which dispatch rows a chain takes: the first and the second half of the static order (the frame's middle and the rest) --
@@ -443,8 +467,9 @@ struct MarchCacheObject {
     DeferCounters* h_stats = nullptr;      /* pinned: what the fill used, copied behind it */
     hipEvent_t chained = nullptr;
     unsigned long long launches = 0;
-    /* layout of the current key's fill */
-    size_t off_fin = 0, off_rows = 0, off_out = 0, n_lanes = 0;
+    /* layout of the current key's fill; off_out: pass 2's planes (KeepArgs), behind the sample blocks */
+    PoolLayout lay{};
+    size_t off_out = 0;
     unsigned cap_blocks = 0, used_blocks = 0;
 };
 struct MarchCacheRegistry {
@@ -536,17 +561,13 @@ constexpr size_t kCacheBlockBytes = (size_t)kBlockBytes + kOutBlockBytes;
 
 /* memory and layout for a fill of `grid` with (at least) the capacity rule's blocks; rrt_mc::kWhy* if there is none to be had */
 int march_cache_reserve(MarchCacheObject& c, const FrameArgs& a, dim3 grid, bool grown) {
-    auto align = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t n_waves = (size_t)grid.x * grid.y * kWGWaves, n_lanes = n_waves * 64;
-    const size_t off_fin = align(256 + n_waves * sizeof(WaveHdr));
-    const size_t off_rows = align(off_fin + n_lanes * 4 * kCacheFinalPlanes);
-    const size_t fixed = off_rows + 256;
+    const PoolLayout lay = pool_layout(grid, kCacheFinalPlanes);
+    const size_t fixed = lay.off_rows + 256;
     const uint64_t rays = (uint64_t)a.width * (uint64_t)a.rows.n_local_rows;
     uint64_t blocks = rrt_mc::blocks_in_budget(rrt_mc::wanted_blocks(rays, kBlockBytes, grown), march_cache_budget(c), fixed, kCacheBlockBytes);
     if (blocks == 0) return rrt_mc::kWhyBudget;
     if (c.bytes > fixed) {                           /* memory an earlier key left: use all of it */
-        uint64_t have = (c.bytes - fixed) / kCacheBlockBytes;
-        if (have > 0x0fffffffull) have = 0x0fffffffull;
+        const uint64_t have = PoolLayout::blocks_in(c.bytes - fixed, kCacheBlockBytes);
         if (have > blocks) blocks = have;
     }
     if (grown && blocks <= c.cap_blocks) return rrt_mc::kWhyOverflow;       /* the budget leaves nothing to grow into */
@@ -565,9 +586,9 @@ int march_cache_reserve(MarchCacheObject& c, const FrameArgs& a, dim3 grid, bool
         if (hipMalloc(reinterpret_cast<void**>(&c.d_base), need) != hipSuccess) { (void)hipGetLastError(); c.d_base = nullptr; return rrt_mc::kWhyAlloc; }
         c.bytes = need;
     }
-    c.off_fin = off_fin; c.off_rows = off_rows; c.n_lanes = n_lanes;
+    c.lay = lay;
     c.cap_blocks = (unsigned)blocks;
-    c.off_out = align(off_rows + (size_t)blocks * kBlockBytes);
+    c.off_out = PoolLayout::align(lay.off_rows + (size_t)blocks * kBlockBytes);
     c.used_blocks = 0;
     return rrt_mc::kWhyNone;
 }
@@ -576,17 +597,17 @@ int march_cache_reserve(MarchCacheObject& c, const FrameArgs& a, dim3 grid, bool
  * one chain on the caller's stream.  Two chains were measured for a whole-frame replay and bought nothing (3.78 against 3.78 ms,
  * profiles/r07_march_cache_ab.txt): no second stream, no pool split. */
 int march_cache_enqueue(MarchCacheObject& c, FrameArgs a, int arith, int media, dim3 grid, bool fill, hipStream_t st) {
-    a.hdr = reinterpret_cast<WaveHdr*>(c.d_base + 256);
-    a.finals = reinterpret_cast<float*>(c.d_base + c.off_fin);
-    a.n_lanes = c.n_lanes;
+    a.hdr = reinterpret_cast<WaveHdr*>(c.d_base + c.lay.off_hdr);
+    a.finals = reinterpret_cast<float*>(c.d_base + c.lay.off_fin);
+    a.n_lanes = c.lay.n_lanes;
     if (c.launches > 0) RRT_HIP(hipStreamWaitEvent(st, c.chained, 0));
     if (fill) {
-        hipLaunchKernelGGL(zero_words, dim3((unsigned)((c.off_fin / 16 + 255) / 256)), dim3(256), 0, st,
-                           reinterpret_cast<uint4*>(c.d_base), c.off_fin / 16);
+        hipLaunchKernelGGL(zero_words, dim3((unsigned)((c.lay.off_fin / 16 + 255) / 256)), dim3(256), 0, st,
+                           reinterpret_cast<uint4*>(c.d_base), c.lay.off_fin / 16);
         RRT_HIP(hipGetLastError());
     }
     a.ctr = reinterpret_cast<DeferCounters*>(c.d_base);
-    a.sample_blocks = c.d_base + c.off_rows;
+    a.sample_blocks = c.d_base + c.lay.off_rows;
     a.block_capacity = c.cap_blocks;
     const KeepArgs kp{c.d_base + c.off_out, fill ? 0u : c.used_blocks, fill ? 0 : 1};
     const int rc = enqueue_chain(a, arith, media, grid, 0, 1, (int)grid.y, 1, st, &kp);
@@ -602,9 +623,7 @@ int march_cache_enqueue(MarchCacheObject& c, FrameArgs a, int arith, int media, 
 int march_cache_launch(const FrameArgs& a, const LaunchOpts& o, dim3 grid, hipStream_t st, bool& launched) {
     launched = false;
     if (march_cache_env_off() || faked_device() >= 0) return RRT_OK;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (st != nullptr && hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
-    if (cap != hipStreamCaptureStatusNone) return RRT_OK;             /* a replayed graph must not read what a later launch rewrites */
+    if (stream_is_capturing(st)) return RRT_OK;                       /* a replayed graph must not read what a later launch rewrites */
     const int dev = current_device();
     if (dev < 0) return RRT_OK;
     MarchCacheObject* cp = march_cache_of(dev, true);
@@ -674,23 +693,6 @@ int enqueue_probe(const FrameArgs& a, ProbeArgs& q, unsigned* cells, int stride_
     return RRT_OK;
 }
 
-/* The template instance of a single-kernel launch: f(SPIN, MEDIA, ARITH) with the three as std::integral_constants */
-template <class F>
-void dispatch_kernel(bool spin, int media, int arith, F&& f) {
-    const auto by_arith = [&](auto S, auto M) {
-        if (arith == kArithFast) f(S, M, std::integral_constant<int, kArithFast>{});
-        else if (arith == kArithFmad) f(S, M, std::integral_constant<int, kArithFmad>{});
-        else f(S, M, std::integral_constant<int, kArithStrict>{});
-    };
-    const auto by_media = [&](auto S) {
-        if (media == 3) by_arith(S, std::integral_constant<int, 3>{});
-        else if (media == 2) by_arith(S, std::integral_constant<int, 2>{});
-        else if (media == 1) by_arith(S, std::integral_constant<int, 1>{});
-        else by_arith(S, std::integral_constant<int, 0>{});
-    };
-    if (spin) by_media(std::true_type{}); else by_media(std::false_type{});
-}
-
 int launch(const FrameArgs& a, const LaunchOpts& o, bool debug, hipStream_t st) {
     dim3 block(kWGThreads);
     if (a.rows.n_local_rows == 0) return RRT_OK;
@@ -720,9 +722,7 @@ int launch(const FrameArgs& a, const LaunchOpts& o, bool debug, hipStream_t st) 
     std::unique_lock<std::mutex> order_lock;
     const size_t n_tiles = (size_t)grid.x * grid.y;
     if (a.tile_order_id != 0 && !debug && kWGWaves == 1) {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (st != nullptr && hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
-        if (cap == hipStreamCaptureStatusNone) {
+        if (!stream_is_capturing(st)) {
             order = tile_order_lookup(a.tile_order_id);
             if (!order || !on_current_device(order->device)) return RRT_ERR_BAD_HANDLE;
             order_lock = std::unique_lock<std::mutex>(order->mu);

@@ -266,23 +266,6 @@ __device__ __forceinline__ void shade_and_store(const FrameArgs& a, int x, int y
     }
 }
 
-/* The same with the strict square root seeded by an estimate of 1/r (rrt_device.h: sqrt_seeded): `seed` = 1/|p4| of
- * the previous step, whose end point differs from this position by O(h^2); 0 on a ray's first step (falls back). */
-template <bool FAST>
-__device__ __forceinline__ void march_radius_seeded(v3 rel_p, float seed, float& r2, float& r, float& y) {
-    if (FAST) {
-        r2 = dot_fma(rel_p, rel_p);
-        y = __builtin_amdgcn_rsqf(r2);
-        r = r2 * y;
-        if (__builtin_expect(__any(!(r2 >= 1.0f)), 0)) {
-            if (!(r2 >= 1.0f)) { r = sqrtf(r2); y = 1.0f; }
-        }
-    } else {
-        r2 = dot(rel_p, rel_p);
-        stage_radius<1>(r2, seed, r, y);
-    }
-}
-
 /* The step size takes three values (the `in_cloud_zone` arm of raymarcher.cu:62 is unreachable: the
  * cloud zone lies inside the disk zone); h*0.5f and h/6.0f (integrators.h:31,57) are folded per value
  * at compile time. */
@@ -290,11 +273,12 @@ constexpr float kHVac = kStepSize, kHNear = kStepSize * 0.1f, kHDisk = kStepSize
 
 /*
  * Per-pixel pipeline, one ray per lane (reference raymarch_kernel, src/raymarcher.cu:15-174).
- * A 256-thread workgroup covers a 16x16 pixel block as four 8x8 wave tiles so that the 64 rays of a
- * wavefront stay spatially coherent (similar step counts, similar zone entry).
+ * A wavefront covers an 8x8 pixel tile (the workgroup geometry is further down) so that its 64 rays
+ * stay spatially coherent (similar step counts, similar zone entry).
  */
-/* radius of the pre-step position exactly as the march sees it (strict: correctly rounded root of the unfused r2; FMAD: the
- * correctly rounded root of the fused r2; fast: r2*rsq) */
+/* radius of a position exactly as the march sees it (strict: correctly rounded root of the unfused r2; FMAD: the
+ * correctly rounded root of the fused r2; fast: r2*rsq), with the `r2 < 1` case of geodesic_acc().  The loop top of the
+ * fast march, pass 2's samples and the unit hooks; the lean loop has its own seeded roots (rrt_device.h: sqrt_seeded_yh). */
 constexpr int kArithStrict = RRT_ARITH_STRICT, kArithFast = RRT_ARITH_FAST, kArithFmad = RRT_ARITH_FMAD;
 template <int ARITH>
 __device__ __forceinline__ void march_radius(v3 rel_p, float& r2, float& r, float& y) {
@@ -311,41 +295,12 @@ __device__ __forceinline__ void march_radius(v3 rel_p, float& r2, float& r, floa
     }
 }
 
-/* One RK4 step of the march (integrate_rk4, integrators.h:23-59) from the loop-top radius of the pre-step
- * position.  (A variant without the per-stage `r < 1` guards -- 5 fewer vector instructions per step, repeated
- * with guards in the unreachable case -- was measured and dropped: the longer basic blocks it leaves let the
- * scheduler interleave independent chains, and on gfx950 a VALU instruction issued 2-6 slots after its producer
- * costs 10-15 % more than one issued right behind it; profiles/README.md, round 2.)
- * -DRRT_SEEDED_SQRT=0 builds the v_rsq-based stage radii instead (A/B: profiles/README.md). */
-#ifndef RRT_SEEDED_SQRT
-#define RRT_SEEDED_SQRT 1
-#endif
-template <bool SPIN, bool FAST>
-__device__ __forceinline__ void march_step(v3& p, v3& vel, float h, float hh, float h6, float drag_c, float r2, float r, float y,
-                                           float& y_seed) {
-    if (FAST) integrate_rk4_fast<SPIN>(p, vel, h, hh, h6, drag_c, r2, y);
-    else if (RRT_SEEDED_SQRT) integrate_rk4_seeded<SPIN>(p, vel, h, hh, h6, drag_c, r2, r, y, y_seed);
-    else integrate_rk4_r<SPIN>(p, vel, h, hh, h6, drag_c, r2, r, y);
-}
-
 /* Step size of raymarcher.cu:54-62 from the zone flags; h*0.5f is exact, h/6.0f is folded per value. */
 __device__ __forceinline__ void zone_step(bool near_bh, bool in_disk, float& h, float& hh, float& h6) {
     h = near_bh ? kHNear : (in_disk ? kHDisk : kHVac);
     hh = 0.5f * h;                                      /* == h * 0.5f of integrators.h:31, one multiply */
     h6 = near_bh ? kHNear / 6.0f : (in_disk ? kHDisk / 6.0f : kHVac / 6.0f);
 }
-
-/* Round 3: RRT_MARCH_V2 = the lean RK4 step (rrt_device.h: integrate_rk4_lean) and, with
- * RRT_VACUUM_PATH, a wave-uniform vacuum step.  -DRRT_MARCH_V2=0 builds round 2's loop (A/B: profiles/README.md). */
-#ifndef RRT_MARCH_V2
-#define RRT_MARCH_V2 1
-#endif
-#ifndef RRT_VACUUM_PATH
-#define RRT_VACUUM_PATH 1
-#endif
-#ifndef RRT_HORIZON_IN_GENERIC
-#define RRT_HORIZON_IN_GENERIC 0
-#endif
 
 /* r >= kVacuumR rules out the horizon test (r < 2.02) and every zone of raymarcher.cu:56-58 (near_bh r < 18, disk zone
  * r < 30, cloud zone r < 25): the step is h = STEP_SIZE_M with no media sample.  About nine steps in ten of the bench
@@ -356,17 +311,21 @@ constexpr float kVacuumR = kDiskOut + 5.0f;
  * MEDIA: 0 = densities read 0 ("skybox only"), 1 = full media, 2 = full media with the lattice-hash tables, 3 = with the
  * tables in their banded layout (rrt_device.h: DustBands).
  * `i`: in = first step (0, or where a resumed ray stopped), out = steps taken.  When every lane starts at the
- * same step the loop counter stays in a scalar register; the per-ray count is written once, at the exit. */
-template <bool SPIN, int MEDIA, bool FAST>
-__device__ __forceinline__ void march_inline_v1(const FrameArgs& a, v3& p, v3& vel, Radiance& acc, bool& hit, int& i,
-                                                unsigned* oob) {
+ * same step the loop counter stays in a scalar register; the per-ray count is written once, at the exit.
+ *
+ * The loop of RRT_ARITH_FAST (not the parity path): one flat loop, v_rsq radius, integrate_rk4_fast (rrt_device.h).  (A step
+ * without the per-stage `r < 1` guards -- 5 fewer vector instructions, repeated with guards in the unreachable case -- was
+ * measured and dropped: the longer basic blocks it leaves let the scheduler interleave independent chains, and on gfx950 a
+ * VALU instruction issued 2-6 slots after its producer costs 10-15 % more than one issued right behind it;
+ * profiles/README.md, round 2.) */
+template <bool SPIN, int MEDIA>
+__device__ __forceinline__ void march_inline_fast(const FrameArgs& a, v3& p, v3& vel, Radiance& acc, bool& hit, int& i,
+                                                  unsigned* oob) {
     int steps = i > a.max_steps ? i : a.max_steps;      /* if the loop runs out */
-    float y_seed = 0.0f;                                /* 1/r estimate for the next step's radius; 0: none yet */
     for (int k = i; k < a.max_steps; ++k) {
         const v3 rel_p = p;                             /* p - MASS_POS, MASS_POS = 0 */
         float r2, r, y;
-        if (RRT_SEEDED_SQRT) march_radius_seeded<FAST>(rel_p, y_seed, r2, r, y);
-        else march_radius<FAST>(rel_p, r2, r, y);
+        march_radius<kArithFast>(rel_p, r2, r, y);
         if (r < kEventHorizon * 1.01f) { hit = true; acc.t = 0.0f; steps = k; break; }
 
         const bool near_bh = r < 18.0f;
@@ -375,7 +334,7 @@ __device__ __forceinline__ void march_inline_v1(const FrameArgs& a, v3& p, v3& v
         float h, hh, h6;
         zone_step(near_bh, in_disk, h, hh, h6);
 
-        march_step<SPIN, FAST>(p, vel, h, hh, h6, a.drag_c, r2, r, y, y_seed);
+        integrate_rk4_fast<SPIN>(p, vel, h, hh, h6, a.drag_c, r2, y);
 
         if (MEDIA != 0 && (in_disk || in_cloud)) {
             float d_disk, d_cloud;
@@ -387,26 +346,24 @@ __device__ __forceinline__ void march_inline_v1(const FrameArgs& a, v3& p, v3& v
     i = steps;
 }
 
-/* Round 6: the vacuum steps of a wavefront in a loop of their own, every exit of which is wave-uniform.  In the flat loop
- * of rounds 3-5 the vacuum and the generic path met before the back edge, and the step that is taken nine times in ten paid
- * the register copies of that meeting (FMAD: 14 v_mov on 221 arithmetic instructions; strict: 5 on 278).  Here the
+/* The vacuum steps of a wavefront run in a loop of their own, every exit of which is wave-uniform.  In a flat loop the vacuum
+ * and the generic path meet before the back edge, and the step that is taken nine times in ten pays the register copies of
+ * that meeting (FMAD: 14 v_mov on 221 arithmetic instructions; strict: 5 on 278).  Here the
  * loop-carried state has one producer; with the body written out twice a step can write its results into the registers of
  * the state before last, which the escape test (pre-step position, post-step velocity: raymarcher.cu:120) has released by
  * then: 216 VALU per FMAD vacuum step, 276 strict, no copy left (tools/isa_histogram.py; 4K bench frame 32.2 -> 30.3 ms
  * FMAD, 37.2 -> 35.9 strict, same bytes: profiles/r06_vac_inner_ab.txt).  A lane that escapes does not leave by itself -- a
  * divergent exit would make the step counter a per-lane value: the WAVE leaves (1), the escaped lanes end their march at the
- * caller, the others come back in.
+ * caller, the others come back in.  The escape test's dot product sits behind a wave-uniform `some lane is beyond r = 250`
+ * (evaluated on every step it cost the 4K frame 0.4 ms).
  * In: the loop-top radius (r2, r, y, hy) of p, accepted and >= kVacuumR in every live lane.  Returns why the wave left:
  * 1 = a lane escaped (`escaped`; k counts its last step), 2 = out of steps, 3 = some lane needs the generic step: (r2, r, y,
- * hy, rejected, rej_mask) are then the loop-top values of the new p. */
+ * hy, rejected, rej_mask) are then the loop-top values of the new p.
+ * RRT_VAC_INNER: how many times the body is written out, 1 or 2. */
 #ifndef RRT_VAC_INNER
 #define RRT_VAC_INNER 2
 #endif
-/* the escape test's dot product behind a wave-uniform `some lane is beyond r = 250` (1), or evaluated on every step (0:
- * 0.4 ms slower on the 4K frame) */
-#ifndef RRT_VAC_ESC_BRANCH
-#define RRT_VAC_ESC_BRANCH 1
-#endif
+static_assert(RRT_VAC_INNER == 1 || RRT_VAC_INNER == 2, "vacuum_run writes its body out once or twice");
 template <bool SPIN, bool FMA>
 __device__ __forceinline__ int vacuum_run(v3& p, v3& vel, float drag_c, int& k, int max_steps, float& r2, float& r, float& y, float& hy,
                                           float& ys, float& hs, float& hcp, bool& rejected, unsigned long long& rej_mask, bool& escaped) {
@@ -416,7 +373,7 @@ __device__ __forceinline__ int vacuum_run(v3& p, v3& vel, float drag_c, int& k, 
         integrate_rk4_lean<SPIN, true, FMA>(p, vel, 0.f, 0.f, 0.f, drag_c, r2, r, y, hy, ys, hs, hcp);                \
         ++k;                                                                                                          \
         escaped = false;                                                                                              \
-        if (!RRT_VAC_ESC_BRANCH || __builtin_amdgcn_ballot_w64(r > 250.0f) != 0ull) { /* raymarcher.cu:120 */         \
+        if (__builtin_amdgcn_ballot_w64(r > 250.0f) != 0ull) {                        /* raymarcher.cu:120 */         \
             escaped = r > 250.0f && (FMA ? dot_fma(q, vel) : dot(q, vel)) > 0.0f;                                     \
             if (__builtin_amdgcn_ballot_w64(escaped) != 0ull) return 1;                                               \
         }                                                                                                             \
@@ -435,21 +392,21 @@ __device__ __forceinline__ int vacuum_run(v3& p, v3& vel, float drag_c, int& k, 
 #undef RRT_VAC_STEP
 }
 
-/* UK: every lane of the wave enters at the same step `i` (the single kernel: 0), so the step counter is one number per wave;
+/* FAST: march_inline_fast.  Otherwise the lean loop (rrt_device.h: integrate_rk4_lean; FMAD: with fused multiply-adds): the
+ * loop-top radius from the seed pair the previous step handed on, the vacuum steps in vacuum_run, every other step generic.
+ * UK: every lane of the wave enters at the same step `i` (the single kernel: 0), so the step counter is one number per wave;
  * the loop says so once per outer iteration (v_readfirstlane), which keeps the counter and the vacuum loop's exit code in
  * scalar registers whatever the compiler makes of the merged exits of the outer loop. */
 template <bool SPIN, int MEDIA, int ARITH, bool UK = false>
 __device__ __forceinline__ void march_inline(const FrameArgs& a, v3& p, v3& vel, Radiance& acc, bool& hit, int& i,
                                              unsigned* oob) {
-    constexpr bool FMA = ARITH == kArithFmad;           /* the lean loop with fused multiply-adds (rrt_device.h: integrate_rk4_lean) */
-    if constexpr (ARITH == kArithFast || !RRT_MARCH_V2) {
-        march_inline_v1<SPIN, MEDIA, ARITH == kArithFast>(a, p, vel, acc, hit, i, oob);
+    constexpr bool FMA = ARITH == kArithFmad;
+    if constexpr (ARITH == kArithFast) {
+        march_inline_fast<SPIN, MEDIA>(a, p, vel, acc, hit, i, oob);
     } else {
         int steps = i > a.max_steps ? i : a.max_steps;  /* if the loop runs out */
         float ys = 0.0f, hs = 0.0f;                     /* (1/r, 1/(2r)) estimate for the next loop-top radius; 0: none yet */
         float hcp = 0.0f;                               /* 1/(2r) at the previous vacuum step's stage 3 (seed extrapolation) */
-#if RRT_VAC_INNER
-        /* vacuum steps in a loop of their own (vacuum_run); #else: the flat loop of rounds 3-5 */
         int k = i;
         while (k < a.max_steps) {
             if (UK) k = __builtin_amdgcn_readfirstlane(k);
@@ -459,7 +416,7 @@ __device__ __forceinline__ void march_inline(const FrameArgs& a, v3& p, v3& vel,
             bool rejected = sqrt_seeded_yh<1>(r2, ys, hs, r, y, hy);
             /* wave-uniform: every live lane holds an accepted radius >= kVacuumR (two compares, scalar logic) */
             unsigned long long rej_mask = __builtin_amdgcn_ballot_w64(rejected);
-            if (RRT_VACUUM_PATH && (rej_mask | __builtin_amdgcn_ballot_w64(!(r >= kVacuumR))) == 0ull) {
+            if ((rej_mask | __builtin_amdgcn_ballot_w64(!(r >= kVacuumR))) == 0ull) {
                 bool escaped;
                 const int why = vacuum_run<SPIN, FMA>(p, vel, a.drag_c, k, a.max_steps, r2, r, y, hy, ys, hs, hcp, rejected, rej_mask, escaped);
                 if (escaped) { steps = k; break; }      /* k counts the step just taken */
@@ -485,50 +442,6 @@ __device__ __forceinline__ void march_inline(const FrameArgs& a, v3& p, v3& vel,
             ++k;
             if (r > 250.0f && (FMA ? dot_fma(rel_p, vel) : dot(rel_p, vel)) > 0.0f) { steps = k; break; }     /* raymarcher.cu:120 */
         }
-#else
-        for (int k = i; k < a.max_steps; ++k) {
-            const v3 rel_p = p;                         /* p - MASS_POS, MASS_POS = 0 */
-            const float r2 = FMA ? dot_fma(rel_p, rel_p) : dot(rel_p, rel_p);
-            float r, y, hy;
-            const bool rejected = sqrt_seeded_yh<1>(r2, ys, hs, r, y, hy);
-            /* wave-uniform: every live lane holds an accepted radius >= kVacuumR (two compares, scalar logic) */
-            const unsigned long long rej_mask = __builtin_amdgcn_ballot_w64(rejected);
-            const bool vacuum = RRT_VACUUM_PATH && (rej_mask | __builtin_amdgcn_ballot_w64(!(r >= kVacuumR))) == 0ull;
-#if RRT_HORIZON_IN_GENERIC
-            if (vacuum) {
-                integrate_rk4_lean<SPIN, true, FMA>(p, vel, 0.f, 0.f, 0.f, a.drag_c, r2, r, y, hy, ys, hs, hcp);
-            } else {
-                if (rej_mask != 0ull) {
-                    bool small;
-                    if (rejected) radius_fallback(r2, r, y, hy, small);
-                }
-                if (r < kEventHorizon * 1.01f) { hit = true; acc.t = 0.0f; steps = k; break; }
-#else
-            if (!vacuum && rej_mask != 0ull) {
-                bool small;                             /* r < 1 ends the ray at the horizon test below */
-                if (rejected) radius_fallback(r2, r, y, hy, small);
-            }
-            if (r < kEventHorizon * 1.01f) { hit = true; acc.t = 0.0f; steps = k; break; }
-
-            if (vacuum) {
-                integrate_rk4_lean<SPIN, true, FMA>(p, vel, 0.f, 0.f, 0.f, a.drag_c, r2, r, y, hy, ys, hs, hcp);
-            } else {
-#endif
-                const bool near_bh = r < 18.0f;
-                const bool in_disk = fabsf(rel_p.y) < kDiskH * 5.0f && r < kDiskOut + 5.0f;
-                const bool in_cloud = fabsf(rel_p.y) < kCloudH * 1.5f && r < kCloudOut;
-                float h, hh, h6;
-                zone_step(near_bh, in_disk, h, hh, h6);
-                integrate_rk4_lean<SPIN, false, FMA>(p, vel, h, hh, h6, a.drag_c, r2, r, y, hy, ys, hs, hcp);
-                if (MEDIA != 0 && (in_disk || in_cloud)) {
-                    float d_disk, d_cloud;
-                    media_densities<MEDIA>(rel_p, a.time, in_disk, in_cloud, a.lut_acc, a.lut_dust, a.dust_bands, oob, d_disk, d_cloud);
-                    accumulate_sample(acc, d_disk, d_cloud, rel_p, r, vel, h, a.spin);
-                }
-            }
-            if (r > 250.0f && (FMA ? dot_fma(rel_p, vel) : dot(rel_p, vel)) > 0.0f) { steps = k + 1; break; }     /* raymarcher.cu:120 */
-        }
-#endif
         i = steps;
     }
 }
@@ -639,11 +552,6 @@ __device__ __forceinline__ void add_tile_cost(const FrameArgs& a, unsigned long 
 template <bool SPIN, int MEDIA, bool DEBUG, int ARITH>
 __global__ __launch_bounds__(kWGThreads, (MEDIA != 0 && !DEBUG ? RRT_MEDIA_WAVES : 1))      /* 2nd: minimum waves per SIMD */
 void raymarch_pixels(const FrameArgs a) {
-#if defined(RRT_OCC_PROBE_LDS)      /* dev probe: cap the occupancy of the kernel WITHOUT media code through its LDS footprint (8192 B per one-wave
-                                     * workgroup = 20 workgroups per CU = 5 waves per SIMD): what the march loses at the media kernels' occupancy */
-    __shared__ volatile int occ_pad[RRT_OCC_PROBE_LDS / 4];
-    if (MEDIA == 0) occ_pad[threadIdx.x] = 0;
-#endif
     const unsigned long long t_start = a.tile_cost ? __builtin_readcyclecounter() : 0ull;
     int x, y, out_row;
     if (!lane_pixel(a, x, y, out_row)) return;
@@ -935,24 +843,26 @@ __global__ __launch_bounds__(kWGThreads, RRT_DEFER_WAVES) RRT_DEFER_SGPR_ATTR vo
     unsigned used = kBlockRows;                                   /* rows used in the current block */
     bool overflow = false;                                        /* this lane stopped because the pool is full */
 
-    constexpr bool LEAN = !FAST && RRT_MARCH_V2;               /* round 3's step (march_inline has the notes) */
-    float y_seed = 0.0f, h_seed = 0.0f, hc_prev = 0.0f;        /* a resumed ray starts without seeds: its first root takes the
-                                                                * v_rsq fall-back, which is the same correctly rounded root */
+    constexpr bool LEAN = !FAST;                               /* the lean step and vacuum_run (march_inline has the notes) */
+    float y_seed = 0.0f, h_seed = 0.0f, hc_prev = 0.0f;        /* (LEAN) a resumed ray starts without seeds: its first root takes
+                                                                * the v_rsq fall-back, which is the same correctly rounded root */
     /* `i` is a per-lane variable only across rounds: the lanes that march in a round all start at the same step (0, or the
      * step the pool ran out at, which is a wave-uniform event) -- but a first round can PROVE it to the compiler-independent
      * v_readfirstlane below, a resumed one only by that argument, so only the first round keeps the counter scalar */
-    constexpr bool UK = !RESUME && LEAN && RRT_VAC_INNER;
+    constexpr bool UK = !RESUME && LEAN;
     for (; active && i < a.max_steps; ++i) {
         if (UK) i = __builtin_amdgcn_readfirstlane(i);
         v3 rel_p = p;
         float r2, r, yv, hv = 0.0f;
+        /* `vacuum` is false wherever it is read below vacuum_run: it and the branches it guards are what is left of the flat
+         * loop.  They stay because the compiler's output depends on them (without them every instance of this kernel comes
+         * out different, the lean ones ~400 instructions shorter): taking them out is a change to measure, not a clean-up. */
         bool vacuum = false;
         if constexpr (LEAN) {
             r2 = FMA ? dot_fma(rel_p, rel_p) : dot(rel_p, rel_p);
             bool rejected = sqrt_seeded_yh<1>(r2, y_seed, h_seed, r, yv, hv);
             unsigned long long rej_mask = __builtin_amdgcn_ballot_w64(rejected);
-            vacuum = RRT_VACUUM_PATH && (rej_mask | __builtin_amdgcn_ballot_w64(!(r >= kVacuumR))) == 0ull;
-#if RRT_VAC_INNER
+            vacuum = (rej_mask | __builtin_amdgcn_ballot_w64(!(r >= kVacuumR))) == 0ull;
             if (vacuum) {                                          /* the vacuum steps in their own loop (vacuum_run) */
                 bool escaped;
                 const int why = vacuum_run<SPIN, FMA>(p, vel, a.drag_c, i, a.max_steps, r2, r, yv, hv, y_seed, h_seed, hc_prev, rejected,
@@ -962,13 +872,11 @@ __global__ __launch_bounds__(kWGThreads, RRT_DEFER_WAVES) RRT_DEFER_SGPR_ATTR vo
                 rel_p = p;
                 vacuum = false;
             }
-#endif
             if (!vacuum && rej_mask != 0ull) {
                 bool small;
                 if (rejected) radius_fallback(r2, r, yv, hv, small);
             }
-        } else if (RRT_SEEDED_SQRT) march_radius_seeded<FAST>(rel_p, y_seed, r2, r, yv);
-        else march_radius<ARITH>(rel_p, r2, r, yv);
+        } else march_radius<kArithFast>(rel_p, r2, r, yv);
         if (r < kEventHorizon * 1.01f) { hit = true; break; }
 
         bool in_disk = false, in_cloud = false;
@@ -1053,7 +961,7 @@ __global__ __launch_bounds__(kWGThreads, RRT_DEFER_WAVES) RRT_DEFER_SGPR_ATTR vo
         if constexpr (LEAN) {
             if (vacuum) integrate_rk4_lean<SPIN, true, FMA>(p, vel, 0.f, 0.f, 0.f, a.drag_c, r2, r, yv, hv, y_seed, h_seed, hc_prev);
             else integrate_rk4_lean<SPIN, false, FMA>(p, vel, h, hh, h6, a.drag_c, r2, r, yv, hv, y_seed, h_seed, hc_prev);
-        } else march_step<SPIN, FAST>(p, vel, h, hh, h6, a.drag_c, r2, r, yv, y_seed);
+        } else integrate_rk4_fast<SPIN>(p, vel, h, hh, h6, a.drag_c, r2, yv);
 
         if (!vacuum && need) {                                                /* pre-step position, post-step velocity */
             row_f[0] = rel_p.x; row_f[64] = rel_p.y; row_f[128] = rel_p.z;

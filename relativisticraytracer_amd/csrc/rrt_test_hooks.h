@@ -27,7 +27,7 @@ __global__ void k_rk4(int n, float* p, float* v, const float* h, float spin) {
     else integrate_rk4<false>(pp, vv, h[i], drag_c);
     st3(p, i, pp); st3(v, i, vv);
 }
-/* The PRODUCTION step (round 3's integrate_rk4_lean, what every render kernel runs) as a chain of n_steps steps per
+/* The PRODUCTION step (integrate_rk4_lean, what every strict and FMAD render kernel runs) as a chain of n_steps steps per
  * element, driven exactly as march_inline drives it: loop-top radius from the seed pair the previous step handed on
  * (seeded Goldschmidt root, v_rsq fall-back where the seed is rejected), horizon test r < 2.02 (the ray stops; the lean
  * step's stage 1 relies on it), then
@@ -56,7 +56,7 @@ __global__ __launch_bounds__(64) void k_rk4_lean(int n, float* p, float* v, cons
         float r, y, hy;
         const bool rejected = sqrt_seeded_yh<1>(r2, ys, hs, r, y, hy);
         const unsigned long long rej_mask = __builtin_amdgcn_ballot_w64(rejected);
-        const bool vacuum = h_in == nullptr && RRT_VACUUM_PATH && (rej_mask | __builtin_amdgcn_ballot_w64(!(r >= kVacuumR))) == 0ull;
+        const bool vacuum = h_in == nullptr && (rej_mask | __builtin_amdgcn_ballot_w64(!(r >= kVacuumR))) == 0ull;
         if (!vacuum && rej_mask != 0ull) {
             bool small;
             if (rejected) radius_fallback(r2, r, y, hy, small);
@@ -309,8 +309,8 @@ __global__ void k_selfcheck_div_march(unsigned long long n, uint32_t seed, float
     atomicAdd(counters + 3, checked);
 }
 
-/* sqrt_seeded against sqrtf: every float whose bits lie in [lo, hi), with estimates of 1/sqrt(x) that are off by
- * 0, +-1e-5 ... +-1.2e-2 relative (a fixed ladder plus 16 pseudo-random errors per x), one and two iterations.  Wherever sqrt_seeded ACCEPTS its result (returns true) the
+/* sqrt_seeded_yh against sqrtf: every float whose bits lie in [lo, hi), with estimates of 1/sqrt(x) that are off by
+ * 0, +-1e-5 ... +-1.2e-2 relative (a fixed ladder plus 16 pseudo-random errors per x), one and two iterations.  Wherever sqrt_seeded_yh ACCEPTS its result (returns false: not rejected) the
  * root must be sqrtf(x) bit for bit.  counters[0] += mismatches, [1]/[2] one failing case (x bits, seed bits),
  * [3] += accepted cases (so that a test can see the check was not vacuous). */
 __global__ void k_selfcheck_sqrt_seeded(uint32_t lo, uint32_t hi, unsigned long long* counters) {
@@ -334,8 +334,7 @@ __global__ void k_selfcheck_sqrt_seeded(uint32_t lo, uint32_t hi, unsigned long 
                 }
                 const float seed = y_exact * (1.0f + (float)sgn * delta);
                 float r1, y1, r2, y2;
-#if RRT_MARCH_V2
-                /* the form the march uses since round 3: (y, y/2) handed on, acceptance on the FIRST residual */
+                /* the form the march uses: (y, y/2) handed on, acceptance on the FIRST residual */
                 float h1, h2;
                 if (!sqrt_seeded_yh<1>(x, seed, 0.5f * seed, r1, y1, h1)) { ++accepted; if (rrt_f2u(r1) != rrt_f2u(want) || y1 != h1 + h1) { ++bad; counters[1] = b; counters[2] = rrt_f2u(seed); } }
                 if (!sqrt_seeded_yh<2>(x, seed, 0.5f * seed, r2, y2, h2)) { ++accepted; if (rrt_f2u(r2) != rrt_f2u(want) || y2 != h2 + h2) { ++bad; counters[1] = b; counters[2] = rrt_f2u(seed); } }
@@ -343,10 +342,6 @@ __global__ void k_selfcheck_sqrt_seeded(uint32_t lo, uint32_t hi, unsigned long 
                 if (k == 0 && sgn > 0) {
                     if (!sqrt_seeded_yh<2>(x, 2.0f * y_exact, y_exact, r2, y2, h2) || !sqrt_seeded_yh<1>(x, 2.0f * y_exact, y_exact, r1, y1, h1)) { ++bad; counters[1] = b; counters[2] = 4; }
                 }
-#else
-                if (sqrt_seeded<1>(x, seed, r1, y1)) { ++accepted; if (rrt_f2u(r1) != rrt_f2u(want)) { ++bad; counters[1] = b; counters[2] = rrt_f2u(seed); } }
-                if (sqrt_seeded<2>(x, seed, r2, y2)) { ++accepted; if (rrt_f2u(r2) != rrt_f2u(want)) { ++bad; counters[1] = b; counters[2] = rrt_f2u(seed); } }
-#endif
             }
         }
     }
