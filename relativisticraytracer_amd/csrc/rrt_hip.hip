@@ -10,8 +10,12 @@
  * Sections (round 5: one 3 100-line file became four)
  *   rrt_kernels.h      the kernels and the structures they share with the host (included below: a kernel and its launch
  *                      site share a translation unit)
- *   this file          handle registries (sky, workspace, noise table, tile map, tile order), noise-table planning, path choice
- *                      and launch logic, the march cache's device object, the C ABI
+ *   this file          host helpers (the five handle tables, path choice and launch logic, the march cache's device object, what
+ *                      the entry points share) in ONE anonymous namespace, then the C ABI in ONE extern "C" block, grouped by
+ *                      object in the order include/rrt.h declares them; the C++ launch_raymarch at the end
+ *   rrt_handles.h      HandleTable: the registry behind every kind of handle, and the list of what the entry points do
+ *                      differently on purpose (host only, no HIP)
+ *   rrt_noise_plan.h   NoiseTableObject and the noise tables' planning; rrt_tile_objects.h: TileMapObject, TileOrderObject
  *   rrt_march_cache.h  the march cache's key, policy state machine and capacity rule (host only, no HIP)
  *   rrt_camera.cpp     camera basis / path playback / recording clock (plain C++)
  *   rrt_test_hooks.h   rrt_unit_*, rrt_selfcheck_*, rrt_debug_fake_device -- compiled only with -DRRT_TEST_HOOKS, i.e. into
@@ -40,10 +44,12 @@
 #include "rrt_device.h"
 #include "rrt_tile_sort.h"              /* the native radix sort behind rrt_tile_order */
 #include "rrt_march_cache.h"            /* the march cache's key, policy and capacity rule (host only) */
+#include "rrt_handles.h"                /* HandleTable (host only) */
 
 namespace {
 
 using namespace rrt;
+using rrt_handles::HandleTable;
 
 thread_local char g_hip_err[256] = "";
 
@@ -64,10 +70,8 @@ bool stream_is_capturing(hipStream_t st) {
     return cap != hipStreamCaptureStatusNone;
 }
 
-/* ------------------------------------------------------------------ sky handles
- * A handle is an id into a process-wide registry, never a raw pointer: a stale or made-up handle is
- * reported as RRT_ERR_BAD_HANDLE instead of being dereferenced. */
-/* Every handle records the HIP device it was created on, and every entry point that would dereference its
+/* ------------------------------------------------------------------ handles (the tables: rrt_handles.h)
+ * Every handle records the HIP device it was created on, and every entry point that would dereference its
  * allocation from a kernel or a copy compares that with the calling thread's current device: a sky, workspace or
  * noise table used under another hipSetDevice() is RRT_ERR_BAD_HANDLE, not a wild device pointer inside a kernel
  * (the one-process N-GPU driver and the process-global launch defaults make that mistake easy).
@@ -102,23 +106,6 @@ struct SkyObject {
     bool owned;
     int device;
 };
-std::mutex g_sky_mu;
-std::unordered_map<unsigned long long, SkyObject> g_sky;
-unsigned long long g_sky_next = 0x5254000000000001ull;
-
-bool sky_lookup(rrt_sky_t h, SkyObject& out) {
-    std::lock_guard<std::mutex> lk(g_sky_mu);
-    auto it = g_sky.find(h);
-    if (it == g_sky.end()) return false;
-    out = it->second;
-    return true;
-}
-rrt_sky_t sky_register(const SkyObject& s) {
-    std::lock_guard<std::mutex> lk(g_sky_mu);
-    rrt_sky_t h = g_sky_next++;
-    g_sky.emplace(h, s);
-    return h;
-}
 
 /* ------------------------------------------------------------------ device code (kernels, kernel arguments, pool layout) */
 #include "rrt_kernels.h"
@@ -130,16 +117,33 @@ struct WorkspaceObject {
     hipStream_t side;            /* the second chain's stream (round 4), with the two events that fork it from and join it to the caller's */
     hipEvent_t forked, joined;
 };
-std::mutex g_ws_mu;
-std::unordered_map<int, WorkspaceObject> g_ws;
-int g_ws_next = 1;
 
-/* ------------------------------------------------------------------ lattice-hash tables: planning + registry */
+/* ------------------------------------------------------------------ lattice-hash tables: NoiseTableObject + planning */
 #include "rrt_noise_plan.h"
 
-/* ------------------------------------------------------------------ rrt_tile_map / rrt_tile_order objects + registries */
+/* ------------------------------------------------------------------ TileMapObject (rrt_tile_map), TileOrderObject (rrt_tile_order) */
 #include "rrt_tile_objects.h"
 
+/* ------------------------------------------------------------------ the five handle tables
+ * Process-lifetime objects; an element's destructor never calls HIP (device memory is freed by the destroy entry points only:
+ * what is still registered at exit goes with the process).  rrt_sky_t ids start at "RT" << 48 | 1, the int ids at 1. */
+HandleTable<rrt_sky_t, SkyObject> g_skies(0x5254000000000001ull);
+HandleTable<int, WorkspaceObject> g_workspaces(1);
+HandleTable<int, NoiseTableObject> g_noise_tables(1);
+HandleTable<int, std::shared_ptr<TileMapObject>> g_tile_maps(1);
+HandleTable<int, std::shared_ptr<TileOrderObject>> g_tile_orders(1);
+
+template <class T> int device_of(const T& object) { return object.device; }
+template <class T> int device_of(const std::shared_ptr<T>& object) { return object->device; }
+/* the object behind `id`, for a caller that will dereference its device memory: unknown, or made under another device than the
+ * calling thread's current one, is RRT_ERR_BAD_HANDLE */
+template <class Id, class T>
+int lookup_here(HandleTable<Id, T>& table, std::common_type_t<Id> id, T& out) {
+    return table.get(id, out) && on_current_device(device_of(out)) ? RRT_OK : RRT_ERR_BAD_HANDLE;
+}
+/* take()'s predicate of the two kinds that are destroyed under their own device only */
+template <class T>
+bool made_here(const std::shared_ptr<T>& object) { return on_current_device(object->device); }
 
 #ifdef RRT_TEST_HOOKS
 #define RRT_TEST_HOOKS_PART 1
@@ -201,7 +205,7 @@ int fill_args(FrameArgs& a, LaunchOpts& o, void* out, int width, int height, flo
     rrt_params prm;
     load_params(prm_in, prm);
     SkyObject so;
-    if (!sky_lookup(sky, so) || !on_current_device(so.device)) return RRT_ERR_BAD_HANDLE;
+    if (lookup_here(g_skies, sky, so)) return RRT_ERR_BAD_HANDLE;
     const SkyObject* s = &so;
     a.out = static_cast<uchar4*>(out);
     a.width = width; a.height = height; a.time = time; a.cam = *cam;
@@ -219,20 +223,14 @@ int fill_args(FrameArgs& a, LaunchOpts& o, void* out, int width, int height, flo
     a.tile_perm = nullptr; a.tile_cost = nullptr; a.tile_order_id = prm.tile_order;
     a.grid_rows = 0; a.grid_row_base = 0; a.grid_row_stride = 1;
     if (prm.tile_order != 0) {                      /* whatever path the launch takes: a stale or foreign id is an error */
-        const std::shared_ptr<TileOrderObject> to = tile_order_lookup(prm.tile_order);
-        if (!to || !on_current_device(to->device)) return RRT_ERR_BAD_HANDLE;
+        std::shared_ptr<TileOrderObject> to;
+        if (lookup_here(g_tile_orders, prm.tile_order, to)) return RRT_ERR_BAD_HANDLE;
     }
     o.media = prm.volumetrics != 0 ? 1 : 0;
     memset(&a.lut_acc, 0, sizeof(a.lut_acc)); memset(&a.lut_dust, 0, sizeof(a.lut_dust)); memset(&a.dust_bands, 0, sizeof(a.dust_bands));
     if (prm.noise_table != 0) {
         NoiseTableObject nt;
-        {
-            std::lock_guard<std::mutex> lk(g_nt_mu);
-            auto it = g_nt.find(prm.noise_table);
-            if (it == g_nt.end()) return RRT_ERR_BAD_HANDLE;
-            nt = it->second;
-        }
-        if (!on_current_device(nt.device)) return RRT_ERR_BAD_HANDLE;
+        if (lookup_here(g_noise_tables, prm.noise_table, nt)) return RRT_ERR_BAD_HANDLE;
         /* the boxes were sized for t0 <= time <= t1; any other time runs the arithmetic kernels (same bytes) */
         if (o.media && time >= nt.t0 && time <= nt.t1) {
             o.media = nt.banded ? 3 : 2;
@@ -489,7 +487,7 @@ struct MarchCacheRegistry {
         (void)hipGetLastError();
     }
 };
-/* Never destroyed, like the other registries of this file: a static destructor would call into the HIP runtime at process exit
+/* Never destroyed, and the handle tables hold nothing whose destructor touches HIP either: a static destructor would call into the HIP runtime at process exit
  * or library unload, when the runtime may already be gone.  rrt_march_cache_release() is the way to give the memory back; what
  * is still held at exit goes with the process. */
 MarchCacheRegistry& march_caches() { static MarchCacheRegistry* const r = new MarchCacheRegistry; return *r; }
@@ -651,6 +649,19 @@ int march_cache_launch(const FrameArgs& a, const LaunchOpts& o, dim3 grid, hipSt
     return RRT_OK;
 }
 
+int march_cache_device(int device) { return device >= 0 ? device : current_device(); }
+/* runs f with `device` current (the cache's memory is freed and allocated there) */
+template <class F>
+int on_device(int device, F&& f) {
+    int prev = -1;
+    if (faked_device() >= 0) return f();
+    RRT_HIP(hipGetDevice(&prev));
+    if (prev != device) RRT_HIP(hipSetDevice(device));
+    const int rc = f();
+    if (prev != device) (void)hipSetDevice(prev);
+    return rc;
+}
+
 /* room for n tiles in a tile-order object (grows only; growing forgets the order) */
 int tile_order_reserve(TileOrderObject& o, size_t n) {
     if (n <= o.n_cap) return RRT_OK;
@@ -702,13 +713,7 @@ int launch(const FrameArgs& a, const LaunchOpts& o, bool debug, hipStream_t st) 
     WorkspaceObject ws{};
     bool deferred = false;
     if (o.workspace != 0) {
-        {
-            std::lock_guard<std::mutex> lk(g_ws_mu);
-            auto it = g_ws.find(o.workspace);
-            if (it == g_ws.end()) return RRT_ERR_BAD_HANDLE;
-            ws = it->second;
-        }
-        if (!on_current_device(ws.device)) return RRT_ERR_BAD_HANDLE;
+        if (lookup_here(g_workspaces, o.workspace, ws)) return RRT_ERR_BAD_HANDLE;
         const long long rays = (long long)a.width * a.rows.n_local_rows;
         const bool want = o.policy == RRT_PATH_THREE_PASS || (o.policy == RRT_PATH_AUTO && rays <= kThreePassMaxRays);
         deferred = o.media != 0 && !debug && want && a.max_steps <= kThreePassMaxSteps;
@@ -723,8 +728,7 @@ int launch(const FrameArgs& a, const LaunchOpts& o, bool debug, hipStream_t st) 
     const size_t n_tiles = (size_t)grid.x * grid.y;
     if (a.tile_order_id != 0 && !debug && kWGWaves == 1) {
         if (!stream_is_capturing(st)) {
-            order = tile_order_lookup(a.tile_order_id);
-            if (!order || !on_current_device(order->device)) return RRT_ERR_BAD_HANDLE;
+            if (lookup_here(g_tile_orders, a.tile_order_id, order)) return RRT_ERR_BAD_HANDLE;
             order_lock = std::unique_lock<std::mutex>(order->mu);
             if (order->dead) return RRT_ERR_BAD_HANDLE;            /* destroyed while this thread waited for it */
             int rc = tile_order_reserve(*order, n_tiles);
@@ -783,6 +787,19 @@ int launch(const FrameArgs& a, const LaunchOpts& o, bool debug, hipStream_t st) 
         order->grid_x = grid.x; order->grid_y = grid.y; order->width = a.width; order->height = a.height; order->rows = a.rows;
     }
     return RRT_OK;
+}
+
+/* the plain frame (rrt_launch_raymarch_rows, _ex, _tiles, _tilemap) once the entry point has made its own checks and built the
+ * rows it renders; dbg: a debug launch (rrt_launch_raymarch_ex) */
+int launch_frame(void* out, int width, int height, const RowMap& rows, float time, const rrt_camera* cam, rrt_sky_t sky,
+                 const rrt_effects* fx, const rrt_params* prm, const rrt_debug_outputs* dbg, void* stream) {
+    FrameArgs a;
+    LaunchOpts o;
+    const int rc = fill_args(a, o, out, width, height, time, cam, sky, fx, prm);
+    if (rc) return rc;
+    a.rows = rows;
+    if (dbg) a.dbg = *dbg;
+    return launch(a, o, dbg != nullptr, static_cast<hipStream_t>(stream));
 }
 
 /* ---- sampled launches (rrt_launch_raymarch_ss*, _mb*, _pano*, _stereo*): one kernel over the virtual (s w) x (s h) frame, static order */
@@ -1064,6 +1081,58 @@ int launch_glow(uchar4* out, const float4* hdr, int width, int height, const rrt
     return RRT_OK;
 }
 
+/* ---- workspace counters (rrt_workspace_stats, _rounds) */
+hipError_t read_chain_counters(const WorkspaceObject& w, DeferCounters* out) {
+    uint8_t raw[kMaxChains * kCounterStride];
+    const hipError_t e = hipMemcpy(raw, w.d_base, sizeof(raw), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return e;
+    for (int k = 0; k < kMaxChains; ++k) memcpy(&out[k], raw + (size_t)k * kCounterStride, sizeof(DeferCounters));
+    return hipSuccess;
+}
+
+/* rrt_launch_auto_resources (round 6): the objects the library owns on behalf of a host that only ever calls the
+ * reference-signature launch_raymarch() */
+struct AutoResources {
+    bool on = false;
+    int device = -1;
+    int pool = 0, order = 0, table = 0;
+    size_t table_budget = 0;
+    float t0 = 0.0f, t1 = -1.0f;           /* the window the table (or the remembered "nothing fits") covers; empty at first */
+    int table_builds = 0;
+    rrt_params base;
+};
+std::mutex g_auto_mu;
+AutoResources g_auto;
+
+void auto_release_locked() {
+    if (g_auto.table) rrt_noise_table_destroy(g_auto.table);
+    if (g_auto.order) rrt_tile_order_destroy(g_auto.order);
+    if (g_auto.pool) rrt_workspace_destroy(g_auto.pool);
+    g_auto = AutoResources();
+}
+
+/* the parameters of one launch_raymarch() call under auto resources; slides the table's window when `time` has left it */
+bool auto_params(float time, rrt_params& prm) {
+    std::lock_guard<std::mutex> lk(g_auto_mu);
+    if (!g_auto.on) return false;
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != g_auto.device) return false;       /* another device is current: plain defaults */
+    if (g_auto.table_budget > 0 && g_auto.base.volumetrics && !(time >= g_auto.t0 && time <= g_auto.t1)) {
+        /* The one place a launch_raymarch() call waits for the device and allocates -- opted into by the caller: the frames that
+         * may still read the old table drain, the next window is fitted to the budget and built (milliseconds). */
+        (void)hipDeviceSynchronize();
+        if (g_auto.table) { rrt_noise_table_destroy(g_auto.table); g_auto.table = 0; }
+        float t1 = time; int cov = RRT_TABLE_FULL; size_t bytes = 0;
+        rrt_noise_table_fit_window(time, time + 120.0f, g_auto.table_budget, &t1, &cov, &bytes);
+        if (bytes != 0 && rrt_noise_table_create_window(time, t1, cov, &g_auto.table) == RRT_OK) ++g_auto.table_builds;
+        else { g_auto.table = 0; if (bytes == 0) t1 = time + 5.0f; }                  /* nothing fits / no memory: look again after 5 s */
+        g_auto.t0 = time; g_auto.t1 = t1;
+    }
+    prm = g_auto.base;
+    prm.workspace = g_auto.pool; prm.tile_order = g_auto.order; prm.noise_table = g_auto.table;
+    return true;
+}
+
 }  // namespace
 
 /* ====================================================================== C ABI */
@@ -1149,7 +1218,7 @@ int rrt_sky_create(const uint8_t* rgba8_host, int width, int height, rrt_sky_t* 
     if (e != hipSuccess) return hip_fail(e, "hipMalloc(sky)");
     e = hipMemcpy(s.d_texels, rgba8_host, bytes, hipMemcpyHostToDevice);
     if (e != hipSuccess) { (void)hipFree(s.d_texels); return hip_fail(e, "hipMemcpy(sky)"); }
-    *out = sky_register(s);
+    *out = g_skies.insert(s);
     return RRT_OK;
 }
 
@@ -1161,19 +1230,13 @@ int rrt_sky_create_from_device(const void* d_rgba8, int width, int height, rrt_s
     if (faked_device() < 0 && hipPointerGetAttributes(&attr, d_rgba8) == hipSuccess) device = attr.device;
     else (void)hipGetLastError();
     SkyObject s{const_cast<uint8_t*>(static_cast<const uint8_t*>(d_rgba8)), width, height, false, device};
-    *out = sky_register(s);
+    *out = g_skies.insert(s);
     return RRT_OK;
 }
 
 int rrt_sky_destroy(rrt_sky_t sky) {
     SkyObject s;
-    {
-        std::lock_guard<std::mutex> lk(g_sky_mu);
-        auto it = g_sky.find(sky);
-        if (it == g_sky.end()) return RRT_ERR_BAD_HANDLE;
-        s = it->second;
-        g_sky.erase(it);
-    }
+    if (g_skies.take(sky, s)) return RRT_ERR_BAD_HANDLE;
     if (s.owned) {
         hipError_t e = hipFree(s.d_texels);
         if (e != hipSuccess) return hip_fail(e, "hipFree(sky)");
@@ -1200,9 +1263,58 @@ int rrt_workspace_create(size_t bytes, int* out) {
         if (w.forked) (void)hipEventDestroy(w.forked);
         w.side = nullptr; w.forked = nullptr; w.joined = nullptr;
     }
-    std::lock_guard<std::mutex> lk(g_ws_mu);
-    *out = g_ws_next++;
-    g_ws.emplace(*out, w);
+    *out = g_workspaces.insert(w);
+    return RRT_OK;
+}
+
+int rrt_workspace_destroy(int id) {
+    WorkspaceObject w;
+    if (g_workspaces.take(id, w)) return RRT_ERR_BAD_HANDLE;
+    if (w.side) { (void)hipStreamSynchronize(w.side); (void)hipStreamDestroy(w.side); }
+    if (w.forked) (void)hipEventDestroy(w.forked);
+    if (w.joined) (void)hipEventDestroy(w.joined);
+    hipError_t e = hipFree(w.d_base);
+    if (w.h_stats) (void)hipHostFree(w.h_stats);
+    if (e != hipSuccess) return hip_fail(e, "hipFree(workspace)");
+    return RRT_OK;
+}
+
+int rrt_workspace_stats(int id, unsigned* rows_used, unsigned* overflow_waves) {
+    WorkspaceObject w;
+    if (lookup_here(g_workspaces, id, w)) return RRT_ERR_BAD_HANDLE;
+    DeferCounters c[kMaxChains];
+    RRT_HIP(read_chain_counters(w, c));
+    unsigned long long rows = 0; unsigned left = 0;
+    for (int k = 0; k < kMaxChains; ++k) { rows += c[k].total_blocks * kBlockRows; left += c[k].suspended_left; }
+    if (rows_used) *rows_used = rows > 0xffffffffull ? 0xffffffffu : (unsigned)rows;
+    if (overflow_waves) *overflow_waves = left;
+    return RRT_OK;
+}
+
+int rrt_workspace_rounds(int id, unsigned* rounds_enqueued, unsigned* rounds_with_work, unsigned* peak_rows, unsigned* pool_rows) {
+    WorkspaceObject w;
+    if (lookup_here(g_workspaces, id, w)) return RRT_ERR_BAD_HANDLE;
+    DeferCounters c[kMaxChains];
+    RRT_HIP(read_chain_counters(w, c));
+    unsigned run = 0, work = 0, peak = 0;
+    for (int k = 0; k < kMaxChains; ++k) {        /* rounds: of the chain that needed most; rows of the fullest round: both chains' */
+        run = c[k].rounds_run > run ? c[k].rounds_run : run;
+        work = c[k].rounds_with_work > work ? c[k].rounds_with_work : work;
+        peak += c[k].peak_blocks;
+    }
+    if (rounds_enqueued) *rounds_enqueued = run;
+    if (rounds_with_work) *rounds_with_work = work;
+    if (peak_rows) *peak_rows = peak * kBlockRows;
+    if (pool_rows) *pool_rows = (unsigned)((w.bytes / kBlockBytes) * kBlockRows);      /* upper bound: before the launch's bookkeeping */
+    return RRT_OK;
+}
+
+int rrt_workspace_read(int id, size_t offset, size_t bytes, void* host_dst) {
+    WorkspaceObject w;
+    if (!g_workspaces.get(id, w)) return RRT_ERR_BAD_HANDLE;
+    if (!host_dst || offset > w.bytes || bytes > w.bytes - offset) return RRT_ERR_INVALID_ARGUMENT;
+    if (!on_current_device(w.device)) return RRT_ERR_BAD_HANDLE;
+    RRT_HIP(hipMemcpy(host_dst, w.d_base + offset, bytes, hipMemcpyDeviceToHost));
     return RRT_OK;
 }
 
@@ -1215,30 +1327,13 @@ int rrt_tile_order_create(int* out) {
     o->grid_x = o->grid_y = 0; o->width = o->height = 0; o->rows = RowMap{0, 0, 1, 0, 1, nullptr};
     o->launches = o->ordered = o->seeded = 0; o->no_seed = false; o->dead = false;
     RRT_HIP(hipEventCreateWithFlags(&o->chained, hipEventDisableTiming));
-    std::lock_guard<std::mutex> lk(g_to_mu);
-    *out = g_to_next++;
-    g_to.emplace(*out, o);
-    return RRT_OK;
-}
-
-int rrt_tile_order_set_seeding(int id, int on) {
-    const std::shared_ptr<TileOrderObject> o = tile_order_lookup(id);
-    if (!o) return RRT_ERR_BAD_HANDLE;
-    std::lock_guard<std::mutex> lk(o->mu);
-    o->no_seed = on == 0;
+    *out = g_tile_orders.insert(o);
     return RRT_OK;
 }
 
 int rrt_tile_order_destroy(int id) {
     std::shared_ptr<TileOrderObject> o;
-    {
-        std::lock_guard<std::mutex> lk(g_to_mu);
-        auto it = g_to.find(id);
-        if (it == g_to.end()) return RRT_ERR_BAD_HANDLE;
-        if (!on_current_device(it->second->device)) return RRT_ERR_BAD_HANDLE;
-        o = it->second;
-        g_to.erase(it);
-    }
+    if (g_tile_orders.take(id, o, made_here<TileOrderObject>)) return RRT_ERR_BAD_HANDLE;
     std::lock_guard<std::mutex> lk(o->mu);                          /* after any launch that holds the object */
     o->dead = true;
     if (o->launches > 0) (void)hipEventSynchronize(o->chained);     /* its last launch and sort have finished */
@@ -1249,12 +1344,30 @@ int rrt_tile_order_destroy(int id) {
     return RRT_OK;
 }
 
+int rrt_tile_order_set_seeding(int id, int on) {
+    std::shared_ptr<TileOrderObject> o;
+    if (!g_tile_orders.get(id, o)) return RRT_ERR_BAD_HANDLE;
+    std::lock_guard<std::mutex> lk(o->mu);
+    o->no_seed = on == 0;
+    return RRT_OK;
+}
+
+/* launches whose order came from the coarse probe (no history for their geometry) */
+int rrt_tile_order_seeded(int id, unsigned long long* seeded_launches) {
+    std::shared_ptr<TileOrderObject> o;
+    if (!g_tile_orders.get(id, o)) return RRT_ERR_BAD_HANDLE;
+    if (!seeded_launches) return RRT_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lk(o->mu);
+    *seeded_launches = o->seeded;
+    return RRT_OK;
+}
+
 /* counters of an object, and (optionally, after waiting for its last launch) the order the NEXT matching launch will
  * use plus the costs the last one recorded: perm_host / cost_host may be NULL, capacity counts elements */
 int rrt_tile_order_info(int id, unsigned long long* launches, unsigned long long* ordered_launches, unsigned* n_tiles,
                         unsigned* perm_host, unsigned* cost_host, unsigned capacity) {
-    const std::shared_ptr<TileOrderObject> op = tile_order_lookup(id);
-    if (!op) return RRT_ERR_BAD_HANDLE;
+    std::shared_ptr<TileOrderObject> op;
+    if (!g_tile_orders.get(id, op)) return RRT_ERR_BAD_HANDLE;
     std::lock_guard<std::mutex> lk(op->mu);
     const TileOrderObject& o = *op;
     if (!on_current_device(o.device)) return RRT_ERR_BAD_HANDLE;
@@ -1271,12 +1384,153 @@ int rrt_tile_order_info(int id, unsigned long long* launches, unsigned long long
     return RRT_OK;
 }
 
-/* launches whose order came from the coarse probe (no history for their geometry) */
-int rrt_tile_order_seeded(int id, unsigned long long* seeded_launches) {
-    const std::shared_ptr<TileOrderObject> o = tile_order_lookup(id);
-    if (!o || !seeded_launches) return o ? RRT_ERR_INVALID_ARGUMENT : RRT_ERR_BAD_HANDLE;
-    std::lock_guard<std::mutex> lk(o->mu);
-    *seeded_launches = o->seeded;
+int rrt_noise_table_create(float t_max, int* out_id) {
+    if (!(t_max >= 0.0f)) return RRT_ERR_INVALID_ARGUMENT;
+    return rrt_noise_table_create_window(0.0f, t_max, RRT_TABLE_FULL, out_id);
+}
+
+int rrt_noise_table_create_window(float t0, float t1, int coverage, int* out_id) {
+    if (!out_id) return RRT_ERR_INVALID_ARGUMENT;
+    NoiseTableObject nt;
+    const int rc = plan_table(t0, t1, coverage, nt);
+    if (rc != RRT_OK) return rc;
+    RRT_HIP(hipGetDevice(&nt.device));
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&nt.d_cells), nt.bytes);
+    if (e != hipSuccess) { (void)hipGetLastError(); snprintf(g_hip_err, sizeof(g_hip_err), "hipMalloc(noise table, %zu bytes): %s", nt.bytes, hipGetErrorString(e)); return e == hipErrorOutOfMemory ? RRT_ERR_OUT_OF_MEMORY : RRT_ERR_HIP; }
+    auto fill_box = [&](const LutBox& bx, size_t cell0) {
+        const size_t n = (size_t)bx.nx * bx.ny * bx.nz;
+        hipLaunchKernelGGL(build_noise_table, dim3((unsigned)std::min<size_t>(4096, (n + 255) / 256)), dim3(256), 0, nullptr, nt.d_cells + cell0, bx);
+    };
+    auto record = [&](const LutBox& bx, unsigned cell0) {
+        const NoiseLut L = make_lut(nullptr, bx, 0u);
+        rrt::BandLut r;
+        memset(&r, 0, sizeof(r));
+        r.cell0 = cell0; r.origin = L.origin; r.nx = L.nx; r.nxy = L.nxy; r.last = L.last;
+        return r;
+    };
+    if (!nt.banded) fill_box(nt.acc, 0);
+    fill_box(nt.dust, dust_cell0(nt));
+    e = hipGetLastError();
+    if (e == hipSuccess && nt.banded) {
+        std::vector<rrt::BandLut> recs((size_t)rrt::kBandFamilies * nt.bands.n_bands + rrt::kLutAccOctaves);
+        for (int o = 0; o < rrt::kLutAccOctaves; ++o) {
+            fill_box(nt.bands.acc_box[o], nt.bands.acc_cell0[o]);
+            recs[(size_t)rrt::kBandFamilies * nt.bands.n_bands + o] = record(nt.bands.acc_box[o], nt.bands.acc_cell0[o]);
+        }
+        for (int f = 0; f < rrt::kBandFamilies; ++f)
+            for (int b = 0; b < nt.bands.n_bands; ++b) {
+                fill_box(nt.bands.box[f][b], nt.bands.cell0[f][b]);
+                recs[(size_t)f * nt.bands.n_bands + b] = record(nt.bands.box[f][b], nt.bands.cell0[f][b]);
+            }
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpy(reinterpret_cast<char*>(nt.d_cells) + nt.bands.entries_offset, recs.data(),
+                                           recs.size() * sizeof(rrt::BandLut), hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) { (void)hipFree(nt.d_cells); return hip_fail(e, "build_noise_table"); }
+    *out_id = g_noise_tables.insert(nt);
+    return RRT_OK;
+}
+
+int rrt_noise_table_destroy(int id) {
+    NoiseTableObject nt;
+    if (g_noise_tables.take(id, nt)) return RRT_ERR_BAD_HANDLE;
+    hipError_t e = hipFree(nt.d_cells);
+    if (e != hipSuccess) return hip_fail(e, "hipFree(noise table)");
+    return RRT_OK;
+}
+
+int rrt_noise_table_info(int id, float* t_max, size_t* bytes, int* boxes12) {
+    NoiseTableObject nt;                       /* any device: nothing of the table's memory is read */
+    if (!g_noise_tables.get(id, nt)) return RRT_ERR_BAD_HANDLE;
+    if (t_max) *t_max = nt.t1;
+    if (bytes) *bytes = nt.bytes;
+    if (boxes12) { memcpy(boxes12, &nt.acc, sizeof(LutBox)); memcpy(boxes12 + 6, &nt.dust, sizeof(LutBox)); }
+    return RRT_OK;
+}
+
+int rrt_noise_table_window(int id, float* t0, float* t1, int* coverage, int* device) {
+    NoiseTableObject nt;
+    if (!g_noise_tables.get(id, nt)) return RRT_ERR_BAD_HANDLE;
+    if (t0) *t0 = nt.t0;
+    if (t1) *t1 = nt.t1;
+    if (coverage) *coverage = nt.coverage | (nt.banded ? RRT_TABLE_BANDED : 0);
+    if (device) *device = nt.device;
+    return RRT_OK;
+}
+
+int rrt_noise_table_plan(float t_max, size_t* bytes, int* boxes12) {
+    if (!(t_max >= 0.0f)) return RRT_ERR_INVALID_ARGUMENT;
+    return rrt_noise_table_plan_window(0.0f, t_max, RRT_TABLE_FULL, bytes, boxes12);
+}
+
+/* boxes only (host arithmetic, no device): what rrt_noise_table_create_window would allocate, with the same
+ * RRT_ERR_INVALID_ARGUMENT for a box it would refuse */
+int rrt_noise_table_plan_window(float t0, float t1, int coverage, size_t* bytes, int* boxes12) {
+    NoiseTableObject nt;
+    const int rc = plan_table(t0, t1, coverage, nt);
+    if (bytes) *bytes = rc == RRT_OK ? nt.bytes : 0;
+    if (rc != RRT_OK) return rc;
+    if (boxes12) { memcpy(boxes12, &nt.acc, sizeof(LutBox)); memcpy(boxes12 + 6, &nt.dust, sizeof(LutBox)); }
+    return RRT_OK;
+}
+
+int rrt_noise_table_plan_layout(float t0, float t1, int coverage, int* banded, int* n_bands, float* w_min, float* w_scale,
+                                int32_t* band_boxes, int cap_bands, int32_t* acc_octave_boxes) {
+    if (!banded || !n_bands) return RRT_ERR_INVALID_ARGUMENT;
+    NoiseTableObject nt;
+    const int rc = plan_table(t0, t1, coverage, nt);
+    if (rc != RRT_OK) return rc;
+    *banded = nt.banded ? 1 : 0;
+    *n_bands = nt.banded ? nt.bands.n_bands : 0;
+    if (w_min) *w_min = nt.bands.w_min;
+    if (w_scale) *w_scale = nt.bands.w_scale;
+    if (nt.banded && band_boxes) {
+        if (cap_bands < nt.bands.n_bands) return RRT_ERR_INVALID_ARGUMENT;
+        for (int f = 0; f < rrt::kBandFamilies; ++f)
+            for (int b = 0; b < nt.bands.n_bands; ++b) {
+                const LutBox& bx = nt.bands.box[f][b];
+                const int v[6] = {bx.x0, bx.y0, bx.z0, bx.nx, bx.ny, bx.nz};
+                memcpy(band_boxes + ((size_t)f * cap_bands + b) * 6, v, sizeof(v));
+            }
+    }
+    if (nt.banded && acc_octave_boxes)
+        for (int o = 0; o < rrt::kLutAccOctaves; ++o) {
+            const LutBox& bx = nt.bands.acc_box[o];
+            const int v[6] = {bx.x0, bx.y0, bx.z0, bx.nx, bx.ny, bx.nz};
+            memcpy(acc_octave_boxes + (size_t)o * 6, v, sizeof(v));
+        }
+    return RRT_OK;
+}
+
+/* The window a frame driver should build next: the longest [t_from, t1], t1 <= t_until, at the richest coverage,
+ * whose table fits `budget_bytes` -- the window is halved (down to 0.5 s) before the coverage is lowered, because a
+ * rebuild costs milliseconds while a coarser table costs every frame.  RRT_OK with *bytes_out == 0 when nothing fits
+ * (the driver then renders without a table: same bytes, slower). */
+int rrt_noise_table_fit_window(float t_from, float t_until, size_t budget_bytes, float* t1_out, int* coverage_out, size_t* bytes_out) {
+    if (!t1_out || !coverage_out || !bytes_out || !(t_from <= t_until)) return RRT_ERR_INVALID_ARGUMENT;
+    *t1_out = t_from; *coverage_out = RRT_TABLE_FULL; *bytes_out = 0;
+    for (int cov = RRT_TABLE_FULL; cov <= RRT_TABLE_COARSEST; ++cov) {
+        float span = t_until - t_from;
+        for (;;) {
+            NoiseTableObject nt;
+            const float t1 = t_from + span;
+            if (plan_table(t_from, t1, cov, nt) == RRT_OK && nt.bytes <= budget_bytes) {
+                *t1_out = t1; *coverage_out = cov; *bytes_out = nt.bytes;
+                return RRT_OK;
+            }
+            if (span <= 0.5f) break;
+            span = span * 0.5f < 0.5f ? 0.5f : span * 0.5f;
+        }
+    }
+    return RRT_OK;
+}
+
+int rrt_clock_probe(unsigned long long* d_counters2, unsigned duration_us, void* stream) {
+    if (!d_counters2 || duration_us == 0 || duration_us > 2000000u) return RRT_ERR_INVALID_ARGUMENT;
+    hipLaunchKernelGGL(clock_probe_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), d_counters2,
+                       (unsigned long long)duration_us * 100ull);
+    RRT_HIP(hipGetLastError());
     return RRT_OK;
 }
 
@@ -1312,57 +1566,6 @@ int rrt_get_launch_defaults_sized(void* out, uint32_t size) {
 #undef rrt_get_launch_defaults
 int rrt_get_launch_defaults(void* abi4_48) { return rrt_get_launch_defaults_sized(abi4_48, kParamsSizeAbi4); }
 #pragma pop_macro("rrt_get_launch_defaults")
-
-/* launch_raymarch() as the reference spells it, minus the C++ types: cam12 = pos, forward, right, up;
- * effects36 = the 36 bytes of struct CameraEffects.  Asynchronous on the null stream.  The reference's
- * launcher reports nothing (src/raymarcher.cu:176-180); this one returns the status and, the first time a
- * launch fails, says why on stderr. */
-}  // extern "C"
-namespace {
-/* rrt_launch_auto_resources (round 6): the objects the library owns on behalf of a host that only ever calls the
- * reference-signature launch_raymarch() */
-struct AutoResources {
-    bool on = false;
-    int device = -1;
-    int pool = 0, order = 0, table = 0;
-    size_t table_budget = 0;
-    float t0 = 0.0f, t1 = -1.0f;           /* the window the table (or the remembered "nothing fits") covers; empty at first */
-    int table_builds = 0;
-    rrt_params base;
-};
-std::mutex g_auto_mu;
-AutoResources g_auto;
-
-void auto_release_locked() {
-    if (g_auto.table) rrt_noise_table_destroy(g_auto.table);
-    if (g_auto.order) rrt_tile_order_destroy(g_auto.order);
-    if (g_auto.pool) rrt_workspace_destroy(g_auto.pool);
-    g_auto = AutoResources();
-}
-
-/* the parameters of one launch_raymarch() call under auto resources; slides the table's window when `time` has left it */
-bool auto_params(float time, rrt_params& prm) {
-    std::lock_guard<std::mutex> lk(g_auto_mu);
-    if (!g_auto.on) return false;
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev != g_auto.device) return false;       /* another device is current: plain defaults */
-    if (g_auto.table_budget > 0 && g_auto.base.volumetrics && !(time >= g_auto.t0 && time <= g_auto.t1)) {
-        /* The one place a launch_raymarch() call waits for the device and allocates -- opted into by the caller: the frames that
-         * may still read the old table drain, the next window is fitted to the budget and built (milliseconds). */
-        (void)hipDeviceSynchronize();
-        if (g_auto.table) { rrt_noise_table_destroy(g_auto.table); g_auto.table = 0; }
-        float t1 = time; int cov = RRT_TABLE_FULL; size_t bytes = 0;
-        rrt_noise_table_fit_window(time, time + 120.0f, g_auto.table_budget, &t1, &cov, &bytes);
-        if (bytes != 0 && rrt_noise_table_create_window(time, t1, cov, &g_auto.table) == RRT_OK) ++g_auto.table_builds;
-        else { g_auto.table = 0; if (bytes == 0) t1 = time + 5.0f; }                  /* nothing fits / no memory: look again after 5 s */
-        g_auto.t0 = time; g_auto.t1 = t1;
-    }
-    prm = g_auto.base;
-    prm.workspace = g_auto.pool; prm.tile_order = g_auto.order; prm.noise_table = g_auto.table;
-    return true;
-}
-}  // namespace
-extern "C" {
 
 int rrt_launch_auto_resources(int on, const rrt_params* base, size_t table_budget_bytes, size_t pool_bytes) {
     std::lock_guard<std::mutex> lk(g_auto_mu);
@@ -1410,6 +1613,10 @@ int rrt_launch_auto_resources_info(int* on, int* table_builds, float* table_t0, 
     return RRT_OK;
 }
 
+/* launch_raymarch() as the reference spells it, minus the C++ types: cam12 = pos, forward, right, up;
+ * effects36 = the 36 bytes of struct CameraEffects.  Asynchronous on the null stream.  The reference's
+ * launcher reports nothing (src/raymarcher.cu:176-180); this one returns the status and, the first time a
+ * launch fails, says why on stderr. */
 int rrt_launch_raymarch_compat(void* d_out_rgba8, int width, int height, float time, const float* cam12,
                                rrt_sky_t sky, const void* effects36) {
     if (!cam12 || !effects36) return RRT_ERR_INVALID_ARGUMENT;
@@ -1430,300 +1637,9 @@ int rrt_launch_raymarch_compat(void* d_out_rgba8, int width, int height, float t
     return rc;
 }
 
-int rrt_workspace_destroy(int id) {
-    WorkspaceObject w;
-    {
-        std::lock_guard<std::mutex> lk(g_ws_mu);
-        auto it = g_ws.find(id);
-        if (it == g_ws.end()) return RRT_ERR_BAD_HANDLE;
-        w = it->second;
-        g_ws.erase(it);
-    }
-    if (w.side) { (void)hipStreamSynchronize(w.side); (void)hipStreamDestroy(w.side); }
-    if (w.forked) (void)hipEventDestroy(w.forked);
-    if (w.joined) (void)hipEventDestroy(w.joined);
-    hipError_t e = hipFree(w.d_base);
-    if (w.h_stats) (void)hipHostFree(w.h_stats);
-    if (e != hipSuccess) return hip_fail(e, "hipFree(workspace)");
-    return RRT_OK;
-}
-
-}  // extern "C"
-namespace {
-hipError_t read_chain_counters(const WorkspaceObject& w, DeferCounters* out) {
-    uint8_t raw[kMaxChains * kCounterStride];
-    const hipError_t e = hipMemcpy(raw, w.d_base, sizeof(raw), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return e;
-    for (int k = 0; k < kMaxChains; ++k) memcpy(&out[k], raw + (size_t)k * kCounterStride, sizeof(DeferCounters));
-    return hipSuccess;
-}
-}  // namespace
-extern "C" {
-int rrt_workspace_stats(int id, unsigned* rows_used, unsigned* overflow_waves) {
-    WorkspaceObject w;
-    {
-        std::lock_guard<std::mutex> lk(g_ws_mu);
-        auto it = g_ws.find(id);
-        if (it == g_ws.end()) return RRT_ERR_BAD_HANDLE;
-        w = it->second;
-    }
-    if (!on_current_device(w.device)) return RRT_ERR_BAD_HANDLE;
-    DeferCounters c[kMaxChains];
-    RRT_HIP(read_chain_counters(w, c));
-    unsigned long long rows = 0; unsigned left = 0;
-    for (int k = 0; k < kMaxChains; ++k) { rows += c[k].total_blocks * kBlockRows; left += c[k].suspended_left; }
-    if (rows_used) *rows_used = rows > 0xffffffffull ? 0xffffffffu : (unsigned)rows;
-    if (overflow_waves) *overflow_waves = left;
-    return RRT_OK;
-}
-
-int rrt_workspace_rounds(int id, unsigned* rounds_enqueued, unsigned* rounds_with_work, unsigned* peak_rows, unsigned* pool_rows) {
-    WorkspaceObject w;
-    {
-        std::lock_guard<std::mutex> lk(g_ws_mu);
-        auto it = g_ws.find(id);
-        if (it == g_ws.end()) return RRT_ERR_BAD_HANDLE;
-        w = it->second;
-    }
-    if (!on_current_device(w.device)) return RRT_ERR_BAD_HANDLE;
-    DeferCounters c[kMaxChains];
-    RRT_HIP(read_chain_counters(w, c));
-    unsigned run = 0, work = 0, peak = 0;
-    for (int k = 0; k < kMaxChains; ++k) {        /* rounds: of the chain that needed most; rows of the fullest round: both chains' */
-        run = c[k].rounds_run > run ? c[k].rounds_run : run;
-        work = c[k].rounds_with_work > work ? c[k].rounds_with_work : work;
-        peak += c[k].peak_blocks;
-    }
-    if (rounds_enqueued) *rounds_enqueued = run;
-    if (rounds_with_work) *rounds_with_work = work;
-    if (peak_rows) *peak_rows = peak * kBlockRows;
-    if (pool_rows) *pool_rows = (unsigned)((w.bytes / kBlockBytes) * kBlockRows);      /* upper bound: before the launch's bookkeeping */
-    return RRT_OK;
-}
-
-int rrt_workspace_read(int id, size_t offset, size_t bytes, void* host_dst) {
-    WorkspaceObject w;
-    {
-        std::lock_guard<std::mutex> lk(g_ws_mu);
-        auto it = g_ws.find(id);
-        if (it == g_ws.end()) return RRT_ERR_BAD_HANDLE;
-        w = it->second;
-    }
-    if (!host_dst || offset > w.bytes || bytes > w.bytes - offset) return RRT_ERR_INVALID_ARGUMENT;
-    if (!on_current_device(w.device)) return RRT_ERR_BAD_HANDLE;
-    RRT_HIP(hipMemcpy(host_dst, w.d_base + offset, bytes, hipMemcpyDeviceToHost));
-    return RRT_OK;
-}
-
-int rrt_noise_table_create_window(float t0, float t1, int coverage, int* out_id) {
-    if (!out_id) return RRT_ERR_INVALID_ARGUMENT;
-    NoiseTableObject nt;
-    const int rc = plan_table(t0, t1, coverage, nt);
-    if (rc != RRT_OK) return rc;
-    RRT_HIP(hipGetDevice(&nt.device));
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&nt.d_cells), nt.bytes);
-    if (e != hipSuccess) { (void)hipGetLastError(); snprintf(g_hip_err, sizeof(g_hip_err), "hipMalloc(noise table, %zu bytes): %s", nt.bytes, hipGetErrorString(e)); return e == hipErrorOutOfMemory ? RRT_ERR_OUT_OF_MEMORY : RRT_ERR_HIP; }
-    auto fill_box = [&](const LutBox& bx, size_t cell0) {
-        const size_t n = (size_t)bx.nx * bx.ny * bx.nz;
-        hipLaunchKernelGGL(build_noise_table, dim3((unsigned)std::min<size_t>(4096, (n + 255) / 256)), dim3(256), 0, nullptr, nt.d_cells + cell0, bx);
-    };
-    auto record = [&](const LutBox& bx, unsigned cell0) {
-        const NoiseLut L = make_lut(nullptr, bx, 0u);
-        rrt::BandLut r;
-        memset(&r, 0, sizeof(r));
-        r.cell0 = cell0; r.origin = L.origin; r.nx = L.nx; r.nxy = L.nxy; r.last = L.last;
-        return r;
-    };
-    if (!nt.banded) fill_box(nt.acc, 0);
-    fill_box(nt.dust, dust_cell0(nt));
-    e = hipGetLastError();
-    if (e == hipSuccess && nt.banded) {
-        std::vector<rrt::BandLut> recs((size_t)rrt::kBandFamilies * nt.bands.n_bands + rrt::kLutAccOctaves);
-        for (int o = 0; o < rrt::kLutAccOctaves; ++o) {
-            fill_box(nt.bands.acc_box[o], nt.bands.acc_cell0[o]);
-            recs[(size_t)rrt::kBandFamilies * nt.bands.n_bands + o] = record(nt.bands.acc_box[o], nt.bands.acc_cell0[o]);
-        }
-        for (int f = 0; f < rrt::kBandFamilies; ++f)
-            for (int b = 0; b < nt.bands.n_bands; ++b) {
-                fill_box(nt.bands.box[f][b], nt.bands.cell0[f][b]);
-                recs[(size_t)f * nt.bands.n_bands + b] = record(nt.bands.box[f][b], nt.bands.cell0[f][b]);
-            }
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpy(reinterpret_cast<char*>(nt.d_cells) + nt.bands.entries_offset, recs.data(),
-                                           recs.size() * sizeof(rrt::BandLut), hipMemcpyHostToDevice);
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) { (void)hipFree(nt.d_cells); return hip_fail(e, "build_noise_table"); }
-    std::lock_guard<std::mutex> lk(g_nt_mu);
-    *out_id = g_nt_next++;
-    g_nt.emplace(*out_id, nt);
-    return RRT_OK;
-}
-
-int rrt_noise_table_create(float t_max, int* out_id) {
-    if (!(t_max >= 0.0f)) return RRT_ERR_INVALID_ARGUMENT;
-    return rrt_noise_table_create_window(0.0f, t_max, RRT_TABLE_FULL, out_id);
-}
-
-int rrt_noise_table_destroy(int id) {
-    NoiseTableObject nt;
-    {
-        std::lock_guard<std::mutex> lk(g_nt_mu);
-        auto it = g_nt.find(id);
-        if (it == g_nt.end()) return RRT_ERR_BAD_HANDLE;
-        nt = it->second;
-        g_nt.erase(it);
-    }
-    hipError_t e = hipFree(nt.d_cells);
-    if (e != hipSuccess) return hip_fail(e, "hipFree(noise table)");
-    return RRT_OK;
-}
-
-int rrt_noise_table_info(int id, float* t_max, size_t* bytes, int* boxes12) {
-    std::lock_guard<std::mutex> lk(g_nt_mu);
-    auto it = g_nt.find(id);
-    if (it == g_nt.end()) return RRT_ERR_BAD_HANDLE;
-    const NoiseTableObject& nt = it->second;
-    if (t_max) *t_max = nt.t1;
-    if (bytes) *bytes = nt.bytes;
-    if (boxes12) { memcpy(boxes12, &nt.acc, sizeof(LutBox)); memcpy(boxes12 + 6, &nt.dust, sizeof(LutBox)); }
-    return RRT_OK;
-}
-
-int rrt_noise_table_window(int id, float* t0, float* t1, int* coverage, int* device) {
-    std::lock_guard<std::mutex> lk(g_nt_mu);
-    auto it = g_nt.find(id);
-    if (it == g_nt.end()) return RRT_ERR_BAD_HANDLE;
-    if (t0) *t0 = it->second.t0;
-    if (t1) *t1 = it->second.t1;
-    if (coverage) *coverage = it->second.coverage | (it->second.banded ? RRT_TABLE_BANDED : 0);
-    if (device) *device = it->second.device;
-    return RRT_OK;
-}
-
-/* boxes only (host arithmetic, no device): what rrt_noise_table_create_window would allocate, with the same
- * RRT_ERR_INVALID_ARGUMENT for a box it would refuse */
-int rrt_noise_table_plan_window(float t0, float t1, int coverage, size_t* bytes, int* boxes12) {
-    NoiseTableObject nt;
-    const int rc = plan_table(t0, t1, coverage, nt);
-    if (bytes) *bytes = rc == RRT_OK ? nt.bytes : 0;
-    if (rc != RRT_OK) return rc;
-    if (boxes12) { memcpy(boxes12, &nt.acc, sizeof(LutBox)); memcpy(boxes12 + 6, &nt.dust, sizeof(LutBox)); }
-    return RRT_OK;
-}
-
-int rrt_noise_table_plan_layout(float t0, float t1, int coverage, int* banded, int* n_bands, float* w_min, float* w_scale,
-                                int32_t* band_boxes, int cap_bands, int32_t* acc_octave_boxes) {
-    if (!banded || !n_bands) return RRT_ERR_INVALID_ARGUMENT;
-    NoiseTableObject nt;
-    const int rc = plan_table(t0, t1, coverage, nt);
-    if (rc != RRT_OK) return rc;
-    *banded = nt.banded ? 1 : 0;
-    *n_bands = nt.banded ? nt.bands.n_bands : 0;
-    if (w_min) *w_min = nt.bands.w_min;
-    if (w_scale) *w_scale = nt.bands.w_scale;
-    if (nt.banded && band_boxes) {
-        if (cap_bands < nt.bands.n_bands) return RRT_ERR_INVALID_ARGUMENT;
-        for (int f = 0; f < rrt::kBandFamilies; ++f)
-            for (int b = 0; b < nt.bands.n_bands; ++b) {
-                const LutBox& bx = nt.bands.box[f][b];
-                const int v[6] = {bx.x0, bx.y0, bx.z0, bx.nx, bx.ny, bx.nz};
-                memcpy(band_boxes + ((size_t)f * cap_bands + b) * 6, v, sizeof(v));
-            }
-    }
-    if (nt.banded && acc_octave_boxes)
-        for (int o = 0; o < rrt::kLutAccOctaves; ++o) {
-            const LutBox& bx = nt.bands.acc_box[o];
-            const int v[6] = {bx.x0, bx.y0, bx.z0, bx.nx, bx.ny, bx.nz};
-            memcpy(acc_octave_boxes + (size_t)o * 6, v, sizeof(v));
-        }
-    return RRT_OK;
-}
-
-int rrt_noise_table_plan(float t_max, size_t* bytes, int* boxes12) {
-    if (!(t_max >= 0.0f)) return RRT_ERR_INVALID_ARGUMENT;
-    return rrt_noise_table_plan_window(0.0f, t_max, RRT_TABLE_FULL, bytes, boxes12);
-}
-
-/* The window a frame driver should build next: the longest [t_from, t1], t1 <= t_until, at the richest coverage,
- * whose table fits `budget_bytes` -- the window is halved (down to 0.5 s) before the coverage is lowered, because a
- * rebuild costs milliseconds while a coarser table costs every frame.  RRT_OK with *bytes_out == 0 when nothing fits
- * (the driver then renders without a table: same bytes, slower). */
-int rrt_noise_table_fit_window(float t_from, float t_until, size_t budget_bytes, float* t1_out, int* coverage_out, size_t* bytes_out) {
-    if (!t1_out || !coverage_out || !bytes_out || !(t_from <= t_until)) return RRT_ERR_INVALID_ARGUMENT;
-    *t1_out = t_from; *coverage_out = RRT_TABLE_FULL; *bytes_out = 0;
-    for (int cov = RRT_TABLE_FULL; cov <= RRT_TABLE_COARSEST; ++cov) {
-        float span = t_until - t_from;
-        for (;;) {
-            NoiseTableObject nt;
-            const float t1 = t_from + span;
-            if (plan_table(t_from, t1, cov, nt) == RRT_OK && nt.bytes <= budget_bytes) {
-                *t1_out = t1; *coverage_out = cov; *bytes_out = nt.bytes;
-                return RRT_OK;
-            }
-            if (span <= 0.5f) break;
-            span = span * 0.5f < 0.5f ? 0.5f : span * 0.5f;
-        }
-    }
-    return RRT_OK;
-}
-
-/* ---- march cache (include/rrt.h) ---- */
-}  // extern "C"
-namespace {
-int march_cache_device(int device) { return device >= 0 ? device : current_device(); }
-/* runs f with `device` current (the cache's memory is freed and allocated there) */
-template <class F>
-int on_device(int device, F&& f) {
-    int prev = -1;
-    if (faked_device() >= 0) return f();
-    RRT_HIP(hipGetDevice(&prev));
-    if (prev != device) RRT_HIP(hipSetDevice(device));
-    const int rc = f();
-    if (prev != device) (void)hipSetDevice(prev);
-    return rc;
-}
-}  // namespace
-extern "C" {
-int rrt_march_cache_configure(int device, size_t max_bytes) {
-    const int dev = march_cache_device(device);
-    if (dev < 0) return RRT_ERR_NO_DEVICE;
-    MarchCacheObject* c = march_cache_of(dev, true);
-    std::lock_guard<std::mutex> lk(c->mu);
-    c->pol.reset();
-    c->configured = true; c->budget_known = true; c->max_bytes = max_bytes;
-    if (c->bytes > max_bytes) return on_device(dev, [&] { MarchCacheRegistry::free_device_memory(*c); return RRT_OK; });
-    return RRT_OK;
-}
-
-int rrt_march_cache_stats(int device, rrt_march_cache_info* out) {
-    if (!out) return RRT_ERR_INVALID_ARGUMENT;
-    memset(out, 0, sizeof(*out));
-    const int dev = march_cache_device(device);
-    if (dev < 0) return RRT_ERR_NO_DEVICE;
-    MarchCacheObject* c = march_cache_of(dev, false);
-    if (!c) return RRT_OK;
-    std::lock_guard<std::mutex> lk(c->mu);
-    out->fills = c->pol.st.fills; out->hits = c->pol.st.hits; out->drops = c->pol.st.drops;
-    out->misses = c->pol.st.misses; out->uncacheable = c->pol.st.uncacheable;
-    out->bytes = c->bytes;
-    out->max_bytes = march_cache_env_off() ? 0 : (c->budget_known ? c->max_bytes : 0);
-    out->state = c->pol.state; out->why = c->pol.why;
-    if (c->pol.state == rrt_mc::kReady || c->pol.state == rrt_mc::kPending) {
-        out->blocks_capacity = c->cap_blocks;
-        if (c->pol.state == rrt_mc::kReady) out->blocks_used = c->used_blocks;
-    }
-    return RRT_OK;
-}
-
-int rrt_march_cache_release(int device) {
-    const int dev = march_cache_device(device);
-    if (dev < 0) return RRT_ERR_NO_DEVICE;
-    MarchCacheObject* c = march_cache_of(dev, false);
-    if (!c) return RRT_OK;
-    std::lock_guard<std::mutex> lk(c->mu);
-    c->pol.reset();
-    return on_device(dev, [&] { MarchCacheRegistry::destroy(*c); return RRT_OK; });
+int rrt_launch_raymarch(void* d_out_rgba8, int width, int height, float time, const rrt_camera* cam,
+                        rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm, void* stream) {
+    return rrt_launch_raymarch_rows(d_out_rgba8, width, height, 0, height, time, cam, sky, fx, prm, stream);
 }
 
 int rrt_launch_raymarch_rows(void* d_out_rows, int width, int height, int y0, int y1, float time,
@@ -1732,38 +1648,8 @@ int rrt_launch_raymarch_rows(void* d_out_rows, int width, int height, int y0, in
     int rc = check_common(d_out_rows, width, height, cam, fx, prm);
     if (rc) return rc;
     if (y0 < 0 || y1 > height || y0 > y1) return RRT_ERR_INVALID_ARGUMENT;
-    FrameArgs a;
-    LaunchOpts o;
-    rc = fill_args(a, o, d_out_rows, width, height, time, cam, sky, fx, prm);
-    if (rc) return rc;
-    a.rows = RowMap{y1 - y0, y0, y1 - y0 > 0 ? y1 - y0 : 1, 0, 1, nullptr};
-    return launch(a, o, false, static_cast<hipStream_t>(stream));
-}
-
-int rrt_launch_raymarch(void* d_out_rgba8, int width, int height, float time, const rrt_camera* cam,
-                        rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm, void* stream) {
-    return rrt_launch_raymarch_rows(d_out_rgba8, width, height, 0, height, time, cam, sky, fx, prm, stream);
-}
-
-int rrt_launch_raymarch_ex(void* d_out_rgba8, int width, int height, float time, const rrt_camera* cam,
-                           rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm,
-                           const rrt_debug_outputs* dbg, void* stream) {
-    int rc = check_common(d_out_rgba8, width, height, cam, fx, prm);
-    if (rc) return rc;
-    FrameArgs a;
-    LaunchOpts o;
-    rc = fill_args(a, o, d_out_rgba8, width, height, time, cam, sky, fx, prm);
-    if (rc) return rc;
-    a.rows = frame_rows(height);
-    if (dbg) a.dbg = *dbg;
-    return launch(a, o, dbg != nullptr, static_cast<hipStream_t>(stream));
-}
-
-int rrt_tile_shard_rows(int height, int tile_rows, int shard, int n_shards, int* rows) {
-    if (!rows || height <= 0 || tile_rows <= 0 || n_shards <= 0 || shard < 0 || shard >= n_shards)
-        return RRT_ERR_INVALID_ARGUMENT;
-    *rows = shard_rows(height, tile_rows, shard, n_shards);
-    return RRT_OK;
+    const RowMap rows{y1 - y0, y0, y1 - y0 > 0 ? y1 - y0 : 1, 0, 1, nullptr};
+    return launch_frame(d_out_rows, width, height, rows, time, cam, sky, fx, prm, nullptr, stream);
 }
 
 int rrt_launch_raymarch_tiles(void* d_out_tiles, int width, int height, int tile_rows, int shard, int n_shards,
@@ -1773,51 +1659,14 @@ int rrt_launch_raymarch_tiles(void* d_out_tiles, int width, int height, int tile
     if (rc) return rc;
     RowMap rows;
     if ((rc = shard_map(height, tile_rows, shard, n_shards, rows))) return rc;
-    FrameArgs a;
-    LaunchOpts o;
-    rc = fill_args(a, o, d_out_tiles, width, height, time, cam, sky, fx, prm);
-    if (rc) return rc;
-    a.rows = rows;
-    return launch(a, o, false, static_cast<hipStream_t>(stream));
+    return launch_frame(d_out_tiles, width, height, rows, time, cam, sky, fx, prm, nullptr, stream);
 }
 
-int rrt_launch_raymarch_ss(void* d_out_rgba8, float* d_hdr_rgba32f, int width, int height, int samples_per_axis, float time,
-                           const rrt_camera* cam, rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm, void* stream) {
-    const int rc = check_ss(d_out_rgba8, width, height, samples_per_axis, cam, fx, prm);
-    if (rc) return rc;
-    return launch_ss(d_out_rgba8, reinterpret_cast<float4*>(d_hdr_rgba32f), width, height, samples_per_axis, frame_rows(height),
-                     nullptr, time, cam, sky, fx, prm, static_cast<hipStream_t>(stream));
-}
-
-int rrt_launch_raymarch_ss_tiles(void* d_out_tiles, int width, int height, int samples_per_axis, int tile_rows, int shard, int n_shards,
-                                 float time, const rrt_camera* cam, rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm,
-                                 void* stream) {
-    int rc = check_ss(d_out_tiles, width, height, samples_per_axis, cam, fx, prm);
-    if (rc) return rc;
-    RowMap rows;
-    if ((rc = shard_map(height, tile_rows, shard, n_shards, rows))) return rc;
-    return launch_ss(d_out_tiles, nullptr, width, height, samples_per_axis, rows, nullptr, time, cam, sky, fx, prm,
-                     static_cast<hipStream_t>(stream));
-}
-
-int rrt_launch_raymarch_mb(void* d_out_rgba8, float* d_hdr_rgba32f, int width, int height, int samples_per_axis, int n_times,
-                           const float* times, const rrt_camera* cams, rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm,
-                           void* stream) {
-    const int rc = check_mb(d_out_rgba8, width, height, samples_per_axis, n_times, times, cams, fx, prm);
-    if (rc) return rc;
-    return launch_mb(d_out_rgba8, reinterpret_cast<float4*>(d_hdr_rgba32f), width, height, samples_per_axis, frame_rows(height),
-                     n_times, times, cams, sky, fx, prm, static_cast<hipStream_t>(stream));
-}
-
-int rrt_launch_raymarch_mb_tiles(void* d_out_tiles, int width, int height, int samples_per_axis, int tile_rows, int shard, int n_shards,
-                                 int n_times, const float* times, const rrt_camera* cams, rrt_sky_t sky, const rrt_effects* fx,
-                                 const rrt_params* prm, void* stream) {
-    int rc = check_mb(d_out_tiles, width, height, samples_per_axis, n_times, times, cams, fx, prm);
-    if (rc) return rc;
-    RowMap rows;
-    if ((rc = shard_map(height, tile_rows, shard, n_shards, rows))) return rc;
-    return launch_mb(d_out_tiles, nullptr, width, height, samples_per_axis, rows, n_times, times, cams, sky, fx, prm,
-                     static_cast<hipStream_t>(stream));
+int rrt_tile_shard_rows(int height, int tile_rows, int shard, int n_shards, int* rows) {
+    if (!rows || height <= 0 || tile_rows <= 0 || n_shards <= 0 || shard < 0 || shard >= n_shards)
+        return RRT_ERR_INVALID_ARGUMENT;
+    *rows = shard_rows(height, tile_rows, shard, n_shards);
+    return RRT_OK;
 }
 
 int rrt_assemble_tiles(void* d_frame, const void* d_tiles, int width, int height, int tile_rows, int shard,
@@ -1876,30 +1725,21 @@ int rrt_tile_map_create(int height, int tile_rows, int n_shards, const int32_t* 
     if (e != hipSuccess) return hip_fail(e, "hipMalloc(tile map)");
     e = hipMemcpy(m->d_img, img.data(), img.size() * sizeof(int), hipMemcpyHostToDevice);
     if (e != hipSuccess) { (void)hipFree(m->d_img); return hip_fail(e, "hipMemcpy(tile map)"); }
-    std::lock_guard<std::mutex> lk(g_tm_mu);
-    *out_id = g_tm_next++;
-    g_tm.emplace(*out_id, m);
+    *out_id = g_tile_maps.insert(m);
     return RRT_OK;
 }
 
 int rrt_tile_map_destroy(int id) {
     std::shared_ptr<TileMapObject> m;
-    {
-        std::lock_guard<std::mutex> lk(g_tm_mu);
-        auto it = g_tm.find(id);
-        if (it == g_tm.end()) return RRT_ERR_BAD_HANDLE;
-        m = it->second;
-        if (!on_current_device(m->device)) return RRT_ERR_BAD_HANDLE;      /* like every other handle: freed under the device that owns it */
-        g_tm.erase(it);
-    }
+    if (g_tile_maps.take(id, m, made_here<TileMapObject>)) return RRT_ERR_BAD_HANDLE;       /* freed under the device that owns it */
     hipError_t e = hipFree(m->d_img);
     if (e != hipSuccess) return hip_fail(e, "hipFree(tile map)");
     return RRT_OK;
 }
 
 int rrt_tile_map_shard_rows(int id, int shard, int* rows, int* max_rows) {
-    const std::shared_ptr<TileMapObject> m = tile_map_lookup(id);
-    if (!m) return RRT_ERR_BAD_HANDLE;
+    std::shared_ptr<TileMapObject> m;
+    if (!g_tile_maps.get(id, m)) return RRT_ERR_BAD_HANDLE;
     if (shard < 0 || shard >= m->n_shards) return RRT_ERR_INVALID_ARGUMENT;
     if (rows) *rows = m->rows[shard];
     if (max_rows) { int mx = 0; for (int r : m->rows) mx = r > mx ? r : mx; *max_rows = mx; }
@@ -1931,36 +1771,6 @@ int rrt_tile_map_balance(int n_tiles, const float* tile_cost, int n_shards, int 
         load[best] += (double)tile_cost[t];
         ++count[best];
     }
-    return RRT_OK;
-}
-
-int rrt_launch_raymarch_tilemap(void* d_out_tiles, int width, int height, int tile_map, int shard, float time,
-                                const rrt_camera* cam, rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm, void* stream) {
-    int rc = check_common(d_out_tiles, width, height, cam, fx, prm);
-    if (rc) return rc;
-    const std::shared_ptr<TileMapObject> m = tile_map_lookup(tile_map);
-    if (!m || !on_current_device(m->device)) return RRT_ERR_BAD_HANDLE;
-    if (m->height != height || shard < 0 || shard >= m->n_shards) return RRT_ERR_INVALID_ARGUMENT;
-    FrameArgs a;
-    LaunchOpts o;
-    rc = fill_args(a, o, d_out_tiles, width, height, time, cam, sky, fx, prm);
-    if (rc) return rc;
-    a.rows = RowMap{m->rows[shard], 0, m->tile_rows, shard, m->n_shards, m->d_img + m->offset[shard]};
-    return launch(a, o, false, static_cast<hipStream_t>(stream));
-}
-
-int rrt_assemble_all_tilemap(void* d_frame, const void* d_tiles_all, size_t shard_stride_bytes, int width, int height,
-                             int tile_map, void* stream) {
-    if (!d_frame || !d_tiles_all || width <= 0 || height <= 0 || (shard_stride_bytes & 3) != 0) return RRT_ERR_INVALID_ARGUMENT;
-    const std::shared_ptr<TileMapObject> m = tile_map_lookup(tile_map);
-    if (!m || !on_current_device(m->device)) return RRT_ERR_BAD_HANDLE;
-    if (m->height != height) return RRT_ERR_INVALID_ARGUMENT;
-    for (int r : m->rows) if (shard_stride_bytes / 4 < (size_t)r * width) return RRT_ERR_INVALID_ARGUMENT;
-    dim3 grid((width + 255) / 256, height < kMaxGridY ? height : kMaxGridY);
-    hipLaunchKernelGGL(assemble_map_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<uchar4*>(d_frame),
-                       static_cast<const uchar4*>(d_tiles_all), shard_stride_bytes / 4, width, height, m->tile_rows,
-                       m->d_img + m->n_tiles, m->d_img + 2 * (size_t)m->n_tiles);
-    RRT_HIP(hipGetLastError());
     return RRT_OK;
 }
 
@@ -2017,12 +1827,77 @@ int rrt_probe_tile_costs(int width, int height, int tile_rows, float time, const
     return RRT_OK;
 }
 
-int rrt_clock_probe(unsigned long long* d_counters2, unsigned duration_us, void* stream) {
-    if (!d_counters2 || duration_us == 0 || duration_us > 2000000u) return RRT_ERR_INVALID_ARGUMENT;
-    hipLaunchKernelGGL(clock_probe_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), d_counters2,
-                       (unsigned long long)duration_us * 100ull);
+int rrt_launch_raymarch_tilemap(void* d_out_tiles, int width, int height, int tile_map, int shard, float time,
+                                const rrt_camera* cam, rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm, void* stream) {
+    const int rc = check_common(d_out_tiles, width, height, cam, fx, prm);
+    if (rc) return rc;
+    std::shared_ptr<TileMapObject> m;
+    if (lookup_here(g_tile_maps, tile_map, m)) return RRT_ERR_BAD_HANDLE;
+    if (m->height != height || shard < 0 || shard >= m->n_shards) return RRT_ERR_INVALID_ARGUMENT;
+    const RowMap rows{m->rows[shard], 0, m->tile_rows, shard, m->n_shards, m->d_img + m->offset[shard]};
+    return launch_frame(d_out_tiles, width, height, rows, time, cam, sky, fx, prm, nullptr, stream);
+}
+
+int rrt_assemble_all_tilemap(void* d_frame, const void* d_tiles_all, size_t shard_stride_bytes, int width, int height,
+                             int tile_map, void* stream) {
+    if (!d_frame || !d_tiles_all || width <= 0 || height <= 0 || (shard_stride_bytes & 3) != 0) return RRT_ERR_INVALID_ARGUMENT;
+    std::shared_ptr<TileMapObject> m;
+    if (lookup_here(g_tile_maps, tile_map, m)) return RRT_ERR_BAD_HANDLE;
+    if (m->height != height) return RRT_ERR_INVALID_ARGUMENT;
+    for (int r : m->rows) if (shard_stride_bytes / 4 < (size_t)r * width) return RRT_ERR_INVALID_ARGUMENT;
+    dim3 grid((width + 255) / 256, height < kMaxGridY ? height : kMaxGridY);
+    hipLaunchKernelGGL(assemble_map_kernel, grid, dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<uchar4*>(d_frame),
+                       static_cast<const uchar4*>(d_tiles_all), shard_stride_bytes / 4, width, height, m->tile_rows,
+                       m->d_img + m->n_tiles, m->d_img + 2 * (size_t)m->n_tiles);
     RRT_HIP(hipGetLastError());
     return RRT_OK;
+}
+
+int rrt_launch_raymarch_ex(void* d_out_rgba8, int width, int height, float time, const rrt_camera* cam,
+                           rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm,
+                           const rrt_debug_outputs* dbg, void* stream) {
+    const int rc = check_common(d_out_rgba8, width, height, cam, fx, prm);
+    if (rc) return rc;
+    return launch_frame(d_out_rgba8, width, height, frame_rows(height), time, cam, sky, fx, prm, dbg, stream);
+}
+
+int rrt_launch_raymarch_ss(void* d_out_rgba8, float* d_hdr_rgba32f, int width, int height, int samples_per_axis, float time,
+                           const rrt_camera* cam, rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm, void* stream) {
+    const int rc = check_ss(d_out_rgba8, width, height, samples_per_axis, cam, fx, prm);
+    if (rc) return rc;
+    return launch_ss(d_out_rgba8, reinterpret_cast<float4*>(d_hdr_rgba32f), width, height, samples_per_axis, frame_rows(height),
+                     nullptr, time, cam, sky, fx, prm, static_cast<hipStream_t>(stream));
+}
+
+int rrt_launch_raymarch_ss_tiles(void* d_out_tiles, int width, int height, int samples_per_axis, int tile_rows, int shard, int n_shards,
+                                 float time, const rrt_camera* cam, rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm,
+                                 void* stream) {
+    int rc = check_ss(d_out_tiles, width, height, samples_per_axis, cam, fx, prm);
+    if (rc) return rc;
+    RowMap rows;
+    if ((rc = shard_map(height, tile_rows, shard, n_shards, rows))) return rc;
+    return launch_ss(d_out_tiles, nullptr, width, height, samples_per_axis, rows, nullptr, time, cam, sky, fx, prm,
+                     static_cast<hipStream_t>(stream));
+}
+
+int rrt_launch_raymarch_mb(void* d_out_rgba8, float* d_hdr_rgba32f, int width, int height, int samples_per_axis, int n_times,
+                           const float* times, const rrt_camera* cams, rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm,
+                           void* stream) {
+    const int rc = check_mb(d_out_rgba8, width, height, samples_per_axis, n_times, times, cams, fx, prm);
+    if (rc) return rc;
+    return launch_mb(d_out_rgba8, reinterpret_cast<float4*>(d_hdr_rgba32f), width, height, samples_per_axis, frame_rows(height),
+                     n_times, times, cams, sky, fx, prm, static_cast<hipStream_t>(stream));
+}
+
+int rrt_launch_raymarch_mb_tiles(void* d_out_tiles, int width, int height, int samples_per_axis, int tile_rows, int shard, int n_shards,
+                                 int n_times, const float* times, const rrt_camera* cams, rrt_sky_t sky, const rrt_effects* fx,
+                                 const rrt_params* prm, void* stream) {
+    int rc = check_mb(d_out_tiles, width, height, samples_per_axis, n_times, times, cams, fx, prm);
+    if (rc) return rc;
+    RowMap rows;
+    if ((rc = shard_map(height, tile_rows, shard, n_shards, rows))) return rc;
+    return launch_mb(d_out_tiles, nullptr, width, height, samples_per_axis, rows, n_times, times, cams, sky, fx, prm,
+                     static_cast<hipStream_t>(stream));
 }
 
 int rrt_glow_default(rrt_glow* g) {
@@ -2087,6 +1962,15 @@ int rrt_projection_ray(const rrt_projection* p, int width, int height, int x, in
     return RRT_OK;
 }
 
+int rrt_launch_raymarch_pano(void* d_out_rgba8, float* d_hdr_rgba32f, int width, int height, int samples_per_axis,
+                             const rrt_projection* proj, float time, const rrt_camera* cam, rrt_sky_t sky, const rrt_effects* fx,
+                             const rrt_params* prm, void* stream) {
+    const int rc = check_pano(d_out_rgba8, width, height, samples_per_axis, proj, cam, fx, prm);
+    if (rc) return rc;
+    return launch_ss(d_out_rgba8, reinterpret_cast<float4*>(d_hdr_rgba32f), width, height, samples_per_axis, frame_rows(height),
+                     proj, time, cam, sky, fx, prm, static_cast<hipStream_t>(stream));
+}
+
 int rrt_launch_projection_map(void* d_dir_rgba32f, int width, int height, const rrt_projection* proj, const rrt_camera* cam,
                               void* stream) {
     const int rc = check_projection(proj);
@@ -2098,15 +1982,6 @@ int rrt_launch_projection_map(void* d_dir_rgba32f, int width, int height, const 
                        static_cast<float4*>(d_dir_rgba32f), width, height, *cam, proj_args(*proj));
     RRT_HIP(hipGetLastError());
     return RRT_OK;
-}
-
-int rrt_launch_raymarch_pano(void* d_out_rgba8, float* d_hdr_rgba32f, int width, int height, int samples_per_axis,
-                             const rrt_projection* proj, float time, const rrt_camera* cam, rrt_sky_t sky, const rrt_effects* fx,
-                             const rrt_params* prm, void* stream) {
-    const int rc = check_pano(d_out_rgba8, width, height, samples_per_axis, proj, cam, fx, prm);
-    if (rc) return rc;
-    return launch_ss(d_out_rgba8, reinterpret_cast<float4*>(d_hdr_rgba32f), width, height, samples_per_axis, frame_rows(height),
-                     proj, time, cam, sky, fx, prm, static_cast<hipStream_t>(stream));
 }
 
 int rrt_launch_raymarch_pano_tiles(void* d_out_tiles, int width, int height, int samples_per_axis, int tile_rows, int shard,
@@ -2167,6 +2042,48 @@ int rrt_launch_raymarch_stereo_tiles(void* d_out_tiles, int width, int height, i
                      static_cast<hipStream_t>(stream), st);
 }
 
+/* ---- march cache (include/rrt.h) ---- */
+int rrt_march_cache_configure(int device, size_t max_bytes) {
+    const int dev = march_cache_device(device);
+    if (dev < 0) return RRT_ERR_NO_DEVICE;
+    MarchCacheObject* c = march_cache_of(dev, true);
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->pol.reset();
+    c->configured = true; c->budget_known = true; c->max_bytes = max_bytes;
+    if (c->bytes > max_bytes) return on_device(dev, [&] { MarchCacheRegistry::free_device_memory(*c); return RRT_OK; });
+    return RRT_OK;
+}
+
+int rrt_march_cache_stats(int device, rrt_march_cache_info* out) {
+    if (!out) return RRT_ERR_INVALID_ARGUMENT;
+    memset(out, 0, sizeof(*out));
+    const int dev = march_cache_device(device);
+    if (dev < 0) return RRT_ERR_NO_DEVICE;
+    MarchCacheObject* c = march_cache_of(dev, false);
+    if (!c) return RRT_OK;
+    std::lock_guard<std::mutex> lk(c->mu);
+    out->fills = c->pol.st.fills; out->hits = c->pol.st.hits; out->drops = c->pol.st.drops;
+    out->misses = c->pol.st.misses; out->uncacheable = c->pol.st.uncacheable;
+    out->bytes = c->bytes;
+    out->max_bytes = march_cache_env_off() ? 0 : (c->budget_known ? c->max_bytes : 0);
+    out->state = c->pol.state; out->why = c->pol.why;
+    if (c->pol.state == rrt_mc::kReady || c->pol.state == rrt_mc::kPending) {
+        out->blocks_capacity = c->cap_blocks;
+        if (c->pol.state == rrt_mc::kReady) out->blocks_used = c->used_blocks;
+    }
+    return RRT_OK;
+}
+
+int rrt_march_cache_release(int device) {
+    const int dev = march_cache_device(device);
+    if (dev < 0) return RRT_ERR_NO_DEVICE;
+    MarchCacheObject* c = march_cache_of(dev, false);
+    if (!c) return RRT_OK;
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->pol.reset();
+    return on_device(dev, [&] { MarchCacheRegistry::destroy(*c); return RRT_OK; });
+}
+
 #ifdef RRT_TEST_HOOKS
 #define RRT_TEST_HOOKS_PART 2
 #include "rrt_test_hooks.h"
@@ -2183,4 +2100,3 @@ void launch_raymarch(uchar4* d_out, int w, int h, float time, CameraState cam, c
                      CameraEffects effects) {
     (void)rrt_launch_raymarch_compat(d_out, w, h, time, reinterpret_cast<const float*>(&cam), skyboxTex, &effects);
 }
-

@@ -1,8 +1,9 @@
 /*
  * rrt_noise_plan.h -- host side of the lattice-hash tables (rrt_noise_table): which lattice points the noise3D call families
  * of densities.h:20-132 can reach within a window of the clock, the boxes (dense layout) and band boxes (banded layout) that
- * cover them, their sizes, and the NoiseTableObject registry.  Included by rrt_hip.hip inside its anonymous namespace, after
- * rrt_kernels.h (round 6: split out of rrt_hip.hip, nothing else changed).  Device side: NoiseLut / DustBands in rrt_device.h.
+ * cover them, their sizes, and the NoiseTableObject a handle stands for (its table, g_noise_tables, is in rrt_hip.hip with the
+ * other four: rrt_handles.h).  Included by rrt_hip.hip inside its anonymous namespace, after rrt_kernels.h.  Device side: NoiseLut /
+ * DustBands in rrt_device.h.
  */
 #ifndef RRT_NOISE_PLAN_H
 #define RRT_NOISE_PLAN_H
@@ -36,9 +37,6 @@ struct NoiseTableObject {
     LutBox acc, dust;
     int device;
 };
-std::mutex g_nt_mu;
-std::unordered_map<int, NoiseTableObject> g_nt;
-int g_nt_next = 1;
 
 struct Interval {
     double lo, hi;

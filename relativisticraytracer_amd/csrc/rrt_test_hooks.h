@@ -529,7 +529,7 @@ int rrt_unit_sky_sample(int n, const float* dir, float off, rrt_sky_t sky, int f
     if (n > 0 && (!dir || !out)) return RRT_ERR_INVALID_ARGUMENT;
     if (frac_bits < 0 || frac_bits > 16) return RRT_ERR_INVALID_ARGUMENT;
     SkyObject so;
-    if (!sky_lookup(sky, so)) return RRT_ERR_BAD_HANDLE;
+    if (!g_skies.get(sky, so)) return RRT_ERR_BAD_HANDLE;
     SkyTex t{so.d_texels, so.w, so.h, frac_bits};
     return unit_launch(n, st, [&](dim3 g, dim3 b, hipStream_t s) { hipLaunchKernelGGL(k_sky, g, b, 0, s, n, dir, off, t, out); });
 }
@@ -556,13 +556,7 @@ int rrt_unit_noise3d_lut(int n, const float* p, int table, int which, float* out
     if (n > 0 && (!p || !out)) return RRT_ERR_INVALID_ARGUMENT;
     if (which < 0 || which > 1) return RRT_ERR_INVALID_ARGUMENT;
     NoiseTableObject nt;
-    {
-        std::lock_guard<std::mutex> lk(g_nt_mu);
-        auto it = g_nt.find(table);
-        if (it == g_nt.end()) return RRT_ERR_BAD_HANDLE;
-        nt = it->second;
-    }
-    if (!on_current_device(nt.device)) return RRT_ERR_BAD_HANDLE;
+    if (lookup_here(g_noise_tables, table, nt)) return RRT_ERR_BAD_HANDLE;
     const NoiseLut L = which == 0 ? make_lut(nt.d_cells, nt.acc, nt.acc_families)
                                   : make_lut(nt.d_cells + dust_cell0(nt), nt.dust, nt.dust_families);
     return unit_launch(n, st, [&](dim3 g, dim3 b, hipStream_t s) { hipLaunchKernelGGL(k_noise3d_lut, g, b, 0, s, n, p, L, out, d_counts); });
@@ -570,13 +564,7 @@ int rrt_unit_noise3d_lut(int n, const float* p, int table, int which, float* out
 int rrt_unit_media_lut(int n, const float* p, float time, int table, float* out_disk, float* out_dust, unsigned* d_counts, void* st) {
     if (n > 0 && (!p || !out_disk || !out_dust)) return RRT_ERR_INVALID_ARGUMENT;
     NoiseTableObject nt;
-    {
-        std::lock_guard<std::mutex> lk(g_nt_mu);
-        auto it = g_nt.find(table);
-        if (it == g_nt.end()) return RRT_ERR_BAD_HANDLE;
-        nt = it->second;
-    }
-    if (!on_current_device(nt.device)) return RRT_ERR_BAD_HANDLE;
+    if (lookup_here(g_noise_tables, table, nt)) return RRT_ERR_BAD_HANDLE;
     if (!(time >= nt.t0 && time <= nt.t1)) return RRT_ERR_INVALID_ARGUMENT;
     const NoiseLut la = make_lut(nt.d_cells, nt.acc, nt.acc_families);
     const NoiseLut ld = make_lut(nt.d_cells + dust_cell0(nt), nt.dust, nt.dust_families);

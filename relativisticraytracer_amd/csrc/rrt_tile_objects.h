@@ -1,7 +1,8 @@
 /*
  * rrt_tile_objects.h -- the host objects behind rrt_tile_map (explicit tile -> shard assignment) and rrt_tile_order (cost-ordered
- * dispatch) and their registries.  Included by rrt_hip.hip inside its anonymous namespace, after rrt_kernels.h (RowMap) (round 6:
- * split out of rrt_hip.hip, nothing else changed).  The sort behind rrt_tile_order: rrt_tile_sort.h.
+ * dispatch).  Both are registered as shared_ptrs (g_tile_maps, g_tile_orders in rrt_hip.hip; the table: rrt_handles.h): a launch
+ * pins the object it uses.  Included by rrt_hip.hip inside its anonymous namespace, after rrt_kernels.h (RowMap).  The sort behind
+ * rrt_tile_order: rrt_tile_sort.h.
  */
 #ifndef RRT_TILE_OBJECTS_H
 #define RRT_TILE_OBJECTS_H
@@ -15,14 +16,6 @@ struct TileMapObject {
     std::vector<int> shard_of_tile, offset, rows;    /* offset[s]: where shard s's tiles start in tile_of_local */
     int* d_img = nullptr;
 };
-std::mutex g_tm_mu;
-std::unordered_map<int, std::shared_ptr<TileMapObject>> g_tm;
-int g_tm_next = 1;
-std::shared_ptr<TileMapObject> tile_map_lookup(int id) {
-    std::lock_guard<std::mutex> lk(g_tm_mu);
-    auto it = g_tm.find(id);
-    return it == g_tm.end() ? nullptr : it->second;
-}
 
 /* ------------------------------------------------------------------ cost-ordered dispatch (rrt_tile_order)
  * Workgroups are dispatched in blockIdx order and a wave tile's cost is only known once it has been rendered, so the
@@ -54,15 +47,7 @@ bool same_row_map(const RowMap& a, const RowMap& b) {
     return a.n_local_rows == b.n_local_rows && a.y_base == b.y_base && a.tile_rows == b.tile_rows && a.shard == b.shard &&
            a.n_shards == b.n_shards && a.tile_of_local == b.tile_of_local;
 }
-/* the registry lock only covers the lookup; an object is pinned by its shared_ptr and serialised by its own mutex, so
+/* the handle table's lock only covers the lookup; an object is pinned by its shared_ptr and serialised by its own mutex, so
  * threads driving different objects (different GPUs) never wait for each other */
-std::mutex g_to_mu;
-std::unordered_map<int, std::shared_ptr<TileOrderObject>> g_to;
-int g_to_next = 1;
-std::shared_ptr<TileOrderObject> tile_order_lookup(int id) {
-    std::lock_guard<std::mutex> lk(g_to_mu);
-    auto it = g_to.find(id);
-    return it == g_to.end() ? nullptr : it->second;
-}
 
 #endif /* RRT_TILE_OBJECTS_H */

@@ -197,6 +197,73 @@ int main() {
     EXPECT(rrt_launch_raymarch_compat(out, 16, 8, 1.0f, cam12, 0x7777ull, &fx) == RRT_ERR_BAD_HANDLE);      // says why, once
     EXPECT(rrt_launch_raymarch_compat(out, 16, 8, 1.0f, cam12, 0x7777ull, &fx) == RRT_ERR_BAD_HANDLE);
     EXPECT(rrt_launch_raymarch_compat(out, 16, 8, 1.0f, nullptr, sky, &fx) == RRT_ERR_INVALID_ARGUMENT);
+    // ---- the five kinds of handle on one table (csrc/rrt_handles.h): a stale id to every entry point that takes one.  Without a
+    // device only a borrowed sky can be created (every other create allocates); the sky here lives on fake device 2, the current one
+    {
+        const int stale = 12345;
+        unsigned u = 0; unsigned long long ull = 0; int rows = 0, dev = 0; float f0 = 0, f1 = 0; size_t nb = 0;
+        // workspace
+        EXPECT(rrt_workspace_rounds(stale, &u, &u, &u, &u) == RRT_ERR_BAD_HANDLE && rrt_workspace_stats(stale, &u, &u) == RRT_ERR_BAD_HANDLE);
+        EXPECT(rrt_workspace_read(stale, 0, 8, nullptr) == RRT_ERR_BAD_HANDLE);          // the handle before the arguments
+        EXPECT(rrt_workspace_destroy(stale) == RRT_ERR_BAD_HANDLE && rrt_workspace_destroy(0) == RRT_ERR_BAD_HANDLE);
+        rrt_params_default(&prm);
+        prm.workspace = stale; prm.path_policy = RRT_PATH_THREE_PASS;
+        EXPECT(rrt_launch_raymarch(out, 16, 8, 1.0f, &cam, sky, &fx, &prm, nullptr) == RRT_ERR_BAD_HANDLE);
+        EXPECT(rrt_launch_raymarch_tiles(out, 16, 8, 4, 0, 2, 1.0f, &cam, sky, &fx, &prm, nullptr) == RRT_ERR_BAD_HANDLE);
+        // noise table
+        EXPECT(rrt_noise_table_info(stale, &f0, &nb, nullptr) == RRT_ERR_BAD_HANDLE);
+        EXPECT(rrt_noise_table_window(stale, &f0, &f1, &rows, &dev) == RRT_ERR_BAD_HANDLE);
+        EXPECT(rrt_noise_table_destroy(stale) == RRT_ERR_BAD_HANDLE && rrt_noise_table_destroy(0) == RRT_ERR_BAD_HANDLE);
+        float pt[3] = {0, 0, 0}, o1 = 0, o2 = 0;
+        EXPECT(rrt_unit_noise3d_lut(1, pt, stale, 0, &o1, nullptr, nullptr) == RRT_ERR_BAD_HANDLE);
+        EXPECT(rrt_unit_media_lut(1, pt, 1.0f, stale, &o1, &o2, nullptr, nullptr) == RRT_ERR_BAD_HANDLE);
+        rrt_params_default(&prm);
+        prm.noise_table = stale;
+        EXPECT(rrt_launch_raymarch_ex(out, 16, 8, 1.0f, &cam, sky, &fx, &prm, nullptr, nullptr) == RRT_ERR_BAD_HANDLE);
+        EXPECT(rrt_launch_raymarch_ss(out, nullptr, 16, 8, 2, 1.0f, &cam, sky, &fx, &prm, nullptr) == RRT_ERR_BAD_HANDLE);
+        // tile order: whatever path the launch takes, and before the noise table is looked at
+        EXPECT(rrt_tile_order_set_seeding(stale, 0) == RRT_ERR_BAD_HANDLE && rrt_tile_order_seeded(stale, &ull) == RRT_ERR_BAD_HANDLE);
+        EXPECT(rrt_tile_order_seeded(stale, nullptr) == RRT_ERR_BAD_HANDLE);             // the handle before the argument
+        EXPECT(rrt_tile_order_info(stale, &ull, &ull, &u, nullptr, nullptr, 0) == RRT_ERR_BAD_HANDLE);
+        EXPECT(rrt_tile_order_destroy(stale) == RRT_ERR_BAD_HANDLE && rrt_tile_order_destroy(0) == RRT_ERR_BAD_HANDLE);
+        rrt_params_default(&prm);
+        prm.tile_order = stale;
+        for (int policy : {(int)RRT_PATH_AUTO, (int)RRT_PATH_SINGLE, (int)RRT_PATH_THREE_PASS}) {
+            prm.path_policy = policy;
+            EXPECT(rrt_launch_raymarch(out, 16, 8, 1.0f, &cam, sky, &fx, &prm, nullptr) == RRT_ERR_BAD_HANDLE);
+        }
+        // tile map: the map is resolved before the sky is looked at
+        EXPECT(rrt_tile_map_shard_rows(stale, 0, &rows, &rows) == RRT_ERR_BAD_HANDLE && rrt_tile_map_destroy(stale) == RRT_ERR_BAD_HANDLE);
+        EXPECT(rrt_tile_map_destroy(0) == RRT_ERR_BAD_HANDLE);
+        rrt_params_default(&prm);
+        EXPECT(rrt_launch_raymarch_tilemap(out, 16, 8, stale, 0, 1.0f, &cam, sky, &fx, &prm, nullptr) == RRT_ERR_BAD_HANDLE);
+        EXPECT(rrt_launch_raymarch_tilemap(out, 16, 8, stale, 0, 1.0f, &cam, 0x7777ull, &fx, &prm, nullptr) == RRT_ERR_BAD_HANDLE);
+        EXPECT(rrt_launch_raymarch_tilemap(nullptr, 16, 8, stale, 0, 1.0f, &cam, sky, &fx, &prm, nullptr) == RRT_ERR_INVALID_ARGUMENT);
+        EXPECT(rrt_assemble_all_tilemap(out, out, 16 * 8 * 4, 16, 8, stale, nullptr) == RRT_ERR_BAD_HANDLE);
+        // sky: every kind of launch, the unit hook; ids are issued upwards from "RT" << 48 | 1 and a destroyed one stays unknown
+        const rrt_sky_t no_sky = sky + 1000;
+        EXPECT((sky >> 48) == 0x5254u);
+        EXPECT(rrt_launch_raymarch(out, 16, 8, 1.0f, &cam, no_sky, &fx, &prm, nullptr) == RRT_ERR_BAD_HANDLE);
+        EXPECT(rrt_launch_raymarch_ss(out, nullptr, 16, 8, 2, 1.0f, &cam, no_sky, &fx, &prm, nullptr) == RRT_ERR_BAD_HANDLE);
+        EXPECT(rrt_launch_raymarch_ss_tiles(out, 16, 8, 2, 4, 0, 2, 1.0f, &cam, no_sky, &fx, &prm, nullptr) == RRT_ERR_BAD_HANDLE);
+        EXPECT(rrt_launch_raymarch_ss_tiles(out, 16, 8, 2, 0, 0, 2, 1.0f, &cam, no_sky, &fx, &prm, nullptr) == RRT_ERR_INVALID_ARGUMENT);   // the shard before the sky
+        const float times[2] = {1.0f, 1.1f}; const rrt_camera cams[2] = {cam, cam};
+        EXPECT(rrt_launch_raymarch_mb(out, nullptr, 16, 8, 1, 2, times, cams, no_sky, &fx, &prm, nullptr) == RRT_ERR_BAD_HANDLE);
+        EXPECT(rrt_unit_sky_sample(0, nullptr, 0.0f, no_sky, 8, nullptr, nullptr) == RRT_ERR_BAD_HANDLE);
+        EXPECT(rrt_unit_sky_sample(0, nullptr, 0.0f, sky, 8, nullptr, nullptr) == RRT_OK);            // n == 0: nothing is launched
+        rrt_sky_t sky2 = 0, sky3 = 0;
+        EXPECT(rrt_sky_create_from_device(reinterpret_cast<void*>(0x3000), 2, 2, &sky2) == RRT_OK && sky2 == sky + 1);
+        // destroy from a foreign device: a sky goes from anywhere (so do a workspace and a noise table; a tile map and a tile order
+        // do not -- those two need a device to exist at all: tests/test_gpu_handles.py)
+        EXPECT(rrt_debug_fake_device(5) == RRT_OK);
+        EXPECT(rrt_launch_raymarch(out, 16, 8, 1.0f, &cam, sky2, &fx, &prm, nullptr) == RRT_ERR_BAD_HANDLE);   // foreign: not usable ...
+        EXPECT(rrt_unit_sky_sample(0, nullptr, 0.0f, sky2, 8, nullptr, nullptr) == RRT_OK);                       // (the hook does not check the device)
+        EXPECT(rrt_sky_destroy(sky2) == RRT_OK && rrt_sky_destroy(sky2) == RRT_ERR_BAD_HANDLE);                // ... but destroyable, once
+        EXPECT(rrt_sky_create_from_device(reinterpret_cast<void*>(0x3000), 2, 2, &sky3) == RRT_OK && sky3 == sky + 2);   // sky2's id is not reused
+        EXPECT(rrt_sky_destroy(sky3) == RRT_OK);
+        EXPECT(rrt_debug_fake_device(2) == RRT_OK);
+        EXPECT(rrt_launch_raymarch(out, 16, 8, 1.0f, &cam, sky2, &fx, &prm, nullptr) == RRT_ERR_BAD_HANDLE);
+    }
     EXPECT(rrt_sky_destroy(sky) == RRT_OK && rrt_sky_destroy(sky) == RRT_ERR_BAD_HANDLE);
     EXPECT(rrt_debug_fake_device(-1) == RRT_OK);
     int n_dev = -1;

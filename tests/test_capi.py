@@ -269,6 +269,35 @@ def test_handles_are_tied_to_their_device_cpu_side():
         lib.rrt_debug_fake_device(-1)
 
 
+def test_stale_ids_of_every_kind_are_bad_handles():
+    """The five kinds of handle share one table (csrc/rrt_handles.h): an id nobody was given is RRT_ERR_BAD_HANDLE at every entry
+    point that takes one, before its other arguments are looked at and before anything touches a device.  A sky is destroyed from
+    any device, once, and its id is not issued again."""
+    from relativisticraytracer_amd import _lib
+    lib = _lib.load()
+    for stale in (12345, 4242, 0):
+        assert lib.rrt_workspace_destroy(stale) == 4 and lib.rrt_workspace_stats(stale, None, None) == 4
+        assert lib.rrt_workspace_rounds(stale, None, None, None, None) == 4 and lib.rrt_workspace_read(stale, 0, 8, None) == 4
+        assert lib.rrt_noise_table_destroy(stale) == 4 and lib.rrt_noise_table_info(stale, None, None, None) == 4
+        assert lib.rrt_noise_table_window(stale, None, None, None, None) == 4
+        assert lib.rrt_tile_order_destroy(stale) == 4 and lib.rrt_tile_order_set_seeding(stale, 1) == 4
+        assert lib.rrt_tile_order_seeded(stale, None) == 4 and lib.rrt_tile_order_info(stale, None, None, None, None, None, 0) == 4
+        assert lib.rrt_tile_map_destroy(stale) == 4 and lib.rrt_tile_map_shard_rows(stale, 0, None, None) == 4
+        assert lib.rrt_assemble_all_tilemap(C.c_void_p(0x1000), C.c_void_p(0x2000), 64, 4, 4, stale, None) == 4
+        assert lib.rrt_sky_destroy(stale) == 4
+    lt = _lib.load_test()
+    try:
+        assert lt.rrt_debug_fake_device(1) == 0
+        a, b = C.c_ulonglong(0), C.c_ulonglong(0)
+        assert lt.rrt_sky_create_from_device(C.c_void_p(0x1000), 2, 2, C.byref(a)) == 0 and a.value >> 48 == 0x5254
+        assert lt.rrt_debug_fake_device(6) == 0                  # a foreign device
+        assert lt.rrt_sky_destroy(a) == 0 and lt.rrt_sky_destroy(a) == 4
+        assert lt.rrt_sky_create_from_device(C.c_void_p(0x1000), 2, 2, C.byref(b)) == 0 and b.value > a.value
+        assert lt.rrt_sky_destroy(b) == 0
+    finally:
+        lt.rrt_debug_fake_device(-1)
+
+
 def test_struct_layouts_match_the_reference_structs():
     from relativisticraytracer_amd import _lib
     # CameraState: 4 x float3 = 48 B (include/raymarcher.h:11-16)
