@@ -523,6 +523,54 @@ int rrt_launch_raymarch_pano_tiles(void* d_out_tiles, int width, int height, int
                                    const rrt_camera* cam, rrt_sky_t sky, const rrt_effects* fx,
                                    const rrt_params* prm, void* stream);
 
+/* ---- adaptive supersampling: the 1x frame, with only the pixels that alias replaced by their s x s supersampled values; no
+ *      counterpart in the reference.  An s x s frame costs s^2 frames, and almost all of it lands on pixels that do not alias; the
+ *      aliasing sits on thin curves (photon ring, shadow edge, the disk's rim, ridge noise, stars).  For a width x height frame,
+ *      s = samples_per_axis in {1, 2, 4, 8} and a threshold T in [0, 255] the frame is DEFINED by two frames of the same arguments:
+ *        1. base: base8 and baseH are the RGBA8 and mean-HDR frames of rrt_launch_raymarch_ss(..., s = 1, ...) -- with a proj
+ *           whose kind is not RRT_PROJ_PINHOLE, of rrt_launch_raymarch_pano(..., s = 1, ...);
+ *        2. mask: on the STORED base8 in integer arithmetic, alpha ignored: pixel p is REFINED iff for one of its four edge
+ *           neighbours q (left, right, up, down; coordinates clamped at the frame's edge, NO horizontal wrap, equirect frames
+ *           included) max over c in {r, g, b} of |base8[p][c] - base8[q][c]| > T.  The rule is symmetric, so both sides of an edge are
+ *           refined; T = 255 refines nothing;
+ *        3. frame: a refined pixel's bytes and HDR are exactly those of the same pixel in the s x s frame of the same launch
+ *           arguments (rrt_launch_raymarch_ss, or _pano): the same virtual grid, the nudge hash on virtual coordinates, the same
+ *           pairwise tree, 1/(s*s) and one tone map.  Every other pixel keeps base8 and baseH.  out = where(mask, ss, base), byte
+ *           for byte and bit for bit; s = 1 is the base frame at any T.
+ *      The refined pixels carry the supersampled frame's (s-1)/(2s) px corner-aligned offset (rrt_launch_raymarch_ss) and the others
+ *      do not: the two grids differ by less than half a pixel, which is invisible where the picture is flat -- and the picture is
+ *      flat, to T, wherever a pixel is not refined.
+ *      The launch is base pass -> zero -> mask -> refine on the caller's stream: the mask pass compacts the refined pixels' frame
+ *      indices into the caller's scratch (ballot / popcount per wavefront, one atomic add per wavefront), the refine pass packs
+ *      them into full wavefronts -- a wave is an 8x8 tile of virtual samples, (8/s)^2 pixels -- and overwrites d_out_rgba8 and
+ *      d_hdr_rgba32f in place.  The host never learns the count: no synchronisation, no allocation, no memset; a launch can be
+ *      captured into a hipGraph as a linear chain.
+ *      d_scratch: rrt_adaptive_scratch_bytes(width, height) bytes or more, 16-byte aligned, the caller's.  Layout once the launch
+ *      has run: the uint32 at offset 0 is the count of refined pixels; from offset 16 on, that many uint32 frame indices (stored row
+ *      * width + x: the RGBA8 frame's own pixel index) in unspecified order.  A caller reads the count with its own 4-byte copy.
+ *      rrt_params honoured and ignored as in rrt_launch_raymarch_ss: single kernel, static order, no march cache.
+ *      RRT_ERR_INVALID_ARGUMENT, before any device call: everything rrt_launch_raymarch_ss (proj NULL) or rrt_launch_raymarch_pano
+ *      (proj given) refuses for the s x s frame, a NULL ad, d_scratch or d_out_rgba8, a threshold outside [0, 255], a scratch that is
+ *      too small or not 16-byte aligned; RRT_ERR_ABI_MISMATCH for another struct_size.  Full frames only: no _tiles form (the mask
+ *      needs the neighbouring rows across tile seams). ---- */
+typedef struct rrt_adaptive {
+    uint32_t struct_size;    /* sizeof(rrt_adaptive): rrt_adaptive_default sets it; any other value is RRT_ERR_ABI_MISMATCH */
+    int32_t threshold;       /* T in [0, 255], in steps of the stored 8-bit channels */
+} rrt_adaptive;
+/* threshold 8: a look, not a measurement */
+int rrt_adaptive_default(rrt_adaptive* ad);
+/* the bytes of the caller-owned scratch rrt_launch_raymarch_adaptive needs for a width x height frame: 16 + 4 width height, rounded
+ * up to 16.  Host only.  RRT_ERR_INVALID_ARGUMENT: NULL bytes, width or height <= 0, width*height >= 2^31. */
+int rrt_adaptive_scratch_bytes(int width, int height, size_t* bytes);
+/* Host only: the mask of a stored RGBA8 frame in HOST memory, from the source the mask pass runs: mask_out[i] = 1 if pixel i is
+ * refined, else 0, in the frame's layout; *count_out (may be NULL) their number.  The launch's refusals of ad, NULL rgba8_host or
+ * mask_out, the frame sizes rrt_adaptive_scratch_bytes refuses. */
+int rrt_adaptive_mask(const uint8_t* rgba8_host, int width, int height, const rrt_adaptive* ad, uint8_t* mask_out, uint32_t* count_out);
+int rrt_launch_raymarch_adaptive(void* d_out_rgba8, float* d_hdr_rgba32f /* may be NULL */, int width, int height,
+                                 int samples_per_axis, const rrt_projection* proj /* NULL = pinhole */, const rrt_adaptive* ad,
+                                 float time, const rrt_camera* cam, rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm,
+                                 void* d_scratch, size_t scratch_bytes, void* stream);
+
 /* ---- stereo frames: omni-directional stereo (ODS) equirect pairs for headsets and off-axis pinhole pairs for 3D displays; no
  *      counterpart in the reference.  width and height are PER EYE; the frame written is one RGBA8 composite of both eyes:
  *        - RRT_STEREO_TOP_BOTTOM: width x 2 height; as displayed the left eye is on top, so with the usual bottom-up rows buffer

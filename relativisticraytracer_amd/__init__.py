@@ -20,7 +20,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import RRTError, rrt_camera, rrt_debug_outputs, rrt_effects, rrt_glow, rrt_params, rrt_projection  # noqa: F401
-from ._lib import rrt_stereo  # noqa: F401
+from ._lib import rrt_adaptive, rrt_stereo  # noqa: F401
 
 __all__ = ["CameraState", "CameraEffects", "RenderParams", "SkyTexture", "Workspace", "NoiseTable", "launch_raymarch",
            "set_launch_defaults", "get_launch_defaults",
@@ -28,6 +28,7 @@ __all__ = ["CameraState", "CameraEffects", "RenderParams", "SkyTexture", "Worksp
            "launch_raymarch_ss", "launch_raymarch_ss_tiles", "launch_raymarch_mb", "launch_raymarch_mb_tiles",
            "GlowSettings", "glow_weights", "glow_scratch_bytes", "launch_glow",
            "Projection", "projection_default", "projection_ray", "launch_projection_map", "launch_raymarch_pano", "launch_raymarch_pano_tiles",
+           "AdaptiveSettings", "adaptive_scratch_bytes", "adaptive_mask", "launch_raymarch_adaptive",
            "Stereo", "stereo_default", "stereo_ray", "launch_raymarch_stereo", "launch_raymarch_stereo_tiles",
            "tile_shard_rows",
            "launch_raymarch_debug", "RRTError", "device_count", "abi_version", "TileOrder", "TileMap",
@@ -142,6 +143,20 @@ class GlowSettings(rrt_glow):
 
     def info(self):
         return {"radius": self.radius, "lobes": self.lobes, "threshold": self.threshold, "intensity": self.intensity}
+
+
+class AdaptiveSettings(rrt_adaptive):
+    """Adaptive supersampling settings (include/rrt.h: rrt_adaptive): threshold T in [0, 255] -- a pixel is refined if it differs
+    from a 4-neighbour by more than T in a colour channel of the stored 1x frame.  Default == rrt_adaptive_default (8)."""
+
+    def __init__(self, threshold=None):
+        super().__init__()
+        _lib.check(_lib.load().rrt_adaptive_default(C.byref(self)), "rrt_adaptive_default")
+        if threshold is not None:
+            self.threshold = int(threshold)
+
+    def info(self):
+        return {"threshold": self.threshold}
 
 
 PROJ_PINHOLE, PROJ_EQUIRECT, PROJ_FISHEYE = 0, 1, 2          # include/rrt.h: RRT_PROJ_*
@@ -654,6 +669,45 @@ def launch_raymarch_pano(d_out, w, h, samples, projection, time, cam, skyboxTex,
                                                     C.byref(cam), _sky_handle(skyboxTex), C.byref(effects),
                                                     C.byref(params) if params is not None else None,
                                                     _stream(stream)), "rrt_launch_raymarch_pano")
+
+
+def adaptive_scratch_bytes(w, h):
+    """bytes of the scratch launch_raymarch_adaptive needs for a w x h frame (rrt_adaptive_scratch_bytes)"""
+    n = C.c_size_t(0)
+    _lib.check(_lib.load().rrt_adaptive_scratch_bytes(w, h, C.byref(n)), "rrt_adaptive_scratch_bytes")
+    return n.value
+
+
+def adaptive_mask(rgba8, adaptive=None):
+    """(mask, count) of a stored RGBA8 frame on the host (rrt_adaptive_mask): rgba8 is an (h, w, 4) uint8 array in the frame's
+    layout, mask an (h, w) uint8 array of 0 / 1 in the same layout -- from the source the device's mask pass runs."""
+    a = np.ascontiguousarray(rgba8, np.uint8)
+    if a.ndim != 3 or a.shape[2] != 4:
+        raise ValueError(f"expected an (h, w, 4) uint8 frame, got {a.shape}")
+    h, w = a.shape[:2]
+    ad = adaptive if adaptive is not None else AdaptiveSettings()
+    mask, n = np.zeros((h, w), np.uint8), C.c_uint32(0)
+    _lib.check(_lib.load().rrt_adaptive_mask(a.ctypes.data_as(C.c_void_p), w, h, C.byref(ad), mask.ctypes.data_as(C.c_void_p),
+                                             C.byref(n)), "rrt_adaptive_mask")
+    return mask, n.value
+
+
+def launch_raymarch_adaptive(d_out, w, h, samples, projection, adaptive, time, cam, skyboxTex, effects, scratch, params=None,
+                             stream=None, hdr=None, scratch_bytes=None):
+    """Adaptively supersampled w x h frame (include/rrt.h: rrt_launch_raymarch_adaptive): launch_raymarch_ss's 1x frame (projection
+    None or "pinhole") or launch_raymarch_pano's, with the pixels that differ from a 4-neighbour by more than adaptive.threshold
+    replaced by their samples x samples values -- out = where(mask, ss, base), bit for bit.  `scratch`: device memory of
+    adaptive_scratch_bytes(w, h) bytes or more (its size is a tensor's own, or scratch_bytes for a raw pointer); after the launch
+    its first uint32 is the number of refined pixels and their frame indices follow from byte 16 on.  `hdr` (optional): w*h*4
+    float32 that receives the frame's HDR.  Nothing synchronises."""
+    if scratch_bytes is None:
+        scratch_bytes = scratch.numel() * scratch.element_size() if hasattr(scratch, "element_size") else adaptive_scratch_bytes(w, h)
+    _lib.check(_lib.load().rrt_launch_raymarch_adaptive(_ptr(d_out), _ptr(hdr), w, h, samples,
+                                                        C.byref(projection) if projection is not None else None,
+                                                        C.byref(adaptive), float(time), C.byref(cam), _sky_handle(skyboxTex),
+                                                        C.byref(effects), C.byref(params) if params is not None else None,
+                                                        _ptr(scratch), scratch_bytes, _stream(stream)),
+               "rrt_launch_raymarch_adaptive")
 
 
 def launch_projection_map(d_dirs, w, h, projection, cam, stream=None):

@@ -76,6 +76,10 @@ class rrt_projection(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_int32), ("fov_deg", C.c_float), ("vfov_deg", C.c_float)]
 
 
+class rrt_adaptive(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("threshold", C.c_int32)]
+
+
 class rrt_stereo(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("layout", C.c_int32), ("base", C.c_float), ("convergence", C.c_float),
                 ("pole_merge_from_deg", C.c_float), ("pole_merge_to_deg", C.c_float)]
@@ -143,6 +147,11 @@ SYMBOLS = [
     ("rrt_launch_raymarch_pano", _i, [_vp, _vp, _i, _i, _i, C.POINTER(rrt_projection), _f, _cam, _ull, _fx, _prm, _vp]),
     ("rrt_launch_projection_map", _i, [_vp, _i, _i, C.POINTER(rrt_projection), _cam, _vp]),
     ("rrt_launch_raymarch_pano_tiles", _i, [_vp, _i, _i, _i, _i, _i, _i, C.POINTER(rrt_projection), _f, _cam, _ull, _fx, _prm, _vp]),
+    ("rrt_adaptive_default", _i, [C.POINTER(rrt_adaptive)]),
+    ("rrt_adaptive_scratch_bytes", _i, [_i, _i, C.POINTER(C.c_size_t)]),
+    ("rrt_adaptive_mask", _i, [_vp, _i, _i, C.POINTER(rrt_adaptive), _vp, C.POINTER(C.c_uint32)]),
+    ("rrt_launch_raymarch_adaptive", _i, [_vp, _vp, _i, _i, _i, C.POINTER(rrt_projection), C.POINTER(rrt_adaptive), _f, _cam, _ull,
+                                          _fx, _prm, _vp, C.c_size_t, _vp]),
     ("rrt_stereo_default", _i, [_i, C.POINTER(rrt_stereo)]),
     ("rrt_stereo_ray", _i, [C.POINTER(rrt_projection), C.POINTER(rrt_stereo), _i, _i, _i, _i, _i, _cam, C.POINTER(_f * 3),
                             C.POINTER(_f * 3), C.POINTER(_i)]),

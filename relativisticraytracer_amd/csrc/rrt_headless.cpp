@@ -21,6 +21,10 @@
 //                                              per frame: rrt_launch_raymarch_stereo*, single kernel, no pool; --width / --height per
 //                                              eye, the composite is written; pinhole (off-axis) or equirect (ODS); not with fisheye,
 //                                              --motion-blur > 1 or --glow; --convergence pinhole only, --pole-merge equirect only)
+//                [--supersample 2|4|8 --adaptive [T]]   (adaptive supersampling: rrt_launch_raymarch_adaptive -- the 1x frame, only the
+//                                              pixels that differ from a 4-neighbour by more than T (0 ... 255, default 8) rendered
+//                                              S x S; one GPU only; not with --motion-blur > 1 or --stereo; combines with
+//                                              --projection and --glow)
 //
 // Noise tables: the reference's simTime runs without bound (main.cpp:515) and a table's size grows with the times
 // it covers, so each device keeps ONE table over a window of the clock that fits --noise-table-gib (default 2;
@@ -254,6 +258,9 @@ int main(int argc, char** argv) {
     bool stereo_base = false, stereo_conv = false, stereo_merge = false;   // which of the stereo options were given
     rrt_stereo stereo;                   // --stereo-base / --convergence / --pole-merge over rrt_stereo_default
     rrt_stereo_default(RRT_STEREO_TOP_BOTTOM, &stereo);
+    bool use_adaptive = false;           // --adaptive [T]: rrt_launch_raymarch_adaptive
+    rrt_adaptive adaptive;
+    rrt_adaptive_default(&adaptive);
     int kSlots = 3;                // frames in flight: frame k renders on stream k mod kSlots while its predecessors are
                                    // gathered / assembled / copied out (a rank's share of a frame is only a few rounds of
                                    // wavefronts; 3 measured best at 8 shards of a 4K frame: profiles/r02_frames_in_flight.txt)
@@ -345,6 +352,16 @@ int main(int argc, char** argv) {
             else if (a == "--convergence") { stereo.convergence = v[0]; stereo_conv = true; }
             else { stereo.pole_merge_from_deg = v[0]; stereo.pole_merge_to_deg = v[1]; stereo_merge = true; }
         }
+        else if (a == "--adaptive") {       // the threshold is optional: the next argument unless it is another option
+            use_adaptive = true;
+            if (i + 1 < argc && strncmp(argv[i + 1], "--", 2) != 0) {
+                const char* m = argv[++i];
+                char* end = nullptr;
+                const long v = strtol(m, &end, 10);
+                if (end == m || *end != 0 || v < 0 || v > 255) { fprintf(stderr, "usage: --adaptive [T]: a threshold in 0 ... 255 (default 8)\n"); return 2; }
+                adaptive.threshold = (int32_t)v;
+            }
+        }
         else if (a == "--arith" && i + 1 < argc) {
             const std::string m = argv[++i];
             if (m == "strict") arith = RRT_ARITH_STRICT; else if (m == "fmad") arith = RRT_ARITH_FMAD; else if (m == "fast") arith = RRT_ARITH_FAST;
@@ -405,6 +422,13 @@ int main(int argc, char** argv) {
             fprintf(stderr, "usage: --stereo-base B >= 0, --convergence Z >= 0, --pole-merge FROM TO with 0 <= FROM <= TO <= 90\n"); return 2;
         }
         if (stereo_layout == RRT_STEREO_SIDE_BY_SIDE) w = 2 * ew; else h = 2 * eh;
+    }
+    // adaptive supersampling needs the whole frame on one device (the mask looks at every pixel's neighbours; no _tiles form)
+    if (use_adaptive) {
+        if (supersample <= 1) { fprintf(stderr, "usage: --adaptive needs --supersample 2 | 4 | 8\n"); return 2; }
+        if (gpus > 1 || force_collective) { fprintf(stderr, "usage: --adaptive renders on one GPU only (--gpus 1)\n"); return 2; }
+        if (motion > 1) { fprintf(stderr, "usage: --adaptive renders one instant per frame (--motion-blur 1)\n"); return 2; }
+        if (use_stereo) { fprintf(stderr, "usage: --adaptive: not with --stereo\n"); return 2; }
     }
     // a supersampled launch is always the single kernel in the static order (include/rrt.h): no pool, no path choice, no tile order
     if (supersample > 1 || motion > 1 || use_glow || pano || use_stereo) { workspace_gib = 0; path_window = -1; tile_order = 0; }
@@ -512,12 +536,18 @@ int main(int argc, char** argv) {
     void* host[kMaxSlots] = {};
     void* hdr[kMaxSlots] = {};         // --glow: each slot's linear frame and the glow's scratch
     void* glow_scratch[kMaxSlots] = {};
+    void* ad_scratch[kMaxSlots] = {};  // --adaptive: each slot's list, and the pinned word its count is copied to
+    void* ad_count[kMaxSlots] = {};
+    size_t ad_bytes = 0;
+    if (use_adaptive && (rc = rrt_adaptive_scratch_bytes(w, h, &ad_bytes)) != RRT_OK) return fail("adaptive scratch", rc);
+    unsigned long long refined_total = 0;
     hipEvent_t done[kMaxSlots];
     const size_t frame_bytes = (size_t)w * h * 4;
     for (int s = 0; s < kSlots; ++s) {
         HIPCHK(hipMalloc(&gathered[s], shard_stride * gpus));
         HIPCHK(hipMalloc(&frame[s], frame_bytes));
         if (use_glow) { HIPCHK(hipMalloc(&hdr[s], frame_bytes * sizeof(float))); HIPCHK(hipMalloc(&glow_scratch[s], glow_bytes)); }
+        if (use_adaptive) { HIPCHK(hipMalloc(&ad_scratch[s], ad_bytes)); HIPCHK(hipHostMalloc(&ad_count[s], 4, hipHostMallocDefault)); }
         HIPCHK(hipEventCreateWithFlags(&done[s], hipEventDisableTiming));
     }
     FILE* f = out_path.empty() ? nullptr : fopen(out_path.c_str(), "wb");
@@ -537,6 +567,7 @@ int main(int argc, char** argv) {
     auto deliver = [&](int slot) -> int {
         HIPCHK(hipEventSynchronize(done[slot]));
         trace("frame complete", ++delivered);
+        if (use_adaptive) refined_total += *static_cast<const uint32_t*>(ad_count[slot]);
         // frame `delivered` has been rendered on every device (the gather waited for all shards): its sustained time on a device =
         // the interval between the ends of frame delivered - 1's and its own render there
         if (delivered >= 2) for (int d = 0; d < gpus; ++d) if (dev[d].chooser) {
@@ -642,11 +673,21 @@ int main(int argc, char** argv) {
                 return tiles ? rrt_launch_raymarch_ss_tiles(dst, w, h, supersample, tile_rows, d, gpus, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot])
                              : rrt_launch_raymarch_ss(dst, lin, w, h, supersample, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
             };
+            // --adaptive: one device (checked above), the whole frame and its HDR (may be NULL); the count of refined pixels follows
+            // in a 4-byte asynchronous copy, read when the frame is delivered
+            auto launch_adaptive = [&](float* lin) {
+                const int st = rrt_launch_raymarch_adaptive(dst, lin, w, h, supersample, pano ? &proj : nullptr, &adaptive, sim_t, &cam, D.sky,
+                                                            &fx, &prm, ad_scratch[slot], ad_bytes, D.stream[slot]);
+                if (st == RRT_OK && hipMemcpyAsync(ad_count[slot], ad_scratch[slot], 4, hipMemcpyDeviceToHost, D.stream[slot]) != hipSuccess)
+                    return (int)RRT_ERR_HIP;
+                return st;
+            };
             if (use_glow) {     // one device (checked above): the slot's HDR through launch_sampled, then the glow on the same stream
                 float* lin = static_cast<float*>(hdr[slot]);
-                rc = launch_sampled(false, lin);
+                rc = use_adaptive ? launch_adaptive(lin) : launch_sampled(false, lin);
                 if (rc == RRT_OK) rc = rrt_launch_glow(dst, lin, w, h, &glow, glow_scratch[slot], glow_bytes, D.stream[slot]);
             }
+            else if (use_adaptive) rc = launch_adaptive(nullptr);
             else if (use_stereo || pano || motion > 1 || supersample > 1) rc = launch_sampled(collective, nullptr);
             else if (collective) rc = rrt_launch_raymarch_tiles(dst, w, h, tile_rows, d, gpus, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
             else rc = rrt_launch_raymarch(dst, w, h, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
@@ -719,6 +760,13 @@ int main(int argc, char** argv) {
                  stereo.pole_merge_from_deg, stereo.pole_merge_to_deg);
         stereo_json = buf;
     }
+    std::string adaptive_json = "null";
+    if (use_adaptive) {
+        char buf[128];
+        snprintf(buf, sizeof(buf), "{\"threshold\": %d, \"refined_fraction\": %.9g}", adaptive.threshold,
+                 frames > 0 ? (double)refined_total / ((double)frames * w * h) : 0.0);
+        adaptive_json = buf;
+    }
     /* which path the frames took through each device's march cache (launches without a workspace: one GPU, or --workspace-gib 0) */
     std::string cache_json = "[";
     for (int d = 0; d < gpus; ++d) {
@@ -736,12 +784,12 @@ int main(int argc, char** argv) {
            "\"path\": \"%s\", \"spin\": %g, \"arith_mode\": \"%s\", \"noise_tables\": {\"builds\": %d, \"table_frames\": %d, "
            "\"arith_frames\": %d, \"coarsest_coverage\": %d, \"peak_bytes\": %zu, \"budget_bytes\": %zu}, \"tile_order\": %s, \"collective\": \"%s\", "
            "\"path_choice\": %s, \"supersample\": %d, \"motion_blur\": %d, \"shutter\": %g, \"glow\": %s, "
-           "\"projection\": \"%s\", \"fov_deg\": %s, \"vfov_deg\": %s, \"stereo\": %s, \"march_cache\": %s}\n",
+           "\"projection\": \"%s\", \"fov_deg\": %s, \"vfov_deg\": %s, \"stereo\": %s, \"adaptive\": %s, \"march_cache\": %s}\n",
            frames, w, h, gpus, dt, frames / dt, (double)frames * w * h / dt / 1e6, path_name, spin,
            arith == RRT_ARITH_FAST ? "fast" : (arith == RRT_ARITH_FMAD ? "fmad" : "strict"),
            table_builds, table_frames, arith_frames, coarsest, table_peak, table_budget, dev[0].order[0] ? "true" : "false",
            collective ? "rccl grouped send/recv gather" : "none", choice.c_str(), supersample, motion, shutter, glow_json.c_str(),
-           proj_name, fov_json, vfov_json, stereo_json.c_str(), cache_json.c_str());
+           proj_name, fov_json, vfov_json, stereo_json.c_str(), adaptive_json.c_str(), cache_json.c_str());
 
     for (int d = 0; d < gpus; ++d) {
         Device& D = dev[d];
@@ -762,6 +810,8 @@ int main(int argc, char** argv) {
     HIPCHK(hipSetDevice(0));
     for (int s = 0; s < kSlots; ++s) {
         (void)hipFree(gathered[s]); (void)hipFree(frame[s]); (void)hipFree(hdr[s]); (void)hipFree(glow_scratch[s]);
+        (void)hipFree(ad_scratch[s]);
+        if (ad_count[s]) (void)hipHostFree(ad_count[s]);
         if (host[s]) (void)hipHostFree(host[s]);
     }
     return 0;

@@ -999,6 +999,57 @@ int shard_map(int height, int tile_rows, int shard, int n_shards, RowMap& m) {
     return RRT_OK;
 }
 
+/* ---- adaptive supersampling (rrt_launch_raymarch_adaptive, rrt_adaptive_mask): the 1x frame, then only its aliasing pixels at s x s */
+int check_adaptive(const rrt_adaptive* ad) {
+    if (!ad) return RRT_ERR_INVALID_ARGUMENT;
+    if (ad->struct_size != (uint32_t)sizeof(rrt_adaptive)) {
+        snprintf(g_hip_err, sizeof(g_hip_err), "rrt_adaptive.struct_size %u, this library's is %zu: recompile against include/rrt.h",
+                 ad->struct_size, sizeof(rrt_adaptive));
+        return RRT_ERR_ABI_MISMATCH;
+    }
+    return ad->threshold >= 0 && ad->threshold <= 255 ? RRT_OK : RRT_ERR_INVALID_ARGUMENT;
+}
+bool adaptive_frame_ok(int width, int height) {
+    return width > 0 && height > 0 && (int64_t)width * (int64_t)height < ((int64_t)1 << 31);
+}
+
+/* base pass -> zero -> mask -> refine, a linear chain on `st`: no synchronisation, allocation or memset (the counter is zeroed by
+ * zero_words, like the workspace's header).  The refine pass overwrites out / hdr in place; stream order puts it behind the
+ * mask pass, which is the last reader of the base bytes.  The host does not know the count: the refine grid covers width*height
+ * list entries and the waves past the device-side count leave on one scalar load. */
+int launch_adaptive(void* out, float4* hdr, int width, int height, int s, const rrt_projection* proj, const rrt_adaptive& ad,
+                    float time, const rrt_camera* cam, rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm_in,
+                    void* scratch, hipStream_t st) {
+    FrameArgs a;
+    LaunchOpts o;
+    dim3 unused;
+    /* the s x s virtual frame's arguments first: whatever _ss refuses for it fails here, before the base pass is enqueued
+     * (launch_ss builds its own for s = 1) */
+    int rc = sampled_args(a, o, unused, out, width, height, s, frame_rows(height), time, time, cam, sky, fx, prm_in);
+    if (rc) return rc;
+    if ((rc = launch_ss(out, hdr, width, height, 1, frame_rows(height), proj, time, cam, sky, fx, prm_in, st))) return rc;
+    unsigned* count = static_cast<unsigned*>(scratch);
+    unsigned* list = reinterpret_cast<unsigned*>(static_cast<uint8_t*>(scratch) + kAdaptiveListOffset);
+    hipLaunchKernelGGL(zero_words, dim3(1), dim3(256), 0, st, static_cast<uint4*>(scratch), kAdaptiveListOffset / 16);
+    const unsigned tiles = (unsigned)((width + kMaskTile - 1) / kMaskTile) * (unsigned)((height + kMaskTile - 1) / kMaskTile);
+    hipLaunchKernelGGL(adaptive_mask, dim3((tiles + kMaskWaves - 1) / kMaskWaves), dim3(64 * kMaskWaves), 0, st,
+                       static_cast<const uint8_t*>(out), width, height, ad.threshold, count, list);
+    const bool pano = proj && proj->kind != RRT_PROJ_PINHOLE;
+    const ProjArgs pj = pano ? proj_args(*proj) : ProjArgs{};
+    if (pano) { a.use_lens = 0; a.use_vignette = 0; }
+    const RefineArgs ra{count, list, hdr, s};
+    const unsigned long long slots = (unsigned long long)((kTileW / s) * (kTileW / s)) * kWGWaves;       /* per workgroup */
+    const unsigned long long groups = ((unsigned long long)width * height + slots - 1) / slots;
+    const unsigned gx = (unsigned)std::min<unsigned long long>(groups, 1ull << 20);
+    const dim3 grid(gx, (unsigned)((groups + gx - 1) / gx));
+    dispatch_kernel(a.spin != 0.0f, o.media, o.arith, [&](auto S, auto M, auto F) {
+        if (pano) hipLaunchKernelGGL((refine_pixels<S, M, F, kRayProjection>), grid, dim3(kWGThreads), 0, st, a, ra, pj);
+        else hipLaunchKernelGGL((refine_pixels<S, M, F, kRayPinhole>), grid, dim3(kWGThreads), 0, st, a, ra, pj);
+    });
+    RRT_HIP(hipGetLastError());
+    return RRT_OK;
+}
+
 /* ---- HDR glow (rrt_launch_glow): the lobes' taps in double, the checks, the three launches */
 struct GlowPlan {
     int lobes, rmax, n_weights;
@@ -1993,6 +2044,50 @@ int rrt_launch_raymarch_pano_tiles(void* d_out_tiles, int width, int height, int
     if ((rc = shard_map(height, tile_rows, shard, n_shards, rows))) return rc;
     return launch_ss(d_out_tiles, nullptr, width, height, samples_per_axis, rows, proj, time, cam, sky, fx, prm,
                      static_cast<hipStream_t>(stream));
+}
+
+int rrt_adaptive_default(rrt_adaptive* ad) {
+    if (!ad) return RRT_ERR_INVALID_ARGUMENT;
+    ad->struct_size = (uint32_t)sizeof(rrt_adaptive);
+    ad->threshold = 8;
+    return RRT_OK;
+}
+
+int rrt_adaptive_scratch_bytes(int width, int height, size_t* bytes) {
+    if (!bytes || !adaptive_frame_ok(width, height)) return RRT_ERR_INVALID_ARGUMENT;
+    *bytes = adaptive_scratch(width, height);
+    return RRT_OK;
+}
+
+int rrt_adaptive_mask(const uint8_t* rgba8_host, int width, int height, const rrt_adaptive* ad, uint8_t* mask_out,
+                      uint32_t* count_out) {
+    const int rc = check_adaptive(ad);
+    if (rc) return rc;
+    if (!rgba8_host || !mask_out || !adaptive_frame_ok(width, height)) return RRT_ERR_INVALID_ARGUMENT;
+    uint32_t n = 0;
+    for (int row = 0; row < height; ++row)
+        for (int x = 0; x < width; ++x) {
+            const bool r = adaptive_refined(rgba8_host, width, height, x, row, ad->threshold);
+            mask_out[(size_t)row * width + x] = r ? 1 : 0;
+            n += r ? 1u : 0u;
+        }
+    if (count_out) *count_out = n;
+    return RRT_OK;
+}
+
+int rrt_launch_raymarch_adaptive(void* d_out_rgba8, float* d_hdr_rgba32f, int width, int height, int samples_per_axis,
+                                 const rrt_projection* proj, const rrt_adaptive* ad, float time, const rrt_camera* cam,
+                                 rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm, void* d_scratch, size_t scratch_bytes,
+                                 void* stream) {
+    int rc = check_adaptive(ad);
+    if (rc) return rc;
+    rc = proj ? check_pano(d_out_rgba8, width, height, samples_per_axis, proj, cam, fx, prm)
+              : check_ss(d_out_rgba8, width, height, samples_per_axis, cam, fx, prm);
+    if (rc) return rc;
+    if (!d_scratch || (reinterpret_cast<uintptr_t>(d_scratch) & 15) || scratch_bytes < adaptive_scratch(width, height))
+        return RRT_ERR_INVALID_ARGUMENT;
+    return launch_adaptive(d_out_rgba8, reinterpret_cast<float4*>(d_hdr_rgba32f), width, height, samples_per_axis, proj, *ad, time,
+                           cam, sky, fx, prm, d_scratch, static_cast<hipStream_t>(stream));
 }
 
 int rrt_stereo_default(int layout, rrt_stereo* st) {

@@ -10,6 +10,8 @@
  *   march_defer / eval_sample_rows / composite_and_shade (/ pool_next_round, zero_words)
  *                                             three-pass path through a caller-owned workspace, in rounds, as two chains;
  *                                             with KEEP: passes 2 and 3 over the march cache's retained rows (KeepArgs)
+ *   supersample_pixels / panorama_pixels / stereo_pixels / motion_pixels      the sampled launches over a virtual (s w) x (s h) frame
+ *   adaptive_mask (rrt_adaptive.h) / refine_pixels<SPIN,MEDIA,ARITH,RAY>      adaptive supersampling: list the aliasing pixels, refine them
  *   probe_costs / probe_to_tiles              coarse march-only probe of a view: first-frame dispatch order, row-tile costs
  *   clock_probe_kernel                        the shader clock the chip holds
  *   assemble_tiles_kernel / assemble_all_kernel / assemble_map_kernel   scatter gathered row-tile shards into the frame
@@ -699,6 +701,60 @@ template <bool SPIN, int MEDIA, int ARITH>
 __global__ __launch_bounds__(kWGThreads, (MEDIA != 0 ? RRT_MEDIA_WAVES : 1))      /* raymarch_pixels' register budget */
 void stereo_pixels(const FrameArgs a, const int s, float4* const hdr_out, const ProjArgs pj, const StereoArgs sa) {
     sampled_pixels<SPIN, MEDIA, ARITH, kRayStereo>(a, s, hdr_out, pj, sa);
+}
+
+/* Adaptive supersampling (rrt_launch_raymarch_adaptive, include/rrt.h has the contract): the refine pass.  adaptive_mask
+ * (rrt_adaptive.h) has left the frame indices of the pixels to refine in a list; this kernel renders exactly those pixels as
+ * supersample_pixels / panorama_pixels would and overwrites them in the base frame.  `a` describes the VIRTUAL (s w) x (s h) frame,
+ * as theirs.  A wave is an 8x8 tile of virtual samples made of (8/s)^2 pixel SLOTS: slot (sa, sb) of wave k takes list entry
+ * k (8/s)^2 + sb (8/s) + sa, and lane (i', j') is sub-sample (i' mod s, j' mod s) of slot (i'/s, j'/s) -- the lane layout pixel_sum
+ * assumes, so the sum's order is supersample_pixels' and the pixel's first lane stores.  A ray's result does not depend on which
+ * rays share its wavefront (tests/test_gpu_march_waves.py), which is what lets scattered pixels fill a wave.
+ * The host does not know the count: it launches for width*height entries, and a slot past the device-side count leaves before
+ * the march -- all of its lanes together, and whole waves on one scalar load.  The ray selection is a private copy of
+ * sampled_pixels' (factoring it out of there would move the existing kernels' registers). */
+#include "rrt_adaptive.h"
+template <bool SPIN, int MEDIA, int ARITH, SampledRay RAY>
+__global__ __launch_bounds__(kWGThreads, (MEDIA != 0 ? RRT_MEDIA_WAVES : 1))      /* raymarch_pixels' register budget */
+void refine_pixels(const FrameArgs a, const RefineArgs ra, const ProjArgs pj) {
+    static_assert(RAY == kRayPinhole || RAY == kRayProjection, "no adaptive stereo");
+    const int s = ra.s, lane = threadIdx.x & 63, li = lane & (kTileW - 1), lj = lane / kTileW;
+    const int shift = __ffs(s) - 1, per = kTileW >> shift;          /* s is a power of two: slots per axis */
+    const unsigned wave = (blockIdx.y * gridDim.x + blockIdx.x) * (unsigned)kWGWaves + (threadIdx.x >> 6);
+    const unsigned slot = wave * (unsigned)(per * per) + (unsigned)((lj >> shift) * per + (li >> shift));
+    if (slot >= *ra.count) return;
+    const unsigned idx = ra.list[slot];                             /* stored row * width + x of the w x h frame */
+    const int w = a.width >> shift, h = a.height >> shift;
+    const int out_row = (int)(idx / (unsigned)w), x = (int)(idx - (unsigned)out_row * (unsigned)w);
+    const int vx = s * x + (li & (s - 1)), vy = s * (h - 1 - out_row) + (lj & (s - 1));       /* rows are stored bottom-up */
+    const auto march_shade = [&](v3 p, v3 vel, float uvx, float uvy) {
+        Radiance acc = {0.f, 0.f, 0.f, 1.0f};
+        bool hit = false;
+        int i = 0;
+        march_inline<SPIN, MEDIA, ARITH, true>(a, p, vel, acc, hit, i, nullptr);
+        return shade_hdr(a, uvx, uvy, hit, vel, acc);
+    };
+    v3 c = mk(0.f, 0.f, 0.f);
+    if constexpr (RAY == kRayProjection) {
+        float d[3];
+        if (projection_dir(pj, a.width, a.height, vx, vy, a.cam, d)) {         /* outside the disc: HDR exactly 0, no march */
+            v3 vel = mk(d[0], d[1], d[2]);
+            if (__builtin_expect(a.nudge_ulps != 0, 0)) {         /* as primary_ray, on the virtual pixel */
+                vel.x = nudge_component(vel.x, a.nudge_ulps, a.nudge_seed, vx, vy, 0u);
+                vel.y = nudge_component(vel.y, a.nudge_ulps, a.nudge_seed, vx, vy, 1u);
+                vel.z = nudge_component(vel.z, a.nudge_ulps, a.nudge_seed, vx, vy, 2u);
+            }
+            c = march_shade(mk(a.cam.pos[0], a.cam.pos[1], a.cam.pos[2]), vel, 0.f, 0.f);
+        }
+    } else {
+        float uvx, uvy;
+        v3 p, vel;
+        primary_ray(a, vx, vy, uvx, uvy, p, vel);
+        c = march_shade(p, vel, uvx, uvy);
+    }
+    pixel_sum(c, s);
+    if (((li | lj) & (s - 1)) != 0) return;
+    store_mean(c, 1.0f / (float)(s * s), a.out, ra.hdr_out, (size_t)idx);
 }
 
 /* Motion-blurred frame (rrt_launch_raymarch_mb, include/rrt.h has the contract): sub-frame k is supersample_pixels' frame at

@@ -211,6 +211,16 @@ def analyse(src, name, pretty):
     print()
 
 
+def pretty_name(dm):
+    """the kernel's name with its template arguments, without namespace, return type and parameter list: `raymarch_pixels<true, 0,
+    false, 0>`; an enumerator argument prints as a cast, `refine_pixels<true, 2, 0, (SampledRay)0>`"""
+    if "anonymous" not in dm:
+        return dm
+    s = dm.replace("(anonymous namespace)::", "")
+    s = s[:s.index(">(") + 1] if ">(" in s else s.split("(")[0]
+    return s.split(" ")[-1] if "<" not in s else s[s.rfind(" ", 0, s.index("<")) + 1:]
+
+
 def main():
     src = listing()
     names = [l.split(":")[0] for l in src if re.match(r"^_ZN12_GLOBAL__N_1\w+:", l)]
@@ -221,7 +231,7 @@ def main():
     for w in want:
         for n in names:
             if w in dm[n]:
-                analyse(src, n, dm[n].split("(")[1].split("::")[-1] if "anonymous" in dm[n] else dm[n])
+                analyse(src, n, pretty_name(dm[n]))
 
 
 if __name__ == "__main__":
