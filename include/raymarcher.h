@@ -88,4 +88,26 @@ void launch_raymarch(uchar4* d_out, int w, int h, float time, CameraState cam,
                      cudaTextureObject_t skyboxTex, CameraEffects effects);
 #endif
 
+/*
+ * Depth of field (no counterpart in the reference): rrt_launch_raymarch_dof / _dof_tiles in this header's types -- n_samples
+ * (time, camera, lens point) samples through a thin lens focused at `focus`; include/rrt.h has the contract.  Header-only, on the
+ * given stream; scene parameters come from `prm` (NULL: the library's defaults).  Returns the launch's status code.
+ */
+inline int launch_raymarch_dof(uchar4* d_out, float4* d_hdr /* may be NULL */, int w, int h, int samples_per_axis, int n_samples,
+                               const float* times, const CameraState* cams, const float2* lens_xy, float focus,
+                               cudaTextureObject_t skyboxTex, const CameraEffects& effects, const rrt_params* prm = nullptr,
+                               void* stream = nullptr) {
+    return rrt_launch_raymarch_dof(d_out, reinterpret_cast<float*>(d_hdr), w, h, samples_per_axis, n_samples, times,
+                                   reinterpret_cast<const rrt_camera*>(cams), reinterpret_cast<const float*>(lens_xy), focus,
+                                   skyboxTex, reinterpret_cast<const rrt_effects*>(&effects), prm, stream);
+}
+inline int launch_raymarch_dof_tiles(uchar4* d_out_tiles, int w, int h, int samples_per_axis, int tile_rows, int shard, int n_shards,
+                                     int n_samples, const float* times, const CameraState* cams, const float2* lens_xy, float focus,
+                                     cudaTextureObject_t skyboxTex, const CameraEffects& effects, const rrt_params* prm = nullptr,
+                                     void* stream = nullptr) {
+    return rrt_launch_raymarch_dof_tiles(d_out_tiles, w, h, samples_per_axis, tile_rows, shard, n_shards, n_samples, times,
+                                         reinterpret_cast<const rrt_camera*>(cams), reinterpret_cast<const float*>(lens_xy), focus,
+                                         skyboxTex, reinterpret_cast<const rrt_effects*>(&effects), prm, stream);
+}
+
 #endif /* RRT_RAYMARCHER_COMPAT_H */

@@ -631,6 +631,52 @@ int rrt_launch_raymarch_stereo_tiles(void* d_out_tiles, int width, int height, i
                                      const rrt_camera* cam, rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm,
                                      void* stream);
 
+/* ---- depth of field: K = n_samples in {1, 2, 4, 8, 16} rays per sub-sample through points of a thin lens focused at `focus`, each
+ *      s x s supersampled (s in {1, 2, 4, 8}); no counterpart in the reference, whose camera is a pinhole.  times[k], cams[k] and
+ *      the lens point (lx, ly) = (lens_xy[2k], lens_xy[2k+1]) of sample k (k < n_samples) are HOST arrays, read during the call; a
+ *      lens point is in scene units along cams[k].right and cams[k].up.  Every sample carries its own time and camera, so ONE
+ *      launch gives a frame that is defocused and motion-blurred from the same K rays.  The frame is DEFINED by
+ *      rrt_launch_raymarch_ss and rrt_launch_raymarch_mb:
+ *        - sample k's ray for virtual pixel (x, y) of the (s*width) x (s*height) frame; every operation binary32, uncontracted, in
+ *          the association written, the same in all three arithmetic modes; fw, rt, up, pos from cams[k]:
+ *          on the host cx = lx / focus and cy = ly / focus.  The direction is the pinhole's primary ray (raymarcher.cu:20-34, the
+ *          lens distortion included) with u_coord = u_coord - cx and v_coord = v_coord - cy between u_coord *= aspect and forming
+ *          D = fw + (rt*u + up*v); then normalize, then the nudge hash on the virtual (x, y), as in rrt_launch_raymarch_ss.  The
+ *          vignette reads the uv primary_ray returns (after the lens distortion, before the shift), as the stereo pinhole does.
+ *          The origin is org = pos; if lx != 0: org_i = org_i + rt_i * lx; if ly != 0: org_i = org_i + up_i * ly.  In flat space
+ *          the rays of all lens points through one pixel meet on the plane `focus` along forward: the plane in focus;
+ *        - zero rule: a zero cx or cy (either sign) leaves its coordinate untouched, a zero lx or ly adds nothing;
+ *        - T_k is the sum rrt_launch_raymarch_ss forms over that sample's (s*width) x (s*height) frame before it scales;
+ *        - the pixel's HDR value is tree(T_0 ... T_{K-1}) * (1 / (s*s*K)), rrt_launch_raymarch_mb's pairwise tree in natural k
+ *          order; tone-mapped once, stored as RGBA8, bottom-up rows.  d_hdr_rgba32f (may be NULL) as in rrt_launch_raymarch_ss.
+ *      Hence: all lens points (0, 0) give the bytes and HDR bits of rrt_launch_raymarch_mb for the same times and cams at any
+ *      focus > 0; K = 1 with a zero lens point is rrt_launch_raymarch_ss, with s = 1 as well rrt_launch_raymarch; K = 1 with the
+ *      lens point (+-lx, 0) and focus Z is the right / left half of rrt_launch_raymarch_stereo's pinhole frame with base 2 lx (exact)
+ *      and convergence Z; K equal samples are K = 1.
+ *      The noise table is used only if EVERY times[k] lies in its window.  rrt_params honoured and ignored as in
+ *      rrt_launch_raymarch_mb: the launch is the single kernel in the static order, and never reads or fills the march cache.
+ *      RRT_ERR_INVALID_ARGUMENT, before any device call: everything rrt_launch_raymarch_mb refuses, a NULL lens_xy, a non-finite
+ *      lens coordinate, a focus that is not finite or <= 0.  No memset, no allocation, no synchronisation: a launch can be captured
+ *      into a hipGraph. ---- */
+int rrt_launch_raymarch_dof(void* d_out_rgba8, float* d_hdr_rgba32f /* may be NULL */, int width, int height, int samples_per_axis,
+                            int n_samples, const float* times, const rrt_camera* cams, const float* lens_xy /* 2 n_samples */,
+                            float focus, rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm, void* stream);
+/* The same frame's row tiles of `shard`, in the buffer layout of rrt_launch_raymarch_mb_tiles (rrt_assemble_(all_)tiles serve it). */
+int rrt_launch_raymarch_dof_tiles(void* d_out_tiles, int width, int height, int samples_per_axis, int tile_rows, int shard, int n_shards,
+                                  int n_samples, const float* times, const rrt_camera* cams, const float* lens_xy /* 2 n_samples */,
+                                  float focus, rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm, void* stream);
+/* Host only: the primary ray of virtual pixel (x, y) of a width x height frame through the lens point (lx, ly), before any nudge
+ * and without the lens distortion (as rrt_stereo_ray's pinhole), from the source the kernel runs: origin_out and the unit
+ * direction dir_out.  RRT_ERR_INVALID_ARGUMENT: NULL cam, origin_out or dir_out, width or height <= 0, (x, y) outside the frame, a
+ * non-finite lx or ly, a focus that is not finite or <= 0. */
+int rrt_lens_ray(int width, int height, int x, int y, const rrt_camera* cam, float lx, float ly, float focus, float origin_out[3],
+                 float dir_out[3]);
+/* Host only, a helper and no part of any bit contract: n_samples lens points on a disc of radius `aperture`.  n_samples = 1 gives
+ * (0, 0); otherwise Vogel's spiral in double, r = aperture * sqrt((k + 0.5) / n_samples), theta = rotation_rad + k pi (3 - sqrt 5),
+ * (r cos theta, r sin theta) rounded to float.  RRT_ERR_INVALID_ARGUMENT: NULL xy_out, a negative or non-finite aperture, a
+ * non-finite rotation, n_samples outside {1, 2, 4, 8, 16}. */
+int rrt_lens_points(float aperture, int n_samples, float rotation_rad, float* xy_out /* 2 n_samples */);
+
 /* ---- which path a rank's share takes while several frames of a sequence are in flight (host only; no GPU call) ----
  * New in this repo (the reference renders one frame at a time on one GPU: src/main.cpp:505-529).  A launch of <= 1.5 M rays
  * with a pool can take the three-pass path (RRT_PATH_AUTO) or the single kernel (RRT_PATH_SINGLE); under frames in flight the

@@ -30,6 +30,7 @@ __all__ = ["CameraState", "CameraEffects", "RenderParams", "SkyTexture", "Worksp
            "Projection", "projection_default", "projection_ray", "launch_projection_map", "launch_raymarch_pano", "launch_raymarch_pano_tiles",
            "AdaptiveSettings", "adaptive_scratch_bytes", "adaptive_mask", "launch_raymarch_adaptive",
            "Stereo", "stereo_default", "stereo_ray", "launch_raymarch_stereo", "launch_raymarch_stereo_tiles",
+           "launch_raymarch_dof", "launch_raymarch_dof_tiles", "lens_ray", "lens_points",
            "tile_shard_rows",
            "launch_raymarch_debug", "RRTError", "device_count", "abi_version", "TileOrder", "TileMap",
            "probe_tile_costs", "balance_tiles", "launch_raymarch_tilemap", "assemble_all_tilemap", "clock_probe", "clock_probe_ghz",
@@ -778,6 +779,59 @@ def launch_raymarch_mb_tiles(d_out_tiles, w, h, samples, tile_rows, shard, n_sha
                                                         _sky_handle(skyboxTex), C.byref(effects),
                                                         C.byref(params) if params is not None else None,
                                                         _stream(stream)), "rrt_launch_raymarch_mb_tiles")
+
+
+def _lens_samples(times, cams, lens_xy):
+    """_sub_frames plus the host array of the samples' lens points (2 floats each), for the _dof entry points"""
+    t, c, n = _sub_frames(times, cams)
+    xy = np.ascontiguousarray(lens_xy, dtype=np.float32).reshape(-1)
+    if xy.size != 2 * n:
+        raise ValueError(f"{n} samples but {xy.size} lens coordinates")
+    return t, c, (C.c_float * xy.size)(*xy.tolist()), n
+
+
+def launch_raymarch_dof(d_out, w, h, samples, times, cams, lens_xy, focus, skyboxTex, effects, params=None, stream=None, hdr=None):
+    """Depth-of-field w x h frame (include/rrt.h: rrt_launch_raymarch_dof): len(times) in {1, 2, 4, 8, 16} samples, sample k the
+    samples x samples supersampled frame at (times[k], cams[k]) seen through the point lens_xy[k] = (lx, ly) of a thin lens
+    focused `focus` units along forward (scene units along the camera's right and up; lens_points gives a disc of them); the pixel
+    is the mean of all their sub-samples' post-FX HDR, summed in launch_raymarch_mb's order and tone-mapped once; RGBA8, bottom-up.
+    All lens points (0, 0) give launch_raymarch_mb's frame.  `hdr` (optional): w*h*4 float32 for the mean HDR.  The params'
+    workspace, path_policy, pool_rounds, pass_chains and tile_order are ignored."""
+    t, c, xy, n = _lens_samples(times, cams, lens_xy)
+    _lib.check(_lib.load().rrt_launch_raymarch_dof(_ptr(d_out), _ptr(hdr), w, h, samples, n, t, c, xy, float(focus),
+                                                   _sky_handle(skyboxTex), C.byref(effects),
+                                                   C.byref(params) if params is not None else None,
+                                                   _stream(stream)), "rrt_launch_raymarch_dof")
+
+
+def launch_raymarch_dof_tiles(d_out_tiles, w, h, samples, tile_rows, shard, n_shards, times, cams, lens_xy, focus, skyboxTex,
+                              effects, params=None, stream=None):
+    """The row tiles of `shard` of launch_raymarch_dof's frame, in launch_raymarch_tiles' buffer layout (assemble_tiles /
+    assemble_all_tiles serve it unchanged)."""
+    t, c, xy, n = _lens_samples(times, cams, lens_xy)
+    _lib.check(_lib.load().rrt_launch_raymarch_dof_tiles(_ptr(d_out_tiles), w, h, samples, tile_rows, shard, n_shards, n, t, c, xy,
+                                                         float(focus), _sky_handle(skyboxTex), C.byref(effects),
+                                                         C.byref(params) if params is not None else None,
+                                                         _stream(stream)), "rrt_launch_raymarch_dof_tiles")
+
+
+def lens_ray(w, h, x, y, cam, lx, ly, focus):
+    """(origin, unit direction) as float32[3] each of virtual pixel (x, y) of a w x h frame through the lens point (lx, ly) of a
+    thin lens focused at `focus` (rrt_lens_ray, host only): the primary ray before any nudge and without the lens distortion, from
+    the source the depth-of-field kernel runs"""
+    o, d = (C.c_float * 3)(), (C.c_float * 3)()
+    _lib.check(_lib.load().rrt_lens_ray(w, h, x, y, C.byref(cam), float(lx), float(ly), float(focus), C.byref(o), C.byref(d)),
+               "rrt_lens_ray")
+    return np.array(o[:], np.float32), np.array(d[:], np.float32)
+
+
+def lens_points(aperture, n_samples, rotation=0.0):
+    """(n_samples, 2) float32 lens points on a disc of radius `aperture` (rrt_lens_points, host only): (0, 0) for one sample,
+    otherwise Vogel's spiral turned by `rotation` radians"""
+    out = np.zeros((max(int(n_samples), 1), 2), np.float32)
+    _lib.check(_lib.load().rrt_lens_points(float(aperture), int(n_samples), float(rotation),
+                                           out.ctypes.data_as(C.POINTER(C.c_float))), "rrt_lens_points")
+    return out
 
 
 def glow_weights(glow, height, lobe):

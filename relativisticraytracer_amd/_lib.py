@@ -159,6 +159,11 @@ SYMBOLS = [
                                         _prm, _vp]),
     ("rrt_launch_raymarch_stereo_tiles", _i, [_vp, _i, _i, _i, _i, _i, _i, C.POINTER(rrt_projection), C.POINTER(rrt_stereo), _f,
                                               _cam, _ull, _fx, _prm, _vp]),
+    ("rrt_launch_raymarch_dof", _i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(_f), _cam, C.POINTER(_f), _f, _ull, _fx, _prm, _vp]),
+    ("rrt_launch_raymarch_dof_tiles", _i, [_vp, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_f), _cam, C.POINTER(_f), _f, _ull, _fx, _prm,
+                                           _vp]),
+    ("rrt_lens_ray", _i, [_i, _i, _i, _i, _cam, _f, _f, _f, C.POINTER(_f * 3), C.POINTER(_f * 3)]),
+    ("rrt_lens_points", _i, [_f, _i, _f, C.POINTER(_f)]),
     ("rrt_tile_shard_rows", _i, [_i, _i, _i, _i, C.POINTER(_i)]),
     ("rrt_assemble_tiles", _i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     ("rrt_assemble_all_tiles", _i, [_vp, _vp, C.c_size_t, _i, _i, _i, _i, _vp]),

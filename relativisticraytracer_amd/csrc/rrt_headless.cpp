@@ -25,6 +25,12 @@
 //                                              pixels that differ from a 4-neighbour by more than T (0 ... 255, default 8) rendered
 //                                              S x S; one GPU only; not with --motion-blur > 1 or --stereo; combines with
 //                                              --projection and --glow)
+//                [--dof APERTURE [--focus Z|hole] [--dof-samples 1|2|4|8|16]]   (depth of field: rrt_launch_raymarch_dof* through K
+//                                              points of a thin lens of radius APERTURE (rrt_lens_points; K default 8), sample m
+//                                              through lens point bitrev_K(m), focused Z along forward (default hole: the frame's
+//                                              camera's distance to the origin); single kernel, no pool; with --motion-blur M > 1
+//                                              the samples are the shutter's sub-frames (K = M); pinhole only, not with --stereo
+//                                              or --adaptive)
 //
 // Noise tables: the reference's simTime runs without bound (main.cpp:515) and a table's size grows with the times
 // it covers, so each device keeps ONE table over a window of the clock that fits --noise-table-gib (default 2;
@@ -261,6 +267,10 @@ int main(int argc, char** argv) {
     bool use_adaptive = false;           // --adaptive [T]: rrt_launch_raymarch_adaptive
     rrt_adaptive adaptive;
     rrt_adaptive_default(&adaptive);
+    bool use_dof = false;                // --dof APERTURE: rrt_launch_raymarch_dof*
+    float dof_aperture = 0.0f, dof_focus = 0.0f;     // --focus Z (0: hole -- the frame's camera's distance to the origin)
+    int dof_samples = 0;                 // --dof-samples K (0: not given -- 8, or --motion-blur's M)
+    bool dof_focus_given = false;
     int kSlots = 3;                // frames in flight: frame k renders on stream k mod kSlots while its predecessors are
                                    // gathered / assembled / copied out (a rank's share of a frame is only a few rounds of
                                    // wavefronts; 3 measured best at 8 shards of a 4K frame: profiles/r02_frames_in_flight.txt)
@@ -362,6 +372,27 @@ int main(int argc, char** argv) {
                 adaptive.threshold = (int32_t)v;
             }
         }
+        else if (a == "--dof") {
+            const char* m = i + 1 < argc ? argv[++i] : "";
+            char* end = nullptr;
+            const float v = strtof(m, &end);
+            if (end == m || *end != 0 || !std::isfinite(v) || v < 0.0f) { fprintf(stderr, "usage: --dof APERTURE: the lens radius in scene units, >= 0\n"); return 2; }
+            dof_aperture = v; use_dof = true;
+        }
+        else if (a == "--focus") {
+            const std::string m = i + 1 < argc ? argv[++i] : "";
+            char* end = nullptr;
+            const float v = m == "hole" ? 0.0f : strtof(m.c_str(), &end);
+            if (m != "hole" && (end == m.c_str() || *end != 0 || !std::isfinite(v) || !(v > 0.0f))) {
+                fprintf(stderr, "usage: --focus: a distance > 0 along forward, or `hole`\n"); return 2;
+            }
+            dof_focus = v; dof_focus_given = true;
+        }
+        else if (a == "--dof-samples") {
+            const std::string m = i + 1 < argc ? argv[++i] : "";
+            if (m == "1" || m == "2" || m == "4" || m == "8" || m == "16") dof_samples = atoi(m.c_str());
+            else { fprintf(stderr, "usage: --dof-samples 1 | 2 | 4 | 8 | 16 (lens samples per sub-sample)\n"); return 2; }
+        }
         else if (a == "--arith" && i + 1 < argc) {
             const std::string m = argv[++i];
             if (m == "strict") arith = RRT_ARITH_STRICT; else if (m == "fmad") arith = RRT_ARITH_FMAD; else if (m == "fast") arith = RRT_ARITH_FAST;
@@ -430,8 +461,28 @@ int main(int argc, char** argv) {
         if (motion > 1) { fprintf(stderr, "usage: --adaptive renders one instant per frame (--motion-blur 1)\n"); return 2; }
         if (use_stereo) { fprintf(stderr, "usage: --adaptive: not with --stereo\n"); return 2; }
     }
+    // depth of field: a thin lens in front of the pinhole camera; its K samples are the shutter's sub-frames when there are any
+    if (!use_dof && (dof_focus_given || dof_samples != 0)) { fprintf(stderr, "usage: --focus / --dof-samples need --dof APERTURE\n"); return 2; }
+    int dof_k = 0;
+    float dof_xy[32];
+    if (use_dof) {
+        if (pano) { fprintf(stderr, "usage: --dof: a thin lens in front of a pinhole camera, not with --projection equirect | fisheye\n"); return 2; }
+        if (use_stereo) { fprintf(stderr, "usage: --dof: not with --stereo\n"); return 2; }
+        if (use_adaptive) { fprintf(stderr, "usage: --dof: not with --adaptive\n"); return 2; }
+        if (motion > 1 && dof_samples != 0 && dof_samples != motion) {
+            fprintf(stderr, "usage: --dof-samples: with --motion-blur M > 1 the lens samples are the shutter's sub-frames (K = M)\n"); return 2;
+        }
+        dof_k = motion > 1 ? motion : (dof_samples != 0 ? dof_samples : 8);
+        float spiral[32];
+        if (rrt_lens_points(dof_aperture, dof_k, 0.0f, spiral) != RRT_OK) { fprintf(stderr, "usage: --dof APERTURE: the lens radius in scene units, >= 0\n"); return 2; }
+        for (int m = 0; m < dof_k; ++m) {       // sample m looks through lens point bitrev_K(m): the spiral's radius grows with its index
+            int r = 0;
+            for (int b = 1, v = m; b < dof_k; b <<= 1, v >>= 1) r = (r << 1) | (v & 1);
+            dof_xy[2 * m] = spiral[2 * r]; dof_xy[2 * m + 1] = spiral[2 * r + 1];
+        }
+    }
     // a supersampled launch is always the single kernel in the static order (include/rrt.h): no pool, no path choice, no tile order
-    if (supersample > 1 || motion > 1 || use_glow || pano || use_stereo) { workspace_gib = 0; path_window = -1; tile_order = 0; }
+    if (supersample > 1 || motion > 1 || use_glow || pano || use_stereo || use_dof) { workspace_gib = 0; path_window = -1; tile_order = 0; }
     int n_dev = 0, rc;
     if ((rc = rrt_device_count(&n_dev)) != RRT_OK) return fail("no GPU", rc);
     if (gpus > n_dev) { fprintf(stderr, "rrt_headless: --gpus %d but %d device(s) visible\n", gpus, n_dev); return 2; }
@@ -601,6 +652,16 @@ int main(int argc, char** argv) {
             }
             fit_t = sub_t[0];
         }
+        // depth of field: without a shutter the K samples share the frame's instant; --focus hole: the camera position's distance to
+        // the origin, the double root of the sum of the exact squares in x, y, z order, rounded to float (headless.py's)
+        float focus = dof_focus;
+        if (use_dof) {
+            if (motion <= 1) for (int m = 0; m < dof_k; ++m) { sub_t[m] = sim_t; sub_cam[m] = cam; }
+            if (focus == 0.0f) {
+                const double x = cam.pos[0], y = cam.pos[1], z = cam.pos[2];
+                focus = (float)std::sqrt(x * x + y * y + z * z);
+            }
+        }
         trace("frame", k);
         // slot reuse: frame k-kSlots used the same buffers; its host copy must have been written out
         if (k > kSlots && deliver(slot)) return 1;
@@ -661,11 +722,13 @@ int main(int argc, char** argv) {
             if (D.chooser) { int pol = RRT_PATH_AUTO; rrt_path_chooser_policy(D.chooser, k, &pol); prm.path_policy = pol; }
             else if (path_policy >= 0) prm.path_policy = path_policy;
             void* dst = collective ? D.tiles[slot] : frame[slot];
-            // the stereo / panorama / blurred / supersampled launch (_stereo, _pano, _mb, _ss): this device's tiles, or the whole frame and
+            // the stereo / defocused / panorama / blurred / supersampled launch (_stereo, _dof, _pano, _mb, _ss): this device's tiles, or the whole frame and
             // its HDR (may be NULL)
             auto launch_sampled = [&](bool tiles, float* lin) {
                 if (use_stereo) return tiles ? rrt_launch_raymarch_stereo_tiles(dst, ew, eh, supersample, tile_rows, d, gpus, &proj, &stereo, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot])
                                              : rrt_launch_raymarch_stereo(dst, lin, ew, eh, supersample, &proj, &stereo, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
+                if (use_dof) return tiles ? rrt_launch_raymarch_dof_tiles(dst, w, h, supersample, tile_rows, d, gpus, dof_k, sub_t, sub_cam, dof_xy, focus, D.sky, &fx, &prm, D.stream[slot])
+                                          : rrt_launch_raymarch_dof(dst, lin, w, h, supersample, dof_k, sub_t, sub_cam, dof_xy, focus, D.sky, &fx, &prm, D.stream[slot]);
                 if (pano) return tiles ? rrt_launch_raymarch_pano_tiles(dst, w, h, supersample, tile_rows, d, gpus, &proj, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot])
                                        : rrt_launch_raymarch_pano(dst, lin, w, h, supersample, &proj, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
                 if (motion > 1) return tiles ? rrt_launch_raymarch_mb_tiles(dst, w, h, supersample, tile_rows, d, gpus, motion, sub_t, sub_cam, D.sky, &fx, &prm, D.stream[slot])
@@ -688,7 +751,7 @@ int main(int argc, char** argv) {
                 if (rc == RRT_OK) rc = rrt_launch_glow(dst, lin, w, h, &glow, glow_scratch[slot], glow_bytes, D.stream[slot]);
             }
             else if (use_adaptive) rc = launch_adaptive(nullptr);
-            else if (use_stereo || pano || motion > 1 || supersample > 1) rc = launch_sampled(collective, nullptr);
+            else if (use_stereo || use_dof || pano || motion > 1 || supersample > 1) rc = launch_sampled(collective, nullptr);
             else if (collective) rc = rrt_launch_raymarch_tiles(dst, w, h, tile_rows, d, gpus, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
             else rc = rrt_launch_raymarch(dst, w, h, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
             if (rc != RRT_OK) return fail("launch", rc);
@@ -767,6 +830,13 @@ int main(int argc, char** argv) {
                  frames > 0 ? (double)refined_total / ((double)frames * w * h) : 0.0);
         adaptive_json = buf;
     }
+    std::string dof_json = "null";
+    if (use_dof) {
+        char buf[160], z[40];
+        if (dof_focus == 0.0f) snprintf(z, sizeof(z), "\"hole\""); else snprintf(z, sizeof(z), "%.9g", dof_focus);
+        snprintf(buf, sizeof(buf), "{\"aperture\": %.9g, \"focus\": %s, \"samples\": %d}", dof_aperture, z, dof_k);
+        dof_json = buf;
+    }
     /* which path the frames took through each device's march cache (launches without a workspace: one GPU, or --workspace-gib 0) */
     std::string cache_json = "[";
     for (int d = 0; d < gpus; ++d) {
@@ -784,12 +854,12 @@ int main(int argc, char** argv) {
            "\"path\": \"%s\", \"spin\": %g, \"arith_mode\": \"%s\", \"noise_tables\": {\"builds\": %d, \"table_frames\": %d, "
            "\"arith_frames\": %d, \"coarsest_coverage\": %d, \"peak_bytes\": %zu, \"budget_bytes\": %zu}, \"tile_order\": %s, \"collective\": \"%s\", "
            "\"path_choice\": %s, \"supersample\": %d, \"motion_blur\": %d, \"shutter\": %g, \"glow\": %s, "
-           "\"projection\": \"%s\", \"fov_deg\": %s, \"vfov_deg\": %s, \"stereo\": %s, \"adaptive\": %s, \"march_cache\": %s}\n",
+           "\"projection\": \"%s\", \"fov_deg\": %s, \"vfov_deg\": %s, \"stereo\": %s, \"dof\": %s, \"adaptive\": %s, \"march_cache\": %s}\n",
            frames, w, h, gpus, dt, frames / dt, (double)frames * w * h / dt / 1e6, path_name, spin,
            arith == RRT_ARITH_FAST ? "fast" : (arith == RRT_ARITH_FMAD ? "fmad" : "strict"),
            table_builds, table_frames, arith_frames, coarsest, table_peak, table_budget, dev[0].order[0] ? "true" : "false",
            collective ? "rccl grouped send/recv gather" : "none", choice.c_str(), supersample, motion, shutter, glow_json.c_str(),
-           proj_name, fov_json, vfov_json, stereo_json.c_str(), adaptive_json.c_str(), cache_json.c_str());
+           proj_name, fov_json, vfov_json, stereo_json.c_str(), dof_json.c_str(), adaptive_json.c_str(), cache_json.c_str());
 
     for (int d = 0; d < gpus; ++d) {
         Device& D = dev[d];

@@ -882,6 +882,46 @@ int launch_mb(void* out, float4* hdr, int width, int height, int s, const RowMap
     return RRT_OK;
 }
 
+/* ---- depth of field (rrt_launch_raymarch_dof*): launch_mb's sub-frames, each through its own point of a thin lens, one kernel */
+/* the checks of check_mb plus the lens's own; all before any device call */
+int check_dof(const void* out, int width, int height, int s, int n_samples, const float* times, const rrt_camera* cams,
+              const float* lens_xy, float focus, const rrt_effects* fx, const rrt_params* prm) {
+    if (!lens_xy || !std::isfinite(focus) || !(focus > 0.0f)) return RRT_ERR_INVALID_ARGUMENT;
+    const int rc = check_mb(out, width, height, s, n_samples, times, cams, fx, prm);
+    if (rc != RRT_OK) return rc;
+    for (int k = 0; k < 2 * n_samples; ++k)
+        if (!std::isfinite(lens_xy[k])) return RRT_ERR_INVALID_ARGUMENT;
+    return RRT_OK;
+}
+
+/* launch_mb with a lens point per sub-frame */
+int launch_dof(void* out, float4* hdr, int width, int height, int s, const RowMap& rows, int n_samples, const float* times,
+               const rrt_camera* cams, const float* lens_xy, float focus, rrt_sky_t sky, const rrt_effects* fx,
+               const rrt_params* prm_in, hipStream_t st) {
+    float t_lo = times[0], t_hi = times[0];
+    LensLaunch L;
+    LensArgs& m = L.m;
+    for (int k = 0; k < kMaxTimes; ++k) {           /* the unused slots repeat the last sample: no uninitialised kernel argument */
+        const int j = k < n_samples ? k : n_samples - 1;
+        m.time[k] = times[j];
+        m.cam[k] = cams[j];
+        m.lx[k] = lens_xy[2 * j]; m.ly[k] = lens_xy[2 * j + 1];
+        m.cx[k] = m.lx[k] / focus; m.cy[k] = m.ly[k] / focus;
+        if (times[j] < t_lo) t_lo = times[j];
+        if (times[j] > t_hi) t_hi = times[j];
+    }
+    LaunchOpts o;
+    dim3 grid;
+    const int rc = sampled_args(L.a, o, grid, out, width, height, s, rows, t_lo, t_hi, &cams[0], sky, fx, prm_in);
+    if (rc || grid.y == 0) return rc;
+    L.s = s; L.n_samples = n_samples; L.hdr_out = hdr;
+    dispatch_kernel(L.a.spin != 0.0f, o.media, o.arith, [&](auto S, auto M, auto F) {
+        hipLaunchKernelGGL((lens_pixels<S, M, F>), grid, dim3(kWGThreads), 0, st, L);
+    });
+    RRT_HIP(hipGetLastError());
+    return RRT_OK;
+}
+
 /* ---- panoramas (rrt_launch_raymarch_pano*, rrt_projection_ray): supersampled frames with the projection's primary ray */
 /* the projection's own refusals (include/rrt.h); a pinhole's spans are not looked at */
 int check_projection(const rrt_projection* p) {
@@ -1949,6 +1989,40 @@ int rrt_launch_raymarch_mb_tiles(void* d_out_tiles, int width, int height, int s
     if ((rc = shard_map(height, tile_rows, shard, n_shards, rows))) return rc;
     return launch_mb(d_out_tiles, nullptr, width, height, samples_per_axis, rows, n_times, times, cams, sky, fx, prm,
                      static_cast<hipStream_t>(stream));
+}
+
+int rrt_launch_raymarch_dof(void* d_out_rgba8, float* d_hdr_rgba32f, int width, int height, int samples_per_axis, int n_samples,
+                            const float* times, const rrt_camera* cams, const float* lens_xy, float focus, rrt_sky_t sky,
+                            const rrt_effects* fx, const rrt_params* prm, void* stream) {
+    const int rc = check_dof(d_out_rgba8, width, height, samples_per_axis, n_samples, times, cams, lens_xy, focus, fx, prm);
+    if (rc) return rc;
+    return launch_dof(d_out_rgba8, reinterpret_cast<float4*>(d_hdr_rgba32f), width, height, samples_per_axis, frame_rows(height),
+                      n_samples, times, cams, lens_xy, focus, sky, fx, prm, static_cast<hipStream_t>(stream));
+}
+
+int rrt_launch_raymarch_dof_tiles(void* d_out_tiles, int width, int height, int samples_per_axis, int tile_rows, int shard, int n_shards,
+                                  int n_samples, const float* times, const rrt_camera* cams, const float* lens_xy, float focus,
+                                  rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm, void* stream) {
+    int rc = check_dof(d_out_tiles, width, height, samples_per_axis, n_samples, times, cams, lens_xy, focus, fx, prm);
+    if (rc) return rc;
+    RowMap rows;
+    if ((rc = shard_map(height, tile_rows, shard, n_shards, rows))) return rc;
+    return launch_dof(d_out_tiles, nullptr, width, height, samples_per_axis, rows, n_samples, times, cams, lens_xy, focus, sky, fx,
+                      prm, static_cast<hipStream_t>(stream));
+}
+
+int rrt_lens_ray(int width, int height, int x, int y, const rrt_camera* cam, float lx, float ly, float focus, float origin_out[3],
+                 float dir_out[3]) {
+    if (!cam || !origin_out || !dir_out || width <= 0 || height <= 0 || x < 0 || x >= width || y < 0 || y >= height ||
+        !std::isfinite(lx) || !std::isfinite(ly) || !std::isfinite(focus) || !(focus > 0.0f))
+        return RRT_ERR_INVALID_ARGUMENT;
+    float uvx, uvy;
+    lens_ray(width, height, x, y, *cam, 0, 0.0f, lx, ly, lx / focus, ly / focus, origin_out, dir_out, uvx, uvy);
+    return RRT_OK;
+}
+
+int rrt_lens_points(float aperture, int n_samples, float rotation_rad, float* xy_out) {
+    return lens_points(aperture, n_samples, rotation_rad, xy_out) ? RRT_OK : RRT_ERR_INVALID_ARGUMENT;
 }
 
 int rrt_glow_default(rrt_glow* g) {

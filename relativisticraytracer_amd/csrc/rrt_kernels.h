@@ -837,6 +837,79 @@ void motion_pixels(const MotionLaunch L) {
     store_mean(c, 1.0f / (float)(s * s * RRT_MB_ARG(n_times)), RRT_MB_ARG(a.out), RRT_MB_ARG(hdr_out), (size_t)oi);
 }
 
+/* Depth of field (rrt_launch_raymarch_dof, include/rrt.h has the contract): motion_pixels with a lens point per sample.  Sample k
+ * is supersample_pixels' frame at (m.time[k], m.cam[k]) whose primary ray is lens_ray's (rrt_projection.h, the source the host
+ * query runs too) through the lens point (m.lx[k], m.ly[k]); cx = lx / focus and cy = ly / focus come rounded from the host.  All
+ * six are read from the by-value LensArgs at the uniform k, so they stay scalar, and a pixel's K rays share the wave's lanes.  The
+ * nudge runs here, after lens_ray, on the virtual pixel (primary_ray's own).  Registers, LDS slots and the re-read kernel
+ * arguments are motion_pixels': a kernel of its own, because a branch or a template parameter there would move that kernel's
+ * registers. */
+struct LensArgs { float time[kMaxTimes]; rrt_camera cam[kMaxTimes]; float lx[kMaxTimes], ly[kMaxTimes], cx[kMaxTimes], cy[kMaxTimes]; };
+struct LensLaunch {                                     /* lens_pixels' one kernel argument */
+    FrameArgs a;                                        /* the virtual frame, as supersample_pixels' */
+    LensArgs m;
+    int s, n_samples;
+    float4* hdr_out;
+};
+#define RRT_DOF_ARG(field) motion_arg<decltype(((LensLaunch*)nullptr)->field)>(offsetof(LensLaunch, field))
+
+template <bool SPIN, int MEDIA, int ARITH>
+__global__ __launch_bounds__(kWGThreads, (MEDIA != 0 ? RRT_MEDIA_WAVES : 1))      /* raymarch_pixels' register budget */
+void lens_pixels(const LensLaunch L) {
+    __shared__ float part[4][3][kWGThreads];            /* levels 0..3: n_samples <= 16 never stores level 4 */
+    __shared__ volatile int where[3][kWGThreads];       /* vx, vy, the output index (-1: another lane of the pixel stores) */
+    const int t = threadIdx.x;
+    {
+        const int s = L.s;
+        SampleLane l;
+        if (!sample_lane(L.a, s, l)) return;
+        where[0][t] = l.vx;
+        where[1][t] = l.vy;
+        where[2][t] = l.stores(s) ? l.out_row * (L.a.width / s) + l.x : -1;
+    }
+    v3 c;
+    for (int k = 0; k < L.n_samples; ++k) {
+        FrameArgs b = L.a;
+        b.time = L.m.time[k];
+        b.cam = L.m.cam[k];
+        float uvx, uvy;
+        v3 p, vel;
+        {
+            const int x = where[0][t], y = where[1][t];
+            float o[3], d[3];
+            lens_ray(RRT_DOF_ARG(a.width), RRT_DOF_ARG(a.height), x, y, b.cam, RRT_DOF_ARG(a.use_lens),
+                     RRT_DOF_ARG(a.distortion_amount), L.m.lx[k], L.m.ly[k], L.m.cx[k], L.m.cy[k], o, d, uvx, uvy);
+            p = mk(o[0], o[1], o[2]);
+            vel = mk(d[0], d[1], d[2]);
+            const int nudge_ulps = RRT_DOF_ARG(a.nudge_ulps);
+            if (__builtin_expect(nudge_ulps != 0, 0)) {             /* as primary_ray, on the virtual pixel */
+                const unsigned seed = RRT_DOF_ARG(a.nudge_seed);
+                vel.x = nudge_component(vel.x, nudge_ulps, seed, x, y, 0u);
+                vel.y = nudge_component(vel.y, nudge_ulps, seed, x, y, 1u);
+                vel.z = nudge_component(vel.z, nudge_ulps, seed, x, y, 2u);
+            }
+        }
+        Radiance acc = {0.f, 0.f, 0.f, 1.0f};
+        bool hit = false;
+        int i = 0;
+        march_inline<SPIN, MEDIA, ARITH, true>(b, p, vel, acc, hit, i, nullptr);
+        b.sky = RRT_DOF_ARG(a.sky);                                                      /* what shade_hdr reads */
+        b.use_bloom = RRT_DOF_ARG(a.use_bloom); b.bloom_threshold = RRT_DOF_ARG(a.bloom_threshold);
+        b.bloom_intensity = RRT_DOF_ARG(a.bloom_intensity); b.use_vignette = RRT_DOF_ARG(a.use_vignette);
+        b.vignette_intensity = RRT_DOF_ARG(a.vignette_intensity); b.use_ca = RRT_DOF_ARG(a.use_ca); b.ca_amount = RRT_DOF_ARG(a.ca_amount);
+        c = shade_hdr(b, uvx, uvy, hit, vel, acc);
+        pixel_sum(c, L.s);
+        int l = 0;                                      /* ((T0 + T1) + (T2 + T3)) ...: close the levels sample k completes */
+        for (int j = k; j & 1; j >>= 1, ++l)
+            c = add(mk(part[l][0][t], part[l][1][t], part[l][2][t]), c);
+        if (k + 1 < L.n_samples) { part[l][0][t] = c.x; part[l][1][t] = c.y; part[l][2][t] = c.z; }
+    }
+    const int oi = where[2][t];
+    if (oi < 0) return;
+    const int s = RRT_DOF_ARG(s);
+    store_mean(c, 1.0f / (float)(s * s * RRT_DOF_ARG(n_samples)), RRT_DOF_ARG(a.out), RRT_DOF_ARG(hdr_out), (size_t)oi);
+}
+
 /* rrt_launch_projection_map: projection_dir of every pixel, (dir, inside) in the frame's bottom-up layout */
 __global__ __launch_bounds__(256) void projection_map(float4* out, int W, int H, const rrt_camera cam, const ProjArgs pj) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;

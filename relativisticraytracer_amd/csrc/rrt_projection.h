@@ -6,6 +6,7 @@
  * code): the same source gives the same bits.
  *
  * stereo_ray, the primary ray of a stereo frame's eye (rrt_stereo), is built on the same pieces: stereo_pixels and rrt_stereo_ray.
+ * lens_ray, the primary ray through a point of a thin lens (rrt_launch_raymarch_dof), likewise: lens_pixels and rrt_lens_ray.
  *
  * A SECTION of rrt_hip.hip, included by rrt_kernels.h inside its anonymous namespace.
  */
@@ -118,6 +119,52 @@ __host__ __device__ __forceinline__ void stereo_ray(const ProjArgs& pj, const St
     }
     if (k != 0.0f) for (int i = 0; i < 3; ++i) org[i] = c.pos[i] + R[i] * k;
     else for (int i = 0; i < 3; ++i) org[i] = c.pos[i];
+}
+
+/* The primary ray of virtual pixel (x, y) of the W x H frame seen through the lens point (lx, ly) of a thin lens focused at `focus`
+ * (rrt_launch_raymarch_dof, include/rrt.h has the contract; cx = lx / focus and cy = ly / focus are rounded on the host): stereo_ray's
+ * off-axis pinhole on two axes -- primary_ray (raymarcher.cu:20-34, lens distortion included) with u - cx and v - cy, from
+ * pos + rt*lx + up*ly.  org, the unit direction dir (before any nudge) and the uv the vignette reads.  Zero rule: a zero cx or cy
+ * leaves its coordinate untouched and a zero lx or ly adds nothing, so the lens point (0, 0) is primary_ray bit for bit and
+ * (k, 0) is stereo_ray's eye.  lens_pixels and rrt_lens_ray (which passes use_lens = 0). */
+__host__ __device__ __forceinline__ void lens_ray(int W, int H, int x, int y, const rrt_camera& c, int use_lens, float lens_k,
+                                                  float lx, float ly, float cx, float cy, float org[3], float dir[3], float& uvx,
+                                                  float& uvy) {
+    uvx = (float)x / (float)W;
+    uvy = (float)y / (float)H;
+    if (use_lens) {                             /* rrt_device.h: lens_distort */
+        const float tx = uvx - 0.5f, ty = uvy - 0.5f;
+        const float r2 = tx * tx + ty * ty;
+        const float f = 1.0f + r2 * lens_k;
+        uvx = tx * f + 0.5f;
+        uvy = ty * f + 0.5f;
+    }
+    float u = uvx * 2.0f - 1.0f;
+    float v = uvy * 2.0f - 1.0f;
+    const float aspect = (float)W / (float)H;
+    u *= aspect;
+    if (cx != 0.0f) u = u - cx;
+    if (cy != 0.0f) v = v - cy;
+    basis_dir(c, 1.0f, u, v, dir);              /* fw*1 == fw: primary_ray's fw + (rt*u + up*v) */
+    for (int i = 0; i < 3; ++i) org[i] = c.pos[i];
+    if (lx != 0.0f) for (int i = 0; i < 3; ++i) org[i] = org[i] + c.right[i] * lx;
+    if (ly != 0.0f) for (int i = 0; i < 3; ++i) org[i] = org[i] + c.up[i] * ly;
+}
+
+/* rrt_lens_points (host only; include/rrt.h): n lens points on a disc of radius `aperture` into xy[2 n] -- (0, 0) for n = 1, else
+ * Vogel's spiral in double (equal-area rings, the golden angle between neighbours), rounded to float.  false: refused. */
+inline bool lens_points(float aperture, int n, float rotation, float* xy) {
+    if (!xy || !(n == 1 || n == 2 || n == 4 || n == 8 || n == 16)) return false;
+    if (!std::isfinite(aperture) || aperture < 0.0f || !std::isfinite(rotation)) return false;
+    if (n == 1) { xy[0] = 0.0f; xy[1] = 0.0f; return true; }
+    const double golden = 3.14159265358979323846 * (3.0 - std::sqrt(5.0));
+    for (int k = 0; k < n; ++k) {
+        const double r = (double)aperture * std::sqrt(((double)k + 0.5) / (double)n);
+        const double th = (double)rotation + (double)k * golden;
+        xy[2 * k] = (float)(r * std::cos(th));
+        xy[2 * k + 1] = (float)(r * std::sin(th));
+    }
+    return true;
 }
 
 #endif /* RRT_PROJECTION_H */

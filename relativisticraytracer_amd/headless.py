@@ -6,6 +6,7 @@
            [--projection pinhole|equirect|fisheye [--fov DEG] [--vfov DEG]]
            [--stereo top-bottom|side-by-side [--stereo-base B] [--convergence Z] [--pole-merge FROM TO]]
            [--supersample 2 --adaptive [T]]
+           [--dof APERTURE [--focus Z|hole] [--dof-samples K]]
     python -m torch.distributed.run --nproc-per-node 8 -m relativisticraytracer_amd.headless ...
 
 Per frame k = 1..N it does what `main()` does while recording: advance the fixed 1/24 s clock
@@ -16,6 +17,7 @@ row-tile sharded and gathered to rank 0 (sharding.FrameSharder).  Prints one JSO
 """
 import argparse
 import json
+import math
 import os
 import sys
 import time
@@ -30,6 +32,35 @@ def _threshold(text):
     if not 0 <= v <= 255:
         raise argparse.ArgumentTypeError("a threshold in 0 ... 255 (default 8)")
     return v
+
+
+def _focus(text):
+    """--focus' Z: a finite distance > 0, or `hole` (None: the frame's camera's distance to the origin)"""
+    if text == "hole":
+        return None
+    try:
+        v = float(text)
+    except ValueError:
+        v = 0.0
+    if not (math.isfinite(v) and v > 0.0):
+        raise argparse.ArgumentTypeError("a distance > 0 along forward, or `hole`")
+    return v
+
+
+def bit_reverse(m, n):
+    """m's log2(n) bits in reverse order (n a power of two): the lens point of sample m"""
+    r = 0
+    while n > 1:
+        r, m, n = (r << 1) | (m & 1), m >> 1, n >> 1
+    return r
+
+
+def hole_distance(cam):
+    """--focus hole: the camera position's distance to the origin, the double root of the sum of the exact squares in x, y, z
+    order, rounded to float (rrt_headless.cpp's)"""
+    import numpy as np
+    x, y, z = (float(v) for v in cam.as_array()[0])
+    return float(np.float32(math.sqrt(x * x + y * y + z * z)))
 
 
 def main(argv=None):
@@ -102,6 +133,16 @@ def main(argv=None):
                     help="with --supersample S > 1: adaptive supersampling (rrt_launch_raymarch_adaptive) -- the 1x frame, and only the "
                          "pixels that differ from a 4-neighbour by more than T (0 ... 255, default 8) in a colour channel are rendered "
                          "S x S.  One GPU only; not with --motion-blur > 1 or --stereo; combines with --projection and --glow")
+    ap.add_argument("--dof", type=float, default=None, metavar="APERTURE",
+                    help="depth of field (rrt_launch_raymarch_dof*): every frame through K points of a thin lens of this radius in "
+                         "scene units (rrt_lens_points), sample m through lens point bitrev_K(m).  Single kernel, static order; "
+                         "combines with --supersample, --motion-blur (the K samples are the shutter's sub-frames), --glow and several "
+                         "GPUs; pinhole only, not with --stereo or --adaptive")
+    ap.add_argument("--focus", type=_focus, default=None, metavar="Z|hole",
+                    help="with --dof: the distance of the plane in focus along forward, > 0, or `hole` (default): the distance from "
+                         "the frame's camera position to the origin")
+    ap.add_argument("--dof-samples", type=int, choices=(1, 2, 4, 8, 16), default=None, metavar="K",
+                    help="with --dof: lens samples per sub-sample (default 8); with --motion-blur M > 1 the samples are shared: K = M")
     ap.add_argument("--out", default=None, help="x.rgba (raw, bottom-up) | dir/ (PPM per frame) | x.mp4 (needs ffmpeg)")
     ap.add_argument("--init-timeout", type=float, default=300.0,
                     help="several ranks: seconds the process-group bring-up may take before the run exits non-zero with "
@@ -146,6 +187,22 @@ def main(argv=None):
             ap.error("--adaptive renders one instant per frame (--motion-blur 1)")
         if args.stereo is not None:
             ap.error("--adaptive: not with --stereo")
+
+    if args.dof is None and (args.focus is not None or args.dof_samples is not None):
+        ap.error("--focus / --dof-samples need --dof APERTURE")
+    dof_k = 0
+    if args.dof is not None:
+        if not (math.isfinite(args.dof) and args.dof >= 0.0):
+            ap.error("--dof APERTURE: the lens radius in scene units, >= 0")
+        if pano:
+            ap.error("--dof: a thin lens in front of a pinhole camera, not with --projection equirect | fisheye")
+        if args.stereo is not None:
+            ap.error("--dof: not with --stereo")
+        if args.adaptive is not None:
+            ap.error("--dof: not with --adaptive")
+        if args.motion_blur > 1 and args.dof_samples not in (None, args.motion_blur):
+            ap.error("--dof-samples: with --motion-blur M > 1 the lens samples are the shutter's sub-frames (K = M)")
+        dof_k = args.motion_blur if args.motion_blur > 1 else (args.dof_samples or 8)
 
     t_start = time.perf_counter()
 
@@ -213,7 +270,9 @@ def main(argv=None):
     w, h = stereo.composite(ew, eh) if stereo is not None else (ew, eh)       # the frame that is sharded, gathered and written
     ss, mb = args.supersample, args.motion_blur
     # supersampled, blurred, glowed, panorama, stereo: single kernel, static order, no pool
-    single = ss > 1 or mb > 1 or glow is not None or pano or stereo is not None
+    single = ss > 1 or mb > 1 or glow is not None or pano or stereo is not None or dof_k > 0
+    # sample m looks through lens point bitrev_K(m): the spiral's radius grows with its index, the shutter's times with m
+    dof_points = rrt.lens_points(args.dof, dof_k)[[bit_reverse(m, dof_k) for m in range(dof_k)]] if dof_k else None
     tex = rrt.SkyTexture(load_sky(args.sky) if args.sky else synthetic_sky())
     fx = rrt.CameraEffects(useChromaticAberration=bool(args.all_effects))
     # with several ranks --frames-in-flight frames are in flight (FrameSharder pipeline mode), each with its own
@@ -262,8 +321,8 @@ def main(argv=None):
         ad_counts = torch.zeros(max(args.frames, 1), dtype=torch.int32, pin_memory=True)
 
     def launch_sampled(buf, prm, hdr=None):
-        """the stereo / panorama / blurred / supersampled launch (_stereo, _pano, _mb, _ss): the whole frame and its HDR when hdr
-        is given, else this rank's tiles"""
+        """the stereo / defocused / panorama / blurred / supersampled launch (_stereo, _dof, _pano, _mb, _ss): the whole frame and its
+        HDR when hdr is given, else this rank's tiles"""
         whole = hdr is not None
         tiles = () if whole else (args.tile_rows, rank, world)
         if stereo is not None:
@@ -271,7 +330,10 @@ def main(argv=None):
             when = (proj if proj is not None else rrt.Projection("pinhole"), stereo, state["t"], state["cam"])
             launch(buf, ew, eh, ss, *tiles, *when, tex, fx, prm, **({"hdr": hdr} if whole else {}))
             return
-        if pano:
+        if dof_k:
+            launch = rrt.launch_raymarch_dof if whole else rrt.launch_raymarch_dof_tiles
+            when = (state["times"], state["cams"], dof_points, state["focus"])
+        elif pano:
             launch, when = (rrt.launch_raymarch_pano if whole else rrt.launch_raymarch_pano_tiles), (proj, state["t"], state["cam"])
         elif mb > 1:
             launch, when = (rrt.launch_raymarch_mb if whole else rrt.launch_raymarch_mb_tiles), (state["times"], state["cams"])
@@ -303,7 +365,7 @@ def main(argv=None):
         k = state["k"]
         if chooser is not None:
             prms[slot].path_policy = chooser.policy(k)
-        if pano or mb > 1 or ss > 1 or stereo is not None:
+        if pano or mb > 1 or ss > 1 or stereo is not None or dof_k:
             launch_sampled(buf, prms[slot])
         else:
             rrt.launch_raymarch_tiles(buf, w, h, args.tile_rows, rank, world, state["t"], state["cam"], tex, fx, prms[slot])
@@ -353,6 +415,10 @@ def main(argv=None):
             state["table"] = nwin.table_id(sim_t)
         if path is not None:
             state["cam"] = path.camera_at(path_t)
+        if dof_k:
+            if mb <= 1:
+                state["times"], state["cams"] = [sim_t] * dof_k, [state["cam"]] * dof_k
+            state["focus"] = args.focus if args.focus is not None else hole_distance(state["cam"])
         frame = render_glowed() if glow is not None else (render_adaptive() if adaptive is not None else fs.step())
         if sink and frame is not None:
             deliver(frame)
@@ -380,6 +446,8 @@ def main(argv=None):
                           "projection": args.projection, "fov_deg": proj.fov_deg if pano else None,
                           "vfov_deg": proj.vfov_deg if args.projection == "equirect" else None,
                           "stereo": stereo.info() if stereo is not None else None,
+                          "dof": ({"aperture": args.dof, "focus": args.focus if args.focus is not None else "hole",
+                                   "samples": dof_k} if dof_k else None),
                           "adaptive": ({"threshold": adaptive.threshold,
                                         "refined_fraction": float(ad_counts[:args.frames].double().mean()) / (w * h) if args.frames > 0 else 0.0}
                                        if adaptive is not None else None),

@@ -1,0 +1,294 @@
+"""Depth-of-field frames (rrt_launch_raymarch_dof*, include/rrt.h) on the GPU against their definition.  The anchor: a lens point
+(+-lx, 0) is an eye of the already-pinned off-axis stereo pair, bytes and HDR bits.  A general lens point's march is tied to the
+pinned pinhole path (a 2x2 pinhole frame at the restated origin whose centre pixel looks exactly along the restated D).  K samples
+are the documented tree over K separate one-sample launches of the (s w) x (s h) frame; zero lens points are the motion-blurred
+frame; tiles, streams, graphs and both drivers.  Small frames: 48x27 and 64x36, s <= 2.  torch is only the device-memory plumbing."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import lens_ref as lr
+import projection_ref as pr
+from conftest import same_bits
+from test_gpu_motion_blur import block_sums, render_mb
+from test_gpu_stereo import _probe_hdr, all_fx, render_stereo
+from test_gpu_supersample import _host, _tree, _zeros, render_ss, tone_map
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+
+
+@pytest.fixture(scope="module")
+def ctx(sky):
+    import torch
+    assert torch.cuda.is_available(), "the -m gpu tests need a GPU"
+    import relativisticraytracer_amd as rrt
+    tex = rrt.SkyTexture(sky)
+    yield rrt, tex
+    tex.destroy()
+
+
+def render_dof(rrt, tex, w, h, s, times, cams, lens, focus, fx, prm, stream=None):
+    """the depth-of-field frame: (rgba8, hdr), both (h, w, 4) bottom-up"""
+    import torch
+    out, hdr = _zeros(h * w * 4, torch.uint8), _zeros(h * w * 4, torch.float32)
+    if stream is not None:
+        torch.cuda.synchronize()                # the buffers were cleared on the default stream
+    rrt.launch_raymarch_dof(out, w, h, s, times, cams, lens, focus, tex, fx, prm, stream=stream, hdr=hdr)
+    return _host(out, (h, w, 4)), _host(hdr, (h, w, 4))
+
+
+def samples(rrt, n, step=0.35, t0=1.0, dt=0.05, aperture=1.5):
+    """n distinct (time, camera, lens point) samples: the default camera sliding along its right vector, a rotated spiral"""
+    a = rrt.CameraState.default().as_array()
+    cams = [rrt.CameraState([a[0][i] + np.float32(step * k) * a[2][i] for i in range(3)], a[1], a[2], a[3]) for k in range(n)]
+    lens = rrt.lens_points(aperture, n, 0.3) if n > 1 else np.array([[0.21, -0.13]], np.float32)
+    return [t0 + dt * k for k in range(n)], cams, lens
+
+
+@pytest.mark.parametrize("s", [1, 2])
+def test_a_horizontal_lens_point_is_the_stereo_eye(ctx, s):
+    """the anchor.  K = 1, lens point (+-0.5, 0), focus 12 == the right / left half of the side-by-side pinhole stereo frame at
+    base 1.0 and convergence 12: bytes and HDR bits, every effect on (lens distortion and vignette included), spin 0 and 0.9,
+    strict and FMAD, nudged rays"""
+    rrt, tex = ctx
+    w, h = 48, 27
+    cam, fx = rrt.CameraState.default(), all_fx(rrt)
+    st, proj = rrt.Stereo("side-by-side", 1.0, 12.0), rrt.Projection("pinhole")
+    for spin, arith, nudge in ((0.0, 0, 0), (0.9, 0, 0), (0.9, 2, 0), (0.0, 2, 0), (0.9, 0, 3), (0.9, 2, 3)):
+        prm = rrt.RenderParams(spin=spin, arith_mode=arith, nudge_ulps=nudge, nudge_seed=7)
+        ref8, ref = render_stereo(rrt, tex, w, h, s, proj, st, 1.0, cam, fx, prm)
+        assert ref8[..., :3].std() > 5.0
+        for lx, half in ((-0.5, slice(0, w)), (0.5, slice(w, 2 * w))):
+            got8, got = render_dof(rrt, tex, w, h, s, [1.0], [cam], [(lx, 0.0)], 12.0, fx, prm)
+            assert np.array_equal(got8, ref8[:, half]) and same_bits(got, ref[:, half]), (s, spin, arith, nudge, lx)
+        assert not np.array_equal(ref8[:, :w], ref8[:, w:])                  # the eyes differ: the lens point matters
+
+
+def test_a_general_lens_point_marches_the_pinned_pinhole_path(ctx):
+    """K = 1, s = 1, (lx, ly) both non-zero, lens distortion and vignette off: 128 random pixels' HDR == the 2x2 pinhole probe's from
+    lens_ref's origin along its D, bit for bit -- spin 0 and 0.9, strict and FMAD, nudged rays; bloom and CA on"""
+    rrt, tex = ctx
+    rng = np.random.default_rng(20261018)
+    cam = rrt.CameraState.default()
+    W, H, t = 64, 36, 1.0
+    fx = all_fx(rrt, False)
+    for (lx, ly, z), (spin, arith, nudge) in (((0.37, -0.21, 12.0), (0.9, 0, 0)), ((-0.6, 0.45, 30.0), (0.0, 2, 0)),
+                                              ((0.37, 0.3, 60.0), (0.9, 2, 3)), ((-0.25, -0.5, 8.0), (0.9, 0, 3))):
+        prm = rrt.RenderParams(spin=spin, arith_mode=arith, nudge_ulps=nudge, nudge_seed=5)
+        probe_prm = rrt.RenderParams(spin=spin, arith_mode=arith)
+        _, hdr = render_dof(rrt, tex, W, H, 1, [t], [cam], [(lx, ly)], z, fx, prm)
+        o, D = lr.ray(W, H, cam.as_array(), lx, ly, z)
+        assert not np.array_equal(o.view(np.uint32), cam.as_array()[0].view(np.uint32))
+        look = D
+        ok = np.all(D != 0, axis=-1)
+        if nudge:
+            ys, xs = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
+            look = pr.nudge(pr.normalize(D), nudge, 5, xs, ys)               # the virtual pixel feeds the hash
+            ok &= np.all(pr.normalize(look).view(np.uint32) == look.view(np.uint32), axis=-1) & np.all(look != 0, axis=-1)
+        cand = np.argwhere(ok)
+        assert len(cand) >= 128, len(cand)
+        pick = cand[rng.choice(len(cand), 128, replace=False)]
+        want = _probe_hdr(rrt, tex, t, cam, [(o, look[y, x]) for y, x in pick], fx, probe_prm)
+        got = np.stack([hdr[H - 1 - y, x, :3] for y, x in pick])
+        bad = ~((got.view(np.uint32) == want.view(np.uint32)) | ((got == 0) & (want == 0))).all(-1)
+        assert not bad.any(), (lx, ly, z, spin, arith, nudge, int(bad.sum()), pick[bad][:4].tolist())
+        assert np.ptp(got) > 0.05                                            # a real picture among the pixels
+
+
+def expected_mean(rrt, tex, w, h, s, times, cams, lens, focus, fx, prm):
+    """tests/test_gpu_motion_blur.py's expected_mean with the lens: the tree over the block sums of K separate K = 1, s = 1 launches
+    of the (s w) x (s h) frame, times 1 / (s^2 K)"""
+    sums = [block_sums(render_dof(rrt, tex, s * w, s * h, 1, [t], [c], [xy], focus, fx, prm)[1], w, h, s)
+            for t, c, xy in zip(times, cams, lens)]
+    mean = _tree(sums) * np.float32(1.0 / (s * s * len(times)))
+    assert mean.dtype == np.float32
+    return mean
+
+
+def check_tree(po, rrt, tex, w, h, s, times, cams, lens, focus, fx, prm, what):
+    mean = expected_mean(rrt, tex, w, h, s, times, cams, lens, focus, fx, prm)
+    got8, got_hdr = render_dof(rrt, tex, w, h, s, times, cams, lens, focus, fx, prm)
+    assert np.isfinite(mean).all(), what
+    assert same_bits(got_hdr[..., :3], mean), (what, int((got_hdr[..., :3] != mean).sum()))
+    assert np.all(got_hdr[..., 3] == 1.0), what
+    want8 = tone_map(po, mean)
+    assert np.array_equal(got8, want8), (what, int((got8 != want8).any(-1).sum()))
+    return got8
+
+
+# (w, h, volumetrics, arith, spin, every effect): 27, 36 and 25 rows and 45 columns are no multiple of the 8x8 wave tile
+TREE_CASES = [(48, 27, 1, 0, 0.9, False), (64, 36, 1, 2, 0.9, True), (45, 25, 0, 0, 0.0, False), (48, 27, 0, 2, 0.9, True)]
+
+
+@pytest.mark.parametrize("case", TREE_CASES, ids=lambda c: "%dx%d_vol%d_arith%d" % c[:4])
+def test_k4_is_the_tree_over_separate_samples(ctx, po, case):
+    """K = 4 with distinct times, cameras and lens points, s = 1 and 2, media on and off, strict and FMAD, ragged sizes; and the
+    defocused frame differs from the zero-aperture frame"""
+    rrt, tex = ctx
+    w, h, vol, arith, spin, every = case
+    fx = all_fx(rrt) if every else rrt.CameraEffects()
+    prm = rrt.RenderParams(spin=spin, volumetrics=vol, arith_mode=arith)
+    times, cams, lens = samples(rrt, 4)
+    for s in (1, 2):
+        got8 = check_tree(po, rrt, tex, w, h, s, times, cams, lens, 20.0, fx, prm, (case, s))
+    sharp8, _ = render_dof(rrt, tex, w, h, 2, times, cams, np.zeros((4, 2), np.float32), 20.0, fx, prm)
+    assert not np.array_equal(got8, sharp8)
+
+
+def test_k16_is_the_tree_over_separate_samples(ctx, po):
+    rrt, tex = ctx
+    times, cams, lens = samples(rrt, 16, step=0.1, dt=0.01)
+    check_tree(po, rrt, tex, 48, 27, 1, times, cams, lens, 35.0, all_fx(rrt), rrt.RenderParams(spin=0.9), "K16")
+
+
+def test_identities(ctx):
+    """zero lens points at K = 4 are rrt_launch_raymarch_mb at any focus; K = 1 with a zero lens point is rrt_launch_raymarch_ss;
+    K equal samples are K = 1; s = 1, K = 1 is rrt_launch_raymarch"""
+    import torch
+    rrt, tex = ctx
+    w, h = 48, 27
+    fx = all_fx(rrt)
+    for arith, vol, nudge in ((0, 1, 0), (2, 1, 0), (0, 0, 3)):
+        prm = rrt.RenderParams(spin=0.9, volumetrics=vol, arith_mode=arith, nudge_ulps=nudge, nudge_seed=3)
+        times, cams, lens = samples(rrt, 4)
+        for s in (1, 2):
+            ref8, ref = render_mb(rrt, tex, w, h, s, times, cams, fx, prm)
+            for zeros, focus in (([(0.0, 0.0)] * 4, 12.0), ([(-0.0, 0.0), (0.0, -0.0), (-0.0, -0.0), (0.0, 0.0)], 0.37)):
+                got8, got = render_dof(rrt, tex, w, h, s, times, cams, zeros, focus, fx, prm)
+                assert np.array_equal(got8, ref8) and same_bits(got, ref), ("mb", arith, vol, nudge, s, focus)
+            ref8, ref = render_ss(rrt, tex, w, h, s, times[1], cams[1], fx, prm)
+            got8, got = render_dof(rrt, tex, w, h, s, times[1:2], cams[1:2], [(0.0, 0.0)], 5.0, fx, prm)
+            assert np.array_equal(got8, ref8) and same_bits(got, ref), ("ss", arith, vol, nudge, s)
+            one8, one = render_dof(rrt, tex, w, h, s, times[2:3], cams[2:3], lens[2:3], 9.0, fx, prm)
+            assert not np.array_equal(one8, render_dof(rrt, tex, w, h, s, times[2:3], cams[2:3], [(0.0, 0.0)], 9.0, fx, prm)[0])
+            for n in (2, 4, 16):
+                got8, got = render_dof(rrt, tex, w, h, s, times[2:3] * n, cams[2:3] * n, np.repeat(lens[2:3], n, 0), 9.0, fx, prm)
+                assert np.array_equal(got8, one8) and same_bits(got, one), ("equal", arith, vol, nudge, s, n)
+        plain = _zeros(h * w * 4, torch.uint8)
+        rrt.launch_raymarch(plain, w, h, times[0], cams[0], tex, fx, prm)
+        got8, _ = render_dof(rrt, tex, w, h, 1, times[:1], cams[:1], [(0.0, 0.0)], 12.0, fx, prm)
+        assert np.array_equal(got8, _host(plain, (h, w, 4))), (arith, vol, nudge)
+
+
+def test_noise_table_window(ctx):
+    """a table whose window holds only some of the samples' times gives the bytes of no table (every sample hashes arithmetically);
+    a table that holds all of them gives the same bytes too"""
+    rrt, tex = ctx
+    w, h = 64, 36
+    cam, fx = rrt.CameraState.default(), rrt.CameraEffects()
+    times, cams = [1.0, 1.5, 2.0, 2.5], [cam] * 4
+    lens = rrt.lens_points(0.3, 4)
+    ref8, ref = render_dof(rrt, tex, w, h, 2, times, cams, lens, 12.0, fx, rrt.RenderParams(spin=0.9))
+    for t0, t1 in ((0.0, 1.7), (1.2, 3.0), (0.0, 4.0)):
+        nt = rrt.NoiseTable.window(t0, t1, 0)
+        try:
+            got8, got = render_dof(rrt, tex, w, h, 2, times, cams, lens, 12.0, fx, rrt.RenderParams(spin=0.9, noise_table=nt.id))
+            assert np.array_equal(got8, ref8) and same_bits(got, ref), (t0, t1)
+        finally:
+            nt.destroy()
+
+
+def test_tile_shards_assemble_to_the_full_frame(ctx):
+    import torch
+    rrt, tex = ctx
+    w, h = 45, 27
+    fx, prm = all_fx(rrt), rrt.RenderParams(spin=0.9)
+    times, cams, lens = samples(rrt, 4)
+    for s in (1, 2):
+        full, _ = render_dof(rrt, tex, w, h, s, times, cams, lens, 15.0, fx, prm)
+        for n, tr in ((2, 8), (3, 16), (3, 8), (2, 16)):
+            rows = [rrt.tile_shard_rows(h, tr, k, n) for k in range(n)]
+            stride = ((max(max(rows), 1) * w * 4) + 255) & ~255
+            tiles = _zeros(stride * n, torch.uint8)
+            for k in range(n):
+                rrt.launch_raymarch_dof_tiles(tiles.data_ptr() + k * stride, w, h, s, tr, k, n, times, cams, lens, 15.0, tex, fx, prm)
+            frame = _zeros(h * w * 4, torch.uint8)
+            rrt.assemble_all_tiles(frame, tiles, stride, w, h, tr, n)
+            assert np.array_equal(_host(frame, (h, w, 4)), full), (s, n, tr)
+
+
+def test_ignored_params_side_stream_and_graph_capture(ctx):
+    """a workspace, a path policy, pool rounds, chains and a tile-order object change nothing; a launch on a side stream and a
+    captured graph's replays give the same bytes"""
+    import torch
+    rrt, tex = ctx
+    w, h = 64, 36
+    fx = rrt.CameraEffects()
+    times, cams, lens = samples(rrt, 4)
+    ref8, ref = render_dof(rrt, tex, w, h, 2, times, cams, lens, 12.0, fx, rrt.RenderParams(spin=0.9))
+    ws, order = rrt.Workspace(64 << 20), rrt.TileOrder()
+    try:
+        prm = rrt.RenderParams(spin=0.9, workspace=ws.id, tile_order=order.id, path_policy=2, pool_rounds=3, pass_chains=2)
+        got8, got = render_dof(rrt, tex, w, h, 2, times, cams, lens, 12.0, fx, prm)
+        assert np.array_equal(got8, ref8) and same_bits(got, ref)
+        assert order.info()["launches"] == 0
+    finally:
+        ws.destroy()
+        order.destroy()
+    prm = rrt.RenderParams(spin=0.9)
+    side = torch.cuda.Stream()
+    got8, got = render_dof(rrt, tex, w, h, 2, times, cams, lens, 12.0, fx, prm, stream=side)
+    assert np.array_equal(got8, ref8) and same_bits(got, ref)
+    b, bh = _zeros(h * w * 4, torch.uint8), _zeros(h * w * 4, torch.float32)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        rrt.launch_raymarch_dof(b, w, h, 2, times, cams, lens, 12.0, tex, fx, prm, hdr=bh)
+    for _ in range(2):
+        b.zero_()
+        bh.zero_()
+        graph.replay()
+        assert np.array_equal(_host(b, (h, w, 4)), ref8) and same_bits(_host(bh, (h, w, 4)), ref)
+
+
+@pytest.mark.parametrize("extra", [["--dof", "0.3", "--focus", "12", "--dof-samples", "4"],
+                                   ["--dof", "0.3", "--focus", "12", "--dof-samples", "4", "--motion-blur", "4", "--supersample", "2"],
+                                   ["--dof", "0.5", "--dof-samples", "2"]],
+                         ids=["dof", "dof_blur_ss", "focus_hole"])
+def test_drivers_write_the_defocused_frames(ctx, tmp_path, extra):
+    """rrt_headless and headless.py write the same file and report the settings, and every frame == launch_raymarch_dof with the
+    documented pairing: sample m at the shutter's time m (or the frame's instant) through lens point bitrev_K(m) of
+    lens_points(aperture, K); --focus hole is the camera's distance to the origin"""
+    import torch
+    from relativisticraytracer_amd import build, headless
+    from relativisticraytracer_amd import camera_paths as cp
+    rrt, tex = ctx
+    exe = build.build_headless()
+    w, h, frames = 48, 27, 2
+    a, b = tmp_path / "cpp.rgba", tmp_path / "py.rgba"
+    args = ["--width", str(w), "--height", str(h), "--frames", str(frames), "--path", "0", "--spin", "0.9", "--all-effects"] + extra
+    blur, ss = "--motion-blur" in extra, 2 if "--supersample" in extra else 1
+    aperture = float(extra[1])
+    K = 2 if aperture == 0.5 else 4
+    want_focus = 12.0 if "--focus" in extra else "hole"
+    metas = []
+    for cmd, out in (([exe], a), ([sys.executable, "-m", "relativisticraytracer_amd.headless"], b)):
+        r = subprocess.run(cmd + args + ["--out", str(out)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        metas.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    for m in metas:
+        assert m["dof"]["samples"] == K and m["dof"]["focus"] == want_focus and abs(m["dof"]["aperture"] - aperture) < 1e-6, m
+        assert m["supersample"] == ss and m["motion_blur"] == (4 if blur else 1), m
+    assert open(a, "rb").read() == open(b, "rb").read()
+    data = np.fromfile(a, np.uint8).reshape(frames, h, w, 4)
+    path = cp.CameraPath(0)
+    fx = rrt.CameraEffects(useChromaticAberration=True)
+    lens = rrt.lens_points(aperture, K)[[lr.bit_reverse(m, K) for m in range(K)]]
+    for k in range(1, frames + 1):
+        t, pt = cp.recording_clock(k)
+        cam = path.camera_at(pt)
+        if blur:
+            times, sub_p = cp.motion_clock(k, 24, 0.5, K)
+            cams = [path.camera_at(p) for p in sub_p]
+        else:
+            times, cams = [t] * K, [cam] * K
+        focus = 12.0 if "--focus" in extra else headless.hole_distance(cam)
+        buf = _zeros(h * w * 4, torch.uint8)
+        rrt.launch_raymarch_dof(buf, w, h, ss, times, cams, lens, focus, tex, fx, rrt.RenderParams(spin=0.9))
+        assert np.array_equal(_host(buf, (h, w, 4)), data[k - 1]), k
+    assert not np.array_equal(data[0], data[1])
