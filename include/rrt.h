@@ -677,6 +677,84 @@ int rrt_lens_ray(int width, int height, int x, int y, const rrt_camera* cam, flo
  * non-finite rotation, n_samples outside {1, 2, 4, 8, 16}. */
 int rrt_lens_points(float aperture, int n_samples, float rotation_rad, float* xy_out /* 2 n_samples */);
 
+/* ---- exposure control: a frame's linear HDR scaled by 2^ev before the tone map, ev given by the caller (manual) or metered from the
+ *      frame and adapted over time on the device (auto); no counterpart in the reference, whose every frame is tone-mapped at the
+ *      fixed EXPOSURE = 0.8f (raymarcher.cu:164-166).  That constant stays inside the tone map; this pass scales what goes into it.
+ *      H is the w x h float4 frame the _ss / _mb / _dof / _pano / _stereo / _adaptive launches write to d_hdr_rgba32f (any layout:
+ *      the pass works per pixel and meters the whole buffer).  The pass writes the scaled HDR (rrt_launch_glow's input), the
+ *      tone-mapped RGBA8 frame, or both.  Every step is integer, binary32 or binary64 arithmetic in the order written, uncontracted:
+ *        1. luma and bin: luma = (r*0.2126f + g*0.7152f) + b*0.0722f (the glow's); u = the bits of luma; the pixel is METERED iff
+ *           0 < u < 0x7f800000, i.e. luma is positive and finite, subnormals included.  Zero (the hole's shadow, sub-samples outside a
+ *           fisheye disc), negative, NaN and infinite lumas are not metered.  bin = clamp((int)(u >> 20) - 888, 0, 255): the float's 8
+ *           exponent bits and top 3 mantissa bits, 256 bins over the 32 octaves [2^-16, 2^16), 8 per octave, linear inside an octave
+ *           (888 = (127 - 16) * 8); darker and brighter lumas fall into bins 0 and 255.  c_b is the count of bin b: exact integers,
+ *           whatever order the pixels are counted in;
+ *        2. bin centres, in double on the host (rrt_exposure_bin_ev returns them; the device is handed the table):
+ *           L_b = (e - 127) + log2(1 + (j + 0.5) / 8) with e = (b + 888) >> 3 and j = (b + 888) & 7;
+ *        3. resolve: N = sum c_b (uint64); lo = N * low_permille / 1000 and hi = N * high_permille / 1000 (integer floor); remove lo
+ *           counts from the lowest bins upwards and hi from the highest downwards, cutting bins partially: the retained counts are r_b,
+ *           M = sum r_b >= 1; m = (sum over ascending b, from 0.0, of (double)r_b * L_b) / (double)M in binary64;
+ *           target = clamp((float)(log2_key - m) + ev, min_ev, max_ev) with log2_key = log2((double)key) from the host, the sum in
+ *           binary32, clamp(x, lo, hi) = x < lo ? lo : (x > hi ? hi : x);
+ *        4. state (caller-owned device memory, carried from frame to frame: S.ev, S.frames): if N == 0, S.ev is unchanged -- except
+ *           on the first frame (S.frames == 0), where it becomes clamp(ev, min_ev, max_ev); else if S.frames == 0, S.ev = target; else
+ *           alpha = target > S.ev ? adapt_up : adapt_down and S.ev = S.ev + (target - S.ev) * alpha in binary32, the multiply and
+ *           then the add.  Then S.frames += 1 (it stops at 2^32 - 1);
+ *        5. scale = rrt_expf(S.ev * 0.693147182f), the portable exp of csrc/rrt_math.h.  In manual mode there is no metering and no
+ *           state: the host computes scale from the settings' ev with the same function.  rrt_expf(0) == 1.0f: EV 0 is the identity;
+ *        6. apply: out.rgb = H.rgb * scale, out.a = H.a; the bytes are that value tone-mapped as raymarcher.cu:164-173 and stored
+ *           as RGBA8 at H's pixel index.
+ *      So manual EV 0 gives the bytes the launch that wrote H stored, and H's bits.
+ *      Auto mode is zero -> meter -> resolve -> apply on the caller's stream, a linear chain; manual mode the apply pass alone.  No
+ *      synchronisation, no allocation, no memset: a launch can be captured into a hipGraph, and a replay advances the state.
+ *      d_scratch: rrt_exposure_scratch_bytes() bytes or more, 16-byte aligned, the caller's; rrt_launch_exposure_reset must have run
+ *      on it once before the first auto launch (it zeroes the state and loads the table of L_b), and starts a sequence over.  Layout:
+ *        offset RRT_EXPOSURE_HIST_OFFSET (0):      uint32 c_b[256], the last launch's histogram
+ *        offset RRT_EXPOSURE_STATE_OFFSET (1024):  float S.ev; uint32 S.frames; float scale; float target; uint64 N; double m;
+ *                                                  32 reserved bytes -- target, N and m are the last launch's (target and m read 0
+ *                                                  when N == 0); a caller reads S.ev with its own 4-byte copy
+ *        offset RRT_EXPOSURE_TABLE_OFFSET (1088):  double L_b[256] ---- */
+#define RRT_EXPOSURE_MANUAL 0
+#define RRT_EXPOSURE_AUTO 1
+#define RRT_EXPOSURE_HIST_OFFSET 0
+#define RRT_EXPOSURE_STATE_OFFSET 1024
+#define RRT_EXPOSURE_TABLE_OFFSET 1088
+typedef struct rrt_exposure {
+    uint32_t struct_size;    /* sizeof(rrt_exposure): rrt_exposure_default sets it; any other value is RRT_ERR_ABI_MISMATCH */
+    int32_t mode;            /* RRT_EXPOSURE_* */
+    float ev;                /* manual: the EV; auto: the compensation added to the metered EV.  Finite */
+    float key;               /* auto: the luminance the retained pixels' log-average is brought to, > 0 and finite */
+    int32_t low_permille;    /* auto: the darkest and the brightest share of the metered pixels left out of the average, in 1/1000; */
+    int32_t high_permille;   /*   each >= 0, their sum < 1000 */
+    float min_ev, max_ev;    /* auto: the target's range, min_ev <= max_ev, both finite */
+    float adapt_up;          /* auto: the share of the way to a HIGHER target (a darker frame) taken per frame, in (0, 1] */
+    float adapt_down;        /* auto: the same towards a lower target (a brighter frame); rrt_exposure_adapt makes them from seconds */
+} rrt_exposure;
+/* manual, ev 0, key 0.5, 400 / 20 per mille, ev in [-8, 8], both adapt factors 1 (no smoothing): a look, not a measurement.  The low
+ * cut is large because most of a typical frame is dark sky, which would otherwise pull the exposure up until the disk clips. */
+int rrt_exposure_default(rrt_exposure* e);
+/* bin `bin`'s centre L_b in log2 units, 0 <= bin < 256.  Host only. */
+int rrt_exposure_bin_ev(int bin, double* ev_out);
+/* the adapt factor of a time constant: *alpha_out = (float)(1 - exp(-dt / tau)), in double, for a frame interval dt and a time
+ * constant tau in the same unit; tau == 0 gives 1.  Host only.  RRT_ERR_INVALID_ARGUMENT: a negative or non-finite dt or tau. */
+int rrt_exposure_adapt(double dt, double tau, float* alpha_out);
+/* the bytes of the caller-owned scratch of an auto launch (the layout above; it does not depend on the frame).  Host only. */
+int rrt_exposure_scratch_bytes(size_t* bytes);
+/* Host only: the histogram c_b of a w x h float4 frame in HOST memory, from the source the meter pass runs.
+ * RRT_ERR_INVALID_ARGUMENT: NULL pointers, width or height <= 0, width*height >= 2^31. */
+int rrt_exposure_meter_host(const float* hdr_rgba32f_host, int width, int height, uint32_t* hist_out /* 256 */);
+/* zeroes the scratch's histogram and state and loads the table (one kernel).  RRT_ERR_INVALID_ARGUMENT, before any device call: a
+ * NULL or not 16-byte aligned d_scratch, scratch_bytes below the query's. */
+int rrt_launch_exposure_reset(void* d_scratch, size_t scratch_bytes, void* stream);
+/* The exposed frame of d_hdr_in (width*height float4): its RGBA8 into d_out_rgba8 (may be NULL), its scaled HDR into d_hdr_out (may
+ * be NULL; may be d_hdr_in itself: in place).  Manual mode accepts a NULL d_scratch.  RRT_ERR_INVALID_ARGUMENT, before any device
+ * call: a NULL e or d_hdr_in, both outputs NULL, d_hdr_in or d_hdr_out not 16-byte aligned, d_out_rgba8 not 4-byte aligned, a
+ * d_hdr_out that overlaps d_hdr_in without being equal to it, width or height <= 0, width*height >= 2^31, a setting outside the
+ * range the struct states, and in auto mode a NULL, misaligned or too small d_scratch; RRT_ERR_ABI_MISMATCH for another
+ * struct_size.  Full frames only: no _tiles form (the meter needs the whole frame). */
+int rrt_launch_exposure(void* d_out_rgba8 /* may be NULL */, float* d_hdr_out /* may be NULL */, const float* d_hdr_in, int width,
+                        int height, const rrt_exposure* e, void* d_scratch, size_t scratch_bytes, void* stream);
+
 /* ---- which path a rank's share takes while several frames of a sequence are in flight (host only; no GPU call) ----
  * New in this repo (the reference renders one frame at a time on one GPU: src/main.cpp:505-529).  A launch of <= 1.5 M rays
  * with a pool can take the three-pass path (RRT_PATH_AUTO) or the single kernel (RRT_PATH_SINGLE); under frames in flight the

@@ -20,7 +20,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import RRTError, rrt_camera, rrt_debug_outputs, rrt_effects, rrt_glow, rrt_params, rrt_projection  # noqa: F401
-from ._lib import rrt_adaptive, rrt_stereo  # noqa: F401
+from ._lib import rrt_adaptive, rrt_exposure, rrt_stereo  # noqa: F401
 
 __all__ = ["CameraState", "CameraEffects", "RenderParams", "SkyTexture", "Workspace", "NoiseTable", "launch_raymarch",
            "set_launch_defaults", "get_launch_defaults",
@@ -31,6 +31,8 @@ __all__ = ["CameraState", "CameraEffects", "RenderParams", "SkyTexture", "Worksp
            "AdaptiveSettings", "adaptive_scratch_bytes", "adaptive_mask", "launch_raymarch_adaptive",
            "Stereo", "stereo_default", "stereo_ray", "launch_raymarch_stereo", "launch_raymarch_stereo_tiles",
            "launch_raymarch_dof", "launch_raymarch_dof_tiles", "lens_ray", "lens_points",
+           "ExposureSettings", "exposure_scratch_bytes", "exposure_bin_ev", "exposure_adapt", "exposure_meter_host",
+           "launch_exposure_reset", "launch_exposure",
            "tile_shard_rows",
            "launch_raymarch_debug", "RRTError", "device_count", "abi_version", "TileOrder", "TileMap",
            "probe_tile_costs", "balance_tiles", "launch_raymarch_tilemap", "assemble_all_tilemap", "clock_probe", "clock_probe_ghz",
@@ -158,6 +160,30 @@ class AdaptiveSettings(rrt_adaptive):
 
     def info(self):
         return {"threshold": self.threshold}
+
+
+EXPOSURE_MANUAL, EXPOSURE_AUTO = 0, 1                         # include/rrt.h: RRT_EXPOSURE_*
+EXPOSURE_MODES = {"manual": EXPOSURE_MANUAL, "auto": EXPOSURE_AUTO}
+EXPOSURE_HIST_OFFSET, EXPOSURE_STATE_OFFSET, EXPOSURE_TABLE_OFFSET = 0, 1024, 1088      # RRT_EXPOSURE_*_OFFSET: the scratch's layout
+
+
+class ExposureSettings(rrt_exposure):
+    """Exposure settings (include/rrt.h: rrt_exposure): mode "manual" | "auto" (or RRT_EXPOSURE_*), ev (the manual EV, or the
+    compensation in auto mode), key, low_permille / high_permille (the shares of the metered pixels left out of the average),
+    min_ev / max_ev, adapt_up / adapt_down (exposure_adapt makes them from time constants).  Defaults == rrt_exposure_default."""
+
+    def __init__(self, **kw):
+        super().__init__()
+        _lib.check(_lib.load().rrt_exposure_default(C.byref(self)), "rrt_exposure_default")
+        for k, v in kw.items():
+            if not hasattr(self, k):
+                raise AttributeError(k)
+            setattr(self, k, EXPOSURE_MODES.get(v, v) if k == "mode" else v)
+
+    def info(self):
+        return {"mode": "auto" if self.mode == EXPOSURE_AUTO else "manual", "ev": self.ev, "key": self.key,
+                "low_permille": self.low_permille, "high_permille": self.high_permille, "min_ev": self.min_ev, "max_ev": self.max_ev,
+                "adapt_up": self.adapt_up, "adapt_down": self.adapt_down}
 
 
 PROJ_PINHOLE, PROJ_EQUIRECT, PROJ_FISHEYE = 0, 1, 2          # include/rrt.h: RRT_PROJ_*
@@ -858,6 +884,67 @@ def launch_glow(d_out, hdr, w, h, glow, scratch, stream=None, scratch_bytes=None
         scratch_bytes = scratch.numel() * scratch.element_size() if hasattr(scratch, "element_size") else glow_scratch_bytes(w, h, glow)
     _lib.check(_lib.load().rrt_launch_glow(_ptr(d_out), _ptr(hdr), w, h, C.byref(glow), _ptr(scratch), scratch_bytes,
                                            _stream(stream)), "rrt_launch_glow")
+
+
+def exposure_scratch_bytes():
+    """bytes of the scratch an auto launch_exposure needs (rrt_exposure_scratch_bytes): the histogram at EXPOSURE_HIST_OFFSET, the
+    state (float ev, uint32 frames, float scale, float target, uint64 N, double m) at EXPOSURE_STATE_OFFSET, the bin centres at
+    EXPOSURE_TABLE_OFFSET"""
+    n = C.c_size_t(0)
+    _lib.check(_lib.load().rrt_exposure_scratch_bytes(C.byref(n)), "rrt_exposure_scratch_bytes")
+    return n.value
+
+
+def exposure_bin_ev(b):
+    """bin b's centre in log2 units, a Python float (rrt_exposure_bin_ev, host only)"""
+    v = C.c_double(0.0)
+    _lib.check(_lib.load().rrt_exposure_bin_ev(int(b), C.byref(v)), "rrt_exposure_bin_ev")
+    return v.value
+
+
+def exposure_adapt(dt, tau):
+    """the adapt factor (float32) of a time constant tau at a frame interval dt: (float)(1 - exp(-dt / tau)), 1 for tau == 0
+    (rrt_exposure_adapt, host only)"""
+    a = C.c_float(0.0)
+    _lib.check(_lib.load().rrt_exposure_adapt(float(dt), float(tau), C.byref(a)), "rrt_exposure_adapt")
+    return np.float32(a.value)
+
+
+def exposure_meter_host(hdr):
+    """the 256-bin log-luminance histogram (uint32) of an (h, w, 4) float32 frame on the host (rrt_exposure_meter_host): from the
+    source the device's meter pass runs"""
+    a = np.ascontiguousarray(hdr, np.float32)
+    if a.ndim != 3 or a.shape[2] != 4:
+        raise ValueError(f"expected an (h, w, 4) float32 frame, got {a.shape}")
+    hist = np.zeros(256, np.uint32)
+    _lib.check(_lib.load().rrt_exposure_meter_host(a.ctypes.data_as(C.c_void_p), a.shape[1], a.shape[0],
+                                                   hist.ctypes.data_as(C.c_void_p)), "rrt_exposure_meter_host")
+    return hist
+
+
+def _scratch_size(scratch, scratch_bytes, default):
+    if scratch_bytes is not None:
+        return scratch_bytes
+    if scratch is None:
+        return 0
+    return scratch.numel() * scratch.element_size() if hasattr(scratch, "element_size") else default()
+
+
+def launch_exposure_reset(scratch, stream=None, scratch_bytes=None):
+    """zero the exposure state in `scratch` (device memory of exposure_scratch_bytes() bytes or more) and load the bin centres
+    (rrt_launch_exposure_reset): once before the first auto launch_exposure, and again to start a sequence over"""
+    _lib.check(_lib.load().rrt_launch_exposure_reset(_ptr(scratch), _scratch_size(scratch, scratch_bytes, exposure_scratch_bytes),
+                                                     _stream(stream)), "rrt_launch_exposure_reset")
+
+
+def launch_exposure(d_out, hdr_out, hdr_in, w, h, exposure, scratch=None, stream=None, scratch_bytes=None):
+    """The exposed frame of `hdr_in` (include/rrt.h: rrt_launch_exposure; w*h*4 float32 on the device, as the sampled launches write
+    it): hdr_in.rgb * 2^ev tone-mapped into d_out (w*h*4 uint8, may be None) and / or as linear HDR into hdr_out (may be None, may
+    be hdr_in: in place -- launch_glow's input).  Manual mode takes the EV from the settings; auto mode meters the frame and adapts
+    the EV kept in `scratch` (launch_exposure_reset first), all on the device.  Nothing synchronises."""
+    _lib.check(_lib.load().rrt_launch_exposure(_ptr(d_out), _ptr(hdr_out), _ptr(hdr_in), w, h, C.byref(exposure), _ptr(scratch),
+                                               _scratch_size(scratch, scratch_bytes, exposure_scratch_bytes), _stream(stream)),
+               "rrt_launch_exposure")
 
 
 def tile_shard_rows(h, tile_rows, shard, n_shards):

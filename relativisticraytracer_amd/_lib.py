@@ -85,6 +85,12 @@ class rrt_stereo(C.Structure):
                 ("pole_merge_from_deg", C.c_float), ("pole_merge_to_deg", C.c_float)]
 
 
+class rrt_exposure(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("ev", C.c_float), ("key", C.c_float),
+                ("low_permille", C.c_int32), ("high_permille", C.c_int32), ("min_ev", C.c_float), ("max_ev", C.c_float),
+                ("adapt_up", C.c_float), ("adapt_down", C.c_float)]
+
+
 # every symbol include/rrt.h declares: (name, restype, argtypes)
 _vp, _i, _f, _ull = C.c_void_p, C.c_int, C.c_float, C.c_ulonglong
 _cam, _fx, _prm = C.POINTER(rrt_camera), C.POINTER(rrt_effects), C.POINTER(rrt_params)
@@ -164,6 +170,13 @@ SYMBOLS = [
                                            _vp]),
     ("rrt_lens_ray", _i, [_i, _i, _i, _i, _cam, _f, _f, _f, C.POINTER(_f * 3), C.POINTER(_f * 3)]),
     ("rrt_lens_points", _i, [_f, _i, _f, C.POINTER(_f)]),
+    ("rrt_exposure_default", _i, [C.POINTER(rrt_exposure)]),
+    ("rrt_exposure_bin_ev", _i, [_i, C.POINTER(C.c_double)]),
+    ("rrt_exposure_adapt", _i, [C.c_double, C.c_double, C.POINTER(_f)]),
+    ("rrt_exposure_scratch_bytes", _i, [C.POINTER(C.c_size_t)]),
+    ("rrt_exposure_meter_host", _i, [_vp, _i, _i, _vp]),
+    ("rrt_launch_exposure_reset", _i, [_vp, C.c_size_t, _vp]),
+    ("rrt_launch_exposure", _i, [_vp, _vp, _vp, _i, _i, C.POINTER(rrt_exposure), _vp, C.c_size_t, _vp]),
     ("rrt_tile_shard_rows", _i, [_i, _i, _i, _i, C.POINTER(_i)]),
     ("rrt_assemble_tiles", _i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     ("rrt_assemble_all_tiles", _i, [_vp, _vp, C.c_size_t, _i, _i, _i, _i, _vp]),

@@ -31,6 +31,14 @@
 //                                              camera's distance to the origin); single kernel, no pool; with --motion-blur M > 1
 //                                              the samples are the shutter's sub-frames (K = M); pinhole only, not with --stereo
 //                                              or --adaptive)
+//                [--exposure EV | --auto-exposure [KEY]] [--exposure-speed UP DOWN] [--exposure-range MIN MAX]
+//                [--exposure-percentiles LOW HIGH]   (exposure control: the frame renders into an HDR buffer as with --glow,
+//                                              rrt_launch_exposure writes its RGBA8 -- with --glow it scales the HDR in place and the
+//                                              glow follows.  --exposure alone: EV stops, manual; --auto-exposure: metered per frame
+//                                              and adapted on the device (KEY default 0.5), --exposure then the compensation;
+//                                              UP / DOWN: time constants in seconds towards a higher / lower EV, turned into
+//                                              per-frame factors with 1 / fps (default 0 0: no smoothing); LOW HIGH in per mille;
+//                                              one GPU only, single kernel, no pool; with every frame kind)
 //
 // Noise tables: the reference's simTime runs without bound (main.cpp:515) and a table's size grows with the times
 // it covers, so each device keeps ONE table over a window of the clock that fits --noise-table-gib (default 2;
@@ -258,6 +266,10 @@ int main(int argc, char** argv) {
     rrt_glow glow;                 // --glow INTENSITY (+ --glow-radius / -threshold / -lobes): rrt_launch_glow on every frame
     rrt_glow_default(&glow);
     bool use_glow = false;
+    rrt_exposure exposure;         // --exposure EV / --auto-exposure [KEY] (+ --exposure-speed / -range / -percentiles): rrt_launch_exposure
+    rrt_exposure_default(&exposure);
+    bool use_exposure = false, exposure_opts = false;
+    double exposure_tau[2] = {0.0, 0.0};     // --exposure-speed UP DOWN, seconds
     int projection = RRT_PROJ_PINHOLE;   // --projection: the camera (rrt_launch_raymarch_pano* for equirect / fisheye)
     float fov = 0.0f, vfov = 0.0f;       // --fov / --vfov DEG (0: not given -- the kind's default, rrt_projection_default)
     int stereo_layout = 0;               // --stereo: RRT_STEREO_* (0: mono); rrt_launch_raymarch_stereo*
@@ -329,6 +341,34 @@ int main(int argc, char** argv) {
             else if (a == "--glow-threshold") glow.threshold = v;
             else if (v == (float)(int)v) glow.lobes = (int)v;
             else { fprintf(stderr, "--glow-lobes 1 | 2 | 3 | 4\n"); return 2; }
+        }
+        else if (a == "--exposure" || a == "--exposure-speed" || a == "--exposure-range" || a == "--exposure-percentiles") {
+            double v[2] = {0.0, 0.0};
+            const int n = a == "--exposure" ? 1 : 2;
+            for (int j = 0; j < n; ++j) {
+                const char* m = i + 1 < argc ? argv[++i] : "";
+                char* end = nullptr;
+                v[j] = strtod(m, &end);
+                if (end == m || *end != 0 || !std::isfinite(v[j])) { fprintf(stderr, "usage: %s: %s\n", a.c_str(), n == 1 ? "a number" : "two numbers"); return 2; }
+            }
+            if (a == "--exposure") { exposure.ev = (float)v[0]; use_exposure = true; }
+            else {
+                exposure_opts = true;
+                if (a == "--exposure-speed") { exposure_tau[0] = v[0]; exposure_tau[1] = v[1]; }
+                else if (a == "--exposure-range") { exposure.min_ev = (float)v[0]; exposure.max_ev = (float)v[1]; }
+                else if (v[0] == (double)(int)v[0] && v[1] == (double)(int)v[1]) { exposure.low_permille = (int)v[0]; exposure.high_permille = (int)v[1]; }
+                else { fprintf(stderr, "usage: --exposure-percentiles LOW HIGH: whole numbers in per mille\n"); return 2; }
+            }
+        }
+        else if (a == "--auto-exposure") {  // the key is optional: the next argument unless it is another option
+            use_exposure = true;
+            exposure.mode = RRT_EXPOSURE_AUTO;
+            if (i + 1 < argc && strncmp(argv[i + 1], "--", 2) != 0) {
+                const char* m = argv[++i];
+                char* end = nullptr;
+                exposure.key = strtof(m, &end);
+                if (end == m || *end != 0) { fprintf(stderr, "usage: --auto-exposure [KEY]: a luminance > 0 (default 0.5)\n"); return 2; }
+            }
         }
         else if (a == "--projection") {
             const std::string m = i + 1 < argc ? argv[++i] : "";
@@ -413,6 +453,23 @@ int main(int argc, char** argv) {
             return 2;
         }
     }
+    // exposure control needs the whole frame's HDR on one device (the meter sees every pixel; rrt_launch_exposure has no _tiles form)
+    if (!use_exposure && exposure_opts) {
+        fprintf(stderr, "usage: --exposure-speed / --exposure-range / --exposure-percentiles need --exposure EV | --auto-exposure [KEY]\n"); return 2;
+    }
+    if (use_exposure) {
+        if (gpus > 1 || force_collective) { fprintf(stderr, "usage: --exposure / --auto-exposure: one GPU only (--gpus 1)\n"); return 2; }
+        // the settings' ranges are rrt_launch_exposure's own refusals, stated here before any device is touched
+        const bool speeds = rrt_exposure_adapt(1.0 / (double)fps, exposure_tau[0], &exposure.adapt_up) == RRT_OK &&
+                            rrt_exposure_adapt(1.0 / (double)fps, exposure_tau[1], &exposure.adapt_down) == RRT_OK &&
+                            exposure.adapt_up > 0.0f && exposure.adapt_down > 0.0f;
+        if (!speeds || !std::isfinite(exposure.key) || !(exposure.key > 0.0f) || !(exposure.min_ev <= exposure.max_ev) ||
+            exposure.low_permille < 0 || exposure.high_permille < 0 || (long long)exposure.low_permille + exposure.high_permille >= 1000) {
+            fprintf(stderr, "usage: --auto-exposure KEY > 0, --exposure-speed UP DOWN >= 0 (seconds), --exposure-range MIN MAX with MIN <= MAX, "
+                            "--exposure-percentiles LOW HIGH >= 0 with LOW + HIGH < 1000\n");
+            return 2;
+        }
+    }
     // panoramas: the spans are checked by the host query (the launch's own refusals), the combinations the kernels lack up front
     const bool pano = projection != RRT_PROJ_PINHOLE;
     rrt_projection proj;
@@ -482,7 +539,7 @@ int main(int argc, char** argv) {
         }
     }
     // a supersampled launch is always the single kernel in the static order (include/rrt.h): no pool, no path choice, no tile order
-    if (supersample > 1 || motion > 1 || use_glow || pano || use_stereo || use_dof) { workspace_gib = 0; path_window = -1; tile_order = 0; }
+    if (supersample > 1 || motion > 1 || use_glow || use_exposure || pano || use_stereo || use_dof) { workspace_gib = 0; path_window = -1; tile_order = 0; }
     int n_dev = 0, rc;
     if ((rc = rrt_device_count(&n_dev)) != RRT_OK) return fail("no GPU", rc);
     if (gpus > n_dev) { fprintf(stderr, "rrt_headless: --gpus %d but %d device(s) visible\n", gpus, n_dev); return 2; }
@@ -585,8 +642,20 @@ int main(int argc, char** argv) {
     void* gathered[kMaxSlots] = {};
     void* frame[kMaxSlots] = {};
     void* host[kMaxSlots] = {};
-    void* hdr[kMaxSlots] = {};         // --glow: each slot's linear frame and the glow's scratch
+    void* hdr[kMaxSlots] = {};         // --glow / --exposure: each slot's linear frame; the glow's scratch
     void* glow_scratch[kMaxSlots] = {};
+    // --auto-exposure: ONE state for the sequence.  The frames' renders overlap on their slots' streams; their exposure passes run in
+    // frame order, each behind the event its predecessor recorded
+    void* exposure_scratch = nullptr;
+    size_t exposure_bytes = 0;
+    hipEvent_t exposed = nullptr;
+    const bool auto_exposure = use_exposure && exposure.mode == RRT_EXPOSURE_AUTO;
+    if (auto_exposure) {
+        if ((rc = rrt_exposure_scratch_bytes(&exposure_bytes)) != RRT_OK) return fail("exposure scratch", rc);
+        HIPCHK(hipMalloc(&exposure_scratch, exposure_bytes));
+        HIPCHK(hipEventCreateWithFlags(&exposed, hipEventDisableTiming));
+        if ((rc = rrt_launch_exposure_reset(exposure_scratch, exposure_bytes, dev[0].stream[0])) != RRT_OK) return fail("exposure reset", rc);
+    }
     void* ad_scratch[kMaxSlots] = {};  // --adaptive: each slot's list, and the pinned word its count is copied to
     void* ad_count[kMaxSlots] = {};
     size_t ad_bytes = 0;
@@ -597,7 +666,8 @@ int main(int argc, char** argv) {
     for (int s = 0; s < kSlots; ++s) {
         HIPCHK(hipMalloc(&gathered[s], shard_stride * gpus));
         HIPCHK(hipMalloc(&frame[s], frame_bytes));
-        if (use_glow) { HIPCHK(hipMalloc(&hdr[s], frame_bytes * sizeof(float))); HIPCHK(hipMalloc(&glow_scratch[s], glow_bytes)); }
+        if (use_glow || use_exposure) HIPCHK(hipMalloc(&hdr[s], frame_bytes * sizeof(float)));
+        if (use_glow) HIPCHK(hipMalloc(&glow_scratch[s], glow_bytes));
         if (use_adaptive) { HIPCHK(hipMalloc(&ad_scratch[s], ad_bytes)); HIPCHK(hipHostMalloc(&ad_count[s], 4, hipHostMallocDefault)); }
         HIPCHK(hipEventCreateWithFlags(&done[s], hipEventDisableTiming));
     }
@@ -745,10 +815,16 @@ int main(int argc, char** argv) {
                     return (int)RRT_ERR_HIP;
                 return st;
             };
-            if (use_glow) {     // one device (checked above): the slot's HDR through launch_sampled, then the glow on the same stream
+            if (use_glow || use_exposure) {     // one device (checked above): the slot's HDR through launch_sampled, then the post passes on the same stream
                 float* lin = static_cast<float*>(hdr[slot]);
                 rc = use_adaptive ? launch_adaptive(lin) : launch_sampled(false, lin);
-                if (rc == RRT_OK) rc = rrt_launch_glow(dst, lin, w, h, &glow, glow_scratch[slot], glow_bytes, D.stream[slot]);
+                if (rc == RRT_OK && use_exposure) {     // the bytes -- or, in front of the glow, the scaled HDR in place
+                    if (auto_exposure) HIPCHK(hipStreamWaitEvent(D.stream[slot], exposed, 0));
+                    rc = rrt_launch_exposure(use_glow ? nullptr : dst, use_glow ? lin : nullptr, lin, w, h, &exposure, exposure_scratch,
+                                             exposure_bytes, D.stream[slot]);
+                    if (auto_exposure) HIPCHK(hipEventRecord(exposed, D.stream[slot]));
+                }
+                if (rc == RRT_OK && use_glow) rc = rrt_launch_glow(dst, lin, w, h, &glow, glow_scratch[slot], glow_bytes, D.stream[slot]);
             }
             else if (use_adaptive) rc = launch_adaptive(nullptr);
             else if (use_stereo || use_dof || pano || motion > 1 || supersample > 1) rc = launch_sampled(collective, nullptr);
@@ -811,6 +887,17 @@ int main(int argc, char** argv) {
                  glow.threshold, glow.intensity);
         glow_json = buf;
     }
+    std::string exposure_json = "null";
+    if (use_exposure) {     // the final EV: one 4-byte read of the state, after the last frame
+        float final_ev = exposure.ev;
+        if (auto_exposure) HIPCHK(hipMemcpy(&final_ev, static_cast<const uint8_t*>(exposure_scratch) + RRT_EXPOSURE_STATE_OFFSET, 4, hipMemcpyDeviceToHost));
+        char buf[400];
+        snprintf(buf, sizeof(buf), "{\"mode\": \"%s\", \"ev\": %.9g, \"key\": %.9g, \"low_permille\": %d, \"high_permille\": %d, \"min_ev\": %.9g, "
+                 "\"max_ev\": %.9g, \"adapt_up\": %.9g, \"adapt_down\": %.9g, \"final_ev\": %.9g}", auto_exposure ? "auto" : "manual", exposure.ev,
+                 exposure.key, exposure.low_permille, exposure.high_permille, exposure.min_ev, exposure.max_ev, exposure.adapt_up,
+                 exposure.adapt_down, final_ev);
+        exposure_json = buf;
+    }
     const char* proj_name = projection == RRT_PROJ_EQUIRECT ? "equirect" : (projection == RRT_PROJ_FISHEYE ? "fisheye" : "pinhole");
     char fov_json[32] = "null", vfov_json[32] = "null";
     if (pano) snprintf(fov_json, sizeof(fov_json), "%g", proj.fov_deg);
@@ -854,12 +941,14 @@ int main(int argc, char** argv) {
            "\"path\": \"%s\", \"spin\": %g, \"arith_mode\": \"%s\", \"noise_tables\": {\"builds\": %d, \"table_frames\": %d, "
            "\"arith_frames\": %d, \"coarsest_coverage\": %d, \"peak_bytes\": %zu, \"budget_bytes\": %zu}, \"tile_order\": %s, \"collective\": \"%s\", "
            "\"path_choice\": %s, \"supersample\": %d, \"motion_blur\": %d, \"shutter\": %g, \"glow\": %s, "
-           "\"projection\": \"%s\", \"fov_deg\": %s, \"vfov_deg\": %s, \"stereo\": %s, \"dof\": %s, \"adaptive\": %s, \"march_cache\": %s}\n",
+           "\"projection\": \"%s\", \"fov_deg\": %s, \"vfov_deg\": %s, \"stereo\": %s, \"dof\": %s, \"adaptive\": %s, \"exposure\": %s, "
+           "\"march_cache\": %s}\n",
            frames, w, h, gpus, dt, frames / dt, (double)frames * w * h / dt / 1e6, path_name, spin,
            arith == RRT_ARITH_FAST ? "fast" : (arith == RRT_ARITH_FMAD ? "fmad" : "strict"),
            table_builds, table_frames, arith_frames, coarsest, table_peak, table_budget, dev[0].order[0] ? "true" : "false",
            collective ? "rccl grouped send/recv gather" : "none", choice.c_str(), supersample, motion, shutter, glow_json.c_str(),
-           proj_name, fov_json, vfov_json, stereo_json.c_str(), dof_json.c_str(), adaptive_json.c_str(), cache_json.c_str());
+           proj_name, fov_json, vfov_json, stereo_json.c_str(), dof_json.c_str(), adaptive_json.c_str(), exposure_json.c_str(),
+           cache_json.c_str());
 
     for (int d = 0; d < gpus; ++d) {
         Device& D = dev[d];
@@ -878,6 +967,8 @@ int main(int argc, char** argv) {
         rrt_sky_destroy(D.sky);
     }
     HIPCHK(hipSetDevice(0));
+    (void)hipFree(exposure_scratch);
+    if (exposed) (void)hipEventDestroy(exposed);
     for (int s = 0; s < kSlots; ++s) {
         (void)hipFree(gathered[s]); (void)hipFree(frame[s]); (void)hipFree(hdr[s]); (void)hipFree(glow_scratch[s]);
         (void)hipFree(ad_scratch[s]);

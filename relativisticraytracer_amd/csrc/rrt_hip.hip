@@ -9,7 +9,7 @@
  *
  * Sections (round 5: one 3 100-line file became four)
  *   rrt_kernels.h      the kernels and the structures they share with the host (included below: a kernel and its launch
- *                      site share a translation unit)
+ *                      site share a translation unit); rrt_glow.h, rrt_exposure.h: the two post passes' kernels
  *   this file          host helpers (the five handle tables, path choice and launch logic, the march cache's device object, what
  *                      the entry points share) in ONE anonymous namespace, then the C ABI in ONE extern "C" block, grouped by
  *                      object in the order include/rrt.h declares them; the C++ launch_raymarch at the end
@@ -110,6 +110,7 @@ struct SkyObject {
 /* ------------------------------------------------------------------ device code (kernels, kernel arguments, pool layout) */
 #include "rrt_kernels.h"
 #include "rrt_glow.h"                   /* the glow's kernels (rrt_launch_glow) */
+#include "rrt_exposure.h"               /* exposure control: the bin rule and the resolve walk (host and device), its kernels */
 
 struct WorkspaceObject {
     uint8_t* d_base; size_t bytes; int device;
@@ -1172,6 +1173,57 @@ int launch_glow(uchar4* out, const float4* hdr, int width, int height, const rrt
     return RRT_OK;
 }
 
+/* ---- exposure control (rrt_launch_exposure): the settings' checks, the bin centres, the launches */
+static_assert(sizeof(rrt_exposure) == 40, "rrt_exposure layout");
+static_assert(RRT_EXPOSURE_HIST_OFFSET == kExposureHistOffset && RRT_EXPOSURE_STATE_OFFSET == kExposureStateOffset &&
+              RRT_EXPOSURE_TABLE_OFFSET == kExposureTableOffset, "the scratch layout include/rrt.h documents");
+int check_exposure(const rrt_exposure* e) {
+    if (!e) return RRT_ERR_INVALID_ARGUMENT;
+    if (e->struct_size != (uint32_t)sizeof(rrt_exposure)) {
+        snprintf(g_hip_err, sizeof(g_hip_err), "rrt_exposure.struct_size %u, this library's is %zu: recompile against include/rrt.h",
+                 e->struct_size, sizeof(rrt_exposure));
+        return RRT_ERR_ABI_MISMATCH;
+    }
+    if (e->mode != RRT_EXPOSURE_MANUAL && e->mode != RRT_EXPOSURE_AUTO) return RRT_ERR_INVALID_ARGUMENT;
+    if (!std::isfinite(e->ev) || !std::isfinite(e->key) || !(e->key > 0.0f)) return RRT_ERR_INVALID_ARGUMENT;
+    if (e->low_permille < 0 || e->high_permille < 0 || (int64_t)e->low_permille + (int64_t)e->high_permille >= 1000)
+        return RRT_ERR_INVALID_ARGUMENT;
+    if (!std::isfinite(e->min_ev) || !std::isfinite(e->max_ev) || !(e->min_ev <= e->max_ev)) return RRT_ERR_INVALID_ARGUMENT;
+    if (!(e->adapt_up > 0.0f && e->adapt_up <= 1.0f) || !(e->adapt_down > 0.0f && e->adapt_down <= 1.0f)) return RRT_ERR_INVALID_ARGUMENT;
+    return RRT_OK;
+}
+bool exposure_scratch_ok(const void* scratch, size_t bytes) {
+    return scratch && !(reinterpret_cast<uintptr_t>(scratch) & 15) && bytes >= kExposureScratchBytes;
+}
+
+/* auto: zero -> meter -> resolve -> apply, a linear chain on `st` (the histogram is zeroed by zero_words, like the adaptive list's
+ * counter: no memset node); manual: the apply pass alone, the scale computed here by the function the resolve pass runs */
+int launch_exposure(uchar4* out8, float4* hdr_out, const float4* hdr_in, int width, int height, const rrt_exposure& e, void* scratch,
+                    hipStream_t st) {
+    const size_t n = (size_t)width * (size_t)height;
+    const dim3 apply_grid((unsigned)((n + 255) / 256));
+    if (e.mode == RRT_EXPOSURE_MANUAL) {
+        hipLaunchKernelGGL(exposure_apply, apply_grid, dim3(256), 0, st, out8, hdr_out, hdr_in, n,
+                           static_cast<const ExposureState*>(nullptr), rrt_expf(e.ev * 0.693147182f));
+        RRT_HIP(hipGetLastError());
+        return RRT_OK;
+    }
+    uint8_t* base = static_cast<uint8_t*>(scratch);
+    unsigned* hist = reinterpret_cast<unsigned*>(base + kExposureHistOffset);
+    ExposureState* state = reinterpret_cast<ExposureState*>(base + kExposureStateOffset);
+    const double* table = reinterpret_cast<const double*>(base + kExposureTableOffset);
+    ExposureMeter s;
+    s.log2_key = std::log2((double)e.key);
+    s.ev = e.ev; s.min_ev = e.min_ev; s.max_ev = e.max_ev; s.adapt_up = e.adapt_up; s.adapt_down = e.adapt_down;
+    s.low_permille = e.low_permille; s.high_permille = e.high_permille;
+    hipLaunchKernelGGL(zero_words, dim3(1), dim3(256), 0, st, reinterpret_cast<uint4*>(hist), kExposureBins * sizeof(uint32_t) / 16);
+    hipLaunchKernelGGL(exposure_meter, dim3(exposure_meter_groups(n)), dim3(kMeterThreads), 0, st, hdr_in, n, hist);
+    hipLaunchKernelGGL(exposure_resolve, dim3(1), dim3(64), 0, st, hist, state, table, s);
+    hipLaunchKernelGGL(exposure_apply, apply_grid, dim3(256), 0, st, out8, hdr_out, hdr_in, n, state, 0.0f);
+    RRT_HIP(hipGetLastError());
+    return RRT_OK;
+}
+
 /* ---- workspace counters (rrt_workspace_stats, _rounds) */
 hipError_t read_chain_counters(const WorkspaceObject& w, DeferCounters* out) {
     uint8_t raw[kMaxChains * kCounterStride];
@@ -2066,6 +2118,75 @@ int rrt_launch_glow(void* d_out_rgba8, const float* d_hdr_rgba32f, int width, in
     if (scratch_bytes < glow_scratch(p, width, height)) return RRT_ERR_INVALID_ARGUMENT;
     return launch_glow(static_cast<uchar4*>(d_out_rgba8), reinterpret_cast<const float4*>(d_hdr_rgba32f), width, height, g, p,
                        d_scratch, static_cast<hipStream_t>(stream));
+}
+
+int rrt_exposure_default(rrt_exposure* e) {
+    if (!e) return RRT_ERR_INVALID_ARGUMENT;
+    e->struct_size = (uint32_t)sizeof(rrt_exposure);
+    e->mode = RRT_EXPOSURE_MANUAL;
+    e->ev = 0.0f;
+    e->key = 0.5f;
+    e->low_permille = 400;
+    e->high_permille = 20;
+    e->min_ev = -8.0f;
+    e->max_ev = 8.0f;
+    e->adapt_up = 1.0f;
+    e->adapt_down = 1.0f;
+    return RRT_OK;
+}
+
+int rrt_exposure_bin_ev(int bin, double* ev_out) {
+    if (!ev_out || bin < 0 || bin >= kExposureBins) return RRT_ERR_INVALID_ARGUMENT;
+    *ev_out = exposure_bin_centre(bin);
+    return RRT_OK;
+}
+
+int rrt_exposure_adapt(double dt, double tau, float* alpha_out) {
+    if (!alpha_out || !std::isfinite(dt) || !std::isfinite(tau) || dt < 0.0 || tau < 0.0) return RRT_ERR_INVALID_ARGUMENT;
+    *alpha_out = tau == 0.0 ? 1.0f : (float)(1.0 - std::exp(-dt / tau));
+    return RRT_OK;
+}
+
+int rrt_exposure_scratch_bytes(size_t* bytes) {
+    if (!bytes) return RRT_ERR_INVALID_ARGUMENT;
+    *bytes = kExposureScratchBytes;
+    return RRT_OK;
+}
+
+int rrt_exposure_meter_host(const float* hdr_rgba32f_host, int width, int height, uint32_t* hist_out) {
+    if (!hdr_rgba32f_host || !hist_out || !glow_frame_ok(width, height)) return RRT_ERR_INVALID_ARGUMENT;
+    memset(hist_out, 0, kExposureBins * sizeof(uint32_t));
+    const size_t n = (size_t)width * (size_t)height;
+    for (size_t i = 0; i < n; ++i) {
+        const float* p = hdr_rgba32f_host + 4 * i;
+        const int b = exposure_bin(exposure_luma(p[0], p[1], p[2]));
+        if (b >= 0) ++hist_out[b];
+    }
+    return RRT_OK;
+}
+
+int rrt_launch_exposure_reset(void* d_scratch, size_t scratch_bytes, void* stream) {
+    if (!exposure_scratch_ok(d_scratch, scratch_bytes)) return RRT_ERR_INVALID_ARGUMENT;
+    ExposureTable t;
+    for (int b = 0; b < kExposureBins; ++b) t.ev[b] = exposure_bin_centre(b);
+    hipLaunchKernelGGL(exposure_reset, dim3(1), dim3(kExposureBins), 0, static_cast<hipStream_t>(stream),
+                       static_cast<uint8_t*>(d_scratch), t);
+    RRT_HIP(hipGetLastError());
+    return RRT_OK;
+}
+
+int rrt_launch_exposure(void* d_out_rgba8, float* d_hdr_out, const float* d_hdr_in, int width, int height, const rrt_exposure* e,
+                        void* d_scratch, size_t scratch_bytes, void* stream) {
+    const int rc = check_exposure(e);
+    if (rc) return rc;
+    if (!d_hdr_in || (!d_out_rgba8 && !d_hdr_out) || !glow_frame_ok(width, height)) return RRT_ERR_INVALID_ARGUMENT;
+    const uintptr_t in = reinterpret_cast<uintptr_t>(d_hdr_in), out = reinterpret_cast<uintptr_t>(d_hdr_out);
+    if (((in | out) & 15) || (reinterpret_cast<uintptr_t>(d_out_rgba8) & 3)) return RRT_ERR_INVALID_ARGUMENT;
+    const uintptr_t hdr_bytes = (uintptr_t)width * (uintptr_t)height * sizeof(float4);
+    if (out && out != in && out < in + hdr_bytes && in < out + hdr_bytes) return RRT_ERR_INVALID_ARGUMENT;    /* in place or apart */
+    if (e->mode == RRT_EXPOSURE_AUTO && !exposure_scratch_ok(d_scratch, scratch_bytes)) return RRT_ERR_INVALID_ARGUMENT;
+    return launch_exposure(static_cast<uchar4*>(d_out_rgba8), reinterpret_cast<float4*>(d_hdr_out),
+                           reinterpret_cast<const float4*>(d_hdr_in), width, height, *e, d_scratch, static_cast<hipStream_t>(stream));
 }
 
 int rrt_projection_default(int kind, rrt_projection* p) {

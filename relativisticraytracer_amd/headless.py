@@ -7,6 +7,7 @@
            [--stereo top-bottom|side-by-side [--stereo-base B] [--convergence Z] [--pole-merge FROM TO]]
            [--supersample 2 --adaptive [T]]
            [--dof APERTURE [--focus Z|hole] [--dof-samples K]]
+           [--exposure EV | --auto-exposure [KEY]] [--exposure-speed UP DOWN] [--exposure-range MIN MAX] [--exposure-percentiles LOW HIGH]
     python -m torch.distributed.run --nproc-per-node 8 -m relativisticraytracer_amd.headless ...
 
 Per frame k = 1..N it does what `main()` does while recording: advance the fixed 1/24 s clock
@@ -143,6 +144,21 @@ def main(argv=None):
                          "the frame's camera position to the origin")
     ap.add_argument("--dof-samples", type=int, choices=(1, 2, 4, 8, 16), default=None, metavar="K",
                     help="with --dof: lens samples per sub-sample (default 8); with --motion-blur M > 1 the samples are shared: K = M")
+    ap.add_argument("--exposure", type=float, default=None, metavar="EV",
+                    help="exposure control (rrt_launch_exposure): the frame renders into an HDR buffer as with --glow and is scaled by "
+                         "2^EV before the tone map; with --auto-exposure EV is the compensation.  One GPU only; single kernel, no pool; "
+                         "with every frame kind; with --glow the exposure scales the HDR in place and the glow follows")
+    ap.add_argument("--auto-exposure", type=float, nargs="?", const=0.5, default=None, metavar="KEY",
+                    help="meter every frame's log-luminance histogram on the device and adapt the EV so that the retained pixels' "
+                         "log-average lands on KEY (> 0, default 0.5)")
+    ap.add_argument("--exposure-speed", type=float, nargs=2, default=None, metavar=("UP", "DOWN"),
+                    help="with --auto-exposure: time constants in seconds towards a higher / lower EV, turned into per-frame factors "
+                         "with 1 / fps (rrt_exposure_adapt; default 0 0: no smoothing)")
+    ap.add_argument("--exposure-range", type=float, nargs=2, default=None, metavar=("MIN", "MAX"),
+                    help="with --auto-exposure: the metered EV's range (default -8 8)")
+    ap.add_argument("--exposure-percentiles", type=int, nargs=2, default=None, metavar=("LOW", "HIGH"),
+                    help="with --auto-exposure: the darkest / brightest share of the metered pixels left out of the average, in per "
+                         "mille (default 400 20)")
     ap.add_argument("--out", default=None, help="x.rgba (raw, bottom-up) | dir/ (PPM per frame) | x.mp4 (needs ffmpeg)")
     ap.add_argument("--init-timeout", type=float, default=300.0,
                     help="several ranks: seconds the process-group bring-up may take before the run exits non-zero with "
@@ -154,6 +170,12 @@ def main(argv=None):
     # the glow needs the whole frame's HDR on one GPU (no _tiles form); checked before any device is touched
     if args.glow is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         ap.error("--glow: one GPU only (WORLD_SIZE > 1)")
+    # exposure control needs the whole frame's HDR on one GPU as well (the meter sees every pixel; no _tiles form)
+    use_exposure = args.exposure is not None or args.auto_exposure is not None
+    if not use_exposure and (args.exposure_speed is not None or args.exposure_range is not None or args.exposure_percentiles is not None):
+        ap.error("--exposure-speed / --exposure-range / --exposure-percentiles need --exposure EV | --auto-exposure [KEY]")
+    if use_exposure and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        ap.error("--exposure / --auto-exposure: one GPU only (WORLD_SIZE > 1)")
     pano = args.projection != "pinhole"
     if not pano and (args.fov is not None or args.vfov is not None):
         ap.error("--fov / --vfov need --projection equirect | fisheye")
@@ -244,6 +266,23 @@ def main(argv=None):
         except rrt.RRTError:
             ap.error("--glow INTENSITY >= 0, --glow-radius R > 0 (a fraction of the height; widest lobe <= 1024 px), "
                      "--glow-threshold T >= 0")
+    exposure = None
+    if use_exposure:                # the settings' ranges are rrt_launch_exposure's own refusals, stated here before any device is touched
+        up, down = args.exposure_speed or (0.0, 0.0)
+        lo_ev, hi_ev = args.exposure_range or (-8.0, 8.0)
+        low, high = args.exposure_percentiles or (400, 20)
+        key = args.auto_exposure if args.auto_exposure is not None else 0.5
+        try:
+            alphas = [rrt.exposure_adapt(1.0 / args.fps, tau) for tau in (up, down)]
+        except rrt.RRTError:
+            alphas = [0.0, 0.0]
+        ok = all(math.isfinite(v) for v in (args.exposure or 0.0, key, lo_ev, hi_ev)) and key > 0.0 and lo_ev <= hi_ev
+        if not (ok and min(alphas) > 0.0 and low >= 0 and high >= 0 and low + high < 1000):
+            ap.error("--exposure EV finite, --auto-exposure KEY > 0, --exposure-speed UP DOWN >= 0 (seconds), --exposure-range MIN MAX with "
+                     "MIN <= MAX, --exposure-percentiles LOW HIGH >= 0 with LOW + HIGH < 1000")
+        exposure = rrt.ExposureSettings(mode="auto" if args.auto_exposure is not None else "manual", ev=args.exposure or 0.0, key=key,
+                                        low_permille=low, high_permille=high, min_ev=lo_ev, max_ev=hi_ev,
+                                        adapt_up=float(alphas[0]), adapt_down=float(alphas[1]))
 
     world = int(os.environ.get("WORLD_SIZE", "1")); rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -270,7 +309,7 @@ def main(argv=None):
     w, h = stereo.composite(ew, eh) if stereo is not None else (ew, eh)       # the frame that is sharded, gathered and written
     ss, mb = args.supersample, args.motion_blur
     # supersampled, blurred, glowed, panorama, stereo: single kernel, static order, no pool
-    single = ss > 1 or mb > 1 or glow is not None or pano or stereo is not None or dof_k > 0
+    single = ss > 1 or mb > 1 or glow is not None or exposure is not None or pano or stereo is not None or dof_k > 0
     # sample m looks through lens point bitrev_K(m): the spiral's radius grows with its index, the shutter's times with m
     dof_points = rrt.lens_points(args.dof, dof_k)[[bit_reverse(m, dof_k) for m in range(dof_k)]] if dof_k else None
     tex = rrt.SkyTexture(load_sky(args.sky) if args.sky else synthetic_sky())
@@ -309,14 +348,20 @@ def main(argv=None):
                              path_policy=int(os.environ.get("RRT_PATH_POLICY", "0"))) for j in range(n_slots)]
     path = camera_paths.CameraPath(args.path) if args.path >= 0 else None
     state = {"t": 0.0, "cam": rrt.CameraState.default(), "table": 0, "k": 0}
-    if glow is not None:        # one rank (checked above): the whole frame's HDR, the glow's scratch, the glowed frame
+    post = glow is not None or exposure is not None
+    if post:                    # one rank (checked above): the whole frame's HDR, the glow's scratch, the finished frame
         glow_hdr = torch.zeros(h * w * 4, dtype=torch.float32, device=dev)
-        glow_scratch = torch.empty(rrt.glow_scratch_bytes(w, h, glow), dtype=torch.uint8, device=dev)
         glow_frame = torch.zeros(h * w * 4, dtype=torch.uint8, device=dev)
+    if glow is not None:
+        glow_scratch = torch.empty(rrt.glow_scratch_bytes(w, h, glow), dtype=torch.uint8, device=dev)
+    exposure_scratch = None
+    if exposure is not None and exposure.mode == rrt.EXPOSURE_AUTO:     # the state the sequence's frames share
+        exposure_scratch = torch.empty(rrt.exposure_scratch_bytes(), dtype=torch.uint8, device=dev)
+        rrt.launch_exposure_reset(exposure_scratch)
     adaptive = None
     if args.adaptive is not None:   # one rank (checked above): the whole frame, the list's scratch, every frame's count
         adaptive = rrt.AdaptiveSettings(args.adaptive)
-        ad_frame = glow_frame if glow is not None else torch.zeros(h * w * 4, dtype=torch.uint8, device=dev)
+        ad_frame = glow_frame if post else torch.zeros(h * w * 4, dtype=torch.uint8, device=dev)
         ad_scratch = torch.empty(rrt.adaptive_scratch_bytes(w, h), dtype=torch.uint8, device=dev)
         ad_counts = torch.zeros(max(args.frames, 1), dtype=torch.int32, pin_memory=True)
 
@@ -342,13 +387,18 @@ def main(argv=None):
         launch(buf, w, h, ss, *tiles, *when, tex, fx, prm, **({"hdr": hdr} if whole else {}))
 
     def render_glowed():
-        """the frame through launch_sampled into glow_hdr, then the glow into glow_frame (bottom-up rows, not the tile layout)"""
+        """the frame through launch_sampled into glow_hdr, then the post passes into glow_frame (bottom-up rows, not the tile layout):
+        the exposure writes the bytes -- or, in front of the glow, the scaled HDR in place -- and the glow its own"""
         prms[0].noise_table = state["table"]
         if adaptive is not None:
             render_adaptive(glow_hdr)
         else:
             launch_sampled(glow_frame, prms[0], hdr=glow_hdr)
-        rrt.launch_glow(glow_frame, glow_hdr, w, h, glow, glow_scratch)
+        if exposure is not None:
+            rrt.launch_exposure(None if glow is not None else glow_frame, glow_hdr if glow is not None else None, glow_hdr, w, h,
+                                exposure, exposure_scratch)
+        if glow is not None:
+            rrt.launch_glow(glow_frame, glow_hdr, w, h, glow, glow_scratch)
         return glow_frame
 
     def render_adaptive(hdr=None):
@@ -419,7 +469,7 @@ def main(argv=None):
             if mb <= 1:
                 state["times"], state["cams"] = [sim_t] * dof_k, [state["cam"]] * dof_k
             state["focus"] = args.focus if args.focus is not None else hole_distance(state["cam"])
-        frame = render_glowed() if glow is not None else (render_adaptive() if adaptive is not None else fs.step())
+        frame = render_glowed() if post else (render_adaptive() if adaptive is not None else fs.step())
         if sink and frame is not None:
             deliver(frame)
     for frame in fs.drain():                # the frames still in flight, in order
@@ -432,6 +482,13 @@ def main(argv=None):
         dist.barrier()
     dog.disarm()
     dt = time.perf_counter() - t0
+    exposure_info = None
+    if exposure is not None:        # the final EV: one 4-byte read of the state, after the last frame
+        final_ev = exposure.ev
+        if exposure_scratch is not None:
+            o = rrt.EXPOSURE_STATE_OFFSET
+            final_ev = float(exposure_scratch[o:o + 4].view(torch.float32).cpu()[0])
+        exposure_info = dict(exposure.info(), final_ev=final_ev)
     if rank == 0:
         if sink:
             sink.close()
@@ -451,6 +508,7 @@ def main(argv=None):
                           "adaptive": ({"threshold": adaptive.threshold,
                                         "refined_fraction": float(ad_counts[:args.frames].double().mean()) / (w * h) if args.frames > 0 else 0.0}
                                        if adaptive is not None else None),
+                          "exposure": exposure_info,
                           "march_cache": rrt.march_cache_stats()}),
               flush=True)
     if world > 1:
