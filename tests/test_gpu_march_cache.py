@@ -11,18 +11,11 @@ import threading
 import numpy as np
 import pytest
 
-import march_ref as mr
+from march_cache_util import BUDGET, VIEWS, delta, frame, fresh, plain, uncached
 
 pytestmark = pytest.mark.gpu
 
-BUDGET = 2 << 30
 TIMES = (1.0, 1.0, 1.016, 1.032, 7.5, 31.9)
-VIEWS = {
-    "bench": mr.VIEWS["default"],
-    "key1": ((15.0, 3.0, -30.0), -20.0, -5.0),          # camera_paths.cpp:35
-    "skimmer": mr.VIEWS["skimmer"],
-    "in_disk": mr.VIEWS["in_disk"],
-}
 SIZES = ((61, 37), (157, 83))           # the second: ragged against the 8x8 wave tiles in both directions
 
 
@@ -37,39 +30,6 @@ def ctx(sky):
     rrt.march_cache_configure(BUDGET)
     nt.destroy()
     tex.destroy()
-
-
-def fresh(rrt):
-    """an empty cache with the tests' budget; returns the counters to take differences against"""
-    rrt.march_cache_release()
-    rrt.march_cache_configure(BUDGET)
-    return rrt.march_cache_stats()
-
-
-def delta(rrt, before):
-    now = rrt.march_cache_stats()
-    return {k: now[k] - before[k] for k in ("fills", "hits", "drops", "misses", "uncacheable")}
-
-
-def frame(torch, n_bytes, fn):
-    out = torch.zeros(n_bytes, dtype=torch.uint8, device="cuda")
-    torch.cuda.synchronize()              # the zeroing runs on the null stream; fn may launch on a non-blocking one
-    fn(out)
-    torch.cuda.synchronize()
-    return out.cpu().numpy()
-
-
-def uncached(rrt, fn):
-    """fn() with the cache off; the cache comes back EMPTY with the tests' budget (configure forgets the key)"""
-    rrt.march_cache_configure(0)
-    try:
-        return fn()
-    finally:
-        rrt.march_cache_configure(BUDGET)
-
-
-def plain(torch, rrt, w, h, t, cam, tex, fx, prm, stream=None):
-    return frame(torch, w * h * 4, lambda o: rrt.launch_raymarch(o, w, h, t, cam, tex, fx, prm, stream=stream))
 
 
 @pytest.mark.parametrize("spin", (0.9, 0.0))
