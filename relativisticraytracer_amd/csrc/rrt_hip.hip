@@ -858,16 +858,25 @@ int check_mb(const void* out, int width, int height, int s, int n_times, const f
     return RRT_OK;
 }
 
-/* launch_ss with n_times sub-frames, over the span of their times */
-int launch_mb(void* out, float4* hdr, int width, int height, int s, const RowMap& rows, int n_times, const float* times,
-              const rrt_camera* cams, rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm_in, hipStream_t st) {
+/* launch_ss with n sub-frames, over the span of their times; with Launch = LensLaunch (rrt_launch_raymarch_dof*), each through its
+ * own point (lens_xy[2k], lens_xy[2k + 1]) of a thin lens focused at `focus`.  A LensLaunch reads all 2n of lens_xy and divides by
+ * focus: its callers have passed check_dof (lens_xy non-null and finite, focus > 0); a MotionLaunch looks at neither. */
+template <class Launch = MotionLaunch>
+int launch_mb(void* out, float4* hdr, int width, int height, int s, const RowMap& rows, int n, const float* times,
+              const rrt_camera* cams, rrt_sky_t sky, const rrt_effects* fx, const rrt_params* prm_in, hipStream_t st,
+              const float* lens_xy = nullptr, float focus = 0.0f) {
+    constexpr bool kLens = std::is_same<Launch, LensLaunch>::value;
     float t_lo = times[0], t_hi = times[0];
-    MotionLaunch L;
-    MotionArgs& m = L.m;
+    Launch L;
+    auto& m = L.m;
     for (int k = 0; k < kMaxTimes; ++k) {           /* the unused slots repeat the last sub-frame: no uninitialised kernel argument */
-        const int j = k < n_times ? k : n_times - 1;
+        const int j = k < n ? k : n - 1;
         m.time[k] = times[j];
         m.cam[k] = cams[j];
+        if constexpr (kLens) {
+            m.lx[k] = lens_xy[2 * j]; m.ly[k] = lens_xy[2 * j + 1];
+            m.cx[k] = m.lx[k] / focus; m.cy[k] = m.ly[k] / focus;
+        }
         if (times[j] < t_lo) t_lo = times[j];
         if (times[j] > t_hi) t_hi = times[j];
     }
@@ -875,9 +884,10 @@ int launch_mb(void* out, float4* hdr, int width, int height, int s, const RowMap
     dim3 grid;
     const int rc = sampled_args(L.a, o, grid, out, width, height, s, rows, t_lo, t_hi, &cams[0], sky, fx, prm_in);
     if (rc || grid.y == 0) return rc;
-    L.s = s; L.n_times = n_times; L.hdr_out = hdr;
+    L.s = s; L.n = n; L.hdr_out = hdr;
     dispatch_kernel(L.a.spin != 0.0f, o.media, o.arith, [&](auto S, auto M, auto F) {
-        hipLaunchKernelGGL((motion_pixels<S, M, F>), grid, dim3(kWGThreads), 0, st, L);
+        if constexpr (kLens) hipLaunchKernelGGL((lens_pixels<S, M, F>), grid, dim3(kWGThreads), 0, st, L);
+        else hipLaunchKernelGGL((motion_pixels<S, M, F>), grid, dim3(kWGThreads), 0, st, L);
     });
     RRT_HIP(hipGetLastError());
     return RRT_OK;
@@ -892,34 +902,6 @@ int check_dof(const void* out, int width, int height, int s, int n_samples, cons
     if (rc != RRT_OK) return rc;
     for (int k = 0; k < 2 * n_samples; ++k)
         if (!std::isfinite(lens_xy[k])) return RRT_ERR_INVALID_ARGUMENT;
-    return RRT_OK;
-}
-
-/* launch_mb with a lens point per sub-frame */
-int launch_dof(void* out, float4* hdr, int width, int height, int s, const RowMap& rows, int n_samples, const float* times,
-               const rrt_camera* cams, const float* lens_xy, float focus, rrt_sky_t sky, const rrt_effects* fx,
-               const rrt_params* prm_in, hipStream_t st) {
-    float t_lo = times[0], t_hi = times[0];
-    LensLaunch L;
-    LensArgs& m = L.m;
-    for (int k = 0; k < kMaxTimes; ++k) {           /* the unused slots repeat the last sample: no uninitialised kernel argument */
-        const int j = k < n_samples ? k : n_samples - 1;
-        m.time[k] = times[j];
-        m.cam[k] = cams[j];
-        m.lx[k] = lens_xy[2 * j]; m.ly[k] = lens_xy[2 * j + 1];
-        m.cx[k] = m.lx[k] / focus; m.cy[k] = m.ly[k] / focus;
-        if (times[j] < t_lo) t_lo = times[j];
-        if (times[j] > t_hi) t_hi = times[j];
-    }
-    LaunchOpts o;
-    dim3 grid;
-    const int rc = sampled_args(L.a, o, grid, out, width, height, s, rows, t_lo, t_hi, &cams[0], sky, fx, prm_in);
-    if (rc || grid.y == 0) return rc;
-    L.s = s; L.n_samples = n_samples; L.hdr_out = hdr;
-    dispatch_kernel(L.a.spin != 0.0f, o.media, o.arith, [&](auto S, auto M, auto F) {
-        hipLaunchKernelGGL((lens_pixels<S, M, F>), grid, dim3(kWGThreads), 0, st, L);
-    });
-    RRT_HIP(hipGetLastError());
     return RRT_OK;
 }
 
@@ -2048,8 +2030,9 @@ int rrt_launch_raymarch_dof(void* d_out_rgba8, float* d_hdr_rgba32f, int width, 
                             const rrt_effects* fx, const rrt_params* prm, void* stream) {
     const int rc = check_dof(d_out_rgba8, width, height, samples_per_axis, n_samples, times, cams, lens_xy, focus, fx, prm);
     if (rc) return rc;
-    return launch_dof(d_out_rgba8, reinterpret_cast<float4*>(d_hdr_rgba32f), width, height, samples_per_axis, frame_rows(height),
-                      n_samples, times, cams, lens_xy, focus, sky, fx, prm, static_cast<hipStream_t>(stream));
+    return launch_mb<LensLaunch>(d_out_rgba8, reinterpret_cast<float4*>(d_hdr_rgba32f), width, height, samples_per_axis,
+                                 frame_rows(height), n_samples, times, cams, sky, fx, prm, static_cast<hipStream_t>(stream), lens_xy,
+                                 focus);
 }
 
 int rrt_launch_raymarch_dof_tiles(void* d_out_tiles, int width, int height, int samples_per_axis, int tile_rows, int shard, int n_shards,
@@ -2059,8 +2042,8 @@ int rrt_launch_raymarch_dof_tiles(void* d_out_tiles, int width, int height, int 
     if (rc) return rc;
     RowMap rows;
     if ((rc = shard_map(height, tile_rows, shard, n_shards, rows))) return rc;
-    return launch_dof(d_out_tiles, nullptr, width, height, samples_per_axis, rows, n_samples, times, cams, lens_xy, focus, sky, fx,
-                      prm, static_cast<hipStream_t>(stream));
+    return launch_mb<LensLaunch>(d_out_tiles, nullptr, width, height, samples_per_axis, rows, n_samples, times, cams, sky, fx, prm,
+                                 static_cast<hipStream_t>(stream), lens_xy, focus);
 }
 
 int rrt_lens_ray(int width, int height, int x, int y, const rrt_camera* cam, float lx, float ly, float focus, float origin_out[3],

@@ -177,6 +177,16 @@ __device__ __forceinline__ float nudge_component(float v, int K, unsigned seed, 
     const uint32_t out = m < 0 ? (0x80000000u | (uint32_t)(-m)) : (uint32_t)m;
     return rrt_u2f(out);
 }
+/* The conditioning probe (rrt_params.nudge_ulps; oracle: rrto_nudge_direction, the same function): every component of the unit
+ * direction of pixel (x, y) -- of the virtual, eye-local pixel in a sampled launch -- moves by a whole number of ulps in [-K, K]
+ * drawn from a hash of (x, y, seed, component).  K == 0, every frame but a probe's: nothing. */
+__device__ __forceinline__ void nudge_direction(v3& vel, int K, unsigned seed, int x, int y) {
+    if (__builtin_expect(K != 0, 0)) {
+        vel.x = nudge_component(vel.x, K, seed, x, y, 0u);
+        vel.y = nudge_component(vel.y, K, seed, x, y, 1u);
+        vel.z = nudge_component(vel.z, K, seed, x, y, 2u);
+    }
+}
 
 /* Primary ray of pixel (x, y): raymarcher.cu:20-34 (+ lens distortion, post_processing.h:19-24). */
 __device__ __forceinline__ void primary_ray(const FrameArgs& a, int x, int y, float& uvx, float& uvy, v3& p, v3& vel) {
@@ -192,13 +202,7 @@ __device__ __forceinline__ void primary_ray(const FrameArgs& a, int x, int y, fl
     const v3 cup = mk(a.cam.up[0], a.cam.up[1], a.cam.up[2]);
     p = mk(a.cam.pos[0], a.cam.pos[1], a.cam.pos[2]);
     vel = normalize(add(cfw, add(mul(crt, u_coord), mul(cup, v_coord))));
-    if (__builtin_expect(a.nudge_ulps != 0, 0)) {
-        /* conditioning probe (rrt_params.nudge_ulps; oracle: rrto_nudge_direction, the same function): every component of
-         * the unit direction moves by a whole number of ulps in [-K, K] drawn from a hash of (x, y, seed, component) */
-        vel.x = nudge_component(vel.x, a.nudge_ulps, a.nudge_seed, x, y, 0u);
-        vel.y = nudge_component(vel.y, a.nudge_ulps, a.nudge_seed, x, y, 1u);
-        vel.z = nudge_component(vel.z, a.nudge_ulps, a.nudge_seed, x, y, 2u);
-    }
+    nudge_direction(vel, a.nudge_ulps, a.nudge_seed, x, y);
 }
 
 /* Everything after the march up to the tone map: sky, composition, post-FX -- raymarcher.cu:124-161.  The ray's HDR value
@@ -772,7 +776,7 @@ struct MotionArgs { float time[kMaxTimes]; rrt_camera cam[kMaxTimes]; };
 struct MotionLaunch {                                   /* motion_pixels' one kernel argument */
     FrameArgs a;                                        /* the virtual frame, as supersample_pixels' */
     MotionArgs m;
-    int s, n_times;
+    int s, n;                                           /* n: the number of sub-frames */
     float4* hdr_out;
 };
 
@@ -788,13 +792,15 @@ __device__ __forceinline__ T motion_arg(size_t offset) {
     return T();
 #endif
 }
-#define RRT_MB_ARG(field) motion_arg<decltype(((MotionLaunch*)nullptr)->field)>(offsetof(MotionLaunch, field))
+/* in a kernel whose one argument is the struct it names `Launch` */
+#define RRT_SUB_ARG(field) motion_arg<decltype(((Launch*)nullptr)->field)>(offsetof(Launch, field))
 
 static_assert(kWGWaves == 1, "motion_pixels' LDS slots are sized for one-wave workgroups");
 template <bool SPIN, int MEDIA, int ARITH>
 __global__ __launch_bounds__(kWGThreads, (MEDIA != 0 ? RRT_MEDIA_WAVES : 1))      /* raymarch_pixels' register budget */
 void motion_pixels(const MotionLaunch L) {
-    __shared__ float part[4][3][kWGThreads];            /* levels 0..3: n_times <= 16 never stores level 4 */
+    using Launch = MotionLaunch;
+    __shared__ float part[4][3][kWGThreads];            /* levels 0..3: n <= 16 never stores level 4 */
     __shared__ volatile int where[3][kWGThreads];       /* vx, vy, the output index (-1: another lane of the pixel stores) */
     const int t = threadIdx.x;
     {
@@ -806,13 +812,13 @@ void motion_pixels(const MotionLaunch L) {
         where[2][t] = l.stores(s) ? l.out_row * (L.a.width / s) + l.x : -1;
     }
     v3 c;
-    for (int k = 0; k < L.n_times; ++k) {
+    for (int k = 0; k < L.n; ++k) {
         FrameArgs b = L.a;
         b.time = L.m.time[k];
         b.cam = L.m.cam[k];
-        b.width = RRT_MB_ARG(a.width); b.height = RRT_MB_ARG(a.height);                 /* what primary_ray reads */
-        b.use_lens = RRT_MB_ARG(a.use_lens); b.distortion_amount = RRT_MB_ARG(a.distortion_amount);
-        b.nudge_ulps = RRT_MB_ARG(a.nudge_ulps); b.nudge_seed = RRT_MB_ARG(a.nudge_seed);
+        b.width = RRT_SUB_ARG(a.width); b.height = RRT_SUB_ARG(a.height);               /* what primary_ray reads */
+        b.use_lens = RRT_SUB_ARG(a.use_lens); b.distortion_amount = RRT_SUB_ARG(a.distortion_amount);
+        b.nudge_ulps = RRT_SUB_ARG(a.nudge_ulps); b.nudge_seed = RRT_SUB_ARG(a.nudge_seed);
         float uvx, uvy;
         v3 p, vel;
         primary_ray(b, where[0][t], where[1][t], uvx, uvy, p, vel);
@@ -820,21 +826,21 @@ void motion_pixels(const MotionLaunch L) {
         bool hit = false;
         int i = 0;
         march_inline<SPIN, MEDIA, ARITH, true>(b, p, vel, acc, hit, i, nullptr);
-        b.sky = RRT_MB_ARG(a.sky);                                                       /* what shade_hdr reads */
-        b.use_bloom = RRT_MB_ARG(a.use_bloom); b.bloom_threshold = RRT_MB_ARG(a.bloom_threshold);
-        b.bloom_intensity = RRT_MB_ARG(a.bloom_intensity); b.use_vignette = RRT_MB_ARG(a.use_vignette);
-        b.vignette_intensity = RRT_MB_ARG(a.vignette_intensity); b.use_ca = RRT_MB_ARG(a.use_ca); b.ca_amount = RRT_MB_ARG(a.ca_amount);
+        b.sky = RRT_SUB_ARG(a.sky);                                                      /* what shade_hdr reads */
+        b.use_bloom = RRT_SUB_ARG(a.use_bloom); b.bloom_threshold = RRT_SUB_ARG(a.bloom_threshold);
+        b.bloom_intensity = RRT_SUB_ARG(a.bloom_intensity); b.use_vignette = RRT_SUB_ARG(a.use_vignette);
+        b.vignette_intensity = RRT_SUB_ARG(a.vignette_intensity); b.use_ca = RRT_SUB_ARG(a.use_ca); b.ca_amount = RRT_SUB_ARG(a.ca_amount);
         c = shade_hdr(b, uvx, uvy, hit, vel, acc);
         pixel_sum(c, L.s);
         int l = 0;                                      /* ((T0 + T1) + (T2 + T3)) ...: close the levels sub-frame k completes */
         for (int j = k; j & 1; j >>= 1, ++l)
             c = add(mk(part[l][0][t], part[l][1][t], part[l][2][t]), c);
-        if (k + 1 < L.n_times) { part[l][0][t] = c.x; part[l][1][t] = c.y; part[l][2][t] = c.z; }
+        if (k + 1 < L.n) { part[l][0][t] = c.x; part[l][1][t] = c.y; part[l][2][t] = c.z; }
     }
     const int oi = where[2][t];
     if (oi < 0) return;
-    const int s = RRT_MB_ARG(s);
-    store_mean(c, 1.0f / (float)(s * s * RRT_MB_ARG(n_times)), RRT_MB_ARG(a.out), RRT_MB_ARG(hdr_out), (size_t)oi);
+    const int s = RRT_SUB_ARG(s);
+    store_mean(c, 1.0f / (float)(s * s * RRT_SUB_ARG(n)), RRT_SUB_ARG(a.out), RRT_SUB_ARG(hdr_out), (size_t)oi);
 }
 
 /* Depth of field (rrt_launch_raymarch_dof, include/rrt.h has the contract): motion_pixels with a lens point per sample.  Sample k
@@ -842,21 +848,21 @@ void motion_pixels(const MotionLaunch L) {
  * query runs too) through the lens point (m.lx[k], m.ly[k]); cx = lx / focus and cy = ly / focus come rounded from the host.  All
  * six are read from the by-value LensArgs at the uniform k, so they stay scalar, and a pixel's K rays share the wave's lanes.  The
  * nudge runs here, after lens_ray, on the virtual pixel (primary_ray's own).  Registers, LDS slots and the re-read kernel
- * arguments are motion_pixels': a kernel of its own, because a branch or a template parameter there would move that kernel's
- * registers. */
+ * arguments are motion_pixels'.  The two kernels stay written out: one forced-inline body behind both keeps every resource figure
+ * but moves motion_pixels' register allocation, and its FMAD s = 1 frames measured 1.5-2 % slower (depth of field). */
 struct LensArgs { float time[kMaxTimes]; rrt_camera cam[kMaxTimes]; float lx[kMaxTimes], ly[kMaxTimes], cx[kMaxTimes], cy[kMaxTimes]; };
 struct LensLaunch {                                     /* lens_pixels' one kernel argument */
     FrameArgs a;                                        /* the virtual frame, as supersample_pixels' */
     LensArgs m;
-    int s, n_samples;
+    int s, n;                                           /* n: the number of lens samples */
     float4* hdr_out;
 };
-#define RRT_DOF_ARG(field) motion_arg<decltype(((LensLaunch*)nullptr)->field)>(offsetof(LensLaunch, field))
 
 template <bool SPIN, int MEDIA, int ARITH>
 __global__ __launch_bounds__(kWGThreads, (MEDIA != 0 ? RRT_MEDIA_WAVES : 1))      /* raymarch_pixels' register budget */
 void lens_pixels(const LensLaunch L) {
-    __shared__ float part[4][3][kWGThreads];            /* levels 0..3: n_samples <= 16 never stores level 4 */
+    using Launch = LensLaunch;
+    __shared__ float part[4][3][kWGThreads];            /* levels 0..3: n <= 16 never stores level 4 */
     __shared__ volatile int where[3][kWGThreads];       /* vx, vy, the output index (-1: another lane of the pixel stores) */
     const int t = threadIdx.x;
     {
@@ -868,7 +874,7 @@ void lens_pixels(const LensLaunch L) {
         where[2][t] = l.stores(s) ? l.out_row * (L.a.width / s) + l.x : -1;
     }
     v3 c;
-    for (int k = 0; k < L.n_samples; ++k) {
+    for (int k = 0; k < L.n; ++k) {
         FrameArgs b = L.a;
         b.time = L.m.time[k];
         b.cam = L.m.cam[k];
@@ -877,13 +883,13 @@ void lens_pixels(const LensLaunch L) {
         {
             const int x = where[0][t], y = where[1][t];
             float o[3], d[3];
-            lens_ray(RRT_DOF_ARG(a.width), RRT_DOF_ARG(a.height), x, y, b.cam, RRT_DOF_ARG(a.use_lens),
-                     RRT_DOF_ARG(a.distortion_amount), L.m.lx[k], L.m.ly[k], L.m.cx[k], L.m.cy[k], o, d, uvx, uvy);
+            lens_ray(RRT_SUB_ARG(a.width), RRT_SUB_ARG(a.height), x, y, b.cam, RRT_SUB_ARG(a.use_lens),
+                     RRT_SUB_ARG(a.distortion_amount), L.m.lx[k], L.m.ly[k], L.m.cx[k], L.m.cy[k], o, d, uvx, uvy);
             p = mk(o[0], o[1], o[2]);
             vel = mk(d[0], d[1], d[2]);
-            const int nudge_ulps = RRT_DOF_ARG(a.nudge_ulps);
-            if (__builtin_expect(nudge_ulps != 0, 0)) {             /* as primary_ray, on the virtual pixel */
-                const unsigned seed = RRT_DOF_ARG(a.nudge_seed);
+            const int nudge_ulps = RRT_SUB_ARG(a.nudge_ulps);
+            if (__builtin_expect(nudge_ulps != 0, 0)) {             /* nudge_direction written out: the seed is read only here */
+                const unsigned seed = RRT_SUB_ARG(a.nudge_seed);
                 vel.x = nudge_component(vel.x, nudge_ulps, seed, x, y, 0u);
                 vel.y = nudge_component(vel.y, nudge_ulps, seed, x, y, 1u);
                 vel.z = nudge_component(vel.z, nudge_ulps, seed, x, y, 2u);
@@ -893,21 +899,21 @@ void lens_pixels(const LensLaunch L) {
         bool hit = false;
         int i = 0;
         march_inline<SPIN, MEDIA, ARITH, true>(b, p, vel, acc, hit, i, nullptr);
-        b.sky = RRT_DOF_ARG(a.sky);                                                      /* what shade_hdr reads */
-        b.use_bloom = RRT_DOF_ARG(a.use_bloom); b.bloom_threshold = RRT_DOF_ARG(a.bloom_threshold);
-        b.bloom_intensity = RRT_DOF_ARG(a.bloom_intensity); b.use_vignette = RRT_DOF_ARG(a.use_vignette);
-        b.vignette_intensity = RRT_DOF_ARG(a.vignette_intensity); b.use_ca = RRT_DOF_ARG(a.use_ca); b.ca_amount = RRT_DOF_ARG(a.ca_amount);
+        b.sky = RRT_SUB_ARG(a.sky);                                                      /* what shade_hdr reads */
+        b.use_bloom = RRT_SUB_ARG(a.use_bloom); b.bloom_threshold = RRT_SUB_ARG(a.bloom_threshold);
+        b.bloom_intensity = RRT_SUB_ARG(a.bloom_intensity); b.use_vignette = RRT_SUB_ARG(a.use_vignette);
+        b.vignette_intensity = RRT_SUB_ARG(a.vignette_intensity); b.use_ca = RRT_SUB_ARG(a.use_ca); b.ca_amount = RRT_SUB_ARG(a.ca_amount);
         c = shade_hdr(b, uvx, uvy, hit, vel, acc);
         pixel_sum(c, L.s);
         int l = 0;                                      /* ((T0 + T1) + (T2 + T3)) ...: close the levels sample k completes */
         for (int j = k; j & 1; j >>= 1, ++l)
             c = add(mk(part[l][0][t], part[l][1][t], part[l][2][t]), c);
-        if (k + 1 < L.n_samples) { part[l][0][t] = c.x; part[l][1][t] = c.y; part[l][2][t] = c.z; }
+        if (k + 1 < L.n) { part[l][0][t] = c.x; part[l][1][t] = c.y; part[l][2][t] = c.z; }
     }
     const int oi = where[2][t];
     if (oi < 0) return;
-    const int s = RRT_DOF_ARG(s);
-    store_mean(c, 1.0f / (float)(s * s * RRT_DOF_ARG(n_samples)), RRT_DOF_ARG(a.out), RRT_DOF_ARG(hdr_out), (size_t)oi);
+    const int s = RRT_SUB_ARG(s);
+    store_mean(c, 1.0f / (float)(s * s * RRT_SUB_ARG(n)), RRT_SUB_ARG(a.out), RRT_SUB_ARG(hdr_out), (size_t)oi);
 }
 
 /* rrt_launch_projection_map: projection_dir of every pixel, (dir, inside) in the frame's bottom-up layout */
