@@ -64,10 +64,12 @@
 #include <atomic>
 #include <chrono>
 #include <cmath>
+#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -250,9 +252,9 @@ struct Device {                // everything one GPU owns
     hipEvent_t render_end[2 * kMaxSlots] = {};
 };
 
-}  // namespace
+// ---- the command line
 
-int main(int argc, char** argv) {
+struct Options {               // what the command line sets (parse_options), then what check_options derives from it
     int w = 1000, h = 700, frames = 24, fps = 24, path = -1, sky_seed = 1, all_fx = 0;   // config.h:7-9
     int arith = RRT_ARITH_STRICT;  // --arith strict | fmad | fast (--fast = --arith fast)
     int path_policy = -1;          // --path-policy auto|single|three-pass pins rrt_params.path_policy for every launch (no per-window choice)
@@ -264,10 +266,8 @@ int main(int argc, char** argv) {
     int motion = 1;                // --motion-blur K: K shutter sub-frames per frame (rrt_launch_raymarch_mb*); 1 = one instant
     float shutter = 0.5f;          // --shutter F: the fraction of the frame interval the shutter is open (180 degrees)
     rrt_glow glow;                 // --glow INTENSITY (+ --glow-radius / -threshold / -lobes): rrt_launch_glow on every frame
-    rrt_glow_default(&glow);
     bool use_glow = false;
     rrt_exposure exposure;         // --exposure EV / --auto-exposure [KEY] (+ --exposure-speed / -range / -percentiles): rrt_launch_exposure
-    rrt_exposure_default(&exposure);
     bool use_exposure = false, exposure_opts = false;
     double exposure_tau[2] = {0.0, 0.0};     // --exposure-speed UP DOWN, seconds
     int projection = RRT_PROJ_PINHOLE;   // --projection: the camera (rrt_launch_raymarch_pano* for equirect / fisheye)
@@ -275,705 +275,794 @@ int main(int argc, char** argv) {
     int stereo_layout = 0;               // --stereo: RRT_STEREO_* (0: mono); rrt_launch_raymarch_stereo*
     bool stereo_base = false, stereo_conv = false, stereo_merge = false;   // which of the stereo options were given
     rrt_stereo stereo;                   // --stereo-base / --convergence / --pole-merge over rrt_stereo_default
-    rrt_stereo_default(RRT_STEREO_TOP_BOTTOM, &stereo);
     bool use_adaptive = false;           // --adaptive [T]: rrt_launch_raymarch_adaptive
     rrt_adaptive adaptive;
-    rrt_adaptive_default(&adaptive);
     bool use_dof = false;                // --dof APERTURE: rrt_launch_raymarch_dof*
     float dof_aperture = 0.0f, dof_focus = 0.0f;     // --focus Z (0: hole -- the frame's camera's distance to the origin)
     int dof_samples = 0;                 // --dof-samples K (0: not given -- 8, or --motion-blur's M)
     bool dof_focus_given = false;
-    int kSlots = 3;                // frames in flight: frame k renders on stream k mod kSlots while its predecessors are
+    int slots = 3;                 // frames in flight: frame k renders on stream k mod slots while its predecessors are
                                    // gathered / assembled / copied out (a rank's share of a frame is only a few rounds of
                                    // wavefronts; 3 measured best at 8 shards of a 4K frame: profiles/r02_frames_in_flight.txt)
     float spin = 0.0f;
     double table_gib = 2.0;
     double init_timeout = 300.0, frame_timeout = 120.0;       // watchdog limits in seconds (0: none)
     std::string out_path, sky_path;
+
+    // derived: w x h is the frame that is sharded and written (with --stereo the composite of two ew x eh eyes)
+    bool pano = false, use_stereo = false, collective = false, auto_exposure = false;
+    int ew = 0, eh = 0;
+    rrt_projection proj;
+    int dof_k = 0;                 // lens samples per sub-sample; sample m looks through dof_xy[2m], dof_xy[2m + 1]
+    float dof_xy[32];
+    size_t glow_bytes = 0;
+
+    Options() {
+        rrt_glow_default(&glow);
+        rrt_exposure_default(&exposure);
+        rrt_stereo_default(RRT_STEREO_TOP_BOTTOM, &stereo);
+        rrt_adaptive_default(&adaptive);
+    }
+};
+
+// a refusal: the message on stderr (each keeps the prefix it has always had), exit status 2
+__attribute__((format(printf, 1, 2))) int refuse(const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vfprintf(stderr, fmt, ap);
+    va_end(ap);
+    fputc('\n', stderr);
+    return 2;
+}
+const char kFovRange[] = "--fov DEG in (0, 360], --vfov DEG in (0, 180]";        // said by the parser (0) and by the host query
+const char kDofAperture[] = "usage: --dof APERTURE: the lens radius in scene units, >= 0";   // by the parser and by rrt_lens_points
+
+// all of `text` as a number: false when it is empty or has characters left over; `finite` also refuses inf and nan
+bool parse_float(const char* text, float& v, bool finite) {
+    char* end = nullptr;
+    v = strtof(text, &end);
+    return end != text && *end == 0 && (!finite || std::isfinite(v));
+}
+bool parse_double(const char* text, double& v) {
+    char* end = nullptr;
+    v = strtod(text, &end);
+    return end != text && *end == 0 && std::isfinite(v);
+}
+bool parse_whole(const char* text, long& v) {
+    char* end = nullptr;
+    v = strtol(text, &end, 10);
+    return end != text && *end == 0;
+}
+// the index of `text` among `names`; -1: none of them
+int one_of(const char* text, std::initializer_list<const char*> names) {
+    int j = 0;
+    for (const char* n : names) { if (strcmp(text, n) == 0) return j; ++j; }
+    return -1;
+}
+
+int parse_options(int argc, char** argv, Options& o) {
     for (int i = 1; i < argc; ++i) {
-        std::string a = argv[i];
-        auto val = [&](int& dst) { if (i + 1 < argc) dst = atoi(argv[++i]); };
-        if (a == "--width") val(w); else if (a == "--height") val(h); else if (a == "--frames") val(frames);
-        else if (a == "--fps") val(fps); else if (a == "--path") val(path); else if (a == "--sky-seed") val(sky_seed);
-        else if (a == "--gpus") val(gpus); else if (a == "--tile-rows") val(tile_rows); else if (a == "--workspace-gib") val(workspace_gib);
-        else if (a == "--frames-in-flight") val(kSlots);
-        else if (a == "--spin" && i + 1 < argc) spin = (float)atof(argv[++i]);
-        else if (a == "--noise-table-gib" && i + 1 < argc) table_gib = atof(argv[++i]);
-        else if (a == "--init-timeout" && i + 1 < argc) init_timeout = atof(argv[++i]);
-        else if (a == "--frame-timeout" && i + 1 < argc) frame_timeout = atof(argv[++i]);
-        else if (a == "--no-noise-table") use_table = 0;
-        else if (a == "--tile-order") tile_order = 1; else if (a == "--no-tile-order") tile_order = 0;
-        else if (a == "--force-collective") force_collective = 1;     // run the RCCL exchange even with one GPU (self-check)
-        else if (a == "--out" && i + 1 < argc) out_path = argv[++i];
-        else if (a == "--sky" && i + 1 < argc) sky_path = argv[++i];
-        else if (a == "--all-effects") all_fx = 1; else if (a == "--fast") arith = RRT_ARITH_FAST;
-        else if (a == "--path-window") val(path_window);
-        else if (a == "--path-policy" && i + 1 < argc) {
-            const std::string m = argv[++i];
-            if (m == "auto") path_policy = RRT_PATH_AUTO; else if (m == "single") path_policy = RRT_PATH_SINGLE; else if (m == "three-pass") path_policy = RRT_PATH_THREE_PASS;
-            else { fprintf(stderr, "--path-policy auto | single | three-pass\n"); return 2; }
-            path_window = -1;
+        const std::string a = argv[i];
+        const bool more = i + 1 < argc;
+        auto next = [&]() -> const char* { return i + 1 < argc ? argv[++i] : ""; };     // the option's value ("": the line ends here)
+        auto val = [&](int& dst) { if (more) dst = atoi(argv[++i]); };
+        int j;
+        const char* m;
+        if (a == "--width") val(o.w); else if (a == "--height") val(o.h); else if (a == "--frames") val(o.frames);
+        else if (a == "--fps") val(o.fps); else if (a == "--path") val(o.path); else if (a == "--sky-seed") val(o.sky_seed);
+        else if (a == "--gpus") val(o.gpus); else if (a == "--tile-rows") val(o.tile_rows); else if (a == "--workspace-gib") val(o.workspace_gib);
+        else if (a == "--frames-in-flight") val(o.slots);
+        else if (a == "--spin" && more) o.spin = (float)atof(next());
+        else if (a == "--noise-table-gib" && more) o.table_gib = atof(next());
+        else if (a == "--init-timeout" && more) o.init_timeout = atof(next());
+        else if (a == "--frame-timeout" && more) o.frame_timeout = atof(next());
+        else if (a == "--no-noise-table") o.use_table = 0;
+        else if (a == "--tile-order") o.tile_order = 1; else if (a == "--no-tile-order") o.tile_order = 0;
+        else if (a == "--force-collective") o.force_collective = 1;     // run the RCCL exchange even with one GPU (self-check)
+        else if (a == "--out" && more) o.out_path = next();
+        else if (a == "--sky" && more) o.sky_path = next();
+        else if (a == "--all-effects") o.all_fx = 1; else if (a == "--fast") o.arith = RRT_ARITH_FAST;
+        else if (a == "--path-window") val(o.path_window);
+        else if (a == "--path-policy" && more) {
+            const int policy[] = {RRT_PATH_AUTO, RRT_PATH_SINGLE, RRT_PATH_THREE_PASS};
+            if ((j = one_of(next(), {"auto", "single", "three-pass"})) < 0) return refuse("--path-policy auto | single | three-pass");
+            o.path_policy = policy[j]; o.path_window = -1;
         }
         else if (a == "--supersample") {
-            const std::string m = i + 1 < argc ? argv[++i] : "";
-            if (m == "1" || m == "2" || m == "4" || m == "8") supersample = atoi(m.c_str());
-            else { fprintf(stderr, "--supersample 1 | 2 | 4 | 8 (sub-samples per pixel along each axis)\n"); return 2; }
+            if (one_of(m = next(), {"1", "2", "4", "8"}) < 0) return refuse("--supersample 1 | 2 | 4 | 8 (sub-samples per pixel along each axis)");
+            o.supersample = atoi(m);
         }
         else if (a == "--motion-blur") {
-            const std::string m = i + 1 < argc ? argv[++i] : "";
-            if (m == "1" || m == "2" || m == "4" || m == "8" || m == "16") motion = atoi(m.c_str());
-            else { fprintf(stderr, "--motion-blur 1 | 2 | 4 | 8 | 16 (sub-frames per frame)\n"); return 2; }
+            if (one_of(m = next(), {"1", "2", "4", "8", "16"}) < 0) return refuse("--motion-blur 1 | 2 | 4 | 8 | 16 (sub-frames per frame)");
+            o.motion = atoi(m);
         }
         else if (a == "--shutter") {
-            const char* m = i + 1 < argc ? argv[++i] : "";
-            char* end = nullptr;
-            const float f = strtof(m, &end);
-            if (end != m && *end == 0 && f >= 0.0f && f <= 1.0f) shutter = f;
-            else { fprintf(stderr, "--shutter F: a fraction of the frame interval in [0, 1]\n"); return 2; }
+            if (!parse_float(next(), o.shutter, false) || !(o.shutter >= 0.0f && o.shutter <= 1.0f))
+                return refuse("--shutter F: a fraction of the frame interval in [0, 1]");
         }
         else if (a == "--glow" || a == "--glow-radius" || a == "--glow-threshold" || a == "--glow-lobes") {
-            const char* m = i + 1 < argc ? argv[++i] : "";
-            char* end = nullptr;
-            const float v = strtof(m, &end);
-            if (end == m || *end != 0 || !std::isfinite(v)) { fprintf(stderr, "%s: a number\n", a.c_str()); return 2; }
-            if (a == "--glow") { glow.intensity = v; use_glow = true; }
-            else if (a == "--glow-radius") glow.radius = v;
-            else if (a == "--glow-threshold") glow.threshold = v;
-            else if (v == (float)(int)v) glow.lobes = (int)v;
-            else { fprintf(stderr, "--glow-lobes 1 | 2 | 3 | 4\n"); return 2; }
+            float v;
+            if (!parse_float(next(), v, true)) return refuse("%s: a number", a.c_str());
+            if (a == "--glow") { o.glow.intensity = v; o.use_glow = true; }
+            else if (a == "--glow-radius") o.glow.radius = v;
+            else if (a == "--glow-threshold") o.glow.threshold = v;
+            else if (v == (float)(int)v) o.glow.lobes = (int)v;
+            else return refuse("--glow-lobes 1 | 2 | 3 | 4");
         }
         else if (a == "--exposure" || a == "--exposure-speed" || a == "--exposure-range" || a == "--exposure-percentiles") {
             double v[2] = {0.0, 0.0};
             const int n = a == "--exposure" ? 1 : 2;
-            for (int j = 0; j < n; ++j) {
-                const char* m = i + 1 < argc ? argv[++i] : "";
-                char* end = nullptr;
-                v[j] = strtod(m, &end);
-                if (end == m || *end != 0 || !std::isfinite(v[j])) { fprintf(stderr, "usage: %s: %s\n", a.c_str(), n == 1 ? "a number" : "two numbers"); return 2; }
-            }
-            if (a == "--exposure") { exposure.ev = (float)v[0]; use_exposure = true; }
-            else {
-                exposure_opts = true;
-                if (a == "--exposure-speed") { exposure_tau[0] = v[0]; exposure_tau[1] = v[1]; }
-                else if (a == "--exposure-range") { exposure.min_ev = (float)v[0]; exposure.max_ev = (float)v[1]; }
-                else if (v[0] == (double)(int)v[0] && v[1] == (double)(int)v[1]) { exposure.low_permille = (int)v[0]; exposure.high_permille = (int)v[1]; }
-                else { fprintf(stderr, "usage: --exposure-percentiles LOW HIGH: whole numbers in per mille\n"); return 2; }
-            }
+            for (j = 0; j < n; ++j)
+                if (!parse_double(next(), v[j])) return refuse("usage: %s: %s", a.c_str(), n == 1 ? "a number" : "two numbers");
+            o.exposure_opts = o.exposure_opts || n == 2;
+            if (a == "--exposure") { o.exposure.ev = (float)v[0]; o.use_exposure = true; }
+            else if (a == "--exposure-speed") { o.exposure_tau[0] = v[0]; o.exposure_tau[1] = v[1]; }
+            else if (a == "--exposure-range") { o.exposure.min_ev = (float)v[0]; o.exposure.max_ev = (float)v[1]; }
+            else if (v[0] == (double)(int)v[0] && v[1] == (double)(int)v[1]) { o.exposure.low_permille = (int)v[0]; o.exposure.high_permille = (int)v[1]; }
+            else return refuse("usage: --exposure-percentiles LOW HIGH: whole numbers in per mille");
         }
         else if (a == "--auto-exposure") {  // the key is optional: the next argument unless it is another option
-            use_exposure = true;
-            exposure.mode = RRT_EXPOSURE_AUTO;
-            if (i + 1 < argc && strncmp(argv[i + 1], "--", 2) != 0) {
-                const char* m = argv[++i];
-                char* end = nullptr;
-                exposure.key = strtof(m, &end);
-                if (end == m || *end != 0) { fprintf(stderr, "usage: --auto-exposure [KEY]: a luminance > 0 (default 0.5)\n"); return 2; }
-            }
+            o.use_exposure = true;
+            o.exposure.mode = RRT_EXPOSURE_AUTO;
+            if (more && strncmp(argv[i + 1], "--", 2) != 0 && !parse_float(next(), o.exposure.key, false))
+                return refuse("usage: --auto-exposure [KEY]: a luminance > 0 (default 0.5)");
         }
         else if (a == "--projection") {
-            const std::string m = i + 1 < argc ? argv[++i] : "";
-            if (m == "pinhole") projection = RRT_PROJ_PINHOLE; else if (m == "equirect") projection = RRT_PROJ_EQUIRECT;
-            else if (m == "fisheye") projection = RRT_PROJ_FISHEYE;
-            else { fprintf(stderr, "--projection pinhole | equirect | fisheye\n"); return 2; }
+            if ((j = one_of(next(), {"pinhole", "equirect", "fisheye"})) < 0) return refuse("--projection pinhole | equirect | fisheye");
+            o.projection = j == 0 ? RRT_PROJ_PINHOLE : (j == 1 ? RRT_PROJ_EQUIRECT : RRT_PROJ_FISHEYE);
         }
         else if (a == "--fov" || a == "--vfov") {
-            const char* m = i + 1 < argc ? argv[++i] : "";
-            char* end = nullptr;
-            const float v = strtof(m, &end);
-            if (end == m || *end != 0) { fprintf(stderr, "%s DEG: a number of degrees\n", a.c_str()); return 2; }
-            (a == "--fov" ? fov : vfov) = v;
-            if (v == 0.0f) { fprintf(stderr, "--fov DEG in (0, 360], --vfov DEG in (0, 180]\n"); return 2; }
+            float& v = a == "--fov" ? o.fov : o.vfov;
+            if (!parse_float(next(), v, false)) return refuse("%s DEG: a number of degrees", a.c_str());
+            if (v == 0.0f) return refuse("%s", kFovRange);
         }
         else if (a == "--stereo") {
-            const std::string m = i + 1 < argc ? argv[++i] : "";
-            if (m == "top-bottom") stereo_layout = RRT_STEREO_TOP_BOTTOM; else if (m == "side-by-side") stereo_layout = RRT_STEREO_SIDE_BY_SIDE;
-            else { fprintf(stderr, "usage: --stereo top-bottom | side-by-side\n"); return 2; }
+            if ((j = one_of(next(), {"top-bottom", "side-by-side"})) < 0) return refuse("usage: --stereo top-bottom | side-by-side");
+            o.stereo_layout = j == 0 ? RRT_STEREO_TOP_BOTTOM : RRT_STEREO_SIDE_BY_SIDE;
         }
         else if (a == "--stereo-base" || a == "--convergence" || a == "--pole-merge") {
             float v[2];
             const int n = a == "--pole-merge" ? 2 : 1;
-            for (int j = 0; j < n; ++j) {
-                const char* m = i + 1 < argc ? argv[++i] : "";
-                char* end = nullptr;
-                v[j] = strtof(m, &end);
-                if (end == m || *end != 0) { fprintf(stderr, "usage: %s: a number\n", a.c_str()); return 2; }
-            }
-            if (a == "--stereo-base") { stereo.base = v[0]; stereo_base = true; }
-            else if (a == "--convergence") { stereo.convergence = v[0]; stereo_conv = true; }
-            else { stereo.pole_merge_from_deg = v[0]; stereo.pole_merge_to_deg = v[1]; stereo_merge = true; }
+            for (j = 0; j < n; ++j)
+                if (!parse_float(next(), v[j], false)) return refuse("usage: %s: a number", a.c_str());
+            if (a == "--stereo-base") { o.stereo.base = v[0]; o.stereo_base = true; }
+            else if (a == "--convergence") { o.stereo.convergence = v[0]; o.stereo_conv = true; }
+            else { o.stereo.pole_merge_from_deg = v[0]; o.stereo.pole_merge_to_deg = v[1]; o.stereo_merge = true; }
         }
         else if (a == "--adaptive") {       // the threshold is optional: the next argument unless it is another option
-            use_adaptive = true;
-            if (i + 1 < argc && strncmp(argv[i + 1], "--", 2) != 0) {
-                const char* m = argv[++i];
-                char* end = nullptr;
-                const long v = strtol(m, &end, 10);
-                if (end == m || *end != 0 || v < 0 || v > 255) { fprintf(stderr, "usage: --adaptive [T]: a threshold in 0 ... 255 (default 8)\n"); return 2; }
-                adaptive.threshold = (int32_t)v;
+            o.use_adaptive = true;
+            if (more && strncmp(argv[i + 1], "--", 2) != 0) {
+                long v;
+                if (!parse_whole(next(), v) || v < 0 || v > 255) return refuse("usage: --adaptive [T]: a threshold in 0 ... 255 (default 8)");
+                o.adaptive.threshold = (int32_t)v;
             }
         }
         else if (a == "--dof") {
-            const char* m = i + 1 < argc ? argv[++i] : "";
-            char* end = nullptr;
-            const float v = strtof(m, &end);
-            if (end == m || *end != 0 || !std::isfinite(v) || v < 0.0f) { fprintf(stderr, "usage: --dof APERTURE: the lens radius in scene units, >= 0\n"); return 2; }
-            dof_aperture = v; use_dof = true;
+            if (!parse_float(next(), o.dof_aperture, true) || o.dof_aperture < 0.0f) return refuse("%s", kDofAperture);
+            o.use_dof = true;
         }
         else if (a == "--focus") {
-            const std::string m = i + 1 < argc ? argv[++i] : "";
-            char* end = nullptr;
-            const float v = m == "hole" ? 0.0f : strtof(m.c_str(), &end);
-            if (m != "hole" && (end == m.c_str() || *end != 0 || !std::isfinite(v) || !(v > 0.0f))) {
-                fprintf(stderr, "usage: --focus: a distance > 0 along forward, or `hole`\n"); return 2;
-            }
-            dof_focus = v; dof_focus_given = true;
+            o.dof_focus = 0.0f;
+            if (strcmp(m = next(), "hole") != 0 && (!parse_float(m, o.dof_focus, true) || !(o.dof_focus > 0.0f)))
+                return refuse("usage: --focus: a distance > 0 along forward, or `hole`");
+            o.dof_focus_given = true;
         }
         else if (a == "--dof-samples") {
-            const std::string m = i + 1 < argc ? argv[++i] : "";
-            if (m == "1" || m == "2" || m == "4" || m == "8" || m == "16") dof_samples = atoi(m.c_str());
-            else { fprintf(stderr, "usage: --dof-samples 1 | 2 | 4 | 8 | 16 (lens samples per sub-sample)\n"); return 2; }
+            if (one_of(m = next(), {"1", "2", "4", "8", "16"}) < 0) return refuse("usage: --dof-samples 1 | 2 | 4 | 8 | 16 (lens samples per sub-sample)");
+            o.dof_samples = atoi(m);
         }
-        else if (a == "--arith" && i + 1 < argc) {
-            const std::string m = argv[++i];
-            if (m == "strict") arith = RRT_ARITH_STRICT; else if (m == "fmad") arith = RRT_ARITH_FMAD; else if (m == "fast") arith = RRT_ARITH_FAST;
-            else { fprintf(stderr, "--arith strict | fmad | fast\n"); return 2; }
+        else if (a == "--arith" && more) {
+            const int mode[] = {RRT_ARITH_STRICT, RRT_ARITH_FMAD, RRT_ARITH_FAST};
+            if ((j = one_of(next(), {"strict", "fmad", "fast"})) < 0) return refuse("--arith strict | fmad | fast");
+            o.arith = mode[j];
         }
-        else { fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
+        else return refuse("unknown argument %s", a.c_str());
     }
-    if (w <= 0 || h <= 0 || frames < 0 || fps <= 0 || gpus < 1 || tile_rows < 1 || kSlots < 1 || kSlots > kMaxSlots) {
-        fprintf(stderr, "bad arguments\n"); return 2;
-    }
+    return 0;
+}
+
+// Every refusal that depends on more than one option, in the order that decides which message a command line gets, and the values
+// derived from the options.  Host arithmetic and the library's host-only queries: no device is touched before this has returned.
+int check_options(Options& o) {
+    if (o.w <= 0 || o.h <= 0 || o.frames < 0 || o.fps <= 0 || o.gpus < 1 || o.tile_rows < 1 || o.slots < 1 || o.slots > kMaxSlots)
+        return refuse("bad arguments");
+    o.collective = o.gpus > 1 || o.force_collective;
     // the glow needs the whole frame's HDR on one device (rrt_launch_glow has no _tiles form); its settings are checked up front
-    size_t glow_bytes = 0;
-    if (use_glow) {
-        if (gpus > 1 || force_collective) { fprintf(stderr, "rrt_headless: --glow renders on one GPU only (--gpus 1)\n"); return 2; }
-        if (rrt_glow_scratch_bytes(w, h, &glow, &glow_bytes) != RRT_OK) {
-            fprintf(stderr, "--glow INTENSITY >= 0, --glow-radius R > 0 (a fraction of the height; widest lobe <= 1024 px), "
-                            "--glow-threshold T >= 0, --glow-lobes 1 | 2 | 3 | 4\n");
-            return 2;
-        }
+    if (o.use_glow) {
+        if (o.collective) return refuse("rrt_headless: --glow renders on one GPU only (--gpus 1)");
+        if (rrt_glow_scratch_bytes(o.w, o.h, &o.glow, &o.glow_bytes) != RRT_OK)
+            return refuse("--glow INTENSITY >= 0, --glow-radius R > 0 (a fraction of the height; widest lobe <= 1024 px), "
+                          "--glow-threshold T >= 0, --glow-lobes 1 | 2 | 3 | 4");
     }
     // exposure control needs the whole frame's HDR on one device (the meter sees every pixel; rrt_launch_exposure has no _tiles form)
-    if (!use_exposure && exposure_opts) {
-        fprintf(stderr, "usage: --exposure-speed / --exposure-range / --exposure-percentiles need --exposure EV | --auto-exposure [KEY]\n"); return 2;
-    }
-    if (use_exposure) {
-        if (gpus > 1 || force_collective) { fprintf(stderr, "usage: --exposure / --auto-exposure: one GPU only (--gpus 1)\n"); return 2; }
+    if (!o.use_exposure && o.exposure_opts)
+        return refuse("usage: --exposure-speed / --exposure-range / --exposure-percentiles need --exposure EV | --auto-exposure [KEY]");
+    if (o.use_exposure) {
+        if (o.collective) return refuse("usage: --exposure / --auto-exposure: one GPU only (--gpus 1)");
         // the settings' ranges are rrt_launch_exposure's own refusals, stated here before any device is touched
-        const bool speeds = rrt_exposure_adapt(1.0 / (double)fps, exposure_tau[0], &exposure.adapt_up) == RRT_OK &&
-                            rrt_exposure_adapt(1.0 / (double)fps, exposure_tau[1], &exposure.adapt_down) == RRT_OK &&
-                            exposure.adapt_up > 0.0f && exposure.adapt_down > 0.0f;
-        if (!speeds || !std::isfinite(exposure.key) || !(exposure.key > 0.0f) || !(exposure.min_ev <= exposure.max_ev) ||
-            exposure.low_permille < 0 || exposure.high_permille < 0 || (long long)exposure.low_permille + exposure.high_permille >= 1000) {
-            fprintf(stderr, "usage: --auto-exposure KEY > 0, --exposure-speed UP DOWN >= 0 (seconds), --exposure-range MIN MAX with MIN <= MAX, "
-                            "--exposure-percentiles LOW HIGH >= 0 with LOW + HIGH < 1000\n");
-            return 2;
-        }
+        rrt_exposure& e = o.exposure;
+        const bool speeds = rrt_exposure_adapt(1.0 / (double)o.fps, o.exposure_tau[0], &e.adapt_up) == RRT_OK &&
+                            rrt_exposure_adapt(1.0 / (double)o.fps, o.exposure_tau[1], &e.adapt_down) == RRT_OK &&
+                            e.adapt_up > 0.0f && e.adapt_down > 0.0f;
+        if (!speeds || !std::isfinite(e.key) || !(e.key > 0.0f) || !(e.min_ev <= e.max_ev) ||
+            e.low_permille < 0 || e.high_permille < 0 || (long long)e.low_permille + e.high_permille >= 1000)
+            return refuse("usage: --auto-exposure KEY > 0, --exposure-speed UP DOWN >= 0 (seconds), --exposure-range MIN MAX with MIN <= MAX, "
+                          "--exposure-percentiles LOW HIGH >= 0 with LOW + HIGH < 1000");
+        o.auto_exposure = e.mode == RRT_EXPOSURE_AUTO;
     }
     // panoramas: the spans are checked by the host query (the launch's own refusals), the combinations the kernels lack up front
-    const bool pano = projection != RRT_PROJ_PINHOLE;
-    rrt_projection proj;
-    rrt_projection_default(projection, &proj);
-    if (!pano && (fov != 0.0f || vfov != 0.0f)) { fprintf(stderr, "--fov / --vfov need --projection equirect | fisheye\n"); return 2; }
-    if (projection == RRT_PROJ_FISHEYE && vfov != 0.0f) { fprintf(stderr, "--vfov: equirect only (a fisheye's aperture is --fov)\n"); return 2; }
-    if (fov != 0.0f) proj.fov_deg = fov;
-    if (vfov != 0.0f) proj.vfov_deg = vfov;
-    if (pano) {
-        const rrt_camera c0 = {};
-        float d[3];
-        if (rrt_projection_ray(&proj, 1, 1, 0, 0, &c0, d, nullptr) != RRT_OK) {
-            fprintf(stderr, "--fov DEG in (0, 360], --vfov DEG in (0, 180]\n"); return 2;
-        }
-        if (motion > 1) { fprintf(stderr, "rrt_headless: a panorama renders one instant per frame (--motion-blur 1)\n"); return 2; }
-        if (projection == RRT_PROJ_EQUIRECT && use_glow) {
-            fprintf(stderr, "rrt_headless: --glow clamps at the frame's edge and an equirect frame wraps: not with --projection equirect\n");
-            return 2;
-        }
+    o.pano = o.projection != RRT_PROJ_PINHOLE;
+    rrt_projection_default(o.projection, &o.proj);
+    if (!o.pano && (o.fov != 0.0f || o.vfov != 0.0f)) return refuse("--fov / --vfov need --projection equirect | fisheye");
+    if (o.projection == RRT_PROJ_FISHEYE && o.vfov != 0.0f) return refuse("--vfov: equirect only (a fisheye's aperture is --fov)");
+    if (o.fov != 0.0f) o.proj.fov_deg = o.fov;
+    if (o.vfov != 0.0f) o.proj.vfov_deg = o.vfov;
+    const rrt_camera c0 = {};
+    float org[3], dir[3];
+    if (o.pano) {
+        if (rrt_projection_ray(&o.proj, 1, 1, 0, 0, &c0, dir, nullptr) != RRT_OK) return refuse("%s", kFovRange);
+        if (o.motion > 1) return refuse("rrt_headless: a panorama renders one instant per frame (--motion-blur 1)");
+        if (o.projection == RRT_PROJ_EQUIRECT && o.use_glow)
+            return refuse("rrt_headless: --glow clamps at the frame's edge and an equirect frame wraps: not with --projection equirect");
     }
     // stereo: the values are checked by the host query (the launch's own refusals), the combinations the kernel lacks up front;
     // --width / --height stay per eye (ew x eh, what the launch takes), w x h becomes the composite that is sharded and written
-    const bool use_stereo = stereo_layout != 0;
-    const int ew = w, eh = h;
-    if (!use_stereo && (stereo_base || stereo_conv || stereo_merge)) {
-        fprintf(stderr, "usage: --stereo-base / --convergence / --pole-merge need --stereo top-bottom | side-by-side\n"); return 2;
-    }
-    if (use_stereo) {
-        stereo.layout = stereo_layout;
-        if (projection == RRT_PROJ_FISHEYE) { fprintf(stderr, "usage: --stereo: pinhole or equirect (no stereo fisheye domes)\n"); return 2; }
-        if (motion > 1) { fprintf(stderr, "usage: --stereo renders one instant per frame (--motion-blur 1)\n"); return 2; }
-        if (use_glow) { fprintf(stderr, "usage: --stereo: not with --glow\n"); return 2; }
-        if (stereo_conv && projection != RRT_PROJ_PINHOLE) { fprintf(stderr, "usage: --convergence: pinhole only\n"); return 2; }
-        if (stereo_merge && projection != RRT_PROJ_EQUIRECT) { fprintf(stderr, "usage: --pole-merge: equirect only\n"); return 2; }
-        const rrt_camera c0 = {};
-        float o[3], d[3];
-        if (rrt_stereo_ray(&proj, &stereo, 1, 1, RRT_EYE_LEFT, 0, 0, &c0, o, d, nullptr) != RRT_OK) {
-            fprintf(stderr, "usage: --stereo-base B >= 0, --convergence Z >= 0, --pole-merge FROM TO with 0 <= FROM <= TO <= 90\n"); return 2;
-        }
-        if (stereo_layout == RRT_STEREO_SIDE_BY_SIDE) w = 2 * ew; else h = 2 * eh;
+    o.use_stereo = o.stereo_layout != 0;
+    o.ew = o.w; o.eh = o.h;
+    if (!o.use_stereo && (o.stereo_base || o.stereo_conv || o.stereo_merge))
+        return refuse("usage: --stereo-base / --convergence / --pole-merge need --stereo top-bottom | side-by-side");
+    if (o.use_stereo) {
+        o.stereo.layout = o.stereo_layout;
+        if (o.projection == RRT_PROJ_FISHEYE) return refuse("usage: --stereo: pinhole or equirect (no stereo fisheye domes)");
+        if (o.motion > 1) return refuse("usage: --stereo renders one instant per frame (--motion-blur 1)");
+        if (o.use_glow) return refuse("usage: --stereo: not with --glow");
+        if (o.stereo_conv && o.projection != RRT_PROJ_PINHOLE) return refuse("usage: --convergence: pinhole only");
+        if (o.stereo_merge && o.projection != RRT_PROJ_EQUIRECT) return refuse("usage: --pole-merge: equirect only");
+        if (rrt_stereo_ray(&o.proj, &o.stereo, 1, 1, RRT_EYE_LEFT, 0, 0, &c0, org, dir, nullptr) != RRT_OK)
+            return refuse("usage: --stereo-base B >= 0, --convergence Z >= 0, --pole-merge FROM TO with 0 <= FROM <= TO <= 90");
+        if (o.stereo_layout == RRT_STEREO_SIDE_BY_SIDE) o.w = 2 * o.ew; else o.h = 2 * o.eh;
     }
     // adaptive supersampling needs the whole frame on one device (the mask looks at every pixel's neighbours; no _tiles form)
-    if (use_adaptive) {
-        if (supersample <= 1) { fprintf(stderr, "usage: --adaptive needs --supersample 2 | 4 | 8\n"); return 2; }
-        if (gpus > 1 || force_collective) { fprintf(stderr, "usage: --adaptive renders on one GPU only (--gpus 1)\n"); return 2; }
-        if (motion > 1) { fprintf(stderr, "usage: --adaptive renders one instant per frame (--motion-blur 1)\n"); return 2; }
-        if (use_stereo) { fprintf(stderr, "usage: --adaptive: not with --stereo\n"); return 2; }
+    if (o.use_adaptive) {
+        if (o.supersample <= 1) return refuse("usage: --adaptive needs --supersample 2 | 4 | 8");
+        if (o.collective) return refuse("usage: --adaptive renders on one GPU only (--gpus 1)");
+        if (o.motion > 1) return refuse("usage: --adaptive renders one instant per frame (--motion-blur 1)");
+        if (o.use_stereo) return refuse("usage: --adaptive: not with --stereo");
     }
     // depth of field: a thin lens in front of the pinhole camera; its K samples are the shutter's sub-frames when there are any
-    if (!use_dof && (dof_focus_given || dof_samples != 0)) { fprintf(stderr, "usage: --focus / --dof-samples need --dof APERTURE\n"); return 2; }
-    int dof_k = 0;
-    float dof_xy[32];
-    if (use_dof) {
-        if (pano) { fprintf(stderr, "usage: --dof: a thin lens in front of a pinhole camera, not with --projection equirect | fisheye\n"); return 2; }
-        if (use_stereo) { fprintf(stderr, "usage: --dof: not with --stereo\n"); return 2; }
-        if (use_adaptive) { fprintf(stderr, "usage: --dof: not with --adaptive\n"); return 2; }
-        if (motion > 1 && dof_samples != 0 && dof_samples != motion) {
-            fprintf(stderr, "usage: --dof-samples: with --motion-blur M > 1 the lens samples are the shutter's sub-frames (K = M)\n"); return 2;
-        }
-        dof_k = motion > 1 ? motion : (dof_samples != 0 ? dof_samples : 8);
+    if (!o.use_dof && (o.dof_focus_given || o.dof_samples != 0)) return refuse("usage: --focus / --dof-samples need --dof APERTURE");
+    if (o.use_dof) {
+        if (o.pano) return refuse("usage: --dof: a thin lens in front of a pinhole camera, not with --projection equirect | fisheye");
+        if (o.use_stereo) return refuse("usage: --dof: not with --stereo");
+        if (o.use_adaptive) return refuse("usage: --dof: not with --adaptive");
+        if (o.motion > 1 && o.dof_samples != 0 && o.dof_samples != o.motion)
+            return refuse("usage: --dof-samples: with --motion-blur M > 1 the lens samples are the shutter's sub-frames (K = M)");
+        o.dof_k = o.motion > 1 ? o.motion : (o.dof_samples != 0 ? o.dof_samples : 8);
         float spiral[32];
-        if (rrt_lens_points(dof_aperture, dof_k, 0.0f, spiral) != RRT_OK) { fprintf(stderr, "usage: --dof APERTURE: the lens radius in scene units, >= 0\n"); return 2; }
-        for (int m = 0; m < dof_k; ++m) {       // sample m looks through lens point bitrev_K(m): the spiral's radius grows with its index
+        if (rrt_lens_points(o.dof_aperture, o.dof_k, 0.0f, spiral) != RRT_OK) return refuse("%s", kDofAperture);
+        for (int m = 0; m < o.dof_k; ++m) {       // sample m looks through lens point bitrev_K(m): the spiral's radius grows with its index
             int r = 0;
-            for (int b = 1, v = m; b < dof_k; b <<= 1, v >>= 1) r = (r << 1) | (v & 1);
-            dof_xy[2 * m] = spiral[2 * r]; dof_xy[2 * m + 1] = spiral[2 * r + 1];
+            for (int b = 1, v = m; b < o.dof_k; b <<= 1, v >>= 1) r = (r << 1) | (v & 1);
+            o.dof_xy[2 * m] = spiral[2 * r]; o.dof_xy[2 * m + 1] = spiral[2 * r + 1];
         }
     }
     // a supersampled launch is always the single kernel in the static order (include/rrt.h): no pool, no path choice, no tile order
-    if (supersample > 1 || motion > 1 || use_glow || use_exposure || pano || use_stereo || use_dof) { workspace_gib = 0; path_window = -1; tile_order = 0; }
-    int n_dev = 0, rc;
-    if ((rc = rrt_device_count(&n_dev)) != RRT_OK) return fail("no GPU", rc);
-    if (gpus > n_dev) { fprintf(stderr, "rrt_headless: --gpus %d but %d device(s) visible\n", gpus, n_dev); return 2; }
-    const bool collective = gpus > 1 || force_collective;
-    trace("start");
-    std::thread dog(watchdog, init_timeout, frame_timeout);
-    struct DogStop { std::thread& t; ~DogStop() { g_tr.stop.store(true); t.join(); } } dog_stop{dog};      // every return path
-    // the RCCL library's pages, read sequentially in the background while the per-device resources are set up
-    std::thread warm;
-    if (collective && !getenv("RRT_NO_LIBRARY_WARMUP")) warm = std::thread(warm_library_pages, (const void*)&ncclCommInitAll);
-    struct WarmJoin { std::thread& t; ~WarmJoin() { if (t.joinable()) t.join(); } } warm_join{warm};
-    // a failing communicator says why (RCCL prints nothing below WARN); the caller's setting wins
-    if (collective) setenv("NCCL_DEBUG", "WARN", 0);
-    // one process, one node: RCCL's bootstrap and RAS sockets need no interface but the loopback (by default it picks
-    // the first non-loopback one -- in a container a veth whose state is not this program's business)
-    if (collective) setenv("NCCL_SOCKET_IFNAME", "lo", 0);
-
-    // the recording clock (main.cpp:511-516) says which times the sequence reaches; the tables slide along it
-    float seq_end = 0.0f;
-    { float unused = 0.0f; rrt_recording_clock(frames, fps, &seq_end, &unused); seq_end += 1.0f; }
-    const size_t table_budget = table_gib > 0.0 ? (size_t)(table_gib * (double)(1ull << 30)) : 0;
-    if (table_budget == 0) use_table = 0;
-    int table_builds = 0, table_frames = 0, arith_frames = 0, coarsest = RRT_TABLE_FULL;
-    size_t table_peak = 0;
-    bool table_warned = false;
-    float win_t0 = 0.0f, win_t1 = -1.0f;         // the window the devices' tables (or the remembered failure) cover; empty at first
-    bool win_has_table = false;
-
-    std::vector<uint8_t> sky;
-    int sky_w = 2048, sky_h = 1024;
-    if (sky_path.empty()) sky = synthetic_sky(sky_w, sky_h, sky_seed);
-    else if (!load_sky_raw(sky_path, sky, sky_w, sky_h)) return 2;
-    rrt_effects fx; rrt_effects_default(&fx);
-    fx.use_chromatic_aberration = (uint8_t)all_fx;
-
-    // ---- per-device resources
-    std::vector<Device> dev(gpus);
-    size_t shard_stride = 0;                       // bytes between shards in the gathered buffer
-    for (int d = 0; d < gpus; ++d) {
-        int rows = 0;
-        rrt_tile_shard_rows(h, tile_rows, d, gpus, &rows);
-        dev[d].shard_rows = rows;
-        if ((size_t)rows * w * 4 > shard_stride) shard_stride = (size_t)rows * w * 4;
+    if (o.supersample > 1 || o.motion > 1 || o.use_glow || o.use_exposure || o.pano || o.use_stereo || o.use_dof) {
+        o.workspace_gib = 0; o.path_window = -1; o.tile_order = 0;
     }
-    shard_stride = (shard_stride + 255) & ~(size_t)255;
-    for (int d = 0; d < gpus; ++d) {
-        Device& D = dev[d];
-        D.id = d;
-        HIPCHK(hipSetDevice(d));
-        const int rows = collective ? D.shard_rows : h;            // image rows of one launch on this device
-        if ((rc = rrt_sky_create(sky.data(), sky_w, sky_h, &D.sky)) != RRT_OK) return fail("sky", rc);
-        HIPCHK(hipMalloc(&D.probe, 256 * (size_t)(gpus + 1)));
-        HIPCHK(hipEventCreateWithFlags(&D.comm_free, hipEventDisableTiming));
-        // the path is a choice only where a launch could take either: a pool, a share under RRT_PATH_AUTO's threshold, frames in
-        // flight (one frame at a time the three-pass path's two chains win: DESIGN.md section 5)
-        if (path_window >= 0 && kSlots >= 2 && workspace_gib > 0 && (long long)w * rows <= (long long)rrt_path_auto_max_rays()) {
-            if ((rc = rrt_path_chooser_create(kSlots, path_window, &D.chooser)) != RRT_OK) return fail("path chooser", rc);
-            for (int e = 0; e < 2 * kSlots; ++e) HIPCHK(hipEventCreate(&D.render_end[e]));
-        }
-        for (int s = 0; s < kSlots; ++s) {
-            HIPCHK(hipStreamCreateWithFlags(&D.stream[s], hipStreamNonBlocking));
-            HIPCHK(hipMalloc(&D.tiles[s], shard_stride));
-            if (workspace_gib > 0 && (rc = rrt_workspace_create(((size_t)workspace_gib << 30) / kSlots, &D.pool[s])) != RRT_OK)
-                return fail("workspace", rc);
-            // every frame's wave tiles dispatched longest-first by what the slot's previous frame measured (the first frame: by
-            // the library's probe of the view): worth it when the frames do not overlap (their drains are exposed) AND the
-            // launch takes the single kernel; a wash when frames overlap, and measured harmful on the three-pass path's two
-            // chains (it piles every expensive tile into the first chain: an eighth of a 4K frame 5.15 -> 5.45 ms, of a
-            // disk-heavy one 7.7 -> 10.6; profiles/r04_shard_kernel_times_*.txt), which is what small launches with a pool take
-            const bool three_pass_likely = workspace_gib > 0 && (long long)w * rows <= (long long)rrt_path_auto_max_rays();   // RRT_PATH_AUTO's own threshold
-            if ((tile_order == 1 || (tile_order < 0 && kSlots == 1 && !three_pass_likely)) && (rc = rrt_tile_order_create(&D.order[s])) != RRT_OK)
-                return fail("tile order", rc);
-        }
-    }
-    trace("per-device resources ready");
-    if (collective) {
-        std::vector<int> ids(gpus);
-        std::vector<ncclComm_t> comms(gpus);
-        for (int d = 0; d < gpus; ++d) ids[d] = d;
-        if (warm.joinable()) { trace("waiting for the RCCL library pages"); warm.join(); }
-        trace("ncclCommInitAll ...");
-        NCCLCHK(ncclCommInitAll(comms.data(), gpus, ids.data()));
-        trace("ncclCommInitAll done");
-        for (int d = 0; d < gpus; ++d) dev[d].comm = comms[d];
-        { std::lock_guard<std::mutex> lk(g_tr.mu); g_tr.comms = comms; }
-        // One untimed exchange of a few bytes brings up the peer-to-peer channels and loads RCCL's code object now, under
-        // the bring-up limit, instead of under frame 1's.
-        trace("first exchange (channel set-up) ...");
-        NCCLCHK(ncclGroupStart());
-        for (int d = 0; d < gpus; ++d) {
-            NCCLCHK(ncclSend(dev[d].probe, 256, ncclUint8, 0, dev[d].comm, dev[d].stream[0]));
-            NCCLCHK(ncclRecv(static_cast<uint8_t*>(dev[0].probe) + 256 * (size_t)(d + 1), 256, ncclUint8, d, dev[0].comm, dev[0].stream[0]));
-        }
-        NCCLCHK(ncclGroupEnd());
-        for (int d = 0; d < gpus; ++d) { HIPCHK(hipSetDevice(d)); HIPCHK(hipStreamSynchronize(dev[d].stream[0])); }
-        trace("first exchange done");
-    }
-    // device 0: gathered shards + assembled frame, per slot; pinned host frames for the sink
-    HIPCHK(hipSetDevice(0));
+    return 0;
+}
+
+// ---- the run's resources
+
+struct Slots {                 // what device 0 owns per frame slot: gathered shards + assembled frame, the pinned host frame for the sink
     void* gathered[kMaxSlots] = {};
     void* frame[kMaxSlots] = {};
     void* host[kMaxSlots] = {};
-    void* hdr[kMaxSlots] = {};         // --glow / --exposure: each slot's linear frame; the glow's scratch
+    void* hdr[kMaxSlots] = {};             // --glow / --exposure: each slot's linear frame; the glow's scratch
     void* glow_scratch[kMaxSlots] = {};
+    void* ad_scratch[kMaxSlots] = {};      // --adaptive: each slot's list, and the pinned word its count is copied to
+    void* ad_count[kMaxSlots] = {};
+    hipEvent_t done[kMaxSlots] = {};
+    size_t shard_stride = 0;               // bytes between shards in the gathered buffer
+    size_t frame_bytes = 0, ad_bytes = 0;
     // --auto-exposure: ONE state for the sequence.  The frames' renders overlap on their slots' streams; their exposure passes run in
     // frame order, each behind the event its predecessor recorded
     void* exposure_scratch = nullptr;
     size_t exposure_bytes = 0;
     hipEvent_t exposed = nullptr;
-    const bool auto_exposure = use_exposure && exposure.mode == RRT_EXPOSURE_AUTO;
-    if (auto_exposure) {
-        if ((rc = rrt_exposure_scratch_bytes(&exposure_bytes)) != RRT_OK) return fail("exposure scratch", rc);
-        HIPCHK(hipMalloc(&exposure_scratch, exposure_bytes));
-        HIPCHK(hipEventCreateWithFlags(&exposed, hipEventDisableTiming));
-        if ((rc = rrt_launch_exposure_reset(exposure_scratch, exposure_bytes, dev[0].stream[0])) != RRT_OK) return fail("exposure reset", rc);
+};
+
+// each device's shard of the frame; the stride between shards in the gathered buffer
+void plan_shards(const Options& o, std::vector<Device>& dev, Slots& R) {
+    for (int d = 0; d < o.gpus; ++d) {
+        int rows = 0;
+        rrt_tile_shard_rows(o.h, o.tile_rows, d, o.gpus, &rows);
+        dev[d].id = d;
+        dev[d].shard_rows = rows;
+        if ((size_t)rows * o.w * 4 > R.shard_stride) R.shard_stride = (size_t)rows * o.w * 4;
     }
-    void* ad_scratch[kMaxSlots] = {};  // --adaptive: each slot's list, and the pinned word its count is copied to
-    void* ad_count[kMaxSlots] = {};
-    size_t ad_bytes = 0;
-    if (use_adaptive && (rc = rrt_adaptive_scratch_bytes(w, h, &ad_bytes)) != RRT_OK) return fail("adaptive scratch", rc);
-    unsigned long long refined_total = 0;
-    hipEvent_t done[kMaxSlots];
-    const size_t frame_bytes = (size_t)w * h * 4;
-    for (int s = 0; s < kSlots; ++s) {
-        HIPCHK(hipMalloc(&gathered[s], shard_stride * gpus));
-        HIPCHK(hipMalloc(&frame[s], frame_bytes));
-        if (use_glow || use_exposure) HIPCHK(hipMalloc(&hdr[s], frame_bytes * sizeof(float)));
-        if (use_glow) HIPCHK(hipMalloc(&glow_scratch[s], glow_bytes));
-        if (use_adaptive) { HIPCHK(hipMalloc(&ad_scratch[s], ad_bytes)); HIPCHK(hipHostMalloc(&ad_count[s], 4, hipHostMallocDefault)); }
-        HIPCHK(hipEventCreateWithFlags(&done[s], hipEventDisableTiming));
+    R.shard_stride = (R.shard_stride + 255) & ~(size_t)255;
+}
+
+int create_device(Device& D, const Options& o, const std::vector<uint8_t>& sky, int sky_w, int sky_h, size_t shard_stride) {
+    int rc;
+    HIPCHK(hipSetDevice(D.id));
+    const int rows = o.collective ? D.shard_rows : o.h;            // image rows of one launch on this device
+    if ((rc = rrt_sky_create(sky.data(), sky_w, sky_h, &D.sky)) != RRT_OK) return fail("sky", rc);
+    HIPCHK(hipMalloc(&D.probe, 256 * (size_t)(o.gpus + 1)));
+    HIPCHK(hipEventCreateWithFlags(&D.comm_free, hipEventDisableTiming));
+    const bool three_pass_likely = o.workspace_gib > 0 && (long long)o.w * rows <= (long long)rrt_path_auto_max_rays();   // RRT_PATH_AUTO's own threshold
+    // the path is a choice only where a launch could take either: a pool, a share under RRT_PATH_AUTO's threshold, frames in
+    // flight (one frame at a time the three-pass path's two chains win: DESIGN.md section 5)
+    if (o.path_window >= 0 && o.slots >= 2 && three_pass_likely) {
+        if ((rc = rrt_path_chooser_create(o.slots, o.path_window, &D.chooser)) != RRT_OK) return fail("path chooser", rc);
+        for (int e = 0; e < 2 * o.slots; ++e) HIPCHK(hipEventCreate(&D.render_end[e]));
     }
-    FILE* f = out_path.empty() ? nullptr : fopen(out_path.c_str(), "wb");
-    if (!out_path.empty() && !f) { perror("fopen"); return 1; }
-    if (f) for (int s = 0; s < kSlots; ++s) HIPCHK(hipHostMalloc(&host[s], frame_bytes, hipHostMallocDefault));
+    for (int s = 0; s < o.slots; ++s) {
+        HIPCHK(hipStreamCreateWithFlags(&D.stream[s], hipStreamNonBlocking));
+        HIPCHK(hipMalloc(&D.tiles[s], shard_stride));
+        if (o.workspace_gib > 0 && (rc = rrt_workspace_create(((size_t)o.workspace_gib << 30) / o.slots, &D.pool[s])) != RRT_OK)
+            return fail("workspace", rc);
+        // every frame's wave tiles dispatched longest-first by what the slot's previous frame measured (the first frame: by
+        // the library's probe of the view): worth it when the frames do not overlap (their drains are exposed) AND the
+        // launch takes the single kernel; a wash when frames overlap, and measured harmful on the three-pass path's two
+        // chains (it piles every expensive tile into the first chain: an eighth of a 4K frame 5.15 -> 5.45 ms, of a
+        // disk-heavy one 7.7 -> 10.6; profiles/r04_shard_kernel_times_*.txt), which is what small launches with a pool take
+        if ((o.tile_order == 1 || (o.tile_order < 0 && o.slots == 1 && !three_pass_likely)) && (rc = rrt_tile_order_create(&D.order[s])) != RRT_OK)
+            return fail("tile order", rc);
+    }
+    return 0;
+}
 
-    rrt_camera cam;
-    const float start_pos[3] = {0.0f, 10.0f, -60.0f};
-    rrt_camera_from_angles(start_pos, 0.0f, -10.0f, &cam);
-    const char* path_name = "";
-    if (path >= 0 && (rc = rrt_path_info(path, &path_name, nullptr, nullptr)) != RRT_OK) return fail("path", rc);
+void destroy_device(Device& D, int slots) {
+    if (D.comm) ncclCommDestroy(D.comm);
+    (void)hipFree(D.probe);
+    (void)hipEventDestroy(D.comm_free);
+    if (D.chooser) { rrt_path_chooser_destroy(D.chooser); for (int e = 0; e < 2 * slots; ++e) (void)hipEventDestroy(D.render_end[e]); }
+    for (int s = 0; s < slots; ++s) {
+        if (D.pool[s]) rrt_workspace_destroy(D.pool[s]);
+        if (D.order[s]) rrt_tile_order_destroy(D.order[s]);
+        (void)hipFree(D.tiles[s]);
+        (void)hipStreamDestroy(D.stream[s]);
+    }
+    if (D.noise_table) rrt_noise_table_destroy(D.noise_table);
+    rrt_sky_destroy(D.sky);
+}
 
-    // write frame `k`'s pixels once its copy has landed (called one frame late, so that the copy overlaps the next render)
-    // (without a sink the wait still happens: the host never runs more than kSlots frames ahead of the device, a device
-    // fault is reported at the frame it belongs to, and the watchdog sees frames complete)
-    int delivered = 0;
-    auto deliver = [&](int slot) -> int {
-        HIPCHK(hipEventSynchronize(done[slot]));
-        trace("frame complete", ++delivered);
-        if (use_adaptive) refined_total += *static_cast<const uint32_t*>(ad_count[slot]);
-        // frame `delivered` has been rendered on every device (the gather waited for all shards): its sustained time on a device =
-        // the interval between the ends of frame delivered - 1's and its own render there
-        if (delivered >= 2) for (int d = 0; d < gpus; ++d) if (dev[d].chooser) {
-            float ms = 0.0f;
-            HIPCHK(hipSetDevice(d));
-            if (hipEventElapsedTime(&ms, dev[d].render_end[(delivered - 1) % (2 * kSlots)], dev[d].render_end[delivered % (2 * kSlots)]) == hipSuccess)
-                rrt_path_chooser_report(dev[d].chooser, delivered, ms > 0.0f ? ms : 0.0f);   // (a frame that ended before its predecessor: 0)
-        }
-        if (f && fwrite(host[slot], 1, frame_bytes, f) != frame_bytes) fprintf(stderr, "Warning: Frame write incomplete\n");
-        return 0;
-    };
+// one RCCL communicator per device, and one untimed exchange of a few bytes
+int create_communicators(std::vector<Device>& dev, std::thread& warm) {
+    const int gpus = (int)dev.size();
+    std::vector<int> ids(gpus);
+    std::vector<ncclComm_t> comms(gpus);
+    for (int d = 0; d < gpus; ++d) ids[d] = d;
+    if (warm.joinable()) { trace("waiting for the RCCL library pages"); warm.join(); }
+    trace("ncclCommInitAll ...");
+    NCCLCHK(ncclCommInitAll(comms.data(), gpus, ids.data()));
+    trace("ncclCommInitAll done");
+    for (int d = 0; d < gpus; ++d) dev[d].comm = comms[d];
+    { std::lock_guard<std::mutex> lk(g_tr.mu); g_tr.comms = comms; }
+    // One untimed exchange of a few bytes brings up the peer-to-peer channels and loads RCCL's code object now, under
+    // the bring-up limit, instead of under frame 1's.
+    trace("first exchange (channel set-up) ...");
+    NCCLCHK(ncclGroupStart());
+    for (int d = 0; d < gpus; ++d) {
+        NCCLCHK(ncclSend(dev[d].probe, 256, ncclUint8, 0, dev[d].comm, dev[d].stream[0]));
+        NCCLCHK(ncclRecv(static_cast<uint8_t*>(dev[0].probe) + 256 * (size_t)(d + 1), 256, ncclUint8, d, dev[0].comm, dev[0].stream[0]));
+    }
+    NCCLCHK(ncclGroupEnd());
+    for (int d = 0; d < gpus; ++d) { HIPCHK(hipSetDevice(d)); HIPCHK(hipStreamSynchronize(dev[d].stream[0])); }
+    trace("first exchange done");
+    return 0;
+}
 
-    for (int d = 0; d < gpus; ++d) { HIPCHK(hipSetDevice(d)); HIPCHK(hipDeviceSynchronize()); }
-    trace("bring-up complete; rendering");
-    g_tr.in_frames.store(true);
-    auto t0 = std::chrono::steady_clock::now();
-    for (int k = 1; k <= frames; ++k) {
-        const int slot = k % kSlots;
-        float sim_t = 0.0f, path_t = 0.0f;
-        rrt_recording_clock(k, fps, &sim_t, &path_t);
-        if (path >= 0 && (rc = rrt_path_camera_at(path, path_t, &cam)) != RRT_OK) return fail("camera", rc);
-        // motion blur: the shutter's sub-times and the path camera at each; the noise table's window is fitted from the earliest
-        float sub_t[16], sub_p[16];
-        rrt_camera sub_cam[16];
-        float fit_t = sim_t;
-        if (motion > 1) {
-            rrt_motion_clock(k, fps, shutter, motion, sub_t, sub_p);
-            for (int m = 0; m < motion; ++m) {
-                sub_cam[m] = cam;
-                if (path >= 0 && (rc = rrt_path_camera_at(path, sub_p[m], &sub_cam[m])) != RRT_OK) return fail("camera", rc);
-            }
-            fit_t = sub_t[0];
-        }
-        // depth of field: without a shutter the K samples share the frame's instant; --focus hole: the camera position's distance to
-        // the origin, the double root of the sum of the exact squares in x, y, z order, rounded to float (headless.py's)
-        float focus = dof_focus;
-        if (use_dof) {
-            if (motion <= 1) for (int m = 0; m < dof_k; ++m) { sub_t[m] = sim_t; sub_cam[m] = cam; }
-            if (focus == 0.0f) {
-                const double x = cam.pos[0], y = cam.pos[1], z = cam.pos[2];
-                focus = (float)std::sqrt(x * x + y * y + z * z);
-            }
-        }
-        trace("frame", k);
-        // slot reuse: frame k-kSlots used the same buffers; its host copy must have been written out
-        if (k > kSlots && deliver(slot)) return 1;
-        // 0. noise tables: when the clock has left the window, every device builds the next one (after its frames in
-        //    flight, which may still read the old table, have drained).  The window is ONE decision for all devices: if it
-        //    cannot be built on any of them (nothing fits the budget, out of memory) it is dropped on all of them and
-        //    REMEMBERED -- no new fit, no device synchronise, no retry until the clock has left it (retrying
-        //    every frame serialised the frames in flight and rebuilt the other devices' tables for nothing).
-        const bool in_window = fit_t >= win_t0 && fit_t <= win_t1;
-        if (use_table && !in_window) {
-            float t1 = fit_t; int cov = RRT_TABLE_FULL; size_t bytes = 0;
+// device 0's per-slot buffers (pinned host frames only with a sink) and the sequence's exposure state
+int create_slots(Slots& R, const Options& o, bool sink, hipStream_t stream0) {
+    int rc;
+    HIPCHK(hipSetDevice(0));
+    if (o.auto_exposure) {
+        if ((rc = rrt_exposure_scratch_bytes(&R.exposure_bytes)) != RRT_OK) return fail("exposure scratch", rc);
+        HIPCHK(hipMalloc(&R.exposure_scratch, R.exposure_bytes));
+        HIPCHK(hipEventCreateWithFlags(&R.exposed, hipEventDisableTiming));
+        if ((rc = rrt_launch_exposure_reset(R.exposure_scratch, R.exposure_bytes, stream0)) != RRT_OK) return fail("exposure reset", rc);
+    }
+    if (o.use_adaptive && (rc = rrt_adaptive_scratch_bytes(o.w, o.h, &R.ad_bytes)) != RRT_OK) return fail("adaptive scratch", rc);
+    R.frame_bytes = (size_t)o.w * o.h * 4;
+    for (int s = 0; s < o.slots; ++s) {
+        HIPCHK(hipMalloc(&R.gathered[s], R.shard_stride * o.gpus));
+        HIPCHK(hipMalloc(&R.frame[s], R.frame_bytes));
+        if (o.use_glow || o.use_exposure) HIPCHK(hipMalloc(&R.hdr[s], R.frame_bytes * sizeof(float)));
+        if (o.use_glow) HIPCHK(hipMalloc(&R.glow_scratch[s], o.glow_bytes));
+        if (o.use_adaptive) { HIPCHK(hipMalloc(&R.ad_scratch[s], R.ad_bytes)); HIPCHK(hipHostMalloc(&R.ad_count[s], 4, hipHostMallocDefault)); }
+        HIPCHK(hipEventCreateWithFlags(&R.done[s], hipEventDisableTiming));
+    }
+    if (sink) for (int s = 0; s < o.slots; ++s) HIPCHK(hipHostMalloc(&R.host[s], R.frame_bytes, hipHostMallocDefault));
+    return 0;
+}
+
+void destroy_slots(Slots& R, int slots) {
+    (void)hipFree(R.exposure_scratch);
+    if (R.exposed) (void)hipEventDestroy(R.exposed);
+    for (int s = 0; s < slots; ++s) {
+        (void)hipFree(R.gathered[s]); (void)hipFree(R.frame[s]); (void)hipFree(R.hdr[s]); (void)hipFree(R.glow_scratch[s]);
+        (void)hipFree(R.ad_scratch[s]);
+        if (R.ad_count[s]) (void)hipHostFree(R.ad_count[s]);
+        if (R.host[s]) (void)hipHostFree(R.host[s]);
+        (void)hipEventDestroy(R.done[s]);
+    }
+}
+
+// ---- the frame loop
+
+// The devices' noise tables over a sliding window of the clock (relativisticraytracer_amd/__init__.py: NoiseWindows).
+struct NoiseWindow {
+    bool enabled;
+    size_t budget;
+    float seq_end;                               // the recording clock's last time + 1 s: the tables slide along it
+    float t0 = 0.0f, t1 = -1.0f;                 // the window the devices' tables (or the remembered failure) cover; empty at first
+    bool has_table = false, warned = false;
+    int builds = 0, table_frames = 0, arith_frames = 0, coarsest = RRT_TABLE_FULL;
+    size_t peak = 0;
+
+    // Frame k reads the noise from fit_t on.  When the clock has left the window, every device builds the next one (after its frames
+    // in flight, which may still read the old table, have drained).  The window is ONE decision for all devices: if it
+    // cannot be built on any of them (nothing fits the budget, out of memory) it is dropped on all of them and
+    // REMEMBERED -- no new fit, no device synchronise, no retry until the clock has left it (retrying
+    // every frame serialised the frames in flight and rebuilt the other devices' tables for nothing).
+    int slide(float fit_t, int k, std::vector<Device>& dev) {
+        if (enabled && !(fit_t >= t0 && fit_t <= t1)) {
+            float end = fit_t; int cov = RRT_TABLE_FULL; size_t bytes = 0;
             // trace points around the rebuild: it synchronises every device and creates a table on each, which on a
             // starved box takes time that must neither count against --frame-timeout under the name of the last frame nor
             // leave the watchdog's notices pointing at the wrong phase
             trace("noise table window: fitting", k);
-            rrt_noise_table_fit_window(fit_t, seq_end > fit_t ? seq_end : fit_t, table_budget, &t1, &cov, &bytes);
+            rrt_noise_table_fit_window(fit_t, seq_end > fit_t ? seq_end : fit_t, budget, &end, &cov, &bytes);
             bool ok = bytes != 0;
-            for (int d = 0; d < gpus; ++d) {
-                Device& D = dev[d];
-                HIPCHK(hipSetDevice(d));
-                trace("noise table window: draining and rebuilding on device", d);
+            for (Device& D : dev) {
+                HIPCHK(hipSetDevice(D.id));
+                trace("noise table window: draining and rebuilding on device", D.id);
                 HIPCHK(hipDeviceSynchronize());
                 if (D.noise_table) { rrt_noise_table_destroy(D.noise_table); D.noise_table = 0; }
-                if (ok && (rc = rrt_noise_table_create_window(fit_t, t1, cov, &D.noise_table)) != RRT_OK) {
+                const int rc = ok ? rrt_noise_table_create_window(fit_t, end, cov, &D.noise_table) : RRT_OK;
+                if (rc != RRT_OK) {
                     D.noise_table = 0;
                     ok = false;
-                    if (!table_warned) {
+                    if (!warned) {
                         fprintf(stderr, "rrt_headless: noise table [%g, %g] not built on device %d: %s (%s); hashing arithmetically\n",
-                                fit_t, t1, d, rrt_status_string(rc), rrt_last_hip_error());
-                        table_warned = true;
+                                fit_t, end, D.id, rrt_status_string(rc), rrt_last_hip_error());
+                        warned = true;
                     }
                 }
             }
             if (!ok) {      // all or nothing: the devices must agree on which kernels a frame runs for the timing to mean anything
-                for (int d = 0; d < gpus; ++d) if (dev[d].noise_table) { HIPCHK(hipSetDevice(d)); rrt_noise_table_destroy(dev[d].noise_table); dev[d].noise_table = 0; }
-                if (bytes == 0) t1 = fit_t + 5.0f;          // nothing fits: look again after 5 s of sim time
+                for (Device& D : dev) if (D.noise_table) { HIPCHK(hipSetDevice(D.id)); rrt_noise_table_destroy(D.noise_table); D.noise_table = 0; }
+                if (bytes == 0) end = fit_t + 5.0f;          // nothing fits: look again after 5 s of sim time
             }
-            win_t0 = fit_t; win_t1 = t1; win_has_table = ok;
+            t0 = fit_t; t1 = end; has_table = ok;
             trace("noise table window: done", k);
-            if (ok) { ++table_builds; if (cov > coarsest) coarsest = cov; if (bytes > table_peak) table_peak = bytes; }
+            if (ok) { ++builds; if (cov > coarsest) coarsest = cov; if (bytes > peak) peak = bytes; }
         }
-        if (use_table && win_has_table) ++table_frames; else ++arith_frames;
-        // 1. every device renders its tiles
-        for (int d = 0; d < gpus; ++d) {
-            Device& D = dev[d];
-            HIPCHK(hipSetDevice(d));
-            rrt_params prm; rrt_params_default(&prm);
-            prm.spin = spin; prm.arith_mode = arith;
-            prm.workspace = D.pool[slot]; prm.noise_table = D.noise_table; prm.tile_order = D.order[slot];
-            // frames in flight fill each other's drains: ONE chain per launch (the second chain's streams only compete with the other
-            // frames: 2-7 % per frame, profiles/r05_sustained_chains.txt).  The plain single kernel would be faster still on most views,
-            // but its longest wavefront (up to 19 ms on a disk-grazing view) bounds a slot's frame rate; a moving camera keeps the
-            // path that is never slow
-            prm.pass_chains = kSlots >= 2 ? 1 : 0;
-            // ... per window, by measurement: rrt_path_chooser (csrc/rrt_path_chooser.cpp) tries the single kernel for a few frames
-            // of a window, keeps it where it sustains the faster frames, and drops it at once on a frame that takes > 1.5 x the
-            // three-pass median (same bytes either way)
-            if (D.chooser) { int pol = RRT_PATH_AUTO; rrt_path_chooser_policy(D.chooser, k, &pol); prm.path_policy = pol; }
-            else if (path_policy >= 0) prm.path_policy = path_policy;
-            void* dst = collective ? D.tiles[slot] : frame[slot];
-            // the stereo / defocused / panorama / blurred / supersampled launch (_stereo, _dof, _pano, _mb, _ss): this device's tiles, or the whole frame and
-            // its HDR (may be NULL)
-            auto launch_sampled = [&](bool tiles, float* lin) {
-                if (use_stereo) return tiles ? rrt_launch_raymarch_stereo_tiles(dst, ew, eh, supersample, tile_rows, d, gpus, &proj, &stereo, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot])
-                                             : rrt_launch_raymarch_stereo(dst, lin, ew, eh, supersample, &proj, &stereo, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
-                if (use_dof) return tiles ? rrt_launch_raymarch_dof_tiles(dst, w, h, supersample, tile_rows, d, gpus, dof_k, sub_t, sub_cam, dof_xy, focus, D.sky, &fx, &prm, D.stream[slot])
-                                          : rrt_launch_raymarch_dof(dst, lin, w, h, supersample, dof_k, sub_t, sub_cam, dof_xy, focus, D.sky, &fx, &prm, D.stream[slot]);
-                if (pano) return tiles ? rrt_launch_raymarch_pano_tiles(dst, w, h, supersample, tile_rows, d, gpus, &proj, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot])
-                                       : rrt_launch_raymarch_pano(dst, lin, w, h, supersample, &proj, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
-                if (motion > 1) return tiles ? rrt_launch_raymarch_mb_tiles(dst, w, h, supersample, tile_rows, d, gpus, motion, sub_t, sub_cam, D.sky, &fx, &prm, D.stream[slot])
-                                             : rrt_launch_raymarch_mb(dst, lin, w, h, supersample, motion, sub_t, sub_cam, D.sky, &fx, &prm, D.stream[slot]);
-                return tiles ? rrt_launch_raymarch_ss_tiles(dst, w, h, supersample, tile_rows, d, gpus, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot])
-                             : rrt_launch_raymarch_ss(dst, lin, w, h, supersample, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
-            };
-            // --adaptive: one device (checked above), the whole frame and its HDR (may be NULL); the count of refined pixels follows
-            // in a 4-byte asynchronous copy, read when the frame is delivered
-            auto launch_adaptive = [&](float* lin) {
-                const int st = rrt_launch_raymarch_adaptive(dst, lin, w, h, supersample, pano ? &proj : nullptr, &adaptive, sim_t, &cam, D.sky,
-                                                            &fx, &prm, ad_scratch[slot], ad_bytes, D.stream[slot]);
-                if (st == RRT_OK && hipMemcpyAsync(ad_count[slot], ad_scratch[slot], 4, hipMemcpyDeviceToHost, D.stream[slot]) != hipSuccess)
-                    return (int)RRT_ERR_HIP;
-                return st;
-            };
-            if (use_glow || use_exposure) {     // one device (checked above): the slot's HDR through launch_sampled, then the post passes on the same stream
-                float* lin = static_cast<float*>(hdr[slot]);
-                rc = use_adaptive ? launch_adaptive(lin) : launch_sampled(false, lin);
-                if (rc == RRT_OK && use_exposure) {     // the bytes -- or, in front of the glow, the scaled HDR in place
-                    if (auto_exposure) HIPCHK(hipStreamWaitEvent(D.stream[slot], exposed, 0));
-                    rc = rrt_launch_exposure(use_glow ? nullptr : dst, use_glow ? lin : nullptr, lin, w, h, &exposure, exposure_scratch,
-                                             exposure_bytes, D.stream[slot]);
-                    if (auto_exposure) HIPCHK(hipEventRecord(exposed, D.stream[slot]));
-                }
-                if (rc == RRT_OK && use_glow) rc = rrt_launch_glow(dst, lin, w, h, &glow, glow_scratch[slot], glow_bytes, D.stream[slot]);
-            }
-            else if (use_adaptive) rc = launch_adaptive(nullptr);
-            else if (use_stereo || use_dof || pano || motion > 1 || supersample > 1) rc = launch_sampled(collective, nullptr);
-            else if (collective) rc = rrt_launch_raymarch_tiles(dst, w, h, tile_rows, d, gpus, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
-            else rc = rrt_launch_raymarch(dst, w, h, sim_t, &cam, D.sky, &fx, &prm, D.stream[slot]);
-            if (rc != RRT_OK) return fail("launch", rc);
-            if (D.chooser) HIPCHK(hipEventRecord(D.render_end[k % (2 * kSlots)], D.stream[slot]));
+        if (enabled && has_table) ++table_frames; else ++arith_frames;
+        return 0;
+    }
+};
+
+struct FrameView {             // one frame's times and cameras
+    float sim_t = 0.0f;
+    float fit_t = 0.0f;        // the earliest time the frame reads the noise at: the noise table's window is fitted from it
+    rrt_camera cam;            // the start-up camera until a path moves it
+    float sub_t[16];           // --motion-blur / --dof: the samples' times and cameras
+    rrt_camera sub_cam[16];
+    float focus = 0.0f;
+};
+
+// frame k as main() sees it while recording: the clock (main.cpp:511-516) and the camera of the active path
+int view_frame(int k, const Options& o, FrameView& v) {
+    int rc;
+    float path_t = 0.0f;
+    rrt_recording_clock(k, o.fps, &v.sim_t, &path_t);
+    if (o.path >= 0 && (rc = rrt_path_camera_at(o.path, path_t, &v.cam)) != RRT_OK) return fail("camera", rc);
+    // motion blur: the shutter's sub-times and the path camera at each; the noise table's window is fitted from the earliest
+    v.fit_t = v.sim_t;
+    if (o.motion > 1) {
+        float sub_p[16];
+        rrt_motion_clock(k, o.fps, o.shutter, o.motion, v.sub_t, sub_p);
+        for (int m = 0; m < o.motion; ++m) {
+            v.sub_cam[m] = v.cam;
+            if (o.path >= 0 && (rc = rrt_path_camera_at(o.path, sub_p[m], &v.sub_cam[m])) != RRT_OK) return fail("camera", rc);
         }
-        // 2. one gather: every device sends its shard, device 0 receives all of them (its own included)
-        if (collective) {
-            // Successive frames use the SAME communicators from DIFFERENT streams (slot k mod kSlots).  RCCL orders the
-            // operations of one communicator by itself; the event chain states that order in the stream graph as well:
-            // a device's part of exchange k starts after its part of exchange k-1 has finished, whatever streams they ran on.
-            if (k > 1) for (int d = 0; d < gpus; ++d) { HIPCHK(hipSetDevice(d)); HIPCHK(hipStreamWaitEvent(dev[d].stream[slot], dev[d].comm_free, 0)); }
-            NCCLCHK(ncclGroupStart());
-            for (int d = 0; d < gpus; ++d) {
-                const size_t bytes = (size_t)dev[d].shard_rows * w * 4;
-                if (bytes == 0) continue;
-                NCCLCHK(ncclSend(dev[d].tiles[slot], bytes, ncclUint8, 0, dev[d].comm, dev[d].stream[slot]));
-                NCCLCHK(ncclRecv(static_cast<uint8_t*>(gathered[slot]) + (size_t)d * shard_stride, bytes, ncclUint8, d, dev[0].comm,
-                                 dev[0].stream[slot]));
-            }
-            NCCLCHK(ncclGroupEnd());
-            for (int d = 0; d < gpus; ++d) { HIPCHK(hipSetDevice(d)); HIPCHK(hipEventRecord(dev[d].comm_free, dev[d].stream[slot])); }
-            // 3. device 0 scatters the shards into the bottom-up frame
-            HIPCHK(hipSetDevice(0));
-            if ((rc = rrt_assemble_all_tiles(frame[slot], gathered[slot], shard_stride, w, h, tile_rows, gpus, dev[0].stream[slot])) != RRT_OK)
-                return fail("assemble", rc);
+        v.fit_t = v.sub_t[0];
+    }
+    // depth of field: without a shutter the K samples share the frame's instant; --focus hole: the camera position's distance to
+    // the origin, the double root of the sum of the exact squares in x, y, z order, rounded to float (headless.py's)
+    v.focus = o.dof_focus;
+    if (o.use_dof) {
+        if (o.motion <= 1) for (int m = 0; m < o.dof_k; ++m) { v.sub_t[m] = v.sim_t; v.sub_cam[m] = v.cam; }
+        if (v.focus == 0.0f) {
+            const double x = v.cam.pos[0], y = v.cam.pos[1], z = v.cam.pos[2];
+            v.focus = (float)std::sqrt(x * x + y * y + z * z);
         }
-        // 4. hand the frame to the sink: asynchronous copy now, the write happens one frame later
+    }
+    return 0;
+}
+
+// frame k on device D: its tiles, or with one device the whole frame and the post passes behind it on the same stream
+int launch_frame(Device& D, int slot, int k, const FrameView& v, const Options& o, const rrt_effects& fx, const Slots& R) {
+    HIPCHK(hipSetDevice(D.id));
+    rrt_params prm; rrt_params_default(&prm);
+    prm.spin = o.spin; prm.arith_mode = o.arith;
+    prm.workspace = D.pool[slot]; prm.noise_table = D.noise_table; prm.tile_order = D.order[slot];
+    // frames in flight fill each other's drains: ONE chain per launch (the second chain's streams only compete with the other
+    // frames: 2-7 % per frame, profiles/r05_sustained_chains.txt).  The plain single kernel would be faster still on most views,
+    // but its longest wavefront (up to 19 ms on a disk-grazing view) bounds a slot's frame rate; a moving camera keeps the
+    // path that is never slow
+    prm.pass_chains = o.slots >= 2 ? 1 : 0;
+    // ... per window, by measurement: rrt_path_chooser (csrc/rrt_path_chooser.cpp) tries the single kernel for a few frames
+    // of a window, keeps it where it sustains the faster frames, and drops it at once on a frame that takes > 1.5 x the
+    // three-pass median (same bytes either way)
+    if (D.chooser) { int pol = RRT_PATH_AUTO; rrt_path_chooser_policy(D.chooser, k, &pol); prm.path_policy = pol; }
+    else if (o.path_policy >= 0) prm.path_policy = o.path_policy;
+    void* dst = o.collective ? D.tiles[slot] : R.frame[slot];
+    const hipStream_t st = D.stream[slot];
+    const int w = o.w, h = o.h, ss = o.supersample, rows = o.tile_rows, d = D.id, n = o.gpus;
+    // the stereo / defocused / panorama / blurred / supersampled launch (_stereo, _dof, _pano, _mb, _ss): this device's tiles, or the whole frame and
+    // its HDR (may be NULL)
+    auto launch_sampled = [&](bool tiles, float* lin) {
+        if (o.use_stereo) return tiles ? rrt_launch_raymarch_stereo_tiles(dst, o.ew, o.eh, ss, rows, d, n, &o.proj, &o.stereo, v.sim_t, &v.cam, D.sky, &fx, &prm, st)
+                                       : rrt_launch_raymarch_stereo(dst, lin, o.ew, o.eh, ss, &o.proj, &o.stereo, v.sim_t, &v.cam, D.sky, &fx, &prm, st);
+        if (o.use_dof) return tiles ? rrt_launch_raymarch_dof_tiles(dst, w, h, ss, rows, d, n, o.dof_k, v.sub_t, v.sub_cam, o.dof_xy, v.focus, D.sky, &fx, &prm, st)
+                                    : rrt_launch_raymarch_dof(dst, lin, w, h, ss, o.dof_k, v.sub_t, v.sub_cam, o.dof_xy, v.focus, D.sky, &fx, &prm, st);
+        if (o.pano) return tiles ? rrt_launch_raymarch_pano_tiles(dst, w, h, ss, rows, d, n, &o.proj, v.sim_t, &v.cam, D.sky, &fx, &prm, st)
+                                 : rrt_launch_raymarch_pano(dst, lin, w, h, ss, &o.proj, v.sim_t, &v.cam, D.sky, &fx, &prm, st);
+        if (o.motion > 1) return tiles ? rrt_launch_raymarch_mb_tiles(dst, w, h, ss, rows, d, n, o.motion, v.sub_t, v.sub_cam, D.sky, &fx, &prm, st)
+                                       : rrt_launch_raymarch_mb(dst, lin, w, h, ss, o.motion, v.sub_t, v.sub_cam, D.sky, &fx, &prm, st);
+        return tiles ? rrt_launch_raymarch_ss_tiles(dst, w, h, ss, rows, d, n, v.sim_t, &v.cam, D.sky, &fx, &prm, st)
+                     : rrt_launch_raymarch_ss(dst, lin, w, h, ss, v.sim_t, &v.cam, D.sky, &fx, &prm, st);
+    };
+    // --adaptive: one device (check_options), the whole frame and its HDR (may be NULL); the count of refined pixels follows
+    // in a 4-byte asynchronous copy, read when the frame is delivered
+    auto launch_adaptive = [&](float* lin) {
+        const int rc = rrt_launch_raymarch_adaptive(dst, lin, w, h, ss, o.pano ? &o.proj : nullptr, &o.adaptive, v.sim_t, &v.cam, D.sky,
+                                                    &fx, &prm, R.ad_scratch[slot], R.ad_bytes, st);
+        if (rc == RRT_OK && hipMemcpyAsync(R.ad_count[slot], R.ad_scratch[slot], 4, hipMemcpyDeviceToHost, st) != hipSuccess)
+            return (int)RRT_ERR_HIP;
+        return rc;
+    };
+    int rc;
+    if (o.use_glow || o.use_exposure) {     // one device (check_options): the slot's HDR through launch_sampled, then the post passes on the same stream
+        float* lin = static_cast<float*>(R.hdr[slot]);
+        rc = o.use_adaptive ? launch_adaptive(lin) : launch_sampled(false, lin);
+        if (rc == RRT_OK && o.use_exposure) {     // the bytes -- or, in front of the glow, the scaled HDR in place
+            if (o.auto_exposure) HIPCHK(hipStreamWaitEvent(st, R.exposed, 0));
+            rc = rrt_launch_exposure(o.use_glow ? nullptr : dst, o.use_glow ? lin : nullptr, lin, w, h, &o.exposure, R.exposure_scratch,
+                                     R.exposure_bytes, st);
+            if (o.auto_exposure) HIPCHK(hipEventRecord(R.exposed, st));
+        }
+        if (rc == RRT_OK && o.use_glow) rc = rrt_launch_glow(dst, lin, w, h, &o.glow, R.glow_scratch[slot], o.glow_bytes, st);
+    }
+    else if (o.use_adaptive) rc = launch_adaptive(nullptr);
+    else if (o.use_stereo || o.use_dof || o.pano || o.motion > 1 || ss > 1) rc = launch_sampled(o.collective, nullptr);
+    else if (o.collective) rc = rrt_launch_raymarch_tiles(dst, w, h, rows, d, n, v.sim_t, &v.cam, D.sky, &fx, &prm, st);
+    else rc = rrt_launch_raymarch(dst, w, h, v.sim_t, &v.cam, D.sky, &fx, &prm, st);
+    if (rc != RRT_OK) return fail("launch", rc);
+    if (D.chooser) HIPCHK(hipEventRecord(D.render_end[k % (2 * o.slots)], st));
+    return 0;
+}
+
+// one gather: every device sends its shard, device 0 receives all of them (its own included) and scatters them into the frame
+int gather_frame(std::vector<Device>& dev, int slot, int k, const Options& o, const Slots& R) {
+    // Successive frames use the SAME communicators from DIFFERENT streams (slot k mod slots).  RCCL orders the
+    // operations of one communicator by itself; the event chain states that order in the stream graph as well:
+    // a device's part of exchange k starts after its part of exchange k-1 has finished, whatever streams they ran on.
+    if (k > 1) for (Device& D : dev) { HIPCHK(hipSetDevice(D.id)); HIPCHK(hipStreamWaitEvent(D.stream[slot], D.comm_free, 0)); }
+    NCCLCHK(ncclGroupStart());
+    for (Device& D : dev) {
+        const size_t bytes = (size_t)D.shard_rows * o.w * 4;
+        if (bytes == 0) continue;
+        NCCLCHK(ncclSend(D.tiles[slot], bytes, ncclUint8, 0, D.comm, D.stream[slot]));
+        NCCLCHK(ncclRecv(static_cast<uint8_t*>(R.gathered[slot]) + (size_t)D.id * R.shard_stride, bytes, ncclUint8, D.id, dev[0].comm,
+                         dev[0].stream[slot]));
+    }
+    NCCLCHK(ncclGroupEnd());
+    for (Device& D : dev) { HIPCHK(hipSetDevice(D.id)); HIPCHK(hipEventRecord(D.comm_free, D.stream[slot])); }
+    // device 0 scatters the shards into the bottom-up frame
+    HIPCHK(hipSetDevice(0));
+    const int rc = rrt_assemble_all_tiles(R.frame[slot], R.gathered[slot], R.shard_stride, o.w, o.h, o.tile_rows, o.gpus, dev[0].stream[slot]);
+    return rc == RRT_OK ? 0 : fail("assemble", rc);
+}
+
+// ---- the summary line
+
+__attribute__((format(printf, 2, 3))) void appendf(std::string& s, const char* fmt, ...) {
+    va_list ap, again;
+    va_start(ap, fmt);
+    va_copy(again, ap);
+    const int n = vsnprintf(nullptr, 0, fmt, ap);
+    va_end(ap);
+    if (n > 0) {
+        const size_t at = s.size();
+        s.resize(at + (size_t)n + 1);
+        vsnprintf(&s[at], (size_t)n + 1, fmt, again);
+        s.resize(at + (size_t)n);
+    }
+    va_end(again);
+}
+
+struct Totals {                // what the frame loop measured
+    double seconds = 0.0;
+    unsigned long long refined = 0;   // --adaptive: refined pixels over all frames
+    float final_ev = 0.0f;            // --exposure / --auto-exposure: the EV after the last frame
+};
+
+std::string summary_line(const Options& o, const std::vector<Device>& dev, const NoiseWindow& nw, const char* path_name, const Totals& t) {
+    const double dt = t.seconds;
+    std::string s;
+    appendf(s, "{\"frames\": %d, \"width\": %d, \"height\": %d, \"n_gpus\": %d, \"seconds\": %.4f, \"fps\": %.3f, \"Mrays_per_s\": %.3f, ",
+            o.frames, o.w, o.h, o.gpus, dt, o.frames / dt, (double)o.frames * o.w * o.h / dt / 1e6);
+    appendf(s, "\"path\": \"%s\", \"spin\": %g, \"arith_mode\": \"%s\", \"noise_tables\": {\"builds\": %d, \"table_frames\": %d, "
+            "\"arith_frames\": %d, \"coarsest_coverage\": %d, \"peak_bytes\": %zu, \"budget_bytes\": %zu}, \"tile_order\": %s, \"collective\": \"%s\", ",
+            path_name, o.spin, o.arith == RRT_ARITH_FAST ? "fast" : (o.arith == RRT_ARITH_FMAD ? "fmad" : "strict"),
+            nw.builds, nw.table_frames, nw.arith_frames, nw.coarsest, nw.peak, nw.budget, dev[0].order[0] ? "true" : "false",
+            o.collective ? "rccl grouped send/recv gather" : "none");
+    s += "\"path_choice\": ";
+    if (dev[0].chooser) {
+        for (const Device& D : dev) {
+            rrt_path_chooser_stats st;
+            rrt_path_chooser_get_stats(D.chooser, &st);
+            appendf(s, "%s{\"device\": %d, \"frames_three_pass\": %d, \"frames_single_kernel\": %d, \"windows\": %d, \"trials\": %d, "
+                    "\"trials_aborted\": %d, \"switches\": %d, \"outliers\": %d}", D.id ? ", " : "[", D.id, st.frames[0], st.frames[1], st.windows, st.trials,
+                    st.trials_aborted, st.switches, st.outliers);
+        }
+        s += "]";
+    } else s += "null";
+    appendf(s, ", \"supersample\": %d, \"motion_blur\": %d, \"shutter\": %g, \"glow\": ", o.supersample, o.motion, o.shutter);
+    if (o.use_glow) appendf(s, "{\"radius\": %g, \"lobes\": %d, \"threshold\": %g, \"intensity\": %g}", o.glow.radius, o.glow.lobes,
+                            o.glow.threshold, o.glow.intensity);
+    else s += "null";
+    appendf(s, ", \"projection\": \"%s\", \"fov_deg\": ",
+            o.projection == RRT_PROJ_EQUIRECT ? "equirect" : (o.projection == RRT_PROJ_FISHEYE ? "fisheye" : "pinhole"));
+    if (o.pano) appendf(s, "%g", o.proj.fov_deg); else s += "null";
+    s += ", \"vfov_deg\": ";
+    if (o.projection == RRT_PROJ_EQUIRECT) appendf(s, "%g", o.proj.vfov_deg); else s += "null";
+    s += ", \"stereo\": ";
+    if (o.use_stereo) appendf(s, "{\"layout\": \"%s\", \"base\": %.17g, \"convergence\": %.17g, \"pole_merge_deg\": [%.17g, %.17g]}",
+                              o.stereo_layout == RRT_STEREO_TOP_BOTTOM ? "top-bottom" : "side-by-side", o.stereo.base, o.stereo.convergence,
+                              o.stereo.pole_merge_from_deg, o.stereo.pole_merge_to_deg);
+    else s += "null";
+    s += ", \"dof\": ";
+    if (o.use_dof) {
+        appendf(s, "{\"aperture\": %.9g, \"focus\": ", o.dof_aperture);
+        if (o.dof_focus == 0.0f) s += "\"hole\""; else appendf(s, "%.9g", o.dof_focus);
+        appendf(s, ", \"samples\": %d}", o.dof_k);
+    } else s += "null";
+    s += ", \"adaptive\": ";
+    if (o.use_adaptive) appendf(s, "{\"threshold\": %d, \"refined_fraction\": %.9g}", o.adaptive.threshold,
+                                o.frames > 0 ? (double)t.refined / ((double)o.frames * o.w * o.h) : 0.0);
+    else s += "null";
+    s += ", \"exposure\": ";
+    if (o.use_exposure) {
+        const rrt_exposure& e = o.exposure;
+        appendf(s, "{\"mode\": \"%s\", \"ev\": %.9g, \"key\": %.9g, \"low_permille\": %d, \"high_permille\": %d, \"min_ev\": %.9g, "
+                "\"max_ev\": %.9g, \"adapt_up\": %.9g, \"adapt_down\": %.9g, \"final_ev\": %.9g}", o.auto_exposure ? "auto" : "manual", e.ev,
+                e.key, e.low_permille, e.high_permille, e.min_ev, e.max_ev, e.adapt_up, e.adapt_down, t.final_ev);
+    } else s += "null";
+    /* which path the frames took through each device's march cache (launches without a workspace: one GPU, or --workspace-gib 0) */
+    s += ", \"march_cache\": ";
+    for (const Device& D : dev) {
+        rrt_march_cache_info mc = {};
+        (void)rrt_march_cache_stats(D.id, &mc);
+        appendf(s, "%s{\"device\": %d, \"fills\": %llu, \"hits\": %llu, \"drops\": %llu, \"misses\": %llu, \"uncacheable\": %llu, "
+                "\"bytes\": %llu, \"max_bytes\": %llu}", D.id ? ", " : "[", D.id, (unsigned long long)mc.fills, (unsigned long long)mc.hits,
+                (unsigned long long)mc.drops, (unsigned long long)mc.misses, (unsigned long long)mc.uncacheable, (unsigned long long)mc.bytes,
+                (unsigned long long)mc.max_bytes);
+    }
+    s += "]}\n";
+    return s;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+    Options o;
+    int rc;
+    if ((rc = parse_options(argc, argv, o)) != 0 || (rc = check_options(o)) != 0) return rc;
+    int n_dev = 0;
+    if ((rc = rrt_device_count(&n_dev)) != RRT_OK) return fail("no GPU", rc);
+    if (o.gpus > n_dev) { fprintf(stderr, "rrt_headless: --gpus %d but %d device(s) visible\n", o.gpus, n_dev); return 2; }
+    trace("start");
+    std::thread dog(watchdog, o.init_timeout, o.frame_timeout);
+    struct DogStop { std::thread& t; ~DogStop() { g_tr.stop.store(true); t.join(); } } dog_stop{dog};      // every return path
+    // the RCCL library's pages, read sequentially in the background while the per-device resources are set up
+    std::thread warm;
+    if (o.collective && !getenv("RRT_NO_LIBRARY_WARMUP")) warm = std::thread(warm_library_pages, (const void*)&ncclCommInitAll);
+    struct WarmJoin { std::thread& t; ~WarmJoin() { if (t.joinable()) t.join(); } } warm_join{warm};
+    // a failing communicator says why (RCCL prints nothing below WARN); the caller's setting wins
+    if (o.collective) setenv("NCCL_DEBUG", "WARN", 0);
+    // one process, one node: RCCL's bootstrap and RAS sockets need no interface but the loopback (by default it picks
+    // the first non-loopback one -- in a container a veth whose state is not this program's business)
+    if (o.collective) setenv("NCCL_SOCKET_IFNAME", "lo", 0);
+
+    // the recording clock (main.cpp:511-516) says which times the sequence reaches; the tables slide along it
+    float seq_end = 0.0f;
+    { float unused = 0.0f; rrt_recording_clock(o.frames, o.fps, &seq_end, &unused); seq_end += 1.0f; }
+    const size_t table_budget = o.table_gib > 0.0 ? (size_t)(o.table_gib * (double)(1ull << 30)) : 0;
+    NoiseWindow noise{o.use_table && table_budget != 0, table_budget, seq_end};
+
+    std::vector<uint8_t> sky;
+    int sky_w = 2048, sky_h = 1024;
+    if (o.sky_path.empty()) sky = synthetic_sky(sky_w, sky_h, o.sky_seed);
+    else if (!load_sky_raw(o.sky_path, sky, sky_w, sky_h)) return 2;
+    rrt_effects fx; rrt_effects_default(&fx);
+    fx.use_chromatic_aberration = (uint8_t)o.all_fx;
+
+    // ---- bring-up: per-device resources, the communicators, device 0's slots, the sink
+    std::vector<Device> dev(o.gpus);
+    Slots R;
+    plan_shards(o, dev, R);
+    for (Device& D : dev) if (create_device(D, o, sky, sky_w, sky_h, R.shard_stride)) return 1;
+    trace("per-device resources ready");
+    if (o.collective && create_communicators(dev, warm)) return 1;
+    FILE* f = o.out_path.empty() ? nullptr : fopen(o.out_path.c_str(), "wb");
+    if (!o.out_path.empty() && !f) { perror("fopen"); return 1; }
+    if (create_slots(R, o, f != nullptr, dev[0].stream[0])) return 1;
+    FrameView view;
+    const float start_pos[3] = {0.0f, 10.0f, -60.0f};
+    rrt_camera_from_angles(start_pos, 0.0f, -10.0f, &view.cam);
+    const char* path_name = "";
+    if (o.path >= 0 && (rc = rrt_path_info(o.path, &path_name, nullptr, nullptr)) != RRT_OK) return fail("path", rc);
+
+    // write frame `k`'s pixels once its copy has landed (called one frame late, so that the copy overlaps the next render)
+    // (without a sink the wait still happens: the host never runs more than `slots` frames ahead of the device, a device
+    // fault is reported at the frame it belongs to, and the watchdog sees frames complete)
+    Totals totals;
+    int delivered = 0;
+    auto deliver = [&](int slot) -> int {
+        HIPCHK(hipEventSynchronize(R.done[slot]));
+        trace("frame complete", ++delivered);
+        if (o.use_adaptive) totals.refined += *static_cast<const uint32_t*>(R.ad_count[slot]);
+        // frame `delivered` has been rendered on every device (the gather waited for all shards): its sustained time on a device =
+        // the interval between the ends of frame delivered - 1's and its own render there
+        if (delivered >= 2) for (Device& D : dev) if (D.chooser) {
+            float ms = 0.0f;
+            HIPCHK(hipSetDevice(D.id));
+            if (hipEventElapsedTime(&ms, D.render_end[(delivered - 1) % (2 * o.slots)], D.render_end[delivered % (2 * o.slots)]) == hipSuccess)
+                rrt_path_chooser_report(D.chooser, delivered, ms > 0.0f ? ms : 0.0f);   // (a frame that ended before its predecessor: 0)
+        }
+        if (f && fwrite(R.host[slot], 1, R.frame_bytes, f) != R.frame_bytes) fprintf(stderr, "Warning: Frame write incomplete\n");
+        return 0;
+    };
+
+    for (Device& D : dev) { HIPCHK(hipSetDevice(D.id)); HIPCHK(hipDeviceSynchronize()); }
+    trace("bring-up complete; rendering");
+    g_tr.in_frames.store(true);
+    auto t0 = std::chrono::steady_clock::now();
+    for (int k = 1; k <= o.frames; ++k) {
+        const int slot = k % o.slots;
+        if (view_frame(k, o, view)) return 1;
+        trace("frame", k);
+        // slot reuse: frame k-slots used the same buffers; its host copy must have been written out
+        if (k > o.slots && deliver(slot)) return 1;
+        if (noise.slide(view.fit_t, k, dev)) return 1;
+        for (Device& D : dev) if (launch_frame(D, slot, k, view, o, fx, R)) return 1;
+        if (o.collective && gather_frame(dev, slot, k, o, R)) return 1;
+        // hand the frame to the sink: asynchronous copy now, the write happens one frame later
         HIPCHK(hipSetDevice(0));
-        if (f) HIPCHK(hipMemcpyAsync(host[slot], frame[slot], frame_bytes, hipMemcpyDeviceToHost, dev[0].stream[slot]));
-        HIPCHK(hipEventRecord(done[slot], dev[0].stream[slot]));
+        if (f) HIPCHK(hipMemcpyAsync(R.host[slot], R.frame[slot], R.frame_bytes, hipMemcpyDeviceToHost, dev[0].stream[slot]));
+        HIPCHK(hipEventRecord(R.done[slot], dev[0].stream[slot]));
     }
     trace("all frames enqueued; draining");
-    // drain: the last min(frames, kSlots) frames, oldest first
-    for (int k = frames - kSlots + 1; k <= frames; ++k)
-        if (k >= 1 && deliver(k % kSlots)) return 1;
-    for (int d = 0; d < gpus; ++d) { HIPCHK(hipSetDevice(d)); HIPCHK(hipDeviceSynchronize()); }
-    const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    // drain: the last min(frames, slots) frames, oldest first
+    for (int k = o.frames - o.slots + 1; k <= o.frames; ++k)
+        if (k >= 1 && deliver(k % o.slots)) return 1;
+    for (Device& D : dev) { HIPCHK(hipSetDevice(D.id)); HIPCHK(hipDeviceSynchronize()); }
+    totals.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (f) fclose(f);
-    std::string choice = "null";
-    if (dev[0].chooser) {
-        choice = "[";
-        for (int d = 0; d < gpus; ++d) {
-            rrt_path_chooser_stats st;
-            rrt_path_chooser_get_stats(dev[d].chooser, &st);
-            char buf[256];
-            snprintf(buf, sizeof(buf), "%s{\"device\": %d, \"frames_three_pass\": %d, \"frames_single_kernel\": %d, \"windows\": %d, \"trials\": %d, "
-                     "\"trials_aborted\": %d, \"switches\": %d, \"outliers\": %d}", d ? ", " : "", d, st.frames[0], st.frames[1], st.windows, st.trials,
-                     st.trials_aborted, st.switches, st.outliers);
-            choice += buf;
-        }
-        choice += "]";
-    }
-    std::string glow_json = "null";
-    if (use_glow) {
-        char buf[160];
-        snprintf(buf, sizeof(buf), "{\"radius\": %g, \"lobes\": %d, \"threshold\": %g, \"intensity\": %g}", glow.radius, glow.lobes,
-                 glow.threshold, glow.intensity);
-        glow_json = buf;
-    }
-    std::string exposure_json = "null";
-    if (use_exposure) {     // the final EV: one 4-byte read of the state, after the last frame
-        float final_ev = exposure.ev;
-        if (auto_exposure) HIPCHK(hipMemcpy(&final_ev, static_cast<const uint8_t*>(exposure_scratch) + RRT_EXPOSURE_STATE_OFFSET, 4, hipMemcpyDeviceToHost));
-        char buf[400];
-        snprintf(buf, sizeof(buf), "{\"mode\": \"%s\", \"ev\": %.9g, \"key\": %.9g, \"low_permille\": %d, \"high_permille\": %d, \"min_ev\": %.9g, "
-                 "\"max_ev\": %.9g, \"adapt_up\": %.9g, \"adapt_down\": %.9g, \"final_ev\": %.9g}", auto_exposure ? "auto" : "manual", exposure.ev,
-                 exposure.key, exposure.low_permille, exposure.high_permille, exposure.min_ev, exposure.max_ev, exposure.adapt_up,
-                 exposure.adapt_down, final_ev);
-        exposure_json = buf;
-    }
-    const char* proj_name = projection == RRT_PROJ_EQUIRECT ? "equirect" : (projection == RRT_PROJ_FISHEYE ? "fisheye" : "pinhole");
-    char fov_json[32] = "null", vfov_json[32] = "null";
-    if (pano) snprintf(fov_json, sizeof(fov_json), "%g", proj.fov_deg);
-    if (projection == RRT_PROJ_EQUIRECT) snprintf(vfov_json, sizeof(vfov_json), "%g", proj.vfov_deg);
-    std::string stereo_json = "null";
-    if (use_stereo) {
-        char buf[200];
-        snprintf(buf, sizeof(buf), "{\"layout\": \"%s\", \"base\": %.17g, \"convergence\": %.17g, \"pole_merge_deg\": [%.17g, %.17g]}",
-                 stereo_layout == RRT_STEREO_TOP_BOTTOM ? "top-bottom" : "side-by-side", stereo.base, stereo.convergence,
-                 stereo.pole_merge_from_deg, stereo.pole_merge_to_deg);
-        stereo_json = buf;
-    }
-    std::string adaptive_json = "null";
-    if (use_adaptive) {
-        char buf[128];
-        snprintf(buf, sizeof(buf), "{\"threshold\": %d, \"refined_fraction\": %.9g}", adaptive.threshold,
-                 frames > 0 ? (double)refined_total / ((double)frames * w * h) : 0.0);
-        adaptive_json = buf;
-    }
-    std::string dof_json = "null";
-    if (use_dof) {
-        char buf[160], z[40];
-        if (dof_focus == 0.0f) snprintf(z, sizeof(z), "\"hole\""); else snprintf(z, sizeof(z), "%.9g", dof_focus);
-        snprintf(buf, sizeof(buf), "{\"aperture\": %.9g, \"focus\": %s, \"samples\": %d}", dof_aperture, z, dof_k);
-        dof_json = buf;
-    }
-    /* which path the frames took through each device's march cache (launches without a workspace: one GPU, or --workspace-gib 0) */
-    std::string cache_json = "[";
-    for (int d = 0; d < gpus; ++d) {
-        rrt_march_cache_info mc = {};
-        (void)rrt_march_cache_stats(d, &mc);
-        char buf[256];
-        snprintf(buf, sizeof(buf), "%s{\"device\": %d, \"fills\": %llu, \"hits\": %llu, \"drops\": %llu, \"misses\": %llu, \"uncacheable\": %llu, "
-                 "\"bytes\": %llu, \"max_bytes\": %llu}", d ? ", " : "", d, (unsigned long long)mc.fills, (unsigned long long)mc.hits,
-                 (unsigned long long)mc.drops, (unsigned long long)mc.misses, (unsigned long long)mc.uncacheable, (unsigned long long)mc.bytes,
-                 (unsigned long long)mc.max_bytes);
-        cache_json += buf;
-    }
-    cache_json += "]";
-    printf("{\"frames\": %d, \"width\": %d, \"height\": %d, \"n_gpus\": %d, \"seconds\": %.4f, \"fps\": %.3f, \"Mrays_per_s\": %.3f, "
-           "\"path\": \"%s\", \"spin\": %g, \"arith_mode\": \"%s\", \"noise_tables\": {\"builds\": %d, \"table_frames\": %d, "
-           "\"arith_frames\": %d, \"coarsest_coverage\": %d, \"peak_bytes\": %zu, \"budget_bytes\": %zu}, \"tile_order\": %s, \"collective\": \"%s\", "
-           "\"path_choice\": %s, \"supersample\": %d, \"motion_blur\": %d, \"shutter\": %g, \"glow\": %s, "
-           "\"projection\": \"%s\", \"fov_deg\": %s, \"vfov_deg\": %s, \"stereo\": %s, \"dof\": %s, \"adaptive\": %s, \"exposure\": %s, "
-           "\"march_cache\": %s}\n",
-           frames, w, h, gpus, dt, frames / dt, (double)frames * w * h / dt / 1e6, path_name, spin,
-           arith == RRT_ARITH_FAST ? "fast" : (arith == RRT_ARITH_FMAD ? "fmad" : "strict"),
-           table_builds, table_frames, arith_frames, coarsest, table_peak, table_budget, dev[0].order[0] ? "true" : "false",
-           collective ? "rccl grouped send/recv gather" : "none", choice.c_str(), supersample, motion, shutter, glow_json.c_str(),
-           proj_name, fov_json, vfov_json, stereo_json.c_str(), dof_json.c_str(), adaptive_json.c_str(), exposure_json.c_str(),
-           cache_json.c_str());
+    totals.final_ev = o.exposure.ev;        // the final EV: one 4-byte read of the state, after the last frame
+    if (o.auto_exposure) HIPCHK(hipMemcpy(&totals.final_ev, static_cast<const uint8_t*>(R.exposure_scratch) + RRT_EXPOSURE_STATE_OFFSET, 4, hipMemcpyDeviceToHost));
+    fputs(summary_line(o, dev, noise, path_name, totals).c_str(), stdout);
 
-    for (int d = 0; d < gpus; ++d) {
-        Device& D = dev[d];
-        HIPCHK(hipSetDevice(d));
-        if (D.comm) ncclCommDestroy(D.comm);
-        (void)hipFree(D.probe);
-        (void)hipEventDestroy(D.comm_free);
-        if (D.chooser) { rrt_path_chooser_destroy(D.chooser); for (int e = 0; e < 2 * kSlots; ++e) (void)hipEventDestroy(D.render_end[e]); }
-        for (int s = 0; s < kSlots; ++s) {
-            if (D.pool[s]) rrt_workspace_destroy(D.pool[s]);
-            if (D.order[s]) rrt_tile_order_destroy(D.order[s]);
-            (void)hipFree(D.tiles[s]);
-            (void)hipStreamDestroy(D.stream[s]);
-        }
-        if (D.noise_table) rrt_noise_table_destroy(D.noise_table);
-        rrt_sky_destroy(D.sky);
-    }
+    for (Device& D : dev) { HIPCHK(hipSetDevice(D.id)); destroy_device(D, o.slots); }
     HIPCHK(hipSetDevice(0));
-    (void)hipFree(exposure_scratch);
-    if (exposed) (void)hipEventDestroy(exposed);
-    for (int s = 0; s < kSlots; ++s) {
-        (void)hipFree(gathered[s]); (void)hipFree(frame[s]); (void)hipFree(hdr[s]); (void)hipFree(glow_scratch[s]);
-        (void)hipFree(ad_scratch[s]);
-        if (ad_count[s]) (void)hipHostFree(ad_count[s]);
-        if (host[s]) (void)hipHostFree(host[s]);
-    }
+    destroy_slots(R, o.slots);
     return 0;
 }

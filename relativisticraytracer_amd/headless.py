@@ -23,6 +23,8 @@ import os
 import sys
 import time
 
+import relativisticraytracer_amd as rrt
+
 
 def _threshold(text):
     """--adaptive's T: a whole number in 0 ... 255, and one message for whatever is not (rrt_headless.cpp's)"""
@@ -64,7 +66,7 @@ def hole_distance(cam):
     return float(np.float32(math.sqrt(x * x + y * y + z * z)))
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(prog="relativisticraytracer_amd.headless")
     ap.add_argument("--width", type=int, default=1000)          # WINDOW_WIDTH, config.h:7
     ap.add_argument("--height", type=int, default=700)          # WINDOW_HEIGHT, config.h:8
@@ -164,17 +166,22 @@ def main(argv=None):
                     help="several ranks: seconds the process-group bring-up may take before the run exits non-zero with "
                          "the tracebacks of all threads, instead of hanging")
     ap.add_argument("--frame-timeout", type=float, default=120.0, help="the same for any single frame (0: no limit)")
-    args = ap.parse_args(argv)
+    return ap
+
+
+def check_args(ap, args, world):
+    """every refusal that needs neither torch nor the library, in the order that decides which message a command line gets;
+    returns pano, use_exposure, dof_k (lens samples per sub-sample; 0: no --dof)"""
     if not 0.0 <= args.shutter <= 1.0:
         ap.error("--shutter: a fraction of the frame interval in [0, 1]")
     # the glow needs the whole frame's HDR on one GPU (no _tiles form); checked before any device is touched
-    if args.glow is not None and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+    if args.glow is not None and world > 1:
         ap.error("--glow: one GPU only (WORLD_SIZE > 1)")
     # exposure control needs the whole frame's HDR on one GPU as well (the meter sees every pixel; no _tiles form)
     use_exposure = args.exposure is not None or args.auto_exposure is not None
     if not use_exposure and (args.exposure_speed is not None or args.exposure_range is not None or args.exposure_percentiles is not None):
         ap.error("--exposure-speed / --exposure-range / --exposure-percentiles need --exposure EV | --auto-exposure [KEY]")
-    if use_exposure and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+    if use_exposure and world > 1:
         ap.error("--exposure / --auto-exposure: one GPU only (WORLD_SIZE > 1)")
     pano = args.projection != "pinhole"
     if not pano and (args.fov is not None or args.vfov is not None):
@@ -203,7 +210,7 @@ def main(argv=None):
     if args.adaptive is not None:       # the whole frame on one GPU (the mask needs every pixel's neighbours); before any device is touched
         if args.supersample <= 1:
             ap.error("--adaptive needs --supersample 2 | 4 | 8")
-        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        if world > 1:
             ap.error("--adaptive: one GPU only (WORLD_SIZE > 1)")
         if args.motion_blur > 1:
             ap.error("--adaptive renders one instant per frame (--motion-blur 1)")
@@ -225,25 +232,12 @@ def main(argv=None):
         if args.motion_blur > 1 and args.dof_samples not in (None, args.motion_blur):
             ap.error("--dof-samples: with --motion-blur M > 1 the lens samples are the shutter's sub-frames (K = M)")
         dof_k = args.motion_blur if args.motion_blur > 1 else (args.dof_samples or 8)
+    return pano, use_exposure, dof_k
 
-    t_start = time.perf_counter()
 
-    def trace(what):        # RRT_HEADLESS_TRACE=1: where the start-up time goes (stderr), as in csrc/rrt_headless.cpp
-        dest = os.environ.get("RRT_HEADLESS_TRACE")        # "1": stderr; anything else: a file to append to
-        if dest:
-            line = f"[headless.py pid {os.getpid()} +{time.perf_counter() - t_start:7.2f}s] {what}"
-            if dest == "1":
-                print(line, file=sys.stderr, flush=True)
-            else:
-                with open(dest, "a") as fh:
-                    print(line, file=fh)
-
-    trace("importing torch")
-    import torch
-    trace("torch imported")
-    import relativisticraytracer_amd as rrt
-    from relativisticraytracer_amd import camera_paths, sharding, sinks
-    from relativisticraytracer_amd.sky import load_sky, synthetic_sky
+def build_settings(ap, args, pano, use_exposure):
+    """proj, stereo, glow, exposure (None: not asked for), each checked by the library's own host query: the launches' refusals,
+    stated before any device is touched"""
     proj = None
     if pano:                        # the spans' checks are the host query's (rrt_projection_ray): the launch's own refusals
         proj = rrt.Projection(args.projection, args.fov, args.vfov)
@@ -267,7 +261,7 @@ def main(argv=None):
             ap.error("--glow INTENSITY >= 0, --glow-radius R > 0 (a fraction of the height; widest lobe <= 1024 px), "
                      "--glow-threshold T >= 0")
     exposure = None
-    if use_exposure:                # the settings' ranges are rrt_launch_exposure's own refusals, stated here before any device is touched
+    if use_exposure:                # the settings' ranges are rrt_launch_exposure's own refusals
         up, down = args.exposure_speed or (0.0, 0.0)
         lo_ev, hi_ev = args.exposure_range or (-8.0, 8.0)
         low, high = args.exposure_percentiles or (400, 20)
@@ -283,8 +277,235 @@ def main(argv=None):
         exposure = rrt.ExposureSettings(mode="auto" if args.auto_exposure is not None else "manual", ev=args.exposure or 0.0, key=key,
                                         low_permille=low, high_permille=high, min_ev=lo_ev, max_ev=hi_ev,
                                         adapt_up=float(alphas[0]), adapt_down=float(alphas[1]))
+    return proj, stereo, glow, exposure
 
-    world = int(os.environ.get("WORLD_SIZE", "1")); rank = int(os.environ.get("RANK", "0"))
+
+class Renderer:
+    """One rank's frames.  What the command line fixes -- sizes, settings, launch parameters per slot, buffers -- is set once in
+    __init__; `set_frame` sets the frame that the render methods launch: k, t, cam, table, and times / cams / focus for the kinds
+    that sample the shutter or the lens."""
+
+    def __init__(self, args, settings, dof_k, rank, world, dev):
+        import torch
+        from relativisticraytracer_amd import camera_paths, sharding
+        from relativisticraytracer_amd.sky import load_sky, synthetic_sky
+        self.args, self.rank, self.world, self.dof_k = args, rank, world, dof_k
+        self.proj, self.stereo, self.glow, self.exposure = settings
+        proj, stereo, glow, exposure = settings
+        self.ew, self.eh = ew, eh = args.width, args.height     # the launch's frame: one eye's with --stereo
+        self.w, self.h = w, h = stereo.composite(ew, eh) if stereo is not None else (ew, eh)     # the frame that is sharded, gathered and written
+        self.ss, self.mb = ss, mb = args.supersample, args.motion_blur
+        self.sampled = proj is not None or mb > 1 or ss > 1 or stereo is not None or dof_k > 0      # launch_sampled's kinds
+        self.post = glow is not None or exposure is not None
+        # supersampled, blurred, glowed, panorama, stereo: single kernel, static order, no pool
+        single = self.sampled or self.post
+        # sample m looks through lens point bitrev_K(m): the spiral's radius grows with its index, the shutter's times with m
+        self.dof_points = rrt.lens_points(args.dof, dof_k)[[bit_reverse(m, dof_k) for m in range(dof_k)]] if dof_k else None
+        self.tex = rrt.SkyTexture(load_sky(args.sky) if args.sky else synthetic_sky())
+        self.fx = rrt.CameraEffects(useChromaticAberration=bool(args.all_effects))
+        # with several ranks --frames-in-flight frames are in flight (FrameSharder pipeline mode), each with its own
+        # share of the pool
+        self.n_slots = n_slots = max(2, args.frames_in_flight) if world > 1 else 1
+        self.pools = pools = ([rrt.Workspace((args.workspace_gib << 30) // n_slots) for _ in range(n_slots)]
+                              if args.workspace_gib > 0 and not single else [])
+        # cost-ordered dispatch pays on single-kernel launches whose frames do not overlap; on the three-pass path (small launches
+        # with a pool) it piles the expensive tiles into the first of the two chains and was measured slower: auto leaves it off there
+        my_rays = w * sharding.shard_rows(h, args.tile_rows, rank, world)
+        three_pass_likely = bool(pools) and my_rays <= rrt._lib.load().rrt_path_auto_max_rays()      # RRT_PATH_AUTO's own threshold
+        use_order = not single and (args.tile_order == "on" or (args.tile_order == "auto" and n_slots == 1 and not three_pass_likely))
+        self.orders = orders = [rrt.TileOrder() for _ in range(n_slots)] if use_order else []
+        self.arith_name = args.arith or ("fast" if args.fast else "strict")
+        arith_mode = {"strict": 0, "fast": 1, "fmad": 2}[self.arith_name]
+        # the path of a small share under frames in flight is chosen per window by measurement (sharding.PathChooser; the rule and the
+        # numbers behind it: csrc/rrt_path_chooser.cpp); RRT_PATH_POLICY pins it
+        self.chooser = (sharding.PathChooser(n_slots, args.path_window)
+                        if (args.path_window >= 0 and n_slots >= 2 and three_pass_likely and "RRT_PATH_POLICY" not in os.environ) else None)
+        self.ends = {}                 # frame -> the event at the end of its render on this rank
+        self.prms = [rrt.RenderParams(spin=args.spin, volumetrics=0 if args.no_volumetrics else 1,
+                                      noise_table=0, tile_order=orders[j].id if orders else 0,
+                                      arith_mode=arith_mode, workspace=pools[j].id if pools else 0,
+                                      # frames in flight fill each other's drains: ONE chain per launch (the second chain's streams only compete with
+                                      # the other frames: 2-7 % per frame, profiles/r05_sustained_chains.txt).  Which PATH a small share takes --
+                                      # the three-pass path, or the plain single kernel, which is 6-8 % faster unless the share holds a wavefront that
+                                      # outlasts the frames in flight -- is chosen per window by measurement (chooser, above; round 6)
+                                      pass_chains=1 if n_slots >= 2 else 0,
+                                      path_policy=int(os.environ.get("RRT_PATH_POLICY", "0"))) for j in range(n_slots)]
+        self.path = camera_paths.CameraPath(args.path) if args.path >= 0 else None
+        self.k, self.t, self.cam, self.table = 0, 0.0, rrt.CameraState.default(), 0
+        self.times = self.cams = self.focus = None
+        if self.post:               # one rank (check_args): the whole frame's HDR, the glow's scratch, the finished frame
+            self.hdr = torch.zeros(h * w * 4, dtype=torch.float32, device=dev)
+            self.frame = torch.zeros(h * w * 4, dtype=torch.uint8, device=dev)
+        if glow is not None:
+            self.glow_scratch = torch.empty(rrt.glow_scratch_bytes(w, h, glow), dtype=torch.uint8, device=dev)
+        self.exposure_scratch = None
+        if exposure is not None and exposure.mode == rrt.EXPOSURE_AUTO:     # the state the sequence's frames share
+            self.exposure_scratch = torch.empty(rrt.exposure_scratch_bytes(), dtype=torch.uint8, device=dev)
+            rrt.launch_exposure_reset(self.exposure_scratch)
+        self.adaptive = None
+        if args.adaptive is not None:   # one rank (check_args): the whole frame, the list's scratch, every frame's count
+            self.adaptive = rrt.AdaptiveSettings(args.adaptive)
+            self.ad_frame = self.frame if self.post else torch.zeros(h * w * 4, dtype=torch.uint8, device=dev)
+            self.ad_scratch = torch.empty(rrt.adaptive_scratch_bytes(w, h), dtype=torch.uint8, device=dev)
+            self.ad_counts = torch.zeros(max(args.frames, 1), dtype=torch.int32, pin_memory=True)
+
+    def set_frame(self, k, table_id):
+        """frame k's clock, camera and noise table (table_id: NoiseWindows.table_id), and the shutter's / the lens' samples"""
+        from relativisticraytracer_amd import camera_paths
+        args, mb = self.args, self.mb
+        self.k = k
+        self.t, path_t = camera_paths.recording_clock(k, args.fps)
+        if mb > 1:
+            # the shutter's sub-times; the table's window is fitted from the earliest, so that the later ones fall inside it
+            self.times, sub_p = camera_paths.motion_clock(k, args.fps, args.shutter, mb)
+            self.cams = [self.path.camera_at(p) for p in sub_p] if self.path is not None else [self.cam] * mb
+            self.table = table_id(float(self.times[0]))
+        else:
+            self.table = table_id(self.t)
+        if self.path is not None:
+            self.cam = self.path.camera_at(path_t)
+        if self.dof_k:
+            if mb <= 1:
+                self.times, self.cams = [self.t] * self.dof_k, [self.cam] * self.dof_k
+            self.focus = args.focus if args.focus is not None else hole_distance(self.cam)
+
+    def launch_sampled(self, buf, prm, hdr=None):
+        """the stereo / defocused / panorama / blurred / supersampled launch (_stereo, _dof, _pano, _mb, _ss): the whole frame and its
+        HDR when hdr is given, else this rank's tiles"""
+        whole = hdr is not None
+        tiles = () if whole else (self.args.tile_rows, self.rank, self.world)
+        w, h = self.w, self.h
+        if self.stereo is not None:
+            launch = rrt.launch_raymarch_stereo if whole else rrt.launch_raymarch_stereo_tiles
+            w, h = self.ew, self.eh
+            when = (self.proj if self.proj is not None else rrt.Projection("pinhole"), self.stereo, self.t, self.cam)
+        elif self.dof_k:
+            launch = rrt.launch_raymarch_dof if whole else rrt.launch_raymarch_dof_tiles
+            when = (self.times, self.cams, self.dof_points, self.focus)
+        elif self.proj is not None:
+            launch, when = (rrt.launch_raymarch_pano if whole else rrt.launch_raymarch_pano_tiles), (self.proj, self.t, self.cam)
+        elif self.mb > 1:
+            launch, when = (rrt.launch_raymarch_mb if whole else rrt.launch_raymarch_mb_tiles), (self.times, self.cams)
+        else:
+            launch, when = (rrt.launch_raymarch_ss if whole else rrt.launch_raymarch_ss_tiles), (self.t, self.cam)
+        launch(buf, w, h, self.ss, *tiles, *when, self.tex, self.fx, prm, **({"hdr": hdr} if whole else {}))
+
+    def render_post(self):
+        """the frame through launch_sampled into self.hdr, then the post passes into self.frame (bottom-up rows, not the tile layout):
+        the exposure writes the bytes -- or, in front of the glow, the scaled HDR in place -- and the glow its own"""
+        glow, hdr, frame = self.glow, self.hdr, self.frame
+        self.prms[0].noise_table = self.table
+        if self.adaptive is not None:
+            self.render_adaptive(hdr)
+        else:
+            self.launch_sampled(frame, self.prms[0], hdr=hdr)
+        if self.exposure is not None:
+            rrt.launch_exposure(None if glow is not None else frame, hdr if glow is not None else None, hdr, self.w, self.h,
+                                self.exposure, self.exposure_scratch)
+        if glow is not None:
+            rrt.launch_glow(frame, hdr, self.w, self.h, glow, self.glow_scratch)
+        return frame
+
+    def render_adaptive(self, hdr=None):
+        """the adaptive frame into ad_frame (bottom-up rows) and, with the glow, its HDR; the count of refined pixels follows in a
+        4-byte asynchronous copy, read after the last frame"""
+        import torch
+        self.prms[0].noise_table = self.table
+        rrt.launch_raymarch_adaptive(self.ad_frame, self.w, self.h, self.ss, self.proj, self.adaptive, self.t, self.cam, self.tex, self.fx,
+                                     self.ad_scratch, self.prms[0], hdr=hdr)
+        self.ad_counts[self.k - 1:self.k].copy_(self.ad_scratch[:4].view(torch.int32), non_blocking=True)
+        return self.ad_frame
+
+    def render_tiles(self, buf, slot):
+        """this rank's tiles of the frame into buf (FrameSharder's render callback, inside the slot's stream)"""
+        import torch
+        prm, k, chooser, ends = self.prms[slot], self.k, self.chooser, self.ends
+        prm.noise_table = self.table
+        if chooser is not None:
+            prm.path_policy = chooser.policy(k)
+        if self.sampled:
+            self.launch_sampled(buf, prm)
+        else:
+            rrt.launch_raymarch_tiles(buf, self.w, self.h, self.args.tile_rows, self.rank, self.world, self.t, self.cam, self.tex, self.fx, prm)
+        if chooser is not None:
+            e = torch.cuda.Event(enable_timing=True)
+            e.record()                                        # on the slot's stream
+            ends[k] = e
+            # sustained time of the frames that have finished since: the interval between consecutive frames' render ends
+            for j in sorted(ends):
+                if j - 1 in ends and ends[j].query() and ends[j - 1].query():
+                    # (a frame that ends BEFORE its predecessor -- the predecessor holds a long wavefront -- reports 0; the
+                    # predecessor's own interval is then the long one, which is what the outlier rule looks for)
+                    chooser.report(j, max(0.0, ends[j - 1].elapsed_time(ends[j])))
+                    del ends[j - 1]
+
+    def assemble(self, frame, buf, shard):
+        rrt.assemble_tiles(frame, buf, self.w, self.h, self.args.tile_rows, shard, self.world)
+
+    def assemble_all(self, frame, bufs, stride):
+        rrt.assemble_all_tiles(frame, bufs, stride, self.w, self.h, self.args.tile_rows, self.world)
+
+    def summary(self, noise_tables):
+        """the summary line's entries from "path" on, in the line's order; noise_tables: NoiseWindows.summary()"""
+        args, proj, w, h = self.args, self.proj, self.w, self.h
+        exposure_info = None
+        if self.exposure is not None:        # the final EV: one 4-byte read of the state, after the last frame
+            import torch
+            final_ev = self.exposure.ev
+            if self.exposure_scratch is not None:
+                o = rrt.EXPOSURE_STATE_OFFSET
+                final_ev = float(self.exposure_scratch[o:o + 4].view(torch.float32).cpu()[0])
+            exposure_info = dict(self.exposure.info(), final_ev=final_ev)
+        return {"path": self.path.name if self.path else None, "spin": args.spin,
+                "arith_mode": self.arith_name, "sink": args.out,
+                "path_choice": self.chooser.stats() if self.chooser else None,
+                "noise_tables": noise_tables,
+                "tile_order": self.orders[0].info() if self.orders else None, "supersample": self.ss,
+                "motion_blur": self.mb, "shutter": args.shutter, "glow": self.glow.info() if self.glow is not None else None,
+                "projection": args.projection, "fov_deg": proj.fov_deg if proj is not None else None,
+                "vfov_deg": proj.vfov_deg if args.projection == "equirect" else None,
+                "stereo": self.stereo.info() if self.stereo is not None else None,
+                "dof": ({"aperture": args.dof, "focus": args.focus if args.focus is not None else "hole",
+                         "samples": self.dof_k} if self.dof_k else None),
+                "adaptive": ({"threshold": self.adaptive.threshold,
+                              "refined_fraction": float(self.ad_counts[:args.frames].double().mean()) / (w * h) if args.frames > 0 else 0.0}
+                             if self.adaptive is not None else None),
+                "exposure": exposure_info,
+                "march_cache": rrt.march_cache_stats()}
+
+    def close(self):
+        if self.chooser is not None:
+            self.chooser.destroy()
+        for o in self.orders:
+            o.destroy()
+        self.tex.destroy()
+
+
+def main(argv=None):
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    pano, use_exposure, dof_k = check_args(ap, args, world)
+
+    t_start = time.perf_counter()
+
+    def trace(what):        # RRT_HEADLESS_TRACE=1: where the start-up time goes (stderr), as in csrc/rrt_headless.cpp
+        dest = os.environ.get("RRT_HEADLESS_TRACE")        # "1": stderr; anything else: a file to append to
+        if dest:
+            line = f"[headless.py pid {os.getpid()} +{time.perf_counter() - t_start:7.2f}s] {what}"
+            if dest == "1":
+                print(line, file=sys.stderr, flush=True)
+            else:
+                with open(dest, "a") as fh:
+                    print(line, file=fh)
+
+    trace("importing torch")
+    import torch
+    trace("torch imported")
+    from relativisticraytracer_amd import camera_paths, sharding, sinks
+    settings = build_settings(ap, args, pano, use_exposure)
+
+    rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if not torch.cuda.is_available():
         sys.exit("the headless driver needs a GPU (no CPU fallback)")
@@ -305,141 +526,17 @@ def main(argv=None):
             warm.join()
 
     trace("process group ready" if world > 1 else "single rank")
-    ew, eh = args.width, args.height                        # the launch's frame: one eye's with --stereo
-    w, h = stereo.composite(ew, eh) if stereo is not None else (ew, eh)       # the frame that is sharded, gathered and written
-    ss, mb = args.supersample, args.motion_blur
-    # supersampled, blurred, glowed, panorama, stereo: single kernel, static order, no pool
-    single = ss > 1 or mb > 1 or glow is not None or exposure is not None or pano or stereo is not None or dof_k > 0
-    # sample m looks through lens point bitrev_K(m): the spiral's radius grows with its index, the shutter's times with m
-    dof_points = rrt.lens_points(args.dof, dof_k)[[bit_reverse(m, dof_k) for m in range(dof_k)]] if dof_k else None
-    tex = rrt.SkyTexture(load_sky(args.sky) if args.sky else synthetic_sky())
-    fx = rrt.CameraEffects(useChromaticAberration=bool(args.all_effects))
-    # with several ranks --frames-in-flight frames are in flight (FrameSharder pipeline mode), each with its own
-    # share of the pool
-    n_slots = max(2, args.frames_in_flight) if world > 1 else 1
-    pools = [rrt.Workspace((args.workspace_gib << 30) // n_slots) for _ in range(n_slots)] if args.workspace_gib > 0 and not single else []
+    r = Renderer(args, settings, dof_k, rank, world, dev)
+    w, h = r.w, r.h
     # lattice-hash tables for the volumetric noise over a sliding window of the recording clock (main.cpp:511-516 lets
     # simTime grow without bound; the table's size grows with it): one table within the byte budget, rebuilt when the
     # clock leaves its window -- never a silent fall-back: frames rendered without a table are counted in the summary
     t_end, _ = camera_paths.recording_clock(max(args.frames, 1), args.fps)
     nwin = rrt.NoiseWindows(float(t_end) + 1.0, int(args.noise_table_gib * (1 << 30)), sync=torch.cuda.synchronize,
                             enabled=not args.no_noise_table and not args.no_volumetrics)
-    # cost-ordered dispatch pays on single-kernel launches whose frames do not overlap; on the three-pass path (small launches
-    # with a pool) it piles the expensive tiles into the first of the two chains and was measured slower: auto leaves it off there
-    my_rays = w * sharding.shard_rows(h, args.tile_rows, rank, world)
-    three_pass_likely = bool(pools) and my_rays <= rrt._lib.load().rrt_path_auto_max_rays()      # RRT_PATH_AUTO's own threshold
-    use_order = not single and (args.tile_order == "on" or (args.tile_order == "auto" and n_slots == 1 and not three_pass_likely))
-    orders = [rrt.TileOrder() for _ in range(n_slots)] if use_order else []
-    arith_name = args.arith or ("fast" if args.fast else "strict")
-    arith_mode = {"strict": 0, "fast": 1, "fmad": 2}[arith_name]
-    # the path of a small share under frames in flight is chosen per window by measurement (sharding.PathChooser; the rule and the
-    # numbers behind it: csrc/rrt_path_chooser.cpp); RRT_PATH_POLICY pins it
-    chooser = (sharding.PathChooser(n_slots, args.path_window)
-               if (args.path_window >= 0 and n_slots >= 2 and three_pass_likely and "RRT_PATH_POLICY" not in os.environ) else None)
-    ends = {}                      # frame -> the event at the end of its render on this rank
-    prms = [rrt.RenderParams(spin=args.spin, volumetrics=0 if args.no_volumetrics else 1,
-                             noise_table=0, tile_order=orders[j].id if orders else 0,
-                             arith_mode=arith_mode, workspace=pools[j].id if pools else 0,
-                             # frames in flight fill each other's drains: ONE chain per launch (the second chain's streams only compete with
-                             # the other frames: 2-7 % per frame, profiles/r05_sustained_chains.txt).  Which PATH a small share takes --
-                             # the three-pass path, or the plain single kernel, which is 6-8 % faster unless the share holds a wavefront that
-                             # outlasts the frames in flight -- is chosen per window by measurement (chooser, above; round 6)
-                             pass_chains=1 if n_slots >= 2 else 0,
-                             path_policy=int(os.environ.get("RRT_PATH_POLICY", "0"))) for j in range(n_slots)]
-    path = camera_paths.CameraPath(args.path) if args.path >= 0 else None
-    state = {"t": 0.0, "cam": rrt.CameraState.default(), "table": 0, "k": 0}
-    post = glow is not None or exposure is not None
-    if post:                    # one rank (checked above): the whole frame's HDR, the glow's scratch, the finished frame
-        glow_hdr = torch.zeros(h * w * 4, dtype=torch.float32, device=dev)
-        glow_frame = torch.zeros(h * w * 4, dtype=torch.uint8, device=dev)
-    if glow is not None:
-        glow_scratch = torch.empty(rrt.glow_scratch_bytes(w, h, glow), dtype=torch.uint8, device=dev)
-    exposure_scratch = None
-    if exposure is not None and exposure.mode == rrt.EXPOSURE_AUTO:     # the state the sequence's frames share
-        exposure_scratch = torch.empty(rrt.exposure_scratch_bytes(), dtype=torch.uint8, device=dev)
-        rrt.launch_exposure_reset(exposure_scratch)
-    adaptive = None
-    if args.adaptive is not None:   # one rank (checked above): the whole frame, the list's scratch, every frame's count
-        adaptive = rrt.AdaptiveSettings(args.adaptive)
-        ad_frame = glow_frame if post else torch.zeros(h * w * 4, dtype=torch.uint8, device=dev)
-        ad_scratch = torch.empty(rrt.adaptive_scratch_bytes(w, h), dtype=torch.uint8, device=dev)
-        ad_counts = torch.zeros(max(args.frames, 1), dtype=torch.int32, pin_memory=True)
-
-    def launch_sampled(buf, prm, hdr=None):
-        """the stereo / defocused / panorama / blurred / supersampled launch (_stereo, _dof, _pano, _mb, _ss): the whole frame and its
-        HDR when hdr is given, else this rank's tiles"""
-        whole = hdr is not None
-        tiles = () if whole else (args.tile_rows, rank, world)
-        if stereo is not None:
-            launch = rrt.launch_raymarch_stereo if whole else rrt.launch_raymarch_stereo_tiles
-            when = (proj if proj is not None else rrt.Projection("pinhole"), stereo, state["t"], state["cam"])
-            launch(buf, ew, eh, ss, *tiles, *when, tex, fx, prm, **({"hdr": hdr} if whole else {}))
-            return
-        if dof_k:
-            launch = rrt.launch_raymarch_dof if whole else rrt.launch_raymarch_dof_tiles
-            when = (state["times"], state["cams"], dof_points, state["focus"])
-        elif pano:
-            launch, when = (rrt.launch_raymarch_pano if whole else rrt.launch_raymarch_pano_tiles), (proj, state["t"], state["cam"])
-        elif mb > 1:
-            launch, when = (rrt.launch_raymarch_mb if whole else rrt.launch_raymarch_mb_tiles), (state["times"], state["cams"])
-        else:
-            launch, when = (rrt.launch_raymarch_ss if whole else rrt.launch_raymarch_ss_tiles), (state["t"], state["cam"])
-        launch(buf, w, h, ss, *tiles, *when, tex, fx, prm, **({"hdr": hdr} if whole else {}))
-
-    def render_glowed():
-        """the frame through launch_sampled into glow_hdr, then the post passes into glow_frame (bottom-up rows, not the tile layout):
-        the exposure writes the bytes -- or, in front of the glow, the scaled HDR in place -- and the glow its own"""
-        prms[0].noise_table = state["table"]
-        if adaptive is not None:
-            render_adaptive(glow_hdr)
-        else:
-            launch_sampled(glow_frame, prms[0], hdr=glow_hdr)
-        if exposure is not None:
-            rrt.launch_exposure(None if glow is not None else glow_frame, glow_hdr if glow is not None else None, glow_hdr, w, h,
-                                exposure, exposure_scratch)
-        if glow is not None:
-            rrt.launch_glow(glow_frame, glow_hdr, w, h, glow, glow_scratch)
-        return glow_frame
-
-    def render_adaptive(hdr=None):
-        """the adaptive frame into ad_frame (bottom-up rows) and, with the glow, its HDR; the count of refined pixels follows in a
-        4-byte asynchronous copy, read after the last frame"""
-        prms[0].noise_table = state["table"]
-        rrt.launch_raymarch_adaptive(ad_frame, w, h, ss, proj, adaptive, state["t"], state["cam"], tex, fx, ad_scratch, prms[0], hdr=hdr)
-        k = state["k"]
-        ad_counts[k - 1:k].copy_(ad_scratch[:4].view(torch.int32), non_blocking=True)
-        return ad_frame
-
-    def render(buf, slot):
-        prms[slot].noise_table = state["table"]
-        k = state["k"]
-        if chooser is not None:
-            prms[slot].path_policy = chooser.policy(k)
-        if pano or mb > 1 or ss > 1 or stereo is not None or dof_k:
-            launch_sampled(buf, prms[slot])
-        else:
-            rrt.launch_raymarch_tiles(buf, w, h, args.tile_rows, rank, world, state["t"], state["cam"], tex, fx, prms[slot])
-        if chooser is not None:
-            e = torch.cuda.Event(enable_timing=True)
-            e.record()                                        # on the slot's stream (FrameSharder runs the callback inside it)
-            ends[k] = e
-            # sustained time of the frames that have finished since: the interval between consecutive frames' render ends
-            for j in sorted(ends):
-                if j - 1 in ends and ends[j].query() and ends[j - 1].query():
-                    # (a frame that ends BEFORE its predecessor -- the predecessor holds a long wavefront -- reports 0; the
-                    # predecessor's own interval is then the long one, which is what the outlier rule looks for)
-                    chooser.report(j, max(0.0, ends[j - 1].elapsed_time(ends[j])))
-                    del ends[j - 1]
-
-    def assemble(frame, buf, shard):
-        rrt.assemble_tiles(frame, buf, w, h, args.tile_rows, shard, world)
-
-    def assemble_all(frame, bufs, stride):
-        rrt.assemble_all_tiles(frame, bufs, stride, w, h, args.tile_rows, world)
-
     # with several ranks the next frames render while frame k is gathered and assembled (frames arrive late, in order)
-    fs = sharding.FrameSharder(w, h, args.tile_rows, rank, world, dev, render, assemble, assemble_all=assemble_all,
-                               pipeline=n_slots if world > 1 else False)
+    fs = sharding.FrameSharder(w, h, args.tile_rows, rank, world, dev, r.render_tiles, r.assemble, assemble_all=r.assemble_all,
+                               pipeline=r.n_slots if world > 1 else False)
     sink = sinks.open_sink(args.out, w, h, args.fps) if rank == 0 else None
     host = torch.empty(h * w * 4, dtype=torch.uint8, pin_memory=True) if sink else None
 
@@ -452,24 +549,8 @@ def main(argv=None):
     t0 = time.perf_counter()
     for k in range(1, args.frames + 1):
         dog.arm(args.frame_timeout + (args.init_timeout if k == 1 else 0.0), f"frame {k}")    # frame 1 brings the communicator's channels up
-        sim_t, path_t = camera_paths.recording_clock(k, args.fps)
-        state["t"] = sim_t
-        state["k"] = k
-        if mb > 1:
-            # the shutter's sub-times; the table's window is fitted from the earliest, so that the later ones fall inside it
-            sub_t, sub_p = camera_paths.motion_clock(k, args.fps, args.shutter, mb)
-            state["times"] = sub_t
-            state["cams"] = [path.camera_at(p) for p in sub_p] if path is not None else [state["cam"]] * mb
-            state["table"] = nwin.table_id(float(sub_t[0]))
-        else:
-            state["table"] = nwin.table_id(sim_t)
-        if path is not None:
-            state["cam"] = path.camera_at(path_t)
-        if dof_k:
-            if mb <= 1:
-                state["times"], state["cams"] = [sim_t] * dof_k, [state["cam"]] * dof_k
-            state["focus"] = args.focus if args.focus is not None else hole_distance(state["cam"])
-        frame = render_glowed() if post else (render_adaptive() if adaptive is not None else fs.step())
+        r.set_frame(k, nwin.table_id)
+        frame = r.render_post() if r.post else (r.render_adaptive() if r.adaptive is not None else fs.step())
         if sink and frame is not None:
             deliver(frame)
     for frame in fs.drain():                # the frames still in flight, in order
@@ -482,43 +563,16 @@ def main(argv=None):
         dist.barrier()
     dog.disarm()
     dt = time.perf_counter() - t0
-    exposure_info = None
-    if exposure is not None:        # the final EV: one 4-byte read of the state, after the last frame
-        final_ev = exposure.ev
-        if exposure_scratch is not None:
-            o = rrt.EXPOSURE_STATE_OFFSET
-            final_ev = float(exposure_scratch[o:o + 4].view(torch.float32).cpu()[0])
-        exposure_info = dict(exposure.info(), final_ev=final_ev)
     if rank == 0:
         if sink:
             sink.close()
         print(json.dumps({"frames": args.frames, "width": w, "height": h, "n_gpus": world, "seconds": round(dt, 4),
-                          "fps": round(args.frames / dt, 3), "Mrays_per_s": round(args.frames * w * h / dt / 1e6, 3),
-                          "path": path.name if path else None, "spin": args.spin,
-                          "arith_mode": arith_name, "sink": args.out,
-                          "path_choice": chooser.stats() if chooser else None,
-                          "noise_tables": nwin.summary(),
-                          "tile_order": orders[0].info() if orders else None, "supersample": ss,
-                          "motion_blur": mb, "shutter": args.shutter, "glow": glow.info() if glow is not None else None,
-                          "projection": args.projection, "fov_deg": proj.fov_deg if pano else None,
-                          "vfov_deg": proj.vfov_deg if args.projection == "equirect" else None,
-                          "stereo": stereo.info() if stereo is not None else None,
-                          "dof": ({"aperture": args.dof, "focus": args.focus if args.focus is not None else "hole",
-                                   "samples": dof_k} if dof_k else None),
-                          "adaptive": ({"threshold": adaptive.threshold,
-                                        "refined_fraction": float(ad_counts[:args.frames].double().mean()) / (w * h) if args.frames > 0 else 0.0}
-                                       if adaptive is not None else None),
-                          "exposure": exposure_info,
-                          "march_cache": rrt.march_cache_stats()}),
+                          "fps": round(args.frames / dt, 3), "Mrays_per_s": round(args.frames * w * h / dt / 1e6, 3), **r.summary(nwin.summary())}),
               flush=True)
     if world > 1:
         dist.destroy_process_group()
     nwin.close()
-    if chooser is not None:
-        chooser.destroy()
-    for o in orders:
-        o.destroy()
-    tex.destroy()
+    r.close()
 
 
 if __name__ == "__main__":

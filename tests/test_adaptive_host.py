@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import adaptive_ref
+from test_driver_refusals import CPP, IDS, PY, TWO_RANKS, refused, rows
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 INVALID, BAD_HANDLE, ABI_MISMATCH = 1, 4, 6
@@ -232,48 +233,17 @@ def test_refine_kernel_keeps_the_vacuum_step_and_the_register_budget():
         assert g["occupancy"] >= 5, (new, g)
 
 
-# ---------------------------------------------------------------- the drivers' refusals
-# each with the refusal's own words: both drivers end their stderr with the line that names what was refused (argparse's usage
-# block, which names every option, comes before it)
-NEEDS_SS = "--adaptive needs --supersample 2 | 4 | 8"
-ONE_INSTANT = "--adaptive renders one instant per frame (--motion-blur 1)"
-NO_STEREO = "--adaptive: not with --stereo"
-THRESHOLD = "a threshold in 0 ... 255"
-DRIVER_REFUSALS = [
-    (["--adaptive"], NEEDS_SS),                                                     # needs --supersample S > 1
-    (["--adaptive", "8"], NEEDS_SS),
-    (["--adaptive", "--supersample", "1"], NEEDS_SS),
-    (["--supersample", "2", "--adaptive", "8", "--motion-blur", "2"], ONE_INSTANT),
-    (["--supersample", "2", "--adaptive", "--stereo", "top-bottom"], NO_STEREO),
-    (["--supersample", "2", "--adaptive", "eight"], THRESHOLD),                     # non-numeric, out of range
-    (["--supersample", "2", "--adaptive", "8.5"], THRESHOLD),
-    (["--supersample", "2", "--adaptive", "256"], THRESHOLD),
-    (["--supersample", "2", "--adaptive", "-1"], THRESHOLD),
-]
-IDS = dict(ids=lambda a: " ".join(a) if isinstance(a, list) else "")
-
-
-def _refused(r, msg):
-    """exit status 2, a usage message, and `msg` in the last line of stderr"""
-    lines = r.stderr.strip().splitlines()
-    assert r.returncode == 2 and "usage" in r.stderr and lines and msg in lines[-1], (r.args, r.returncode, r.stderr[-800:])
-
-
-@pytest.mark.parametrize("args,msg", DRIVER_REFUSALS, **IDS)
+# ---- the drivers' refusals: the rows are tests/test_driver_refusals.py's, run here under the names they have always had
+@pytest.mark.parametrize("args,msg", rows("adaptive", PY), **IDS)
 def test_python_driver_refuses(args, msg):
-    _refused(subprocess.run([sys.executable, "-m", "relativisticraytracer_amd.headless"] + args, cwd=ROOT,
-                            capture_output=True, text=True, timeout=120), msg)
+    refused(PY, args, msg)
 
 
 def test_python_driver_refuses_several_gpus():
-    _refused(subprocess.run([sys.executable, "-m", "relativisticraytracer_amd.headless", "--supersample", "2", "--adaptive"], cwd=ROOT,
-                            capture_output=True, text=True, timeout=120, env=dict(os.environ, WORLD_SIZE="2", RANK="0")),
-             "--adaptive: one GPU only")
+    for args, msg in rows("adaptive", PY, TWO_RANKS):
+        refused(PY, args, msg, TWO_RANKS)
 
 
-@pytest.mark.parametrize("args,msg", DRIVER_REFUSALS + [(["--supersample", "2", "--adaptive", "--gpus", "2"],
-                                                         "--adaptive renders on one GPU only")], **IDS)
+@pytest.mark.parametrize("args,msg", rows("adaptive", CPP), **IDS)
 def test_cpp_driver_refuses(args, msg):
-    from relativisticraytracer_amd import build
-    exe = build.build_headless()
-    _refused(subprocess.run([exe] + args, capture_output=True, text=True, timeout=60), msg)
+    refused(CPP, args, msg)

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import exposure_ref as er
+from test_driver_refusals import CPP, IDS, PY, TWO_RANKS, refused, rows
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 INVALID, ABI_MISMATCH = 1, 6
@@ -388,47 +389,20 @@ def test_exposure_kernels_in_the_built_library_use_no_scratch():
         assert v["group_segment_fixed_size"] == (4 * 256 * 4 if k == "exposure_meter" else 0), (k, v)
 
 
-PY_REFUSALS = [
-    (["--exposure-speed", "0.2", "1.0"], "need --exposure EV | --auto-exposure"),
-    (["--exposure-range", "-4", "4"], "need --exposure EV | --auto-exposure"),
-    (["--exposure-percentiles", "400", "20"], "need --exposure EV | --auto-exposure"),
-    (["--auto-exposure", "0"], "--auto-exposure KEY > 0"),
-    (["--auto-exposure", "-0.5"], "--auto-exposure KEY > 0"),
-    (["--auto-exposure", "--exposure-speed", "-1", "1"], "--exposure-speed UP DOWN >= 0"),
-    (["--auto-exposure", "--exposure-range", "2", "1"], "MIN <= MAX"),
-    (["--auto-exposure", "--exposure-percentiles", "600", "400"], "LOW + HIGH < 1000"),
-    (["--auto-exposure", "--exposure-percentiles", "-1", "20"], "LOW HIGH >= 0"),
-]
-
-
-@pytest.mark.parametrize("args,msg", PY_REFUSALS + [(["--exposure", "nan"], "--exposure EV finite"), (["--exposure"], "--exposure"),
-                                                    (["--exposure", "bright"], "--exposure"),
-                                                    (["--auto-exposure", "--exposure-percentiles", "1.5", "2"], "--exposure-percentiles")],
-                         ids=lambda a: " ".join(a) if isinstance(a, list) else "")
+# ---- the drivers' refusals: the rows are tests/test_driver_refusals.py's, run here under the names they have always had
+@pytest.mark.parametrize("args,msg", rows("exposure", PY), **IDS)
 def test_python_driver_refuses(args, msg):
-    r = subprocess.run([sys.executable, "-m", "relativisticraytracer_amd.headless"] + args, cwd=ROOT,
-                       capture_output=True, text=True, timeout=120)
-    assert r.returncode == 2 and "usage" in r.stderr and msg in r.stderr, r.stderr[-800:]
+    refused(PY, args, msg)
 
 
-@pytest.mark.parametrize("args", [["--exposure", "1"], ["--auto-exposure"], ["--auto-exposure", "0.18", "--glow", "0.25"]],
-                         ids=lambda a: " ".join(a))
+SEVERAL_RANKS = {tuple(args): msg for args, msg in rows("exposure", PY, TWO_RANKS)}
+
+
+@pytest.mark.parametrize("args", [list(args) for args in SEVERAL_RANKS], ids=lambda a: " ".join(a))
 def test_python_driver_refuses_several_ranks(args):
-    env = dict(os.environ, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0")
-    r = subprocess.run([sys.executable, "-m", "relativisticraytracer_amd.headless"] + args, cwd=ROOT, env=env,
-                       capture_output=True, text=True, timeout=120)
-    assert r.returncode == 2 and "one GPU only" in r.stderr, r.stderr[-800:]
+    refused(PY, args, SEVERAL_RANKS[tuple(args)], TWO_RANKS)
 
 
-@pytest.mark.parametrize("args,msg", PY_REFUSALS + [
-    (["--exposure", "nan"], "--exposure: a number"), (["--exposure"], "--exposure: a number"), (["--exposure", "bright"], "--exposure: a number"),
-    (["--auto-exposure", "--exposure-percentiles", "1.5", "2"], "whole numbers"),
-    (["--auto-exposure", "--exposure-speed", "1"], "--exposure-speed: two numbers"),
-    (["--exposure", "1", "--gpus", "2"], "one GPU only"), (["--auto-exposure", "--gpus", "2"], "one GPU only"),
-    (["--auto-exposure", "0.18", "--glow", "0.25", "--gpus", "2"], "one GPU only"),
-    (["--exposure", "1", "--force-collective"], "one GPU only")], ids=lambda a: " ".join(a) if isinstance(a, list) else "")
+@pytest.mark.parametrize("args,msg", rows("exposure", CPP), **IDS)
 def test_cpp_driver_refuses(args, msg):
-    from relativisticraytracer_amd import build
-    exe = build.build_headless()
-    r = subprocess.run([exe] + args, capture_output=True, text=True, timeout=60)
-    assert r.returncode == 2 and msg in r.stderr, (args, r.returncode, r.stderr)
+    refused(CPP, args, msg)

@@ -7,13 +7,13 @@ import math
 import os
 import re
 import subprocess
-import sys
 import tempfile
 
 import numpy as np
 import pytest
 
 import glow_ref
+from test_driver_refusals import CPP, PY, TWO_RANKS, refused, rows
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 INVALID, ABI_MISMATCH = 1, 6
@@ -229,31 +229,17 @@ def test_glow_kernels_compile_for_gfx950_without_scratch():
         assert v["Occupancy"] >= 2, (k, v)
 
 
-@pytest.mark.parametrize("bad", [["--glow", "-1"], ["--glow", "0.5", "--glow-lobes", "5"], ["--glow", "0.5", "--glow-radius", "0"],
-                                 ["--glow", "0.5", "--glow-threshold", "-1"], ["--glow", "0.5", "--glow-radius", "0.5"],
-                                 ["--glow", "nan"], ["--glow", "x"]])
+# ---- the drivers' refusals: the rows are tests/test_driver_refusals.py's, run here under the names they have always had
+@pytest.mark.parametrize("bad", rows("glow", PY))
 def test_python_driver_refuses_bad_glow_arguments(bad):
-    r = subprocess.run([sys.executable, "-m", "relativisticraytracer_amd.headless"] + bad, cwd=ROOT,
-                       capture_output=True, text=True, timeout=120)
-    assert r.returncode == 2 and "usage" in r.stderr and "--glow" in r.stderr, r.stderr[-800:]
+    refused(PY, *bad)
 
 
 def test_python_driver_refuses_glow_on_several_ranks():
-    env = dict(os.environ, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0")
-    r = subprocess.run([sys.executable, "-m", "relativisticraytracer_amd.headless", "--glow", "0.5"], cwd=ROOT, env=env,
-                       capture_output=True, text=True, timeout=120)
-    assert r.returncode == 2 and "one GPU only" in r.stderr, r.stderr[-800:]
+    for args, msg in rows("glow", PY, TWO_RANKS):
+        refused(PY, args, msg, TWO_RANKS)
 
 
 def test_cpp_driver_refuses_bad_or_multi_gpu_glow():
-    from relativisticraytracer_amd import build
-    exe = build.HEADLESS_BIN
-    assert os.path.exists(exe), "build() builds rrt_headless"
-    usage = "--glow INTENSITY >= 0"
-    for bad, msg in ((["--glow", "-1"], usage), (["--glow", "0.5", "--glow-lobes", "5"], usage),
-                     (["--glow", "0.5", "--glow-lobes", "2.5"], "--glow-lobes"), (["--glow", "0.5", "--glow-radius", "0"], usage),
-                     (["--glow", "0.5", "--glow-radius", "0.5"], usage), (["--glow", "0.5", "--glow-threshold", "-1"], usage),
-                     (["--glow", "nan"], "--glow: a number"), (["--glow"], "--glow: a number"),
-                     (["--glow", "0.5", "--gpus", "2"], "one GPU only"), (["--glow", "0.5", "--force-collective"], "one GPU only")):
-        r = subprocess.run([exe] + bad, capture_output=True, text=True, timeout=60)
-        assert r.returncode == 2 and msg in r.stderr, (bad, r.returncode, r.stderr)
+    for args, msg in rows("glow", CPP):
+        refused(CPP, args, msg)

@@ -402,3 +402,84 @@ def test_plain_bench_line_is_the_headline_only(tmp_path):
     for name in ("frame_rgba_sample.npy", "frame_pixel_index.npy"):
         a, b = np.load(tmp_path / "plain" / name), np.load(tmp_path / "full" / name)
         assert a.shape[0] == 320 * 180 and np.array_equal(a, b), name
+
+
+# the summary lines' keys in their order, nested keys included (a list value: the keys of each of its entries)
+NOISE_KEYS = ["builds", "table_frames", "arith_frames", "coarsest_coverage", "peak_bytes", "budget_bytes"]
+GLOW_KEYS = ["radius", "lobes", "threshold", "intensity"]
+STEREO_KEYS = ["layout", "base", "convergence", "pole_merge_deg"]
+DOF_KEYS = ["aperture", "focus", "samples"]
+ADAPTIVE_KEYS = ["threshold", "refined_fraction"]
+EXPOSURE_KEYS = ["mode", "ev", "key", "low_permille", "high_permille", "min_ev", "max_ev", "adapt_up", "adapt_down", "final_ev"]
+CACHE_KEYS = ["fills", "hits", "drops", "misses", "uncacheable", "bytes", "max_bytes"]
+SUMMARY_KEYS = {
+    "cpp": [("frames", None), ("width", None), ("height", None), ("n_gpus", None), ("seconds", None), ("fps", None), ("Mrays_per_s", None),
+            ("path", None), ("spin", None), ("arith_mode", None), ("noise_tables", NOISE_KEYS), ("tile_order", None), ("collective", None),
+            ("path_choice", ["device", "frames_three_pass", "frames_single_kernel", "windows", "trials", "trials_aborted", "switches", "outliers"]),
+            ("supersample", None), ("motion_blur", None), ("shutter", None), ("glow", GLOW_KEYS), ("projection", None), ("fov_deg", None),
+            ("vfov_deg", None), ("stereo", STEREO_KEYS), ("dof", DOF_KEYS), ("adaptive", ADAPTIVE_KEYS), ("exposure", EXPOSURE_KEYS),
+            ("march_cache", ["device"] + CACHE_KEYS)],
+    "py": [("frames", None), ("width", None), ("height", None), ("n_gpus", None), ("seconds", None), ("fps", None), ("Mrays_per_s", None),
+           ("path", None), ("spin", None), ("arith_mode", None), ("sink", None), ("path_choice", None), ("noise_tables", NOISE_KEYS),
+           ("tile_order", None), ("supersample", None), ("motion_blur", None), ("shutter", None), ("glow", GLOW_KEYS), ("projection", None),
+           ("fov_deg", None), ("vfov_deg", None), ("stereo", STEREO_KEYS), ("dof", DOF_KEYS), ("adaptive", ADAPTIVE_KEYS),
+           ("exposure", EXPOSURE_KEYS), ("march_cache", CACHE_KEYS + ["blocks_used", "blocks_capacity", "state", "why"])],
+}
+# argument set -> the sub-objects it fills (every other one of glow ... exposure is null) and the values the arguments determine
+SUMMARY_SETS = {
+    "plain": ([], set(), {"width": 64, "height": 48, "supersample": 1, "motion_blur": 1, "projection": "pinhole", "fov_deg": None,
+                          "vfov_deg": None}),
+    "adaptive": (["--supersample", "2", "--adaptive", "--projection", "fisheye", "--glow", "0.25", "--auto-exposure"],
+                 {"glow", "adaptive", "exposure"},
+                 {"width": 64, "height": 48, "supersample": 2, "motion_blur": 1, "projection": "fisheye", "fov_deg": 180.0, "vfov_deg": None,
+                  "glow.intensity": 0.25, "glow.lobes": 4, "adaptive.threshold": 8, "exposure.mode": "auto", "exposure.key": 0.5,
+                  "exposure.ev": 0.0}),
+    "stereo": (["--projection", "equirect", "--stereo", "top-bottom"], {"stereo"},
+               {"width": 64, "height": 96, "supersample": 1, "motion_blur": 1, "projection": "equirect", "fov_deg": 360.0, "vfov_deg": 180.0,
+                "stereo.layout": "top-bottom", "stereo.base": 1.0, "stereo.convergence": 0.0, "stereo.pole_merge_deg": [90.0, 90.0]}),
+    "dof": (["--dof", "0.3", "--motion-blur", "2"], {"dof"},
+            {"width": 64, "height": 48, "supersample": 1, "motion_blur": 2, "shutter": 0.5, "projection": "pinhole",
+             "dof.aperture": float(np.float32(0.3)), "dof.focus": "hole", "dof.samples": 2}),
+}
+
+
+def check_summary_line(line, driver, filled, values):
+    """`line` parses as JSON with SUMMARY_KEYS[driver] in order, the sub-objects in `filled` present and the others null, and holds
+    `values` (dotted names reach into a sub-object; numbers are compared as binary32, which is what rrt_headless prints)"""
+    meta = json.loads(line, object_pairs_hook=list)             # objects as lists of pairs: the order is the line's
+    assert [k for k, _ in meta] == [k for k, _ in SUMMARY_KEYS[driver]], [k for k, _ in meta]
+    top = dict(meta)
+    for key, nested in SUMMARY_KEYS[driver]:
+        got = top[key]
+        if key in ("glow", "stereo", "dof", "adaptive", "exposure"):
+            assert (got is not None) == (key in filled), (key, got)
+        if nested is None or got is None:
+            continue
+        entries = [got] if isinstance(got[0], tuple) else got    # an object, or a list of objects (one per device)
+        assert entries and all([k for k, _ in e] == nested for e in entries), (key, got)
+    assert top["frames"] == 2 and top["n_gpus"] == 1
+    for name, want in values.items():
+        got = top
+        for part in name.split("."):
+            got = dict(got)[part] if isinstance(got, list) else got[part]
+        if isinstance(want, float):
+            assert np.float32(got) == np.float32(want), (name, got, want)
+        else:
+            assert got == want, (name, got, want)
+    return top
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(SUMMARY_SETS))
+@pytest.mark.parametrize("driver", ["cpp", "py"])
+def test_summary_lines_keep_their_keys(driver, name):
+    """both drivers' summary lines: the keys, nested keys included, in their order, and the values the arguments determine; the four
+    argument sets together fill every sub-object once (64 x 48, 2 frames: nothing in the line's assembly depends on the frame)"""
+    from relativisticraytracer_amd import build
+    args, filled, values = SUMMARY_SETS[name]
+    cmd = [build.build_headless()] if driver == "cpp" else [sys.executable, "-m", "relativisticraytracer_amd.headless"]
+    r = subprocess.run(cmd + ["--width", "64", "--height", "48", "--frames", "2"] + args, cwd=ROOT, capture_output=True, text=True, timeout=240)
+    assert r.returncode == 0, r.stderr[-1500:]
+    top = check_summary_line(r.stdout.strip().splitlines()[-1], driver, filled, values)
+    if driver == "cpp" and name == "plain":         # the default's three frames in flight and pool: a path choice per device
+        assert top["path_choice"] is not None and top["collective"] == "none"

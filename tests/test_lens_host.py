@@ -9,7 +9,6 @@ import math
 import os
 import re
 import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -17,6 +16,7 @@ import pytest
 import lens_ref as lr
 import projection_ref as pr
 from test_projection_host import cameras
+from test_driver_refusals import CPP, IDS, PY, refused, rows
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 INVALID, BAD_HANDLE, ABI_MISMATCH = 1, 4, 6
@@ -330,35 +330,12 @@ def test_drivers_share_the_pairing_and_the_focus():
     assert headless.hole_distance(cam) == float(F(math.sqrt(x * x + y * y + z * z))) > 0
 
 
-DRIVER_REFUSALS = [
-    (["--dof", "0.3", "--projection", "equirect"], "--dof: a thin lens in front of a pinhole camera"),
-    (["--dof", "0.3", "--projection", "fisheye"], "--dof: a thin lens in front of a pinhole camera"),
-    (["--dof", "0.3", "--stereo", "side-by-side"], "--dof: not with --stereo"),
-    (["--dof", "0.3", "--supersample", "2", "--adaptive"], "--dof: not with --adaptive"),
-    (["--dof", "0.3", "--motion-blur", "4", "--dof-samples", "8"], "the lens samples are the shutter's sub-frames (K = M)"),
-    (["--focus", "12"], "--focus / --dof-samples need --dof APERTURE"),
-    (["--dof-samples", "4"], "--focus / --dof-samples need --dof APERTURE"),
-    (["--dof", "-0.3"], "--dof APERTURE: the lens radius in scene units, >= 0"),
-    (["--dof", "nan"], "--dof APERTURE: the lens radius in scene units, >= 0"),
-    (["--dof", "0.3", "--focus", "0"], "a distance > 0 along forward, or `hole`"),
-    (["--dof", "0.3", "--focus", "-2"], "a distance > 0 along forward, or `hole`"),
-    (["--dof", "0.3", "--focus", "inf"], "a distance > 0 along forward, or `hole`"),
-    (["--dof", "0.3", "--focus", "ring"], "a distance > 0 along forward, or `hole`"),
-    (["--dof", "0.3", "--dof-samples", "3"], "--dof-samples"),
-]
-
-
-@pytest.mark.parametrize("args,msg", DRIVER_REFUSALS, ids=lambda a: " ".join(a) if isinstance(a, list) else "")
+# ---- the drivers' refusals: the rows are tests/test_driver_refusals.py's, run here under the names they have always had
+@pytest.mark.parametrize("args,msg", rows("lens", PY), **IDS)
 def test_python_driver_refuses(args, msg):
-    r = subprocess.run([sys.executable, "-m", "relativisticraytracer_amd.headless"] + args, cwd=ROOT,
-                       capture_output=True, text=True, timeout=120)
-    assert r.returncode == 2 and "usage" in r.stderr and msg in r.stderr, r.stderr[-800:]
+    refused(PY, args, msg)
 
 
-@pytest.mark.parametrize("args,msg", DRIVER_REFUSALS + [(["--dof"], "--dof APERTURE"), (["--dof", "wide"], "--dof APERTURE")],
-                         ids=lambda a: " ".join(a) if isinstance(a, list) else "")
+@pytest.mark.parametrize("args,msg", rows("lens", CPP), **IDS)
 def test_cpp_driver_refuses(args, msg):
-    from relativisticraytracer_amd import build
-    exe = build.build_headless()
-    r = subprocess.run([exe] + args, capture_output=True, text=True, timeout=60)
-    assert r.returncode == 2 and "usage" in r.stderr and msg in r.stderr, (args, r.returncode, r.stderr)
+    refused(CPP, args, msg)

@@ -5,13 +5,12 @@ arithmetic, the kernel keeps the march's vacuum step and register budget, and bo
 import ctypes as C
 import math
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from test_supersample_host import _isa
+from test_driver_refusals import CPP, PY, refused, rows
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 INVALID, BAD_HANDLE, ABI_MISMATCH = 1, 4, 6
@@ -156,18 +155,12 @@ def test_motion_kernel_keeps_the_vacuum_step_and_the_register_budget():
         assert got[k]["per_step"] == got[r]["per_step"], (k, got[k], got[r])
 
 
-@pytest.mark.parametrize("bad", [["--motion-blur", "3"], ["--shutter", "1.5"], ["--shutter", "-0.1"]])
+# ---- the drivers' refusals: the rows are tests/test_driver_refusals.py's, run here under the names they have always had
+@pytest.mark.parametrize("bad", rows("motion-blur", PY))
 def test_python_driver_refuses_bad_blur_arguments(bad):
-    r = subprocess.run([sys.executable, "-m", "relativisticraytracer_amd.headless"] + bad, cwd=ROOT,
-                       capture_output=True, text=True, timeout=120)
-    assert r.returncode != 0 and "usage" in r.stderr and bad[0] in r.stderr, r.stderr[-800:]
+    refused(PY, *bad)
 
 
 def test_cpp_driver_refuses_bad_blur_arguments():
-    from relativisticraytracer_amd import build
-    exe = build.HEADLESS_BIN
-    assert os.path.exists(exe), "build() builds rrt_headless"
-    for bad, msg in ((["--motion-blur", "3"], "--motion-blur 1 | 2 | 4 | 8 | 16"), (["--motion-blur"], "--motion-blur 1 | 2 | 4 | 8 | 16"),
-                     (["--shutter", "1.5"], "--shutter F"), (["--shutter", "x"], "--shutter F"), (["--shutter", "nan"], "--shutter F")):
-        r = subprocess.run([exe] + bad, capture_output=True, text=True, timeout=60)
-        assert r.returncode == 2 and msg in r.stderr, (bad, r.returncode, r.stderr)
+    for args, msg in rows("motion-blur", CPP):
+        refused(CPP, args, msg)

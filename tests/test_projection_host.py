@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import projection_ref as pr
+from test_driver_refusals import CPP, IDS, PY, refused, rows
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 INVALID, BAD_HANDLE, ABI_MISMATCH = 1, 4, 6
@@ -271,38 +272,17 @@ def test_panorama_kernel_keeps_the_vacuum_step_and_the_register_budget():
     assert got[fmad]["per_step"] == got[ref_fmad]["per_step"], got
 
 
-DRIVER_REFUSALS = [
-    (["--projection", "equirect", "--fov", "400"], "--fov DEG in (0, 360]"),
-    (["--projection", "equirect", "--vfov", "181"], "--fov DEG in (0, 360]"),
-    (["--projection", "equirect", "--fov", "nan"], "--fov DEG in (0, 360]"),
-    (["--projection", "fisheye", "--fov", "-5"], "--fov DEG in (0, 360]"),
-    (["--projection", "fisheye", "--fov", "0"], "--fov DEG in (0, 360]"),
-    (["--projection", "fisheye", "--vfov", "90"], "--vfov: equirect only"),
-    (["--fov", "90"], "--fov / --vfov need --projection equirect | fisheye"),
-    (["--projection", "equirect", "--motion-blur", "4"], "one instant per frame (--motion-blur 1)"),
-    (["--projection", "fisheye", "--motion-blur", "2"], "one instant per frame (--motion-blur 1)"),
-    (["--projection", "equirect", "--glow", "0.25"], "not with --projection equirect"),
-]
-
-
-@pytest.mark.parametrize("args,msg", DRIVER_REFUSALS, ids=lambda a: " ".join(a) if isinstance(a, list) else "")
+# ---- the drivers' refusals: the rows are tests/test_driver_refusals.py's, run here under the names they have always had
+@pytest.mark.parametrize("args,msg", rows("projection", PY), **IDS)
 def test_python_driver_refuses(args, msg):
-    r = subprocess.run([sys.executable, "-m", "relativisticraytracer_amd.headless"] + args, cwd=ROOT,
-                       capture_output=True, text=True, timeout=120)
-    assert r.returncode == 2 and "usage" in r.stderr and msg in r.stderr, r.stderr[-800:]
+    refused(PY, args, msg)
 
 
 def test_python_driver_refuses_other_projections():
-    r = subprocess.run([sys.executable, "-m", "relativisticraytracer_amd.headless", "--projection", "cubemap"], cwd=ROOT,
-                       capture_output=True, text=True, timeout=120)
-    assert r.returncode == 2 and "--projection" in r.stderr, r.stderr[-800:]
+    for args, msg in rows("projection-kind", PY):
+        refused(PY, args, msg)
 
 
-@pytest.mark.parametrize("args,msg", DRIVER_REFUSALS + [(["--projection", "cubemap"], "--projection pinhole | equirect | fisheye"),
-                                                        (["--projection", "fisheye", "--fov", "wide"], "--fov DEG: a number")],
-                         ids=lambda a: " ".join(a) if isinstance(a, list) else "")
+@pytest.mark.parametrize("args,msg", rows("projection", CPP), **IDS)
 def test_cpp_driver_refuses(args, msg):
-    from relativisticraytracer_amd import build
-    exe = build.build_headless()
-    r = subprocess.run([exe] + args, capture_output=True, text=True, timeout=60)
-    assert r.returncode == 2 and msg in r.stderr, (args, r.returncode, r.stderr)
+    refused(CPP, args, msg)

@@ -5,8 +5,6 @@ kernel keeps the march's vacuum step and register budget, and both headless driv
 themselves: tests/test_gpu_stereo.py."""
 import ctypes as C
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -14,6 +12,7 @@ import pytest
 import projection_ref as pr
 import stereo_ref as sr
 from test_projection_host import _isa, cameras
+from test_driver_refusals import CPP, IDS, PY, refused, rows
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 INVALID, BAD_HANDLE, ABI_MISMATCH = 1, 4, 6
@@ -317,41 +316,17 @@ def test_stereo_kernel_keeps_the_vacuum_step_and_the_register_budget():
     assert got[strict]["per_step"] == 276.0 and got[fmad]["per_step"] == 216.0, got
 
 
-DRIVER_REFUSALS = [
-    (["--stereo", "top-bottom", "--projection", "fisheye"], "no stereo fisheye domes"),
-    (["--stereo", "side-by-side", "--motion-blur", "4"], "--stereo renders one instant per frame (--motion-blur 1)"),
-    (["--stereo", "top-bottom", "--glow", "0.25"], "--stereo: not with --glow"),
-    (["--stereo-base", "0.5"], "need --stereo top-bottom | side-by-side"),
-    (["--convergence", "10"], "need --stereo top-bottom | side-by-side"),
-    (["--pole-merge", "60", "80", "--projection", "equirect"], "need --stereo top-bottom | side-by-side"),
-    (["--stereo", "top-bottom", "--projection", "equirect", "--convergence", "10"], "--convergence: pinhole only"),
-    (["--stereo", "top-bottom", "--pole-merge", "60", "80"], "--pole-merge: equirect only"),
-    (["--stereo", "top-bottom", "--stereo-base", "-1"], "--stereo-base B >= 0"),
-    (["--stereo", "side-by-side", "--stereo-base", "nan"], "--stereo-base B >= 0"),
-    (["--stereo", "side-by-side", "--convergence", "-3"], "--stereo-base B >= 0"),
-    (["--stereo", "top-bottom", "--projection", "equirect", "--pole-merge", "70", "60"], "--stereo-base B >= 0"),
-    (["--stereo", "top-bottom", "--projection", "equirect", "--pole-merge", "60", "95"], "--stereo-base B >= 0"),
-]
-
-
-@pytest.mark.parametrize("args,msg", DRIVER_REFUSALS, ids=lambda a: " ".join(a) if isinstance(a, list) else "")
+# ---- the drivers' refusals: the rows are tests/test_driver_refusals.py's, run here under the names they have always had
+@pytest.mark.parametrize("args,msg", rows("stereo", PY), **IDS)
 def test_python_driver_refuses(args, msg):
-    r = subprocess.run([sys.executable, "-m", "relativisticraytracer_amd.headless"] + args, cwd=ROOT,
-                       capture_output=True, text=True, timeout=120)
-    assert r.returncode == 2 and "usage" in r.stderr and msg in r.stderr, r.stderr[-800:]
+    refused(PY, args, msg)
 
 
-@pytest.mark.parametrize("args,msg", DRIVER_REFUSALS + [(["--stereo", "left-right"], "--stereo top-bottom | side-by-side"),
-                                                        (["--stereo", "top-bottom", "--stereo-base", "wide"], "--stereo-base: a number")],
-                         ids=lambda a: " ".join(a) if isinstance(a, list) else "")
+@pytest.mark.parametrize("args,msg", rows("stereo", CPP), **IDS)
 def test_cpp_driver_refuses(args, msg):
-    from relativisticraytracer_amd import build
-    exe = build.build_headless()
-    r = subprocess.run([exe] + args, capture_output=True, text=True, timeout=60)
-    assert r.returncode == 2 and "usage" in r.stderr and msg in r.stderr, (args, r.returncode, r.stderr)
+    refused(CPP, args, msg)
 
 
 def test_python_driver_refuses_other_layouts():
-    r = subprocess.run([sys.executable, "-m", "relativisticraytracer_amd.headless", "--stereo", "left-right"], cwd=ROOT,
-                       capture_output=True, text=True, timeout=120)
-    assert r.returncode == 2 and "--stereo" in r.stderr, r.stderr[-800:]
+    for args, msg in rows("stereo-layout", PY):
+        refused(PY, args, msg)

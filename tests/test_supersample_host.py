@@ -9,6 +9,8 @@ import sys
 
 import pytest
 
+from test_driver_refusals import CPP, PY, refused, rows
+
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 INVALID, BAD_HANDLE, ABI_MISMATCH = 1, 4, 6
 NO_SKY = 0x7777000000000001          # never a registered sky: a launch that passes every check stops at the handle lookup
@@ -121,17 +123,12 @@ def test_supersample_kernel_keeps_the_vacuum_step_and_the_register_budget():
     assert got[ss_strict]["per_step"] == got[ref]["per_step"], got
 
 
+# ---- the drivers' refusals: the rows are tests/test_driver_refusals.py's, run here under the names they have always had
 def test_python_driver_refuses_other_factors():
-    r = subprocess.run([sys.executable, "-m", "relativisticraytracer_amd.headless", "--supersample", "3"], cwd=ROOT,
-                       capture_output=True, text=True, timeout=120)
-    assert r.returncode != 0 and "usage" in r.stderr and "--supersample" in r.stderr, r.stderr[-800:]
+    for args, msg in rows("supersample", PY):
+        refused(PY, args, msg)
 
 
 def test_cpp_driver_refuses_other_factors():
-    from relativisticraytracer_amd import build
-    exe = build.HEADLESS_BIN
-    if not os.path.exists(exe):
-        pytest.skip("rrt_headless is not built")
-    for bad in (["--supersample", "3"], ["--supersample", "two"], ["--supersample"]):
-        r = subprocess.run([exe] + bad, capture_output=True, text=True, timeout=60)
-        assert r.returncode == 2 and "--supersample 1 | 2 | 4 | 8" in r.stderr, (bad, r.returncode, r.stderr)
+    for args, msg in rows("supersample", CPP):
+        refused(CPP, args, msg)
