@@ -21,6 +21,8 @@ REF_FRAMES_FMA_PATH = os.path.join(HERE, "_ref", "libref_frames_fma.so")     # t
 MATH_LIBM = 0
 MATH_PORTABLE = 1
 MATH_NUDGED_BASE = 16      # + seed: glibc with every transcendental result moved by <= 2-3 ulp (rrt_oracle.c: nudge)
+ARITH_STRICT = 0           # Params.arith_mode: the reference's source, every operation rounded on its own
+ARITH_FMAD = 2             # the fixed fused tree of rrt_oracle.c (geodesic_acc_fmad / integrate_rk4_fmad): RRT_ARITH_FMAD's definition
 
 _f = C.c_float
 _i = C.c_int
@@ -43,7 +45,7 @@ class Effects(C.Structure):
 class Params(C.Structure):
     _fields_ = [("spin", _f), ("volumetrics", C.c_int32), ("max_steps", C.c_int32),
                 ("math_mode", C.c_int32), ("sky_frac_bits", C.c_int32),
-                ("nudge_ulps", C.c_int32), ("nudge_seed", C.c_uint32)]
+                ("nudge_ulps", C.c_int32), ("nudge_seed", C.c_uint32), ("arith_mode", C.c_int32)]
 
 
 class Diag(C.Structure):
@@ -214,6 +216,27 @@ class _Units:
     def rk4(self, p, v, h, spin):
         p = _fa(p).copy(); v = _fa(v).copy(); h = _fa(h)
         self._fn("rk4")(len(p), _p(p), _p(v), _p(h), _f(spin)); return p, v
+
+    def geodesic_acc_arith(self, p, v, spin, arith):
+        """geodesic_acc in arithmetic `arith` (ARITH_STRICT / ARITH_FMAD); the oracle only"""
+        p = _fa(p); v = _fa(v); out = np.empty_like(p)
+        if self._fn("geodesic_acc_arith")(len(p), _p(p), _p(v), _f(spin), int(arith), _p(out)) != 0:
+            raise ValueError(f"no restatement of arithmetic mode {arith}")
+        return out
+
+    def dot_arith(self, a, b, arith):
+        """dot(a, b) per ray as the march of arithmetic `arith` takes it (squared radius, escape test); the oracle only"""
+        a = _fa(a); b = _fa(b); out = np.empty(len(a), np.float32)
+        if self._fn("dot_arith")(len(a), _p(a), _p(b), int(arith), _p(out)) != 0:
+            raise ValueError(f"no restatement of arithmetic mode {arith}")
+        return out
+
+    def rk4_arith(self, p, v, h, spin, arith):
+        """one RK4 step per ray in arithmetic `arith` (ARITH_STRICT / ARITH_FMAD); the oracle only"""
+        p = _fa(p).copy(); v = _fa(v).copy(); h = _fa(h)
+        if self._fn("rk4_arith")(len(p), _p(p), _p(v), _p(h), _f(spin), int(arith)) != 0:
+            raise ValueError(f"no restatement of arithmetic mode {arith}")
+        return p, v
 
     def redshift(self, p, vel, spin, mode=MATH_LIBM):
         p = _fa(p); vel = _fa(vel); out = np.empty(len(p), np.float32)

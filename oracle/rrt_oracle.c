@@ -43,6 +43,7 @@ typedef struct {
     /* hard-gate log of this ray (rrto_render_gates): 0 off, 1 record every decision, 2 replay recorded ones */
     int gate_mode, gate_n, gate_cap, gate_overflow;
     uint8_t* gate_log;
+    int arith;       /* RRTO_ARITH_* of the march this sample belongs to (0 wherever a context is built without one) */
 } ctx_t;
 
 /* The path's hard gates -- `base < 0.001f` (densities.h:85), `d_disk > 0.001f`, `d_cloud > 0.001f`
@@ -206,9 +207,70 @@ static inline void integrate_rk4(f3* p, f3* v, float h, float spin) {
     *p = add3(*p, mul3(kp_sum, h / 6.0f));
 }
 
+/*
+ * ---- RRTO_ARITH_FMAD: the definition of the product's RRT_ARITH_FMAD ----
+ * geodesic_acc / integrate_rk4 above with a FIXED set of multiply-adds fused -- one choice a contracting compiler could make
+ * of geodesics.h:30-45 and integrators.h:23-59 -- and everything else as it stands: IEEE sqrtf and `/`, h * 0.5f, h / 6.0f.
+ *   - every dot product is fmaf(z, z', fmaf(y, y', x * x')): the squared radii, L^2, the march's escape test;
+ *   - every cross-product component is fmaf(a, b, -(c * d));
+ *   - the drag term joins the radial one in a fused multiply-add (x and z; cross((0,1,0), p) has no y part);
+ *   - every stage state and the final combination is fmaf(k, h, x0) per component;
+ *   - the weighted sums k1 + (2 k2 + (2 k3 + k4)) are the strict ones: 2 * k is exact, so fusing changes no bit.
+ * fmaf must be the exact one: this file is built with -mfma (oracle/Makefile: every fmaf below is one vfmadd instruction)
+ * or, in the -march=native build on a host without FMA units, resolves to glibc's fmaf, which is correctly rounded too.
+ */
+static inline float dot3_fmad(f3 a, f3 b) { return fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x)); }
+static inline f3 cross3_fmad(f3 a, f3 b) {
+    return mk3(fmaf(a.y, b.z, -(a.z * b.y)), fmaf(a.z, b.x, -(a.x * b.z)), fmaf(a.x, b.y, -(a.y * b.x)));
+}
+static inline f3 axpy3_fmad(f3 k, float h, f3 x0) { return mk3(fmaf(k.x, h, x0.x), fmaf(k.y, h, x0.y), fmaf(k.z, h, x0.z)); }
+
+static inline f3 geodesic_acc_fmad(f3 p_rel, f3 v, float spin) {
+    float r2 = dot3_fmad(p_rel, p_rel);
+    float r = sqrtf(r2);
+    if (r < EVENT_HORIZON * 0.5f) return mk3(0, 0, 0);      /* <=> r2 < 1: sqrtf is monotonic and sqrtf(1 - 2^-24) < 1 */
+
+    f3 L_vec = cross3_fmad(p_rel, v);
+    float L2 = dot3_fmad(L_vec, L_vec);
+    float radial_mag = -1.5f * EVENT_HORIZON * L2 / (r2 * r2 * r);
+    f3 radial_acc = mul3(p_rel, radial_mag);
+
+    /* drag_dir = cross((0,1,0), p_rel) = (p.z, 0, -p.x): its products with 0 and 1 are exact, nothing to fuse there */
+    float drag_strength = (2.0f * spin * EVENT_HORIZON) / (r2 * r);
+    return mk3(fmaf(p_rel.z, drag_strength, radial_acc.x), radial_acc.y, fmaf(-p_rel.x, drag_strength, radial_acc.z));
+}
+
+static inline void integrate_rk4_fmad(f3* p, f3* v, float h, float spin) {
+    f3 p0 = *p;
+    f3 v0 = *v;
+
+    f3 kv1 = geodesic_acc_fmad(p0, v0, spin);
+    f3 kp1 = v0;
+
+    f3 v2 = axpy3_fmad(kv1, h * 0.5f, v0);
+    f3 p2 = axpy3_fmad(kp1, h * 0.5f, p0);
+    f3 kv2 = geodesic_acc_fmad(p2, v2, spin);
+    f3 kp2 = v2;
+
+    f3 v3 = axpy3_fmad(kv2, h * 0.5f, v0);
+    f3 p3 = axpy3_fmad(kp2, h * 0.5f, p0);
+    f3 kv3 = geodesic_acc_fmad(p3, v3, spin);
+    f3 kp3 = v3;
+
+    f3 v4 = axpy3_fmad(kv3, h, v0);
+    f3 p4 = axpy3_fmad(kp3, h, p0);
+    f3 kv4 = geodesic_acc_fmad(p4, v4, spin);
+    f3 kp4 = v4;
+
+    f3 kv_sum = add3(kv1, axpy3_fmad(kv2, 2.0f, axpy3_fmad(kv3, 2.0f, kv4)));
+    f3 kp_sum = add3(kp1, axpy3_fmad(kp2, 2.0f, axpy3_fmad(kp3, 2.0f, kp4)));
+
+    *v = axpy3_fmad(kv_sum, h / 6.0f, v0);
+    *p = axpy3_fmad(kp_sum, h / 6.0f, p0);
+}
+
 /* ---- geodesics.h:11-25 ---- */
-static inline float redshift_factor(const ctx_t* c, f3 p_rel, f3 ray_vel, float spin) {
-    float r = length3(p_rel);
+static inline float redshift_factor_r(const ctx_t* c, f3 p_rel, float r, f3 ray_vel, float spin) {
     if (r < EVENT_HORIZON * 1.01f) return 0.0f;
 
     float g_gravity = sqrtf(1.0f - EVENT_HORIZON / r);
@@ -221,6 +283,12 @@ static inline float redshift_factor(const ctx_t* c, f3 p_rel, f3 ray_vel, float 
     float g_doppler = 1.0f / (gamma * (1.0f - v_mag * cos_theta));
 
     return g_gravity * g_doppler;
+}
+/* the reference takes the radius anew, `float r = length(p_rel)` (geodesics.h:12): in strict arithmetic that is the march's
+ * loop-top r bit for bit.  An FMAD march hands its own loop-top r on -- the root of the FUSED sum -- which is what a
+ * contracting compiler that merges the two identical length() computations of raymarcher.cu:43 and geodesics.h:12 gives. */
+static inline float redshift_factor(const ctx_t* c, f3 p_rel, f3 ray_vel, float spin) {
+    return redshift_factor_r(c, p_rel, length3(p_rel), ray_vel, spin);
 }
 
 /* ---- densities.h:12-15 ---- */
@@ -331,7 +399,7 @@ static inline int rt_sample(ctx_t* c, float d_disk, float d_cloud, f3 rel_p, flo
         float step_opacity = 0;
 
         if (disk_on) {
-            float g = redshift_factor(c, rel_p, vel, spin);
+            float g = c->arith == RRTO_ARITH_FMAD ? redshift_factor_r(c, rel_p, r, vel, spin) : redshift_factor(c, rel_p, vel, spin);
             float T = disk_temperature(c, r);
             float T_norm = m_pow(c, T / DISK_TEMP_REF, 0.5f);
             float bol_I = m_pow(c, g, 4.0f) * T_norm * d_disk * DISK_LUMINOSITY;
@@ -345,7 +413,7 @@ static inline int rt_sample(ctx_t* c, float d_disk, float d_cloud, f3 rel_p, flo
         }
 
         if (cloud_on) {
-            float g = redshift_factor(c, rel_p, vel, spin);
+            float g = c->arith == RRTO_ARITH_FMAD ? redshift_factor_r(c, rel_p, r, vel, spin) : redshift_factor(c, rel_p, vel, spin);
             float lighting = 0.5f + 3.0f * m_pow(c, ISCO_RADIUS / fmaxf(r, ISCO_RADIUS), 1.2f);
             float cloud_I = d_cloud * CLOUD_LUMINOSITY * lighting;
 
@@ -492,7 +560,8 @@ static void trace_pixel_g(const rrto_camera* cam, const rrto_effects* fx, const 
                           float time, int width, int height, int x, int y,
                           const uint8_t* sky, int sw, int sh, pixel_out* o,
                           int gate_mode, uint8_t* gate_log, int gate_cap, int* gate_n) {
-    ctx_t c = {prm->math_mode, 0, 0, gate_mode, 0, gate_cap, 0, gate_log};
+    ctx_t c = {prm->math_mode, 0, 0, gate_mode, 0, gate_cap, 0, gate_log, prm->arith_mode};
+    const int fmad = prm->arith_mode == RRTO_ARITH_FMAD;
     const float spin = prm->spin;
 
     float uvx = (float)x / width;
@@ -528,8 +597,8 @@ static void trace_pixel_g(const rrto_camera* cam, const rrto_effects* fx, const 
     int i;
     for (i = 0; i < prm->max_steps; i++) {
         f3 rel_p = sub3(p, MASS_POS);
-        float r2 = dot3(rel_p, rel_p);
-        float r = sqrtf(r2);
+        float r2 = fmad ? dot3_fmad(rel_p, rel_p) : dot3(rel_p, rel_p);
+        float r = sqrtf(r2);             /* FMAD: the root of the fused sum is the march's radius from here to the transfer block */
 
         if (r < EVENT_HORIZON * 1.01f) {
             hit_horizon = 1;
@@ -546,7 +615,8 @@ static void trace_pixel_g(const rrto_camera* cam, const rrto_effects* fx, const 
         else if (in_disk_zone) current_h *= 0.3f;
         else if (in_cloud_zone) current_h *= 0.5f;
 
-        integrate_rk4(&p, &vel, current_h, spin);
+        if (fmad) integrate_rk4_fmad(&p, &vel, current_h, spin);
+        else integrate_rk4(&p, &vel, current_h, spin);
 
         if (in_disk_zone || in_cloud_zone) {
             /* volumetrics == 0 is the build's "skybox only" switch (BASELINE.json configs[1]):
@@ -558,7 +628,7 @@ static void trace_pixel_g(const rrto_camera* cam, const rrto_effects* fx, const 
                           &intensity_r, &intensity_g, &intensity_b, &transmittance)) n_samples++;
         }
 
-        if (r > 250.0f && dot3(rel_p, vel) > 0) { i++; break; }
+        if (r > 250.0f && (fmad ? dot3_fmad(rel_p, vel) : dot3(rel_p, vel)) > 0) { i++; break; }
     }
     /* `i` = number of RK4 steps taken */
 
@@ -624,6 +694,7 @@ int rrto_render_gates(const rrto_camera* cam, const rrto_effects* fx, const rrto
                       uint8_t* rgba8, float* ldr, float* hdr, const rrto_diag* diag, int n_threads,
                       int gate_mode, uint8_t* gate_log, int gate_cap, int32_t* gate_count) {
     if (!cam || !fx || !prm || !sky || width <= 0 || height <= 0 || sw <= 0 || sh <= 0) return -1;
+    if (prm->arith_mode != RRTO_ARITH_STRICT && prm->arith_mode != RRTO_ARITH_FMAD) return -1;
     if (gate_mode < 0 || gate_mode > 2 || (gate_mode && (!gate_log || !gate_count || gate_cap <= 0))) return -1;
     if (x0 < 0 || y0 < 0 || x1 > width || y1 > height || sx <= 0 || sy <= 0) return -1;
 #ifdef _OPENMP
@@ -691,6 +762,7 @@ void rrto_default_params(rrto_params* p) {
     p->math_mode = RRTO_MATH_LIBM;
     p->sky_frac_bits = 8;
     p->nudge_ulps = 0; p->nudge_seed = 0u;
+    p->arith_mode = RRTO_ARITH_STRICT;
 }
 
 void rrto_default_effects(rrto_effects* e) {   /* camera_settings.h:5-16 */
@@ -705,25 +777,46 @@ static inline f3 ld3(const float* a, int i) { return mk3(a[3 * i], a[3 * i + 1],
 static inline void st3(float* a, int i, f3 v) { a[3 * i] = v.x; a[3 * i + 1] = v.y; a[3 * i + 2] = v.z; }
 
 void rrto_hash31(int n, const float* p, float* out) { for (int i = 0; i < n; ++i) out[i] = hash31(ld3(p, i)); }
-void rrto_noise3d(int n, const float* p, float* out) { ctx_t c = {0, 0, 0, 0, 0, 0, 0, 0}; for (int i = 0; i < n; ++i) out[i] = noise3d(&c, ld3(p, i)); }
-void rrto_fbm(int n, const float* p, int oct, float* out) { ctx_t c = {0, 0, 0, 0, 0, 0, 0, 0}; for (int i = 0; i < n; ++i) out[i] = fbm(&c, ld3(p, i), oct); }
+void rrto_noise3d(int n, const float* p, float* out) { ctx_t c = {0, 0, 0, 0, 0, 0, 0, 0, 0}; for (int i = 0; i < n; ++i) out[i] = noise3d(&c, ld3(p, i)); }
+void rrto_fbm(int n, const float* p, int oct, float* out) { ctx_t c = {0, 0, 0, 0, 0, 0, 0, 0, 0}; for (int i = 0; i < n; ++i) out[i] = fbm(&c, ld3(p, i), oct); }
 void rrto_geodesic_acc(int n, const float* p, const float* v, float spin, float* out) {
     for (int i = 0; i < n; ++i) st3(out, i, geodesic_acc(ld3(p, i), ld3(v, i), spin));
 }
 void rrto_rk4(int n, float* p, float* v, const float* h, float spin) {
     for (int i = 0; i < n; ++i) { f3 pp = ld3(p, i), vv = ld3(v, i); integrate_rk4(&pp, &vv, h[i], spin); st3(p, i, pp); st3(v, i, vv); }
 }
+int rrto_geodesic_acc_arith(int n, const float* p, const float* v, float spin, int arith, float* out) {
+    if (arith != RRTO_ARITH_STRICT && arith != RRTO_ARITH_FMAD) return -1;
+    for (int i = 0; i < n; ++i) st3(out, i, arith == RRTO_ARITH_FMAD ? geodesic_acc_fmad(ld3(p, i), ld3(v, i), spin) : geodesic_acc(ld3(p, i), ld3(v, i), spin));
+    return 0;
+}
+/* the march's dot product (squared radius, escape test) in either arithmetic */
+int rrto_dot_arith(int n, const float* a, const float* b, int arith, float* out) {
+    if (arith != RRTO_ARITH_STRICT && arith != RRTO_ARITH_FMAD) return -1;
+    for (int i = 0; i < n; ++i) out[i] = arith == RRTO_ARITH_FMAD ? dot3_fmad(ld3(a, i), ld3(b, i)) : dot3(ld3(a, i), ld3(b, i));
+    return 0;
+}
+int rrto_rk4_arith(int n, float* p, float* v, const float* h, float spin, int arith) {
+    if (arith != RRTO_ARITH_STRICT && arith != RRTO_ARITH_FMAD) return -1;
+    for (int i = 0; i < n; ++i) {
+        f3 pp = ld3(p, i), vv = ld3(v, i);
+        if (arith == RRTO_ARITH_FMAD) integrate_rk4_fmad(&pp, &vv, h[i], spin);
+        else integrate_rk4(&pp, &vv, h[i], spin);
+        st3(p, i, pp); st3(v, i, vv);
+    }
+    return 0;
+}
 void rrto_redshift(int n, const float* p, const float* vel, float spin, int mode, float* out) {
-    ctx_t c = {mode, 0, 0, 0, 0, 0, 0, 0}; for (int i = 0; i < n; ++i) out[i] = redshift_factor(&c, ld3(p, i), ld3(vel, i), spin);
+    ctx_t c = {mode, 0, 0, 0, 0, 0, 0, 0, 0}; for (int i = 0; i < n; ++i) out[i] = redshift_factor(&c, ld3(p, i), ld3(vel, i), spin);
 }
 void rrto_disk_temperature(int n, const float* r, int mode, float* out) {
-    ctx_t c = {mode, 0, 0, 0, 0, 0, 0, 0}; for (int i = 0; i < n; ++i) out[i] = disk_temperature(&c, r[i]);
+    ctx_t c = {mode, 0, 0, 0, 0, 0, 0, 0, 0}; for (int i = 0; i < n; ++i) out[i] = disk_temperature(&c, r[i]);
 }
 void rrto_accretion_density(int n, const float* p, float time, int mode, float* out) {
-    ctx_t c = {mode, 0, 0, 0, 0, 0, 0, 0}; for (int i = 0; i < n; ++i) out[i] = accretion_density(&c, ld3(p, i), time);
+    ctx_t c = {mode, 0, 0, 0, 0, 0, 0, 0, 0}; for (int i = 0; i < n; ++i) out[i] = accretion_density(&c, ld3(p, i), time);
 }
 void rrto_dust_density(int n, const float* p, float time, int mode, float* out) {
-    ctx_t c = {mode, 0, 0, 0, 0, 0, 0, 0}; for (int i = 0; i < n; ++i) out[i] = dust_density(&c, ld3(p, i), time);
+    ctx_t c = {mode, 0, 0, 0, 0, 0, 0, 0, 0}; for (int i = 0; i < n; ++i) out[i] = dust_density(&c, ld3(p, i), time);
 }
 void rrto_smoothstep(int n, const float* e0, const float* e1, const float* x, float* out) {
     for (int i = 0; i < n; ++i) out[i] = smoothstepf(e0[i], e1[i], x[i]);
@@ -744,12 +837,12 @@ void rrto_sky_fetch(const uint8_t* sky, int sw, int sh, int frac_bits, float tx,
 }
 void rrto_sky_sample(int n, const float* dir, float off, const uint8_t* sky, int sw, int sh,
                      int frac_bits, int mode, float* out) {
-    ctx_t c = {mode, 0, 0, 0, 0, 0, 0, 0}; for (int i = 0; i < n; ++i) sample_sky(&c, ld3(dir, i), off, sky, sw, sh, frac_bits, out + 4 * i);
+    ctx_t c = {mode, 0, 0, 0, 0, 0, 0, 0, 0}; for (int i = 0; i < n; ++i) sample_sky(&c, ld3(dir, i), off, sky, sw, sh, frac_bits, out + 4 * i);
 }
 /* one radiative-transfer sample per element: rad (r,g,b,T) is updated in place */
 void rrto_rt_sample(int n, const float* d_disk, const float* d_cloud, const float* p, const float* vel,
                     const float* h, float spin, int mode, float* rad) {
-    ctx_t c = {mode, 0, 0, 0, 0, 0, 0, 0};
+    ctx_t c = {mode, 0, 0, 0, 0, 0, 0, 0, 0};
     for (int i = 0; i < n; ++i) {
         f3 rp = ld3(p, i);
         rt_sample(&c, d_disk[i], d_cloud[i], rp, length3(rp), ld3(vel, i), h[i], spin,
@@ -758,7 +851,7 @@ void rrto_rt_sample(int n, const float* d_disk, const float* d_cloud, const floa
 }
 
 void rrto_math(int fn, int mode, int n, const float* a, const float* b, float* out) {
-    ctx_t c = {mode, 0, 0, 0, 0, 0, 0, 0};
+    ctx_t c = {mode, 0, 0, 0, 0, 0, 0, 0, 0};
     for (int i = 0; i < n; ++i) {
         switch (fn) {
             case 0: out[i] = m_exp(&c, a[i]); break;

@@ -50,6 +50,15 @@ extern "C" {
  * inside a GPU math library's documented error class (conditioning probes, tests/test_density_conditioning.py) */
 #define RRTO_MATH_NUDGED_BASE 16
 
+/* arith_mode: which arithmetic the MARCH runs in (the values of RRT_ARITH_STRICT / RRT_ARITH_FMAD, include/rrt.h).
+ *   RRTO_ARITH_STRICT  the reference's source, every operation rounded on its own (default)
+ *   RRTO_ARITH_FMAD    the same source with a fixed set of multiply-adds fused: geodesic_acc_fmad / integrate_rk4_fmad,
+ *                      the fused loop-top radius and escape test, and the transfer block on that radius (rrt_oracle.c;
+ *                      DESIGN.md section 2).  Square roots and divisions are IEEE; the media code is the strict one.
+ * RRT_ARITH_FAST has no restatement (its reciprocal square root is a hardware approximation); any other value is refused. */
+#define RRTO_ARITH_STRICT 0
+#define RRTO_ARITH_FMAD 2
+
 typedef struct {
     float pos[3], forward[3], right[3], up[3];     /* include/raymarcher.h:11-16 */
 } rrto_camera;
@@ -71,6 +80,7 @@ typedef struct {
                                 primary direction by a pseudo-random whole number of ulps in [-K, K]; the product's
                                 rrt_params.nudge_ulps / .nudge_seed is the same function (rrto_nudge_component) */
     uint32_t nudge_seed;
+    int32_t arith_mode;      /* RRTO_ARITH_* */
 } rrto_params;
 
 /* v moved by k ulps, k in [-K, K] from a hash of (x, y, seed, component 0..2) */
@@ -96,6 +106,10 @@ void rrto_noise3d(int n, const float* p, float* out);
 void rrto_fbm(int n, const float* p, int octaves, float* out);
 void rrto_geodesic_acc(int n, const float* p, const float* v, float spin, float* out);
 void rrto_rk4(int n, float* p, float* v, const float* h, float spin);
+/* the same two in either arithmetic (RRTO_ARITH_*); -1 on any other value */
+int rrto_geodesic_acc_arith(int n, const float* p, const float* v, float spin, int arith, float* out);
+int rrto_rk4_arith(int n, float* p, float* v, const float* h, float spin, int arith);
+int rrto_dot_arith(int n, const float* a, const float* b, int arith, float* out);    /* dot(a, b) as the march takes it */
 void rrto_redshift(int n, const float* p, const float* vel, float spin, int math_mode, float* out);
 void rrto_disk_temperature(int n, const float* r, int math_mode, float* out);
 void rrto_accretion_density(int n, const float* p, float time, int math_mode, float* out);

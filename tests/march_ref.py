@@ -7,6 +7,10 @@ RK4 step of the oracle (rrto_rk4, pinned to the reference's integrate_rk4 by tes
 pre-step position and the post-step velocity (r > 250 and dot > 0: the ray ends, the step is counted).  A ray that does neither
 ends with steps = max_steps.  tests/test_march_ref.py proves the restatement against the oracle's own frames, bit for bit.
 
+arith = FMAD is RRT_ARITH_FMAD's march: the squared radius and the escape test's dot product are the fused
+fma(z, z', fma(y, y', x*x')) (rrto_dot_arith: C's exact fmaf), the step is the oracle's FMAD step (rrto_rk4_arith); the loop is
+the same, and the same proof holds it to the oracle's FMAD frames.
+
 VIEWS / SPINS / BUDGETS are the cases of that proof; the GPU modules draw their rays from the same views."""
 import numpy as np
 
@@ -16,6 +20,7 @@ HORIZON = F(2.0) * F(1.01)                     # EVENT_HORIZON * 1.01f
 STEP = F(0.3)                                  # STEP_SIZE_M
 DISK_H5, DISK_R = F(0.8) * F(5.0), F(25.0) + F(5.0)      # DISK_H_M * 5.0f, DISK_OUT_M + 5.0f
 CLOUD_H15, CLOUD_R = F(0.5) * F(1.5), F(25.0)            # CLOUD_H_M * 1.5f, CLOUD_OUT_M
+STRICT, FMAD = 0, 2                            # RRT_ARITH_STRICT, RRT_ARITH_FMAD; FAST has no restatement
 VACUUM_R = F(30.0)                             # beyond it no zone and no horizon: the wave-uniform vacuum step's domain
 
 # (position, yaw, pitch) for CameraState.from_angles
@@ -43,9 +48,16 @@ def radius(p):
     return np.sqrt((x * x + y * y) + z * z)
 
 
-def march_ref(p, v, spin, max_steps, first_step=None, po=None):
+def radius_arith(units, p, arith):
+    """the march's loop-top radius in arithmetic `arith`: the correctly rounded root of the (strict or fused) squared radius"""
+    if arith == STRICT:
+        return radius(p)
+    return np.sqrt(units.dot_arith(p, p, arith))
+
+
+def march_ref(p, v, spin, max_steps, first_step=None, po=None, arith=STRICT):
     """march rays (p, v) (n, 3) until step max_steps; ray i starts at step first_step[i] (default 0).  po: the oracle binding
-    (the `po` fixture; imported here when None).
+    (the `po` fixture; imported here when None).  arith: STRICT or FMAD.
     Returns (p, v, steps, hit): final state, the ray's step count, whether the horizon test ended it."""
     if po is None:
         from oracle import pyoracle as po
@@ -65,7 +77,7 @@ def march_ref(p, v, spin, max_steps, first_step=None, po=None):
                     break
                 continue
             q = p[idx]
-            r = radius(q)
+            r = radius_arith(units, q, arith)
             assert r.dtype == F
             fell = r < HORIZON
             hit[idx[fell]] = 1
@@ -78,9 +90,9 @@ def march_ref(p, v, spin, max_steps, first_step=None, po=None):
             in_disk = (np.abs(q[:, 1]) < DISK_H5) & (r < DISK_R)
             in_cloud = (np.abs(q[:, 1]) < CLOUD_H15) & (r < CLOUD_R)
             hstep = np.where(near, STEP * F(0.1), np.where(in_disk, STEP * F(0.3), np.where(in_cloud, STEP * F(0.5), STEP))).astype(F)
-            pn, vn = units.rk4(q, v[idx], hstep, spin)
+            pn, vn = units.rk4(q, v[idx], hstep, spin) if arith == STRICT else units.rk4_arith(q, v[idx], hstep, spin, arith)
             p[idx], v[idx] = pn, vn
-            d = (q[:, 0] * vn[:, 0] + q[:, 1] * vn[:, 1]) + q[:, 2] * vn[:, 2]
+            d = (q[:, 0] * vn[:, 0] + q[:, 1] * vn[:, 1]) + q[:, 2] * vn[:, 2] if arith == STRICT else units.dot_arith(q, vn, arith)
             out = (r > F(250.0)) & (d > 0)
             steps[idx[out]] = k + 1
             alive[idx[out]] = False

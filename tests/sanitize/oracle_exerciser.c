@@ -49,6 +49,7 @@ int main(void) {
         for (int mode = 0; mode < 2; ++mode) {
             const int w = 37 + 5 * c, h = 19 + 3 * c;          /* ragged sizes */
             prm.math_mode = mode ? RRTO_MATH_PORTABLE : RRTO_MATH_LIBM;
+            prm.arith_mode = (c + mode) & 1 ? RRTO_ARITH_FMAD : RRTO_ARITH_STRICT;      /* both marches in both math modes */
             prm.spin = c & 1 ? 0.9f : 0.0f;
             prm.volumetrics = 1;
             fx.use_ca = c & 1;

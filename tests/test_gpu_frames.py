@@ -120,6 +120,16 @@ def test_live_oracle_random_view(ctx, po, sky):
     assert np.array_equal(r["steps"], o["steps"])
     prod = g.render_gpu(w, h, 0.9, 1, cam, 6.0, tex, fx=fx, debug=False)            # the production instantiation
     assert np.array_equal(prod["rgba8"], o["rgba8"])
+    # RRT_ARITH_FMAD against the oracle's FMAD mode (the fixed fused tree): the same equalities
+    of = po.render(ocam, ofx, po.default_params(spin=0.9, math_mode=po.MATH_PORTABLE, arith_mode=po.ARITH_FMAD), 6.0, w, h, sky,
+                   want=("rgba8", "ldr", "hdr", "diag"))
+    assert not np.array_equal(of["pos"], o["pos"])                                   # another frame than the strict one
+    rf = g.render_gpu(w, h, 0.9, 1, cam, 6.0, tex, fx=fx, arith_mode=2)
+    assert np.array_equal(rf["rgba8"], of["rgba8"])
+    assert same_bits(rf["hdr"], of["hdr"]) and same_bits(rf["ldr"], of["ldr"])
+    assert np.array_equal(rf["steps"], of["steps"]) and same_bits(rf["pos"], of["pos"]) and same_bits(rf["vel"], of["vel"])
+    prod = g.render_gpu(w, h, 0.9, 1, cam, 6.0, tex, fx=fx, debug=False, arith_mode=2)
+    assert np.array_equal(prod["rgba8"], of["rgba8"])
     ol = po.render(ocam, ofx, po.default_params(spin=0.9, math_mode=po.MATH_LIBM), 6.0, w, h, sky,
                    want=("rgba8", "ldr"))
     ok = (np.abs(r["ldr"][..., :3] - ol["ldr"][..., :3]) <= 1e-4 * np.abs(ol["ldr"][..., :3]) + 1e-5).all(axis=2)
@@ -136,18 +146,19 @@ def test_effect_toggles_and_edge_sizes(ctx, po, sky):
     a = cam.as_array(); ocam = po.camera(a[0], a[1], a[2], a[3])
     fx = rrt.CameraEffects(useBloom=False, useVignette=False, useLensDistortion=False)
     ofx = po.default_effects(use_bloom=0, use_vignette=0, use_lens=0)
-    for (w, h) in ((37, 23), (1, 1), (17, 16)):
-        r = g.render_gpu(w, h, 0.9, 1, cam, 1.0, tex, fx=fx)
-        o = po.render(ocam, ofx, po.default_params(spin=0.9, math_mode=po.MATH_PORTABLE), 1.0, w, h, sky)
-        assert np.array_equal(r["rgba8"], o["rgba8"]), (w, h)
-    r = g.render_gpu(33, 9, 0.0, 1, cam, 1.0, tex, max_steps=0)
-    o = po.render(ocam, po.default_effects(), po.default_params(max_steps=0, math_mode=po.MATH_PORTABLE),
-                  1.0, 33, 9, sky)
-    assert np.array_equal(r["rgba8"], o["rgba8"])
-    r = g.render_gpu(33, 9, 0.9, 1, cam, 1.0, tex, frac_bits=0)
-    o = po.render(ocam, po.default_effects(), po.default_params(spin=0.9, sky_frac_bits=0, math_mode=po.MATH_PORTABLE),
-                  1.0, 33, 9, sky)
-    assert np.array_equal(r["rgba8"], o["rgba8"])
+    for arith in (0, 2):                                    # strict, and RRT_ARITH_FMAD against the oracle's FMAD mode
+        for (w, h) in ((37, 23), (1, 1), (17, 16)):
+            r = g.render_gpu(w, h, 0.9, 1, cam, 1.0, tex, fx=fx, arith_mode=arith)
+            o = po.render(ocam, ofx, po.default_params(spin=0.9, math_mode=po.MATH_PORTABLE, arith_mode=arith), 1.0, w, h, sky)
+            assert np.array_equal(r["rgba8"], o["rgba8"]), (w, h, arith)
+        r = g.render_gpu(33, 9, 0.0, 1, cam, 1.0, tex, max_steps=0, arith_mode=arith)
+        o = po.render(ocam, po.default_effects(), po.default_params(max_steps=0, math_mode=po.MATH_PORTABLE, arith_mode=arith),
+                      1.0, 33, 9, sky)
+        assert np.array_equal(r["rgba8"], o["rgba8"]), arith
+        r = g.render_gpu(33, 9, 0.9, 1, cam, 1.0, tex, frac_bits=0, arith_mode=arith)
+        o = po.render(ocam, po.default_effects(), po.default_params(spin=0.9, sky_frac_bits=0, math_mode=po.MATH_PORTABLE, arith_mode=arith),
+                      1.0, 33, 9, sky)
+        assert np.array_equal(r["rgba8"], o["rgba8"]), arith
 
 
 @pytest.mark.parametrize("pos,yaw,pitch,spin", [
@@ -163,15 +174,16 @@ def test_unusual_cameras_match_oracle(ctx, po, sky, pos, yaw, pitch, spin):
     w, h = 48, 28
     cam = rrt.CameraState.from_angles(pos, yaw, pitch)
     fx = rrt.CameraEffects(useChromaticAberration=True)
-    r = g.render_gpu(w, h, spin, 1, cam, 2.5, tex, fx=fx)
     a = cam.as_array()
-    o = po.render(po.camera(a[0], a[1], a[2], a[3]), po.default_effects(use_ca=1),
-                  po.default_params(spin=spin, math_mode=po.MATH_PORTABLE), 2.5, w, h, sky,
-                  want=("rgba8", "ldr", "diag"))
-    assert np.array_equal(r["steps"], o["steps"])
-    assert np.array_equal(r["hit"], o["hit"])
-    assert np.array_equal(r["rgba8"], o["rgba8"])
-    assert same_bits(r["ldr"], o["ldr"])
+    for arith in (0, 2):                                    # strict, and RRT_ARITH_FMAD against the oracle's FMAD mode
+        r = g.render_gpu(w, h, spin, 1, cam, 2.5, tex, fx=fx, arith_mode=arith)
+        o = po.render(po.camera(a[0], a[1], a[2], a[3]), po.default_effects(use_ca=1),
+                      po.default_params(spin=spin, math_mode=po.MATH_PORTABLE, arith_mode=arith), 2.5, w, h, sky,
+                      want=("rgba8", "ldr", "diag"))
+        assert np.array_equal(r["steps"], o["steps"]), arith
+        assert np.array_equal(r["hit"], o["hit"]), arith
+        assert np.array_equal(r["rgba8"], o["rgba8"]), arith
+        assert same_bits(r["ldr"], o["ldr"]), arith
 
 
 def test_row_and_tile_shards_reassemble_to_the_full_frame(ctx):
@@ -1300,7 +1312,8 @@ def test_pipelined_sharder_over_one_rank_rccl(ctx):
 def test_randomized_sweep_every_launch_variant_matches_oracle(ctx, po, sky):
     """Seeded random scenes (camera anywhere from inside the disk to far out, any orientation, spin of either
     sign, random time / effects / ragged size): the single kernel, the three-pass path with an ample and with
-    a starved pool, cost-ordered dispatch, and interleaved tile shards must all give the oracle's bytes (portable math mode)."""
+    a starved pool, cost-ordered dispatch, and interleaved tile shards must all give the oracle's bytes (portable math mode).
+    On even scenes the FMAD single kernel equals the oracle's FMAD mode, and every FMAD path the single kernel."""
     import torch
     g, rrt, tex = ctx
     rng = np.random.default_rng(int(os.environ.get("RRT_SWEEP_SEED", "20261004")))     # soaks vary the seed
@@ -1412,7 +1425,14 @@ def test_randomized_sweep_every_launch_variant_matches_oracle(ctx, po, sky):
             torch.cuda.synchronize()
             assert torch.equal(out, want), (tag, "banded table, three-pass")
             mode = 2 - case % 2                       # RRT_ARITH_FMAD on even scenes, RRT_ARITH_FAST on odd ones
-            rm = g.render_gpu(w, h, spin, 1, cam, t, tex, fx=fx, arith_mode=mode)["rgba8"]
+            rmd = g.render_gpu(w, h, spin, 1, cam, t, tex, fx=fx, arith_mode=mode)
+            rm = rmd["rgba8"]
+            if mode == 2:                             # FMAD has a restatement: the oracle's FMAD mode, same equalities as strict
+                of = po.render(po.camera(a[0], a[1], a[2], a[3]), ofx,
+                               po.default_params(spin=spin, math_mode=po.MATH_PORTABLE, arith_mode=po.ARITH_FMAD), t, w, h, sky,
+                               want=("rgba8", "ldr", "diag"))
+                assert np.array_equal(rmd["steps"], of["steps"]) and np.array_equal(rmd["hit"], of["hit"]), (tag, "FMAD oracle")
+                assert np.array_equal(rm, of["rgba8"]) and same_bits(rmd["ldr"], of["ldr"]), (tag, "FMAD oracle")
             wantm = torch.from_numpy(rm.reshape(-1)).cuda()
             for kw in (dict(noise_table=nt.id), dict(noise_table=nt_banded.id, workspace=starved.id, path_policy=2, pool_rounds=64),
                        dict(workspace=mid.id, path_policy=2, pool_rounds=48, pass_chains=2, tile_order=order3.id)):

@@ -14,8 +14,8 @@ first min(kp.n_blocks, block_capacity) retained blocks and the 28 B terminal sta
 
 A SERVED SEQUENCE of a key is the same launch at times (1.0, 1.75, T, T, 9.25): a miss, a fill and three hits, the last one
 outside the noise table's window (the arithmetic kernels take over passes 2 and 3).  Every frame of it is compared with the
-same launch rendered while the cache is configured to 0 bytes (the single kernel), by equality; in strict arithmetic the first
-hit at T is the oracle's frame too.  The counters are asserted after every sequence, so that no case passes without being served."""
+same launch rendered while the cache is configured to 0 bytes (the single kernel), by equality; in strict and FMAD arithmetic the
+first hit at T is the oracle's frame in that arithmetic too.  The counters are asserted after every sequence, so that no case passes without being served."""
 import numpy as np
 import pytest
 
@@ -63,7 +63,8 @@ def same(got, want, what):
 @pytest.mark.parametrize("view", BUDGET_VIEWS)
 def test_served_frames_at_every_budget(ctx, po, sky, view, spin, arith):
     """61 x 37 with chromatic aberration, every budget of test_gpu_step_budget.py: the served sequence has the uncached launch's
-    bytes in the same arithmetic mode; in strict arithmetic the first hit at T is the oracle's frame at that budget; from inside
+    bytes in the same arithmetic mode; in strict and FMAD arithmetic the first hit at T is the oracle's frame (in that arithmetic)
+    at that budget; from inside
     the disk rows really were retained."""
     torch, rrt, tex, nt = ctx
     cam, fx = camera(view), fx_of(rrt)
@@ -78,8 +79,9 @@ def test_served_frames_at_every_budget(ctx, po, sky, view, spin, arith):
         same(got, want[n], (view, spin, arith, n))
         assert d == SERVED, (view, spin, arith, n, d)
         assert st["state"] == "ready" and st["blocks_used"] <= st["blocks_capacity"], (view, spin, arith, n, st)
-        if arith == "strict":
-            assert np.array_equal(got[2].reshape(H, W, 4), oracle(po, sky, view, spin, n)["rgba8"]), (view, spin, n, "oracle")
+        if arith in ("strict", "fmad"):       # the two arithmetics the oracle restates (FMAD: its fixed fused tree)
+            o = oracle(po, sky, view, spin, n, arith=ARITH[arith])
+            assert np.array_equal(got[2].reshape(H, W, 4), o["rgba8"]), (view, spin, arith, n, "oracle")
         if view == "in_disk":
             assert st["blocks_used"] > 0, (spin, arith, n, st)
     print(view, spin, arith, "blocks retained by budget", used)

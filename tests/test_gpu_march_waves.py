@@ -7,9 +7,11 @@ gives the bits of the generic step, a wave that leaves the vacuum loop because o
 unchanged, and the wave's scalar step counter stays right when lanes end at different steps.  Frames only test that for the
 waves an 8x8 pixel tile happens to hold; here the test decides who shares a wave.
 
-Strict arithmetic: every ray's (position, velocity, steps, hit) equals march_ref bit for bit, in every arrangement.  FMAD has no
-contracted reference, so every ray is compared between the arrangements (what row shards rely on).  FAST runs the loop without
-a vacuum path: the partial-wave and non-finite cases only, between arrangements.  No tolerance anywhere."""
+Strict and FMAD arithmetic: every ray's (position, velocity, steps, hit) equals march_ref in that arithmetic bit for bit, in
+every arrangement -- FMAD's is march_ref(arith=FMAD), the fixed fused tree of the oracle, so a fused term
+in the wrong order, or a template instance that fuses what another does not, fails here even where every arrangement agrees
+with every other.  FAST (a hardware reciprocal root: no restatement) runs the loop without a vacuum path: the partial-wave and
+non-finite cases only, between arrangements.  No tolerance anywhere."""
 import numpy as np
 import pytest
 
@@ -54,6 +56,11 @@ def same(a, b, sel=slice(None)):
             and np.array_equal(a[2][sel], b[2][sel]) and np.array_equal(a[3][sel], b[3][sel]))
 
 
+def refs(po, p, v, spin, max_steps, first_step=None):
+    """march_ref in both restated arithmetics: {STRICT: ..., FMAD: ...}"""
+    return {a: mr.march_ref(p, v, spin, max_steps, first_step=first_step, po=po, arith=a) for a in (STRICT, FMAD)}
+
+
 def pick(res, idx):
     return tuple(x[idx] for x in res)
 
@@ -90,10 +97,11 @@ def solo_waves(p, v, fp, fv, first_step=None):
 
 
 def check_arrangements(g, po, p, v, spin, max_steps, ariths, rng, first_step=None, what=""):
-    """the rays in the given order, in a seeded random order, and each alone among 63 far-vacuum rays: strict == march_ref,
-    every mode the same bits in all three; returns march_ref's result"""
+    """the rays in the given order, in a seeded random order, and each alone among 63 far-vacuum rays: strict and FMAD ==
+    march_ref in that arithmetic, every mode the same bits in all three; returns the strict march_ref's result"""
     n = len(p)
-    ref = mr.march_ref(p, v, spin, max_steps, first_step=first_step, po=po)
+    ref = refs(po, p, v, spin, max_steps, first_step)
+    fref = None
     perm = rng.permutation(n)
     fp, fv = vacuum_fillers(rng)
     sp, sv, sfs, rows = solo_waves(p, v, fp, fv, first_step)
@@ -103,17 +111,16 @@ def check_arrangements(g, po, p, v, spin, max_steps, ariths, rng, first_step=Non
         c = run(g, sp, sv, spin, arith, max_steps, sfs)
         lim = np.maximum(max_steps, 0 if first_step is None else first_step)
         assert (a[2] >= 0).all() and (a[2] <= lim).all() and set(np.unique(a[3])) <= {0, 1}, (what, arith)
-        if arith == STRICT:
-            assert same(a, ref), (what, "image order", int((a[2] != ref[2]).sum()))
+        if arith in ref:
+            assert same(a, ref[arith]), (what, arith, "image order", int((a[2] != ref[arith][2]).sum()))
         inv = np.empty(n, np.int64); inv[perm] = np.arange(n)
         assert same(pick(b, inv), a), (what, arith, "permuted", int((b[2][inv] != a[2]).sum()))
         assert same(pick(c, rows), a), (what, arith, "alone among vacuum rays", int((c[2][rows] != a[2]).sum()))
-        if arith == STRICT:                                   # the fillers too: the same 63 rays whoever the 64th lane is
-            fref = mr.march_ref(fp, fv, spin, max_steps, po=po)
-            if first_step is None:
-                other = np.setdiff1d(np.arange(64), rows[:1] % 64)
-                assert same(pick(c, other), pick(fref, np.where(other < 63, other, 0))), (what, "fillers")
-    return ref
+        if arith in ref and first_step is None:               # the fillers too: the same 63 rays whoever the 64th lane is
+            fref = fref or refs(po, fp, fv, spin, max_steps)
+            other = np.setdiff1d(np.arange(64), rows[:1] % 64)
+            assert same(pick(c, other), pick(fref[arith], np.where(other < 63, other, 0))), (what, arith, "fillers")
+    return ref[STRICT]
 
 
 @pytest.mark.parametrize("view,spin,budget", [("default", 0.9, 1000), ("default", 0.0, 1000), ("skimmer", 0.9, 1000),
@@ -138,15 +145,15 @@ def test_frame_rays_in_three_arrangements(g, po, sky, view, spin, budget):
     chosen = np.array(chosen + list(rng.choice(rest, 64 - len(chosen), replace=False)))
     assert len(np.unique(chosen)) == 64
     # the whole frame: image order and a permutation (check_arrangements' third arrangement is run on the 64 chosen rays)
-    ref = mr.march_ref(p0, v0, spin, budget, po=po)
-    assert np.array_equal(ref[2], o["steps"]) and np.array_equal(ref[3], o["hit"])
+    ref = refs(po, p0, v0, spin, budget)
+    assert np.array_equal(ref[STRICT][2], o["steps"]) and np.array_equal(ref[STRICT][3], o["hit"])
+    assert not same(ref[FMAD], ref[STRICT])                         # the FMAD equalities below are not the strict ones again
     perm = rng.permutation(W * H)
     inv = np.empty(W * H, np.int64); inv[perm] = np.arange(W * H)
     for arith in (STRICT, FMAD):
         a = run(g, p0, v0, spin, arith, budget)
         b = run(g, p0[perm], v0[perm], spin, arith, budget)
-        if arith == STRICT:
-            assert same(a, ref), (view, spin, int((a[2] != ref[2]).sum()))
+        assert same(a, ref[arith]), (view, spin, arith, int((a[2] != ref[arith][2]).sum()))
         assert same(pick(b, inv), a), (view, spin, arith, int((b[2][inv] != a[2]).sum()))
         assert (a[2] <= budget).all()
     check_arrangements(g, po, p0[chosen], v0[chosen], spin, budget, (STRICT, FMAD), rng, what=(view, spin, "chosen"))
@@ -162,13 +169,13 @@ def test_one_near_hole_ray_among_vacuum_rays_and_the_reverse(g, po, spin):
     pure_p, pure_v = np.concatenate([hp, fp]), np.concatenate([hv, fv])
     to_pure = np.concatenate([[0], 64 + np.arange(1, 64), [64], np.arange(1, 64)])       # mixed row -> the same ray's pure row
     for budget in (40, 333, 900):
-        ref = mr.march_ref(pure_p, pure_v, spin, budget, po=po)
+        both = refs(po, pure_p, pure_v, spin, budget)
+        ref = both[STRICT]
         assert not ref[3][64:].any() and (budget < 900 or (ref[3][:64].any() and not ref[3][:64].all()))     # some near-hole rays fall in
         for arith in (STRICT, FMAD):
             pure = run(g, pure_p, pure_v, spin, arith, budget)
             mixed = run(g, mixed_p, mixed_v, spin, arith, budget)
-            if arith == STRICT:
-                assert same(pure, ref), (spin, budget)
+            assert same(pure, both[arith]), (spin, budget, arith)
             assert same(mixed, pick(pure, to_pure)), (spin, budget, arith, int((mixed[2] != pure[2][to_pure]).sum()))
 
 
@@ -201,12 +208,12 @@ def test_partial_waves(g, po, sky, n):
     p0, v0 = mr.primary_rays(po, cam, W, H, sky, spin=0.9)
     rows = np.random.default_rng(n).choice(W * H, 128, replace=False)
     p, v = p0[rows], v0[rows]
-    ref = mr.march_ref(p, v, 0.9, 700, po=po)
+    ref = refs(po, p, v, 0.9, 700)
     for arith in (STRICT, FMAD, FAST):
         full = run(g, p, v, 0.9, arith, 700)
         part = run(g, p, v, 0.9, arith, 700, n=n)
-        if arith == STRICT:
-            assert same(full, ref)
+        if arith in ref:
+            assert same(full, ref[arith]), (n, arith)
         assert same(part, full, slice(0, n)), (n, arith)
         assert np.array_equal(_bits(part[0][n:]), _bits(p[n:])) and np.array_equal(_bits(part[1][n:]), _bits(v[n:])), (n, arith)
         assert (part[2][n:] == -7).all() and (part[3][n:] == -7).all(), (n, arith)
@@ -228,12 +235,12 @@ def test_non_finite_lanes_terminate_and_leave_their_wave_mates_alone(g, po, kind
     bv[17] = (np.inf, 0.0, 0.0)
     bp[40] = (0.0, 0.0, 0.0)
     budget = 300
-    ref = mr.march_ref(p, v, 0.9, budget, po=po)
+    ref = refs(po, p, v, 0.9, budget)
     for arith in (STRICT, FMAD, FAST):
         clean = run(g, p, v, 0.9, arith, budget)
         dirty = run(g, bp, bv, 0.9, arith, budget)
-        if arith == STRICT:
-            assert same(clean, ref)
+        if arith in ref:
+            assert same(clean, ref[arith]), (kind, arith)
         assert same(dirty, clean, good), (kind, arith, int((dirty[2][good] != clean[2][good]).sum()))
         assert (dirty[2][bad] >= 0).all() and (dirty[2][bad] <= budget).all(), (kind, arith, dirty[2][bad])
         assert dirty[2][40] == 0 and dirty[3][40] == 1                       # r = 0 is inside the horizon: ends at step 0

@@ -11,9 +11,10 @@ budget ends among the media samples; around 1000 a frame holds escaped, fallen-i
 COVERAGE IS A CONDITION: test_budget_set_meets_the_coverage_conditions computes, from the oracle's own per-ray diagnostics and
 without a GPU, that the (view, spin, budget) set really holds such frames.
 
-Strict arithmetic: everything equals the oracle in its portable math mode (equality, no tolerance).  FMAD and FAST have no
-contracted oracle at a budget: every path must give the single kernel's bytes exactly, and the single kernel is held to the
-suite's existing bars against the libm oracle at the same budget (test_gpu_frames.py::test_tolerance_modes_against_the_libm_oracle)."""
+Strict and FMAD arithmetic: everything equals the oracle in the same arithmetic mode (FMAD: the oracle's fixed fused tree,
+DESIGN.md section 2) and its portable math mode -- equality, no tolerance.  Every other path must give the single kernel's bytes
+exactly.  FAST has no restatement (a hardware reciprocal root): its single kernel, and FMAD's beside it, is also held to the
+suite's bars against the libm oracle at the same budget (test_gpu_frames.py::test_tolerance_modes_against_the_libm_oracle)."""
 import numpy as np
 import pytest
 
@@ -41,13 +42,14 @@ def camera(view):
     return rrt.CameraState.from_angles(*mr.VIEWS[view])
 
 
-def oracle(po, sky, view, spin, n, vol=1, libm=False):
-    """the oracle's frame and per-ray diagnostics of a case (chromatic aberration on, like the GPU launches below); kept for
-    the other tests of the process"""
-    key = (view, spin, n, vol, libm)
+def oracle(po, sky, view, spin, n, vol=1, libm=False, arith=0):
+    """the oracle's frame and per-ray diagnostics of a case (chromatic aberration on, like the GPU launches below) in arithmetic
+    `arith` (0 strict, 2 FMAD); kept for the other tests of the process"""
+    key = (view, spin, n, vol, libm) + ((arith,) if arith else ())
     if key not in _ORACLE:
         a = camera(view).as_array()
-        prm = po.default_params(spin=spin, volumetrics=vol, max_steps=n, math_mode=po.MATH_LIBM if libm else po.MATH_PORTABLE)
+        prm = po.default_params(spin=spin, volumetrics=vol, max_steps=n, math_mode=po.MATH_LIBM if libm else po.MATH_PORTABLE,
+                                arith_mode=arith)
         _ORACLE[key] = po.render(po.camera(a[0], a[1], a[2], a[3]), po.default_effects(use_ca=1), prm, T, W, H, sky,
                                  want=("rgba8", "ldr", "hdr", "diag"))
     return _ORACLE[key]
@@ -133,6 +135,47 @@ def test_strict_frames_equal_the_oracle_at_every_budget(ctx, po, sky, view, spin
                 assert np.array_equal(prod["rgba8"], o["rgba8"]), what
             tab = g.render_gpu(W, H, spin, 1, cam, T, tex, fx=fx_of(rrt), max_steps=n, debug=False, noise_table=nt.id)
             assert np.array_equal(tab["rgba8"], oracle(po, sky, view, spin, n)["rgba8"]), (view, spin, n, "noise table")
+    finally:
+        nt.destroy()
+
+
+FMAD_VOL_OFF = (1, 200, 1999)      # volumetrics off costs the oracle a second frame per budget: the ends and the middle only
+
+
+def test_fmad_oracle_frames_are_not_the_strict_ones(po, sky):
+    """a condition of the test below: at the budgets that leave room for it the FMAD oracle's per-ray state differs from the
+    strict oracle's, so a kernel that ran strict arithmetic under the FMAD switch could not pass"""
+    for view in VIEWS:
+        for spin in SPINS:
+            a, b = oracle(po, sky, view, spin, 150), oracle(po, sky, view, spin, 150, arith=2)
+            assert (a["pos"].view(np.uint32) != b["pos"].view(np.uint32)).any(axis=1).mean() > 0.3, (view, spin)
+
+
+@gpu
+@pytest.mark.parametrize("spin", SPINS)
+@pytest.mark.parametrize("view", VIEWS)
+def test_fmad_frames_equal_the_fmad_oracle_at_every_budget(ctx, po, sky, view, spin):
+    """the twin of the strict test above in RRT_ARITH_FMAD: the debug launch's per-ray state, HDR, LDR and bytes equal the
+    oracle's FMAD mode at the same budget, the production launch and the noise-table launch give the same bytes; volumetrics
+    off at the first, a middle and the last budget"""
+    g, rrt, tex = ctx
+    cam = camera(view)
+    nt = rrt.NoiseTable(4.0)
+    try:
+        for n in BUDGETS:
+            for vol in ((1, 0) if n in FMAD_VOL_OFF else (1,)):
+                o = oracle(po, sky, view, spin, n, vol, arith=2)
+                r = g.render_gpu(W, H, spin, vol, cam, T, tex, fx=fx_of(rrt), max_steps=n, arith_mode=2)
+                what = (view, spin, n, vol)
+                assert np.array_equal(r["steps"], o["steps"]), (what, int((r["steps"] != o["steps"]).sum()))
+                assert np.array_equal(r["hit"], o["hit"]), what
+                for k in ("pos", "vel", "rad", "hdr", "ldr"):
+                    assert same_bits(r[k], o[k]), (what, k, int((~((r[k].view(np.uint32) == o[k].view(np.uint32)) | ((r[k] == 0) & (o[k] == 0)))).sum()))
+                assert np.array_equal(r["rgba8"], o["rgba8"]), what
+                prod = g.render_gpu(W, H, spin, vol, cam, T, tex, fx=fx_of(rrt), max_steps=n, debug=False, arith_mode=2)
+                assert np.array_equal(prod["rgba8"], o["rgba8"]), what
+            tab = g.render_gpu(W, H, spin, 1, cam, T, tex, fx=fx_of(rrt), max_steps=n, debug=False, noise_table=nt.id, arith_mode=2)
+            assert np.array_equal(tab["rgba8"], oracle(po, sky, view, spin, n, arith=2)["rgba8"]), (view, spin, n, "noise table")
     finally:
         nt.destroy()
 

@@ -78,6 +78,95 @@ def test_production_rk4_chain_matches_the_reference_chain(g, rk4_chain_ref, spin
             assert np.array_equal(g.host(steps), c[f"steps_a{spin:g}_k{k}"]), (k, seed_scale)
 
 
+FMAD = 2
+
+
+def _march(g, p, v, spin, arith, max_steps):
+    """rrt_unit_march (march_inline / vacuum_run themselves; 64 consecutive rays are one wavefront) -> (p, v, steps, hit)"""
+    import torch
+    dp, dv = g.dev(np.ascontiguousarray(p, np.float32)), g.dev(np.ascontiguousarray(v, np.float32))
+    steps = torch.full((len(p),), -7, dtype=torch.int32, device="cuda")
+    hit = torch.full((len(p),), -7, dtype=torch.int32, device="cuda")
+    g.unit("march", len(p), dp, dv, float(spin), int(arith), int(max_steps), None, steps, hit)
+    return g.host(dp).reshape(-1, 3), g.host(dv).reshape(-1, 3), g.host(steps), g.host(hit)
+
+
+def _assert_fmad_march(g, po, p, v, spin, budget, what):
+    import march_ref as mr
+    ref = mr.march_ref(p, v, spin, budget, po=po, arith=mr.FMAD)
+    got = _march(g, p, v, spin, FMAD, budget)
+    assert np.array_equal(got[2], ref[2]) and np.array_equal(got[3], ref[3]), (what, spin, budget)
+    bad = (got[0].view(np.uint32) != ref[0].view(np.uint32)).any(axis=1) | (got[1].view(np.uint32) != ref[1].view(np.uint32)).any(axis=1)
+    assert same_bits(got[0], ref[0]) and same_bits(got[1], ref[1]), (what, spin, budget, int(bad.sum()), np.flatnonzero(bad)[:8])
+    return ref
+
+
+@pytest.mark.parametrize("spin", SPINS)
+def test_fmad_step_matches_the_fmad_restatement_on_reference_vectors(g, po, units_ref, spin):
+    """RRT_ARITH_FMAD's step is the oracle's integrate_rk4_fmad, bit for bit: the reference's one-step
+    vectors through rrt_unit_march with a budget of one step, the step size from the zone rule.  In file order the waves mix
+    zones and take the generic instance; with the r >= 30 rays gathered into whole wavefronts vacuum_run takes them, and a
+    budget of three steps brings in the seeds extrapolated from the step before."""
+    import march_ref as mr
+    p, v = units_ref["geo_p"], units_ref["geo_v"]
+    x = p.astype(np.float64)
+    r = np.sqrt((x * x).sum(axis=1))
+    sel = r > 2.03
+    assert sel.sum() > 900
+    p, v, r = p[sel], v[sel], r[sel]
+    ref = _assert_fmad_march(g, po, p, v, spin, 1, "file order")
+    assert (ref[2] == 1).all() and not ref[3].any()
+    strict = mr.march_ref(p, v, spin, 1, po=po)
+    assert not (same_bits(strict[0], ref[0]) and same_bits(strict[1], ref[1]))      # the vectors tell the two arithmetics apart
+    far = np.flatnonzero(r >= 30.5)
+    far = far[:len(far) // 64 * 64]
+    assert len(far) >= 64                                                            # at least one whole vacuum wavefront
+    for budget in (1, 3):
+        _assert_fmad_march(g, po, p[far], v[far], spin, budget, "vacuum wavefronts")
+
+
+def _rays_at_powers_of_four(po, rng):
+    """4224 rays whose fused squared radius -- of the start position (the loop-top root) or of the stage-2 position
+    fma(v, h/2, p) (a two-iteration seeded root in the generic step, a one-iteration one in the vacuum step) -- lies within
+    64 ulps of 4^k, r = 4 ... 128: the operand class the seeded roots' guard is about.  Only positions on which the fused and
+    the unfused sum differ are kept.  Blocks of 704 = 11 wavefronts per radius, so r >= 32 fills whole vacuum wavefronts."""
+    import march_ref as mr
+    units = po.units()
+    F = np.float32
+    P, V = [], []
+    for k in range(2, 8):
+        x4 = F(4.0) ** k
+        hh = (mr.STEP * F(0.1) if 2.0 ** k < 18.0 else mr.STEP) * F(0.5)
+        for stage, want in ((False, 384), (True, 320)):
+            n = 16 * want
+            d = rng.normal(size=(n, 3)); d /= np.linalg.norm(d, axis=1, keepdims=True)
+            j = np.where(rng.random(n) < 0.5, rng.integers(-4, 5, n), rng.integers(-60, 61, n))
+            target = float(x4) * (1.0 + np.where(j >= 0, j * 2.0 ** -23, j * 2.0 ** -24))
+            q = d * np.sqrt(target)[:, None]
+            vel = rng.normal(size=(n, 3)); vel /= np.linalg.norm(vel, axis=1, keepdims=True)
+            vel = vel.astype(F)
+            p0 = (q - vel.astype(np.float64) * float(hh)).astype(F) if stage else q.astype(F)
+            at = (p0.astype(np.float64) + vel.astype(np.float64) * float(hh)).astype(F) if stage else p0     # fma(v, hh, p0): one rounding
+            fused, plain = units.dot_arith(at, at, mr.FMAD), units.dot_arith(at, at, mr.STRICT)
+            dist = np.abs(fused.view(np.int32).astype(np.int64) - int(np.array(x4, F).view(np.int32)))
+            keep = np.flatnonzero((dist <= 64) & (fused != plain))
+            assert len(keep) >= want, (k, stage, len(keep))
+            P.append(p0[keep[:want]]); V.append(vel[keep[:want]])
+    return np.concatenate(P), np.concatenate(V)
+
+
+@pytest.mark.parametrize("spin", (0.9, 0.0))
+def test_fmad_roots_at_fused_radii_next_to_powers_of_four(g, po, spin):
+    """the seeded roots see the FUSED squared radius in FMAD: rays placed so that it lies within 64 ulps of a power of four
+    where the unfused sum is another float -- a root taken from the wrong sum, or a seeded root that accepts a wrong value on
+    that class, moves the step's bits off the restatement's (IEEE sqrtf of the fused sum)"""
+    rng = np.random.default_rng(4 ** 8)
+    p, v = _rays_at_powers_of_four(po, rng)
+    assert len(p) == 4224 and len(p) <= 65536
+    for budget in (1, 2):
+        _assert_fmad_march(g, po, p, v, spin, budget, "powers of four")
+
+
 def test_hash_noise_fbm_match_reference_vectors(g, units_ref):
     import torch
     n = len(units_ref["lattice"])
