@@ -1,6 +1,7 @@
 """Exposure control (rrt_launch_exposure, include/rrt.h) against its numpy restatement (tests/exposure_ref.py): the histogram the
 meter pass leaves, the state (ev, scale, the diagnostics), the scaled HDR bit for bit and the RGBA8 byte for byte through the portable
-exp -- on synthetic frames of every ragged shape, flat and black frames, sequences on one state without a host synchronisation, manual
+exp -- on synthetic frames of every ragged shape, frames of 2^20 pixels and more (the meter's strided rounds: one pixel over, a
+ragged second round, 1080p), flat and black frames, sequences on one state without a host synchronisation, manual
 mode, real supersampled / fisheye / stereo frames, a captured _ss -> exposure -> glow graph, and both headless drivers.  torch is only
 the device-memory plumbing."""
 import json
@@ -96,11 +97,24 @@ AUTO = dict(mode="auto", key=0.18, ev=0.25, low_permille=100, high_permille=50)
 SHAPES = [(1, 1), (7, 5), (65, 3), (257, 9), (300, 200)]     # below one wave, ragged against 64 and 256, several workgroups
 
 
-@pytest.mark.parametrize("w,h", SHAPES, ids=[f"{w}x{h}" for w, h in SHAPES])
-def test_synthetic_frames_match_the_restatement(ctx, po, w, h):
+# Frames of more than kMeterCUs * kMeterGroupsPerCU * kMeterThreads * kMeterRun = 2^20 pixels send exposure_meter's waves round their
+# `base += stride` loop more than once (tests/test_post_pass_geometry.py asserts, without a GPU, what each of these shapes reaches)
+STRIDED_SHAPES = [
+    (1024, 1024),    # 2^20: the last frame of one round, 1024 workgroups, none ragged
+    (61681, 17),     # 2^20 + 1: a second round taken by one wave with one lane inside the frame
+    (1049, 1000),    # 2^20 + 424: the second round taken by two of workgroup 0's four waves, the second one ragged
+    (1031, 1019),    # 2^20 + 2013: the second round taken by workgroups 0 and 1, the last wave's last run ragged
+    (1920, 1080),    # 1080p: 1.98 rounds, the second taken by 1001 whole workgroups
+]
+RAGGED_SHAPES = [(61681, 17), (1049, 1000), (1031, 1019)]
+VARIANT_SHAPE = (1031, 1019)
+ALONE = 2.0 ** 10         # a luma no pixel of synthetic_hdr has (at most 2^6 * 1.7): the last pixel, which past-the-end lanes load
+
+
+def check_auto_frame(ctx, po, hdr, variants=True):
+    """one auto launch on a fresh state against the restatement: the histogram, the state, the scaled HDR's bits, the RGBA8 bytes"""
     rrt, _, table = ctx
-    rng = np.random.default_rng(w * 1000 + h)
-    hdr = synthetic_hdr(rng, w, h)
+    h, w = hdr.shape[:2]
     s = rrt.ExposureSettings(**AUTO)
     st = er.State()
     want_hist, want_scale, want_hdr, want8 = er.expose(po, rrt, hdr, s, st, table)
@@ -117,12 +131,67 @@ def test_synthetic_frames_match_the_restatement(ctx, po, w, h):
     if w * h > 1:
         assert bits(want_scale) != bits(1.0) and not np.array_equal(want8, er.tone_map(po, hdr[..., :3]))   # the exposure is visible
     # in place, bytes only, HDR only: the same frame from a fresh state
-    for kw in (dict(in_place=True), dict(lin=False), dict(bytes8=False)):
+    for kw in (dict(in_place=True), dict(lin=False), dict(bytes8=False)) if variants else ():
         scratch = new_scratch(rrt)
         a8, ah = launch(rrt, _device(hdr), w, h, s, scratch, **kw)
         assert a8 is None or np.array_equal(a8, want8), kw
         assert ah is None or same_bits(ah, want_hdr), kw
         assert bits(read_state(scratch)["ev"]) == bits(st.ev), kw
+    return want_hist
+
+
+@pytest.mark.parametrize("w,h", SHAPES, ids=[f"{w}x{h}" for w, h in SHAPES])
+def test_synthetic_frames_match_the_restatement(ctx, po, w, h):
+    rng = np.random.default_rng(w * 1000 + h)
+    check_auto_frame(ctx, po, synthetic_hdr(rng, w, h))
+
+
+@pytest.mark.parametrize("w,h", STRIDED_SHAPES, ids=[f"{w}x{h}" for w, h in STRIDED_SHAPES])
+def test_strided_rounds_match_the_restatement(ctx, po, w, h):
+    """frames of 2^20 pixels and more: the meter's second round, taken by one lane, by part of a workgroup, by a thousand workgroups.
+    The last pixel, which every past-the-end lane loads, is alone in its bin: a meter that counted those lanes would count it again"""
+    import torch
+    rrt = ctx[0]
+    rng = np.random.default_rng(w * 1000 + h)
+    hdr = synthetic_hdr(rng, w, h)
+    hdr[h - 1, w - 1, :3] = F(ALONE)
+    alone = er.bin_of(er.luma(hdr[h - 1:, w - 1:]))[1].item()
+    want_hist = check_auto_frame(ctx, po, hdr, variants=(w, h) == VARIANT_SHAPE)
+    assert want_hist[alone] == 1 and int(want_hist.sum()) < w * h
+    if (w, h) in RAGGED_SHAPES:
+        assert np.array_equal(rrt.exposure_meter_host(hdr), want_hist)          # the library's host meter: a third count of the frame
+    torch.cuda.empty_cache()
+
+
+def test_flat_and_black_frames_in_strided_rounds(ctx, po):
+    """1031 x 1019, two rounds: a frame in ONE bin takes the one-add path on every round and the bin holds w * h; a black frame
+    meters nothing in either round and keeps ev -- on the first frame it takes the clamped setting"""
+    import torch
+    rrt, _, table = ctx
+    w, h = VARIANT_SHAPE
+    s = rrt.ExposureSettings(**dict(AUTO, adapt_up=0.5, adapt_down=0.25))
+    flat = np.empty((h, w, 4), F)
+    flat[...] = (0.3, 0.2, 0.1, 1.0)
+    black = np.zeros((h, w, 4), F)
+    black[..., 3] = 1.0
+    scratch, st = new_scratch(rrt), er.State()
+    for what, frame in (("flat", flat), ("black", black), ("flat again", flat)):
+        want_hist, _, want_hdr, want8 = er.expose(po, rrt, frame, s, st, table)
+        got8, got_hdr = launch(rrt, _device(frame), w, h, s, scratch)
+        got = read_state(scratch)
+        assert np.array_equal(got["hist"], want_hist), what
+        check_state(po, got, st, *er.resolve(want_hist, table, s), what)
+        assert same_bits(got_hdr, want_hdr) and np.array_equal(got8, want8), what
+        if what.startswith("flat"):
+            assert (want_hist > 0).sum() == 1 and int(want_hist.max()) == w * h and got["n"] == w * h
+        else:
+            assert got["n"] == 0 and bits(got["ev"]) == kept, what
+        kept = bits(got["ev"])
+    scratch = new_scratch(rrt)                                                   # black first: the setting, clamped
+    launch(rrt, _device(black), w, h, rrt.ExposureSettings(mode="auto", ev=5.0, min_ev=-2.0, max_ev=2.0), scratch, lin=False)
+    got = read_state(scratch)
+    assert (got["n"], got["frames"]) == (0, 1) and got["ev"] == F(2.0) and not got["hist"].any()
+    torch.cuda.empty_cache()
 
 
 def test_flat_and_black_frames(ctx, po):

@@ -1,6 +1,8 @@
 """HDR glow (rrt_launch_glow, include/rrt.h) against its numpy restatement (tests/glow_ref.py): synthetic HDR fields and real
 supersampled / motion-blurred frames, RGBA8 byte for byte through the portable exp; the identities (intensity 0, a threshold
-above every luma); side streams and graph capture; both headless drivers.  torch is only the device-memory plumbing."""
+above every luma); the launch geometry of full-size frames (rows of several glow_hpass segments at both segment sizes, tap tables
+of several glow_load_weights launches) on frames a few rows tall; side streams and graph capture; both headless drivers.  torch is
+only the device-memory plumbing."""
 import json
 import os
 import subprocess
@@ -87,6 +89,53 @@ def test_synthetic_hdr_matches_the_restatement(ctx, po, case):
         assert not np.array_equal(got, plain)                  # the glow is visible
 
 
+# Full-size launch geometry on the smallest frames that reach it (tests/test_post_pass_geometry.py asserts, without a GPU, that each
+# still does): rows of more than one glow_hpass segment at both segment sizes, and tap tables of more than one glow_load_weights
+# launch.  The restatement costs taps x pixels, so the frames are thousands of pixels wide and a few rows tall.
+GEOMETRY_CASES = {  # name: (w, h, lobes, radius, threshold, intensity, (R per lobe))
+    "last_segment_one_pixel": (2049, 2, 2, 2.0, 1.0, 1.0, (12, 24)),
+    "three_segments_one_row": (4097, 1, 2, 4.0, 0.5, 0.7, (12, 24)),
+    "the_4k_row": (3840, 24, 4, 0.36, 1.0, 0.25, (26, 52, 104, 208)),
+    "widest_2048_segment_halo": (2049, 3, 1, 100.33323, 2.0, 0.5, (903,)),
+    "first_1024_segment_radius": (2049, 3, 1, 100.44434, 2.0, 0.5, (904,)),
+    "maximum_radius_four_lobes": (1100, 2, 4, 21.333311, 1.0, 0.5, (128, 256, 512, 1024)),
+    "exactly_one_full_chunk": (70, 2, 2, 26.501, 0.5, 0.3, (160, 319)),
+    "one_chunk_and_a_sliver": (70, 2, 3, 11.334, 0.5, 0.3, (69, 137, 273)),
+}
+
+
+def seam_spikes(hdr, cols):
+    """bright pixels of two different colours on both sides of every segment boundary and in the last column: a halo staged from the
+    wrong place moves bytes.  They are of moderate size and in the even rows only, and the odd rows' pixels there are dim: beside and
+    under a spike the tone map is far from saturation, so that a segment of a single pixel shows a shifted halo too"""
+    for i, x in enumerate(cols):
+        hdr[0::2, x, :3] = (30.0, 2.0, 0.5) if i % 2 == 0 else (0.4, 15.0, 6.0)
+        hdr[1::2, x, :3] = (0.25, 0.5, 0.125)
+    return hdr
+
+
+@pytest.mark.parametrize("name", list(GEOMETRY_CASES))
+def test_full_size_launch_geometry_matches_the_restatement(ctx, po, name):
+    """multi-segment rows (x0 > 0, halos out of the neighbouring segments, a last segment of one pixel, both segment sizes) and tap
+    tables of one chunk exactly, one chunk and one tap, and five chunks: byte for byte the restatement, which knows no segments"""
+    import post_geometry as pg
+    rrt, _ = ctx
+    w, h, lobes, radius, threshold, intensity, radii = GEOMETRY_CASES[name]
+    g = rrt.GlowSettings(lobes=lobes, radius=radius, threshold=threshold, intensity=intensity)
+    assert tuple((t.size - 1) // 2 for t in glow_ref.lobe_taps(rrt, g, h)) == radii, name     # the planner's R, from its taps
+    seams = pg.glow_seams(w, radii[-1])
+    rng = np.random.default_rng(w * 1000 + h)
+    hdr = seam_spikes(synthetic_hdr(rng, w, h), seams)
+    got = glow(rrt, _device_hdr(hdr), w, h, g)
+    want = expected(po, rrt, hdr, g)
+    assert np.array_equal(got, want), (name, int((got != want).any(-1).sum()), np.flatnonzero((got != want).any((0, 2)))[:8])
+    plain = tone_map(po, hdr[..., :3])
+    assert not np.array_equal(got, plain)
+    for x in seams:                                             # the seams are lit: the glow moves bytes around every boundary
+        lo, hi = max(x - 2, 0), min(x + 3, w)
+        assert not np.array_equal(want[:, lo:hi], plain[:, lo:hi]), (name, x)
+
+
 def test_lobe_counts_and_radii(ctx, po):
     rrt, _ = ctx
     rng = np.random.default_rng(77)
@@ -150,39 +199,46 @@ def test_side_stream_and_graph_capture(ctx):
         assert np.array_equal(_host(out, (h, w, 4)), ref)
 
 
-@pytest.mark.parametrize("mode", [["--supersample", "2"], ["--motion-blur", "2"]])
+DRIVER_CASES = [  # (the mode's arguments, w, h, --glow, --glow-radius, --glow-lobes)
+    (["--supersample", "2"], 96, 54, 0.5, 0.01, 3),
+    (["--motion-blur", "2"], 96, 54, 0.5, 0.01, 3),
+    (["--supersample", "1"], 2064, 16, 0.25, 0.1, 3),       # two glow_hpass segments (2048 + 16), R = 5, 10, 20: the drivers' own scratch
+]
+
+
+@pytest.mark.parametrize("mode", DRIVER_CASES)
 def test_drivers_write_the_glowed_frames(ctx, tmp_path, mode):
-    """rrt_headless and headless.py --glow 0.5: the same file, the summary's glow settings, and every frame == the library's _ss /
+    """rrt_headless and headless.py --glow: the same file, the summary's glow settings, and every frame == the library's _ss /
     _mb launch at the driver's clock and CameraPath(0)'s cameras, then rrt_launch_glow"""
+    mode, w, h, intensity, radius, lobes = mode
     import torch
     from relativisticraytracer_amd import build
     from relativisticraytracer_amd import camera_paths as cp
     rrt, tex = ctx
     exe = build.build_headless()
-    w, h = 96, 54
     a, b = tmp_path / "cpp.rgba", tmp_path / "py.rgba"
     args = ["--width", str(w), "--height", str(h), "--frames", "3", "--path", "0", "--spin", "0.9", "--all-effects",
-            "--glow", "0.5", "--glow-threshold", "0.2", "--glow-radius", "0.01", "--glow-lobes", "3"] + mode
+            "--glow", str(intensity), "--glow-threshold", "0.2", "--glow-radius", str(radius), "--glow-lobes", str(lobes)] + mode
     r = subprocess.run([exe] + args + ["--out", str(a)], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     meta = json.loads(r.stdout.strip().splitlines()[-1])
-    assert meta["glow"] == {"radius": 0.01, "lobes": 3, "threshold": 0.2, "intensity": 0.5}, meta
+    assert meta["glow"] == {"radius": radius, "lobes": lobes, "threshold": 0.2, "intensity": intensity}, meta
     r = subprocess.run([sys.executable, "-m", "relativisticraytracer_amd.headless"] + args + ["--out", str(b)], cwd=ROOT,
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     meta = json.loads(r.stdout.strip().splitlines()[-1])
-    assert meta["glow"]["lobes"] == 3 and abs(meta["glow"]["intensity"] - 0.5) < 1e-7 and meta["tile_order"] is None, meta
+    assert meta["glow"]["lobes"] == lobes and abs(meta["glow"]["intensity"] - intensity) < 1e-7 and meta["tile_order"] is None, meta
     assert open(a, "rb").read() == open(b, "rb").read()
     data = np.fromfile(a, np.uint8).reshape(3, h, w, 4)
     path = cp.CameraPath(0)
     fx = rrt.CameraEffects(useChromaticAberration=True)
     prm = rrt.RenderParams(spin=0.9)
-    g = rrt.GlowSettings(lobes=3, radius=0.01, threshold=0.2, intensity=0.5)
+    g = rrt.GlowSettings(lobes=lobes, radius=radius, threshold=0.2, intensity=intensity)
     n_visible = 0
     for k in (1, 2, 3):
         if mode[0] == "--supersample":
             st, pt = cp.recording_clock(k, 24)
-            plain, hdr = render_ss(rrt, tex, w, h, 2, st, path.camera_at(pt), fx, prm)
+            plain, hdr = render_ss(rrt, tex, w, h, int(mode[1]), st, path.camera_at(pt), fx, prm)
         else:
             st, pt = cp.motion_clock(k, 24, 0.5, 2)
             plain, hdr = render_mb(rrt, tex, w, h, 1, st, [path.camera_at(p) for p in pt], fx, prm)
