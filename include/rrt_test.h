@@ -66,6 +66,21 @@ int rrt_unit_noise3d_lut(int n, const float* d_p, int table, int which, float* d
 int rrt_unit_media_lut(int n, const float* d_p, float time, int table, float* d_out_disk, float* d_out_dust,
                        unsigned* d_counts, void* stream);
 
+/* the PRODUCTION tile sort (csrc/rrt_tile_sort.h: rrt_sort::enqueue, its four launches -- the very instance the launches
+ * through a tile-order object call, not a copy) on a cost array the caller chose: d_cost holds one 32-bit cost per wave tile
+ * of a grid_x x grid_y grid (n = grid_x * grid_y), the key is bits lo_bit .. lo_bit + 15 of it.  d_perm_out[slot] = wave
+ * tile, longest first, ties in the static dispatch order.  d_keys_tmp / d_vals_tmp (n words each) are left holding pass 0's
+ * output, d_scratch (scratch_words >= what rrt_unit_tile_sort_plan reports) the two hist[block][digit] matrices: pass 0's at
+ * word 0, pass 1's at word scratch_words / 2 of the reported size.  RRT_ERR_INVALID_ARGUMENT, before any launch, for grid_x
+ * outside [1, 2^18), grid_y outside [1, 65 535], n >= 2^30 (static_tile's preconditions), lo_bit outside [0, 16], a null
+ * pointer or too little scratch.  Enqueues on `stream` and does not synchronise. */
+int rrt_unit_tile_sort(unsigned grid_x, unsigned grid_y, const uint32_t* d_cost, int lo_bit, uint32_t* d_keys_tmp,
+                       uint32_t* d_vals_tmp, uint32_t* d_scratch, size_t scratch_words, uint32_t* d_perm_out, void* stream);
+/* the sort's launch geometry for n keys, on the host (no device is touched): batches per block (reps_for), blocks
+ * (blocks_for), words of scratch any sort needs (kScratchWords).  Any of the three pointers may be NULL.  n == 0 or
+ * n >= 2^30: RRT_ERR_INVALID_ARGUMENT. */
+int rrt_unit_tile_sort_plan(size_t n, unsigned* reps, unsigned* n_blocks, size_t* scratch_words);
+
 /* Self-checks of the march loop's hand-rolled correctly-rounded sqrt / divide against the
  * hardware IEEE forms.  d_counters: 4 x uint64 on the device, zeroed by the caller;
  * [0] receives the number of mismatching cases, [1..3] one failing case. */

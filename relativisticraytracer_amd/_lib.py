@@ -208,6 +208,8 @@ TEST_SYMBOLS = [
     ("rrt_unit_rk4", _i, [_i, _vp, _vp, _vp, _f, _vp]),
     ("rrt_unit_rk4_lean", _i, [_i, _vp, _vp, _vp, _f, _i, _f, _vp, _vp]),
     ("rrt_unit_march", _i, [_i, _vp, _vp, _f, _i, _i, _vp, _vp, _vp, _vp]),
+    ("rrt_unit_tile_sort", _i, [C.c_uint, C.c_uint, _vp, _i, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
+    ("rrt_unit_tile_sort_plan", _i, [C.c_size_t, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_size_t)]),
     ("rrt_unit_div_seeded", _i, [_i, _vp, _vp, _vp, _vp, _vp]),
     ("rrt_unit_hash31", _i, [_i, _vp, _vp, _vp]),
     ("rrt_unit_noise3d", _i, [_i, _vp, _vp, _vp]),

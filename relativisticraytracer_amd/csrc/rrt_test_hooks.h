@@ -491,6 +491,23 @@ int rrt_unit_march(int n, float* p, float* v, float spin, int arith_mode, int ma
     RRT_HIP(hipGetLastError());
     return RRT_OK;
 }
+/* the production tile sort on the caller's costs: rrt_sort::enqueue itself, with the buffers a tile-order object would hand it */
+int rrt_unit_tile_sort(unsigned grid_x, unsigned grid_y, const uint32_t* cost, int lo_bit, uint32_t* keys_tmp, uint32_t* vals_tmp,
+                       uint32_t* scratch, size_t scratch_words, uint32_t* perm_out, void* st) {
+    if (grid_x < 1u || grid_x >= (1u << 18) || grid_y < 1u || grid_y > 65535u) return RRT_ERR_INVALID_ARGUMENT;   /* static_tile */
+    const size_t n = (size_t)grid_x * grid_y;
+    if (n >= ((size_t)1 << 30) || lo_bit < 0 || lo_bit > 16) return RRT_ERR_INVALID_ARGUMENT;
+    if (!cost || !keys_tmp || !vals_tmp || !scratch || !perm_out || scratch_words < rrt_sort::kScratchWords) return RRT_ERR_INVALID_ARGUMENT;
+    RRT_HIP(rrt_sort::enqueue(cost, keys_tmp, vals_tmp, scratch, perm_out, n, grid_x, grid_y, lo_bit, static_cast<hipStream_t>(st)));
+    return RRT_OK;
+}
+int rrt_unit_tile_sort_plan(size_t n, unsigned* reps, unsigned* n_blocks, size_t* scratch_words) {
+    if (n == 0 || n >= ((size_t)1 << 30)) return RRT_ERR_INVALID_ARGUMENT;
+    if (reps) *reps = rrt_sort::reps_for(n);
+    if (n_blocks) *n_blocks = rrt_sort::blocks_for(n);
+    if (scratch_words) *scratch_words = rrt_sort::kScratchWords;
+    return RRT_OK;
+}
 int rrt_unit_div_seeded(int n, const float* a, const float* b, const float* seed, float* out, void* st) {
     if (n > 0 && (!a || !b || !seed || !out)) return RRT_ERR_INVALID_ARGUMENT;
     return unit_launch(n, st, [&](dim3 g, dim3 bl, hipStream_t s) { hipLaunchKernelGGL(k_div_seeded, g, bl, 0, s, n, a, b, seed, out); });

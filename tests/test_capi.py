@@ -42,7 +42,7 @@ def test_product_library_exports_no_test_hooks():
         return sorted(ln.split()[-1] for ln in out.splitlines() if " T " in ln)
     prod, test = exported(build.LIB), exported(build.TEST_LIB)
     hooks = declared_functions("rrt_test.h")
-    assert len(hooks) == 27 and not [s for s in prod if "unit" in s or "selfcheck" in s or "debug" in s]
+    assert len(hooks) == 29 and not [s for s in prod if "unit" in s or "selfcheck" in s or "debug" in s]
     legacy = ["rrt_get_launch_defaults", "rrt_params_default", "rrt_params_default_v4"]
     cpp = [s for s in prod if s.startswith("_Z15launch_raymarch")]
     assert len(cpp) == 2

@@ -1149,6 +1149,10 @@ def test_handles_are_tied_to_their_device(ctx, sky):
             nt.destroy(); ws.destroy(); order.destroy(); tex.destroy()
 
 
+# the frame sizes (w, h; wave tiles of 8 x 8 pixels) the test below sends through a tile-order object
+ORDERED_FRAME_SIZES = ((640, 360), (333, 130), (8200, 8208), (1000, 700), (8, 8))
+
+
 def test_cost_ordered_dispatch_renders_the_same_frames(ctx):
     """rrt_tile_order (round 3): launches through the object record per-wave-tile costs and the next launch of the same
     geometry dispatches longest-first.  Any order renders the same pixels: full frames, tile shards, fast mode, a
@@ -1160,7 +1164,7 @@ def test_cost_ordered_dispatch_renders_the_same_frames(ctx):
     views = [(rrt.CameraState.from_angles((4.2, 0.6, 4.2), -90.0, -5.7), 14.0), (rrt.CameraState.default(), 1.0)]
     order = rrt.TileOrder()
     try:
-        w, h = 640, 360
+        w, h = ORDERED_FRAME_SIZES[0]
         n_tiles = ((w + 7) // 8) * ((h + 7) // 8)
         ref = torch.zeros(h * w * 4, dtype=torch.uint8, device="cuda"); out = torch.zeros_like(ref)
         launches = ordered = 0
@@ -1189,8 +1193,8 @@ def test_cost_ordered_dispatch_renders_the_same_frames(ctx):
                 keys = (cost[static] >> 6) & 0xffff
                 assert np.array_equal(perm, static[np.argsort(-keys.astype(np.int64), kind="stable")])
         # another geometry: ordered by the coarse probe (round 4; no history to go by), and the object starts over
-        w2, h2 = 333, 130
-        ref2 = torch.zeros(h2 * w2 * 4, dtype=torch.uint8, device="cuda"); out2 = torch.zeros_like(ref2)
+        w2, h2 = ORDERED_FRAME_SIZES[1]
+        ref2 =torch.zeros(h2 * w2 * 4, dtype=torch.uint8, device="cuda"); out2 = torch.zeros_like(ref2)
         cam, t = views[0]
         rrt.launch_raymarch(ref2, w2, h2, t, cam, tex, fx, rrt.RenderParams(spin=0.9, noise_table=nt.id))
         for k in range(2):
@@ -1222,9 +1226,11 @@ def test_cost_ordered_dispatch_renders_the_same_frames(ctx):
         with pytest.raises(rrt.RRTError) as e:
             rrt.launch_raymarch(out, w, h, t, cam, tex, fx, rrt.RenderParams(spin=0.9, tile_order=order.id + 1000))
         assert e.value.status == 4
-        # the sort on geometries past one block-chunk per 1 024 keys (csrc/rrt_tile_sort.h: > 2^20 tiles doubles the chunk) and on
-        # ragged ones: a few march steps per ray are enough to give the tiles costs; the order must be the stable sort
-        for wb, hb in ((8200, 8208), (1000, 700), (8, 8)):
+        # the sort on a large geometry (1 051 650 tiles: 514 blocks) and on ragged ones: a few march steps per ray are enough to give the
+        # tiles costs; the order must be the stable sort.  All of them run at ONE batch per block (csrc/rrt_tile_sort.h: reps_for
+        # exceeds 1 past 2 097 152 tiles; tests/test_tile_sort_geometry.py asserts it of ORDERED_FRAME_SIZES): the chunkings with
+        # 2 and 4 batches, and keys the test chooses, are tests/test_gpu_tile_sort.py
+        for wb, hb in ORDERED_FRAME_SIZES[2:]:
             big = torch.zeros(hb * wb * 4, dtype=torch.uint8, device="cuda")
             for _ in range(2):
                 rrt.launch_raymarch(big, wb, hb, 1.0, views[1][0], tex, fx, rrt.RenderParams(spin=0.9, max_steps=6, tile_order=order.id))
