@@ -272,7 +272,8 @@ def load_test():
 class using_test_library:
     """Tests only: inside `with _lib.using_test_library() as lib:` the whole package talks to librrt_hip_test.so instead of
     the product library (load() returns it), so that the Python wrappers and the test hooks share one set of handle
-    registries.  Objects created inside must be destroyed inside."""
+    registries.  A handle object (Handle below) created inside keeps talking to the test library: it can be queried and
+    destroyed outside.  A launch still goes to the current library, and an id of the other registry is RRT_ERR_BAD_HANDLE there."""
 
     def __enter__(self):
         global _lib
@@ -312,3 +313,36 @@ def check(status, where):
         if status == 3:
             msg += " -- " + lib.rrt_last_hip_error().decode()
         raise RRTError(status, where, msg)
+
+
+def call(name, *args, lib=None):
+    """`name`(*args) of `lib` (default: the current library); any status but RRT_OK raises RRTError naming the symbol called."""
+    check(getattr(load() if lib is None else lib, name)(*args), name)
+
+
+class Handle:
+    """Owner of one object in a handle registry of the library.  It remembers the library it was created through and sends every
+    later call there, so an object made inside using_test_library() can be queried and destroyed outside it (and the reverse).
+    A subclass names its destroy entry point, the attribute that holds the id (0: nothing owned, destroy() does nothing) and whether
+    destroy() raises on a refused destroy or ignores the status."""
+    _destroy, _id, _destroy_checked = None, "id", False
+
+    def _create(self, name, *args):
+        self._lib = load()
+        call(name, *args, lib=self._lib)
+
+    def _call(self, name, *args):
+        call(name, *args, lib=self._lib)
+
+    def destroy(self):
+        if getattr(self, self._id, 0):
+            status = getattr(self._lib, self._destroy)(getattr(self, self._id))
+            if self._destroy_checked:
+                check(status, self._destroy)
+            setattr(self, self._id, 0)
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass

@@ -14,14 +14,14 @@ def _f3(v):
 
 def catmull_rom(p0, p1, p2, p3, t):
     out = (C.c_float * 3)()
-    _lib.check(_lib.load().rrt_catmull_rom(C.byref(_f3(p0)), C.byref(_f3(p1)), C.byref(_f3(p2)), C.byref(_f3(p3)),
-                                           float(t), C.byref(out)), "rrt_catmull_rom")
+    _lib.call("rrt_catmull_rom", C.byref(_f3(p0)), C.byref(_f3(p1)), C.byref(_f3(p2)), C.byref(_f3(p3)),
+              float(t), C.byref(out))
     return np.array(list(out), np.float32)
 
 
 def lerp_angle(a, b, t):
     out = C.c_float(0)
-    _lib.check(_lib.load().rrt_lerp_angle(float(a), float(b), float(t), C.byref(out)), "rrt_lerp_angle")
+    _lib.call("rrt_lerp_angle", float(a), float(b), float(t), C.byref(out))
     return np.float32(out.value)
 
 
@@ -29,18 +29,17 @@ class CameraPath:
     """One of the reference's built-in paths (PathManager entry)."""
 
     def __init__(self, index):
-        lib = _lib.load()
         name, n, t_end = C.c_char_p(), C.c_int(0), C.c_float(0)
-        _lib.check(lib.rrt_path_info(index, C.byref(name), C.byref(n), C.byref(t_end)), "rrt_path_info")
+        _lib.call("rrt_path_info", index, C.byref(name), C.byref(n), C.byref(t_end))
         self.index, self.name, self.t_end = index, name.value.decode(), t_end.value
         keys = np.zeros((n.value, 6), np.float32)
-        _lib.check(lib.rrt_path_keyframes(index, keys.ctypes.data_as(C.c_void_p), n.value), "rrt_path_keyframes")
+        _lib.call("rrt_path_keyframes", index, keys.ctypes.data_as(C.c_void_p), n.value)
         self.keyframes = keys          # rows: time, x, y, z, yaw, pitch
 
     def camera_at(self, path_time):
         """PathController::getInterpolatedState (src/main.cpp:176-203)."""
         out = CameraState()
-        _lib.check(_lib.load().rrt_path_camera_at(self.index, float(path_time), C.byref(out)), "rrt_path_camera_at")
+        _lib.call("rrt_path_camera_at", self.index, float(path_time), C.byref(out))
         return out
 
 
@@ -52,7 +51,7 @@ def recording_clock(frame_k, fps=24):
     """(simTime, pathTime) seen by 1-based frame k under the fixed recording clock
     (src/main.cpp:511-516; RECORDING_FPS = 24, config.h:9), accumulated in binary32."""
     s, p = C.c_float(0), C.c_float(0)
-    _lib.check(_lib.load().rrt_recording_clock(int(frame_k), int(fps), C.byref(s), C.byref(p)), "rrt_recording_clock")
+    _lib.call("rrt_recording_clock", int(frame_k), int(fps), C.byref(s), C.byref(p))
     return s.value, p.value
 
 
@@ -62,6 +61,6 @@ def motion_clock(frame_k, fps, shutter, n_times):
     increasing order; shutter 0 gives recording_clock(frame_k, fps) n_times over."""
     s, p = np.zeros(n_times, np.float32), np.zeros(n_times, np.float32)
     fp = C.POINTER(C.c_float)
-    _lib.check(_lib.load().rrt_motion_clock(int(frame_k), int(fps), float(shutter), int(n_times), s.ctypes.data_as(fp),
-                                            p.ctypes.data_as(fp)), "rrt_motion_clock")
+    _lib.call("rrt_motion_clock", int(frame_k), int(fps), float(shutter), int(n_times), s.ctypes.data_as(fp),
+              p.ctypes.data_as(fp))
     return s, p

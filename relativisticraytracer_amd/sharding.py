@@ -13,7 +13,11 @@ backend (= RCCL over xGMI) the buffers are device tensors and `render`/`assemble
 are the HIP entry points; the CPU tests drive the same code over "gloo" with the
 oracle as the renderer.
 """
+import ctypes as C
+
 import numpy as np
+
+from . import _lib                  # loads nothing: this module imports without the built library
 
 
 def tile_plan(height, tile_rows, shard, n_shards, shard_of_tile=None):
@@ -150,41 +154,34 @@ def init_process_group(backend, rank, world, device=None, timeout_s=300.0):
     return dist
 
 
-class PathChooser:
+class PathChooser(_lib.Handle):
     """Which path this rank's share takes while several frames of a sequence are in flight (include/rrt.h: rrt_path_chooser_*;
     the rule lives in csrc/rrt_path_chooser.cpp, the C++ headless driver uses the same object).  Host logic only.
 
         pc = PathChooser(frames_in_flight)
         per frame k = 1, 2, ...:   prm.path_policy = pc.policy(k)  ...  later, when known:  pc.report(k, sustained_ms)
     """
+    _destroy = "rrt_path_chooser_destroy"
 
     def __init__(self, frames_in_flight, window_frames=0):
-        import ctypes as C
-        from . import _lib
-        self._lib, self._C = _lib, C
         out = C.c_int(0)
-        _lib.check(_lib.load().rrt_path_chooser_create(int(frames_in_flight), int(window_frames), C.byref(out)), "rrt_path_chooser_create")
+        self._create("rrt_path_chooser_create", int(frames_in_flight), int(window_frames), C.byref(out))
         self.id = out.value
 
     def policy(self, frame):
-        p = self._C.c_int(0)
-        self._lib.check(self._lib.load().rrt_path_chooser_policy(self.id, int(frame), self._C.byref(p)), "rrt_path_chooser_policy")
+        p = C.c_int(0)
+        self._call("rrt_path_chooser_policy", self.id, int(frame), C.byref(p))
         return p.value
 
     def report(self, frame, sustained_ms):
-        self._lib.check(self._lib.load().rrt_path_chooser_report(self.id, int(frame), float(sustained_ms)), "rrt_path_chooser_report")
+        self._call("rrt_path_chooser_report", self.id, int(frame), float(sustained_ms))
 
     def stats(self):
-        st = self._lib.rrt_path_chooser_stats()
-        self._lib.check(self._lib.load().rrt_path_chooser_get_stats(self.id, self._C.byref(st)), "rrt_path_chooser_get_stats")
+        st = _lib.rrt_path_chooser_stats()
+        self._call("rrt_path_chooser_get_stats", self.id, C.byref(st))
         return {"incumbent": "single kernel" if st.incumbent == 1 else "automatic (three-pass for a small share)", "windows": st.windows,
                 "trials": st.trials, "trials_aborted": st.trials_aborted, "switches": st.switches, "outliers": st.outliers,
                 "frames_three_pass_auto": st.frames[0], "frames_single_kernel": st.frames[1]}
-
-    def destroy(self):
-        if self.id:
-            self._lib.load().rrt_path_chooser_destroy(self.id)
-            self.id = 0
 
 
 class FrameSharder:

@@ -1,7 +1,49 @@
 """Helpers shared by the -m gpu tests: torch is only the device-memory plumbing."""
 import ctypes as C
+import json
+import os
+import subprocess
+import sys
 
 import numpy as np
+import pytest
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+
+
+@pytest.fixture(scope="module")
+def ctx(sky):
+    """(rrt, a sky texture of the suite's sky): import it by name; module scope, so every module gets and destroys its own"""
+    import torch
+    assert torch.cuda.is_available(), "the -m gpu tests need a GPU"
+    import relativisticraytracer_amd as rrt
+    tex = rrt.SkyTexture(sky)
+    yield rrt, tex
+    tex.destroy()
+
+
+def _zeros(n, dtype):
+    import torch
+    return torch.zeros(n, dtype=dtype, device="cuda")
+
+
+def _host(t, shape):
+    import torch
+    torch.cuda.synchronize()
+    return t.cpu().numpy().reshape(shape)
+
+
+def run_drivers(tmp_path, args, timeout=600):
+    """rrt_headless and `python -m relativisticraytracer_amd.headless` with the same arguments, each writing its own file: both
+    end with status 0 and the two files are byte-identical -> (the C++ driver's summary, headless.py's summary, the C++ file)"""
+    from relativisticraytracer_amd import build
+    metas, files = [], (tmp_path / "cpp.rgba", tmp_path / "py.rgba")
+    for cmd, out in zip(([build.build_headless()], [sys.executable, "-m", "relativisticraytracer_amd.headless"]), files):
+        r = subprocess.run(cmd + list(args) + ["--out", str(out)], cwd=ROOT, capture_output=True, text=True, timeout=timeout)
+        assert r.returncode == 0, (out.name, r.stderr[-2000:])
+        metas.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    assert files[0].read_bytes() == files[1].read_bytes()
+    return metas[0], metas[1], files[0]
 
 
 def dev(a):
@@ -13,46 +55,6 @@ def host(t):
     import torch
     torch.cuda.synchronize()
     return t.cpu().numpy()
-
-
-class HookSky:
-    """A sky in librrt_hip_TEST.so's registry (the test library is a separate library: the package's SkyTexture lives in the
-    product library's and is unknown to rrt_unit_sky_sample)."""
-
-    def __init__(self, rgba8):
-        from relativisticraytracer_amd import _lib
-        arr = np.ascontiguousarray(rgba8, dtype=np.uint8)
-        h = C.c_ulonglong(0)
-        _lib.check(_lib.load_test().rrt_sky_create(arr.ctypes.data_as(C.c_void_p), arr.shape[1], arr.shape[0], C.byref(h)), "rrt_sky_create")
-        self.handle = h.value
-
-    def destroy(self):
-        from relativisticraytracer_amd import _lib
-        if self.handle:
-            _lib.load_test().rrt_sky_destroy(self.handle)
-            self.handle = 0
-
-
-class HookNoiseTable:
-    """A noise table in the test library's registry (see HookSky)."""
-
-    def __init__(self, t_max, t0=0.0, coverage=0):
-        from relativisticraytracer_amd import _lib
-        i = C.c_int(0)
-        _lib.check(_lib.load_test().rrt_noise_table_create_window(float(t0), float(t_max), int(coverage), C.byref(i)), "rrt_noise_table_create_window")
-        self.id = i.value
-
-    def info(self):
-        from relativisticraytracer_amd import _lib
-        t, b, boxes = C.c_float(0), C.c_size_t(0), (C.c_int * 12)()
-        _lib.check(_lib.load_test().rrt_noise_table_info(self.id, C.byref(t), C.byref(b), C.byref(boxes)), "rrt_noise_table_info")
-        return {"t_max": t.value, "bytes": b.value, "accretion_box": list(boxes[:6]), "dust_box": list(boxes[6:])}
-
-    def destroy(self):
-        from relativisticraytracer_amd import _lib
-        if self.id:
-            _lib.load_test().rrt_noise_table_destroy(self.id)
-            self.id = 0
 
 
 def unit(name, *args):

@@ -3,20 +3,16 @@ byte for byte and bit for bit, with base the s = 1 frame and ss the s x s frame 
 tests/test_gpu_supersample.py and tests/test_gpu_projection.py pin -- and mask the numpy restatement of the rule on the stored base
 bytes (tests/adaptive_ref.py).  The device's list is compared as a set with the mask, its count with the list's length.  Small frames:
 96x64 and a ragged 67x45, the default view and a disk-grazing one.  torch is only the device-memory plumbing."""
-import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import adaptive_ref
 from conftest import same_bits
+from gpu_util import _host, _zeros, run_drivers
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 SIZES = ((96, 64), (67, 45))
 T_TIME = 1.0
 
@@ -39,17 +35,6 @@ def views(rrt):
 
 def all_effects(rrt):
     return rrt.CameraEffects(useBloom=True, useVignette=True, useChromaticAberration=True, useLensDistortion=True)
-
-
-def _zeros(n, dtype):
-    import torch
-    return torch.zeros(n, dtype=dtype, device="cuda")
-
-
-def _host(t, shape):
-    import torch
-    torch.cuda.synchronize()
-    return t.cpu().numpy().reshape(shape)
 
 
 def render_ref(rrt, tex, w, h, s, cam, fx, prm, proj=None):
@@ -275,9 +260,7 @@ def _driver_frames(rrt, tex, w, h, frames, T, glow=None):
 def test_drivers_write_the_adaptive_frames(ctx, tmp_path, with_glow):
     """rrt_headless and headless.py --supersample 2 --adaptive 8: the frames of the Python launch, a refined_fraction in (0, 1) --
     the mean of the frames' counts --, and with --glow 0.25 rrt_launch_glow applied to the adaptive frame's HDR"""
-    from relativisticraytracer_amd import build
     rrt, tex, _ = ctx
-    exe = build.build_headless()
     w, h, frames = 96, 64, 2
     args = ["--width", str(w), "--height", str(h), "--frames", str(frames), "--spin", "0.9", "--supersample", "2", "--adaptive", "8"]
     glow = None
@@ -286,11 +269,8 @@ def test_drivers_write_the_adaptive_frames(ctx, tmp_path, with_glow):
         glow = rrt.GlowSettings(radius=0.02, threshold=0.2, intensity=0.25)
     want, frac = _driver_frames(rrt, tex, w, h, frames, 8, glow)
     assert 0.0 < frac < 1.0
-    for name, cmd, cwd in (("cpp", [exe], None), ("py", [sys.executable, "-m", "relativisticraytracer_amd.headless"], ROOT)):
-        out = tmp_path / f"{name}.rgba"
-        r = subprocess.run(cmd + args + ["--out", str(out)], cwd=cwd, capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, (name, r.stderr[-2000:])
-        meta = json.loads(r.stdout.strip().splitlines()[-1])
+    meta_c, meta_p, out = run_drivers(tmp_path, args)
+    for name, meta in (("cpp", meta_c), ("py", meta_p)):           # one file: run_drivers found the two byte-identical
         assert meta["adaptive"]["threshold"] == 8 and meta["supersample"] == 2, (name, meta)
         assert 0.0 < meta["adaptive"]["refined_fraction"] < 1.0, (name, meta)
         assert abs(meta["adaptive"]["refined_fraction"] - frac) < 1e-6, (name, meta, frac)

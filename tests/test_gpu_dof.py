@@ -3,10 +3,6 @@
 pinned pinhole path (a 2x2 pinhole frame at the restated origin whose centre pixel looks exactly along the restated D).  K samples
 are the documented tree over K separate one-sample launches of the (s w) x (s h) frame; zero lens points are the motion-blurred
 frame; tiles, streams, graphs and both drivers.  Small frames: 48x27 and 64x36, s <= 2.  torch is only the device-memory plumbing."""
-import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -14,33 +10,11 @@ import pytest
 import lens_ref as lr
 import projection_ref as pr
 from conftest import same_bits
-from test_gpu_motion_blur import block_sums, render_mb
-from test_gpu_stereo import _probe_hdr, all_fx, render_stereo
-from test_gpu_supersample import _host, _tree, _zeros, render_ss, tone_map
+from gpu_util import _host, _zeros, ctx, run_drivers
+from sampled_util import (_tree, all_fx_stereo as all_fx, block_sums, probe_hdr_stereo as _probe_hdr,
+                          render_dof, render_mb, render_ss, render_stereo, tone_map)
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-
-
-@pytest.fixture(scope="module")
-def ctx(sky):
-    import torch
-    assert torch.cuda.is_available(), "the -m gpu tests need a GPU"
-    import relativisticraytracer_amd as rrt
-    tex = rrt.SkyTexture(sky)
-    yield rrt, tex
-    tex.destroy()
-
-
-def render_dof(rrt, tex, w, h, s, times, cams, lens, focus, fx, prm, stream=None):
-    """the depth-of-field frame: (rgba8, hdr), both (h, w, 4) bottom-up"""
-    import torch
-    out, hdr = _zeros(h * w * 4, torch.uint8), _zeros(h * w * 4, torch.float32)
-    if stream is not None:
-        torch.cuda.synchronize()                # the buffers were cleared on the default stream
-    rrt.launch_raymarch_dof(out, w, h, s, times, cams, lens, focus, tex, fx, prm, stream=stream, hdr=hdr)
-    return _host(out, (h, w, 4)), _host(hdr, (h, w, 4))
 
 
 def samples(rrt, n, step=0.35, t0=1.0, dt=0.05, aperture=1.5):
@@ -255,26 +229,19 @@ def test_drivers_write_the_defocused_frames(ctx, tmp_path, extra):
     documented pairing: sample m at the shutter's time m (or the frame's instant) through lens point bitrev_K(m) of
     lens_points(aperture, K); --focus hole is the camera's distance to the origin"""
     import torch
-    from relativisticraytracer_amd import build, headless
+    from relativisticraytracer_amd import headless
     from relativisticraytracer_amd import camera_paths as cp
     rrt, tex = ctx
-    exe = build.build_headless()
     w, h, frames = 48, 27, 2
-    a, b = tmp_path / "cpp.rgba", tmp_path / "py.rgba"
     args = ["--width", str(w), "--height", str(h), "--frames", str(frames), "--path", "0", "--spin", "0.9", "--all-effects"] + extra
     blur, ss = "--motion-blur" in extra, 2 if "--supersample" in extra else 1
     aperture = float(extra[1])
     K = 2 if aperture == 0.5 else 4
     want_focus = 12.0 if "--focus" in extra else "hole"
-    metas = []
-    for cmd, out in (([exe], a), ([sys.executable, "-m", "relativisticraytracer_amd.headless"], b)):
-        r = subprocess.run(cmd + args + ["--out", str(out)], cwd=ROOT, capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stderr[-2000:]
-        metas.append(json.loads(r.stdout.strip().splitlines()[-1]))
-    for m in metas:
+    meta_c, meta_p, a = run_drivers(tmp_path, args)
+    for m in (meta_c, meta_p):
         assert m["dof"]["samples"] == K and m["dof"]["focus"] == want_focus and abs(m["dof"]["aperture"] - aperture) < 1e-6, m
         assert m["supersample"] == ss and m["motion_blur"] == (4 if blur else 1), m
-    assert open(a, "rb").read() == open(b, "rb").read()
     data = np.fromfile(a, np.uint8).reshape(frames, h, w, 4)
     path = cp.CameraPath(0)
     fx = rrt.CameraEffects(useChromaticAberration=True)

@@ -4,10 +4,6 @@ exp -- on synthetic frames of every ragged shape, frames of 2^20 pixels and more
 ragged second round, 1080p), flat and black frames, sequences on one state without a host synchronisation, manual
 mode, real supersampled / fisheye / stereo frames, a captured _ss -> exposure -> glow graph, and both headless drivers.  torch is only
 the device-memory plumbing."""
-import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -15,11 +11,11 @@ import pytest
 import exposure_ref as er
 import glow_ref
 from conftest import same_bits
-from test_gpu_supersample import _host, _zeros, render_ss
+from gpu_util import _host, _zeros, run_drivers
+from sampled_util import render_pano, render_ss, render_stereo
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 F = np.float32
 
 
@@ -299,8 +295,6 @@ def test_manual_mode(ctx, po):
 
 def test_real_frames(ctx, po):
     """a supersampled frame, a fisheye dome (the outside of the disc is not metered) and a top-bottom stereo composite"""
-    from test_gpu_projection import render_pano
-    from test_gpu_stereo import render_stereo
     rrt, tex, table = ctx
     w, h = 96, 64
     cam, fx, prm = rrt.CameraState.default(), rrt.CameraEffects(), rrt.RenderParams(spin=0.9)
@@ -369,10 +363,8 @@ def test_drivers_write_the_exposed_frames(ctx, po, tmp_path, with_glow):
     """rrt_headless and headless.py --auto-exposure --exposure-speed 0.2 1.0 on four frames of path 0: the same file, every frame the
     restatement's exposure of the library's _ss frame at the driver's clock and camera (then glow_ref with --glow), the settings and
     the final ev in the summary"""
-    from relativisticraytracer_amd import build
     from relativisticraytracer_amd import camera_paths as cp
     rrt, tex, table = ctx
-    exe = build.build_headless()
     w, h, frames, fps = 64, 48, 4, 24
     args = ["--width", str(w), "--height", str(h), "--frames", str(frames), "--path", "0", "--spin", "0.9",
             "--auto-exposure", "--exposure-speed", "0.2", "1.0"]
@@ -394,12 +386,8 @@ def test_drivers_write_the_exposed_frames(ctx, po, tmp_path, with_glow):
         want.append(bytes8)
     want = np.stack(want)
     assert n_visible == frames
-    files = []
-    for name, cmd, cwd in (("cpp", [exe], None), ("py", [sys.executable, "-m", "relativisticraytracer_amd.headless"], ROOT)):
-        out = tmp_path / f"{name}.rgba"
-        r = subprocess.run(cmd + args + ["--out", str(out)], cwd=cwd, capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, (name, r.stderr[-2000:])
-        meta = json.loads(r.stdout.strip().splitlines()[-1])
+    meta_c, meta_p, out = run_drivers(tmp_path, args)
+    for name, meta in (("cpp", meta_c), ("py", meta_p)):           # one file: run_drivers found the two byte-identical
         e = meta["exposure"]
         assert e["mode"] == "auto" and (e["key"], e["low_permille"], e["high_permille"], e["min_ev"], e["max_ev"]) == (0.5, 400, 20, -8, 8), (name, e)
         assert bits(e["adapt_up"]) == bits(s.adapt_up) and bits(e["adapt_down"]) == bits(s.adapt_down), (name, e)
@@ -407,5 +395,3 @@ def test_drivers_write_the_exposed_frames(ctx, po, tmp_path, with_glow):
         assert (meta["glow"] is not None) == with_glow, (name, meta)
         data = np.fromfile(out, np.uint8).reshape(frames, h, w, 4)
         assert np.array_equal(data, want), (name, [int((a != b).any(-1).sum()) for a, b in zip(data, want)])
-        files.append(out.read_bytes())
-    assert files[0] == files[1]

@@ -3,31 +3,15 @@ supersampled / motion-blurred frames, RGBA8 byte for byte through the portable e
 above every luma); the launch geometry of full-size frames (rows of several glow_hpass segments at both segment sizes, tap tables
 of several glow_load_weights launches) on frames a few rows tall; side streams and graph capture; both headless drivers.  torch is
 only the device-memory plumbing."""
-import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import glow_ref
-from test_gpu_motion_blur import moving_cameras, render_mb
-from test_gpu_supersample import _host, _zeros, render_ss, scene, tone_map
+from gpu_util import _host, _zeros, ctx, run_drivers
+from sampled_util import moving_cameras, render_mb, render_ss, scene, tone_map
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-
-
-@pytest.fixture(scope="module")
-def ctx(sky):
-    import torch
-    assert torch.cuda.is_available(), "the -m gpu tests need a GPU"
-    import relativisticraytracer_amd as rrt
-    tex = rrt.SkyTexture(sky)
-    yield rrt, tex
-    tex.destroy()
 
 
 def _device_hdr(hdr):
@@ -212,23 +196,14 @@ def test_drivers_write_the_glowed_frames(ctx, tmp_path, mode):
     _mb launch at the driver's clock and CameraPath(0)'s cameras, then rrt_launch_glow"""
     mode, w, h, intensity, radius, lobes = mode
     import torch
-    from relativisticraytracer_amd import build
     from relativisticraytracer_amd import camera_paths as cp
     rrt, tex = ctx
-    exe = build.build_headless()
-    a, b = tmp_path / "cpp.rgba", tmp_path / "py.rgba"
     args = ["--width", str(w), "--height", str(h), "--frames", "3", "--path", "0", "--spin", "0.9", "--all-effects",
             "--glow", str(intensity), "--glow-threshold", "0.2", "--glow-radius", str(radius), "--glow-lobes", str(lobes)] + mode
-    r = subprocess.run([exe] + args + ["--out", str(a)], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    meta = json.loads(r.stdout.strip().splitlines()[-1])
+    meta, meta_p, a = run_drivers(tmp_path, args)
     assert meta["glow"] == {"radius": radius, "lobes": lobes, "threshold": 0.2, "intensity": intensity}, meta
-    r = subprocess.run([sys.executable, "-m", "relativisticraytracer_amd.headless"] + args + ["--out", str(b)], cwd=ROOT,
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    meta = json.loads(r.stdout.strip().splitlines()[-1])
+    meta = meta_p
     assert meta["glow"]["lobes"] == lobes and abs(meta["glow"]["intensity"] - intensity) < 1e-7 and meta["tile_order"] is None, meta
-    assert open(a, "rb").read() == open(b, "rb").read()
     data = np.fromfile(a, np.uint8).reshape(3, h, w, 4)
     path = cp.CameraPath(0)
     fx = rrt.CameraEffects(useChromaticAberration=True)

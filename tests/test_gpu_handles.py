@@ -193,3 +193,21 @@ def test_which_kinds_a_foreign_device_may_destroy(scene):
             lib.rrt_debug_fake_device(-1)
             for o in (tex, ws, nt, tm, order):
                 o.destroy()
+
+
+def test_an_object_of_the_test_library_is_destroyed_there_from_outside():
+    """A handle object remembers the library that made it: a sky and a workspace created inside using_test_library() and destroyed
+    after it are gone from the TEST library's registries (its raw destroy says 4), not sent to the product library's, where the
+    ids mean nothing or something else.  No kernel is launched."""
+    import torch
+    assert torch.cuda.is_available(), "the -m gpu tests need a GPU"
+    import relativisticraytracer_amd as rrt
+    from relativisticraytracer_amd import _lib
+    with _lib.using_test_library() as lib:
+        tex, ws = rrt.SkyTexture(np.arange(8 * 4 * 4, dtype=np.uint8).reshape(4, 8, 4)), rrt.Workspace(1 << 20)
+    handle, wid = tex.handle, ws.id
+    assert handle and wid
+    tex.destroy()
+    ws.destroy()
+    assert tex.handle == 0 and ws.id == 0
+    assert lib.rrt_sky_destroy(handle) == BAD_HANDLE and lib.rrt_workspace_destroy(wid) == BAD_HANDLE

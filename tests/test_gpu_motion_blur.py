@@ -2,74 +2,15 @@
 (s w) x (s h) rendered by the already-pinned debug launch at its own (time, camera), reduced per s x s block in the order of the
 supersampled contract, then over k by the same pairwise tree, times 1/(s^2 K), tone-mapped by the portable exp.  HDR bit for bit,
 RGBA8 byte for byte.  torch is only the device-memory plumbing."""
-import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from conftest import same_bits
-from test_gpu_supersample import _host, _tree, _zeros, render_1x, render_ss, scene, tone_map
+from gpu_util import _host, _zeros, ctx, run_drivers
+from sampled_util import check_parity_mb as check_parity, moving_cameras, render_mb, render_ss, scene
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-
-
-@pytest.fixture(scope="module")
-def ctx(sky):
-    import torch
-    assert torch.cuda.is_available(), "the -m gpu tests need a GPU"
-    import relativisticraytracer_amd as rrt
-    tex = rrt.SkyTexture(sky)
-    yield rrt, tex
-    tex.destroy()
-
-
-def render_mb(rrt, tex, w, h, s, times, cams, fx, prm):
-    """the motion-blurred frame: (rgba8, hdr), both (h, w, 4) bottom-up"""
-    import torch
-    out, hdr = _zeros(h * w * 4, torch.uint8), _zeros(h * w * 4, torch.float32)
-    rrt.launch_raymarch_mb(out, w, h, s, times, cams, tex, fx, prm, hdr=hdr)
-    return _host(out, (h, w, 4)), _host(hdr, (h, w, 4))
-
-
-def block_sums(big_hdr, w, h, s):
-    """T_k: the sum of every s x s block of the (s h) x (s w) frame's HDR in the supersampled contract's order (bottom-up)"""
-    td = np.ascontiguousarray(big_hdr[::-1, :, :3], dtype=np.float32)
-    b = td.reshape(h, s, w, s, 3)
-    rows = [_tree([b[:, j, :, i] for i in range(s)]) for j in range(s)]
-    return _tree(rows)[::-1]
-
-
-def expected_mean(rrt, tex, w, h, s, times, cams, fx, prm):
-    sums = [block_sums(render_1x(rrt, tex, s * w, s * h, t, c, fx, prm)[1], w, h, s) for t, c in zip(times, cams)]
-    mean = _tree(sums) * np.float32(1.0 / (s * s * len(times)))
-    assert mean.dtype == np.float32
-    return mean
-
-
-def moving_cameras(rrt, sc, n, step=0.35):
-    """n cameras sliding along the scene camera's right vector (the same basis, a moved position)"""
-    a = sc["cam"]
-    out = []
-    for k in range(n):
-        pos = [a[0][i] + np.float32(step * k) * a[2][i] for i in range(3)]
-        out.append(rrt.CameraState(pos, a[1], a[2], a[3]))
-    return out
-
-
-def check_parity(po, rrt, tex, w, h, s, times, cams, fx, prm, what):
-    mean = expected_mean(rrt, tex, w, h, s, times, cams, fx, prm)
-    got8, got_hdr = render_mb(rrt, tex, w, h, s, times, cams, fx, prm)
-    assert np.isfinite(mean).all(), what
-    assert same_bits(got_hdr[..., :3], mean), (what, int((got_hdr[..., :3] != mean).sum()))
-    assert np.all(got_hdr[..., 3] == 1.0), what
-    want8 = tone_map(po, mean)
-    assert np.array_equal(got8, want8), (what, int((got8 != want8).any(-1).sum()))
-    return got8
 
 
 def test_random_scenes_k4_match_the_definition(ctx, po):
@@ -189,24 +130,15 @@ def test_drivers_write_the_blurred_frames(ctx, tmp_path, ss):
     """rrt_headless and headless.py --path 0 --motion-blur 4 --shutter 0.5: the same file, the summary keys, and every frame ==
     launch_raymarch_mb at motion_clock's times with CameraPath(0)'s cameras"""
     import torch
-    from relativisticraytracer_amd import build
     from relativisticraytracer_amd import camera_paths as cp
     rrt, tex = ctx
-    exe = build.build_headless()
     w, h = 96, 54
-    a, b = tmp_path / "cpp.rgba", tmp_path / "py.rgba"
     args = ["--width", str(w), "--height", str(h), "--frames", "3", "--path", "0", "--spin", "0.9", "--all-effects",
             "--motion-blur", "4", "--shutter", "0.5"] + (["--supersample", str(ss)] if ss > 1 else [])
-    r = subprocess.run([exe] + args + ["--out", str(a)], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    meta = json.loads(r.stdout.strip().splitlines()[-1])
+    meta, meta_p, a = run_drivers(tmp_path, args)
     assert meta["motion_blur"] == 4 and meta["shutter"] == 0.5 and meta["supersample"] == ss, meta
-    r = subprocess.run([sys.executable, "-m", "relativisticraytracer_amd.headless"] + args + ["--out", str(b)], cwd=ROOT,
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    meta = json.loads(r.stdout.strip().splitlines()[-1])
+    meta = meta_p
     assert meta["motion_blur"] == 4 and meta["shutter"] == 0.5 and meta["supersample"] == ss and meta["tile_order"] is None, meta
-    assert open(a, "rb").read() == open(b, "rb").read()
     data = np.fromfile(a, np.uint8).reshape(3, h, w, 4)
     path = cp.CameraPath(0)
     fx = rrt.CameraEffects(useChromaticAberration=True)

@@ -2,63 +2,25 @@
 host query's bit for bit; every panorama pixel's march is tied to the already-pinned pinhole path (a 2x2 pinhole frame whose centre
 pixel looks exactly along the panorama pixel's D gives its HDR bit for bit); the s x s frame is the documented tree over the 1x
 panorama of (s w) x (s h); the identities, tiles, streams, graphs and both drivers.  torch is only the device-memory plumbing."""
-import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import projection_ref as pr
 from conftest import same_bits
-from test_gpu_supersample import expected_mean, tone_map
+from gpu_util import _host, _zeros, ctx, run_drivers
+from sampled_util import all_fx_pano as all_fx, expected_mean, probe_hdr_pano as _probe_hdr, render_pano, tone_map
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 FRAMES = [(pr.EQUIRECT, 360.0, 180.0, 64, 32), (pr.EQUIRECT, 180.0, 90.0, 64, 32), (pr.EQUIRECT, 360.0, 180.0, 37, 19),
           (pr.FISHEYE, 180.0, 0.0, 48, 48), (pr.FISHEYE, 220.0, 0.0, 48, 48), (pr.FISHEYE, 180.0, 0.0, 33, 27),
           (pr.PINHOLE, 0.0, 0.0, 40, 23)]
 
 
-@pytest.fixture(scope="module")
-def ctx(sky):
-    import torch
-    assert torch.cuda.is_available(), "the -m gpu tests need a GPU"
-    import relativisticraytracer_amd as rrt
-    tex = rrt.SkyTexture(sky)
-    yield rrt, tex
-    tex.destroy()
-
-
-def _zeros(n, dtype):
-    import torch
-    return torch.zeros(n, dtype=dtype, device="cuda")
-
-
-def _host(t, shape):
-    import torch
-    torch.cuda.synchronize()
-    return t.cpu().numpy().reshape(shape)
-
-
 def cameras(rrt):
     from relativisticraytracer_amd import camera_paths as cp
     return [rrt.CameraState.default(), rrt.CameraState.from_angles((12.0, -3.0, 40.0), 137.0, 21.5), cp.CameraPath(0).camera_at(3.7)]
-
-
-def all_fx(rrt, vignette_lens=True):
-    return rrt.CameraEffects(useBloom=True, useChromaticAberration=True, caAmount=0.004, useVignette=vignette_lens,
-                             useLensDistortion=vignette_lens)
-
-
-def render_pano(rrt, tex, w, h, s, proj, t, cam, fx, prm, stream=None):
-    """(rgba8, hdr), both (h, w, 4) bottom-up"""
-    import torch
-    out, hdr = _zeros(h * w * 4, torch.uint8), _zeros(h * w * 4, torch.float32)
-    rrt.launch_raymarch_pano(out, w, h, s, proj, t, cam, tex, fx, prm, stream=stream, hdr=hdr)
-    return _host(out, (h, w, 4)), _host(hdr, (h, w, 4))
 
 
 def test_device_directions_equal_the_host_query(ctx):
@@ -79,19 +41,6 @@ def test_device_directions_equal_the_host_query(ctx):
                     want[j, i, 3] = 1.0 if inside else 0.0
             assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (kind, fov, W, H, int((got != want).any(-1).sum()))
             assert (kind != pr.FISHEYE) == bool(want[..., 3].all())
-
-
-def _probe_hdr(rrt, tex, t, pos, cam, forwards, fx, prm):
-    """the post-FX HDR of pixel (1, 1) of a 2x2 pinhole frame looking along each of `forwards` (from `pos`, cam's right and up):
-    u = v = 0 there, so its ray is exactly normalize(forward).  All launches first, one synchronisation."""
-    import torch
-    n = len(forwards)
-    out, hdr = _zeros(n * 16, torch.uint8), _zeros(n * 16, torch.float32)
-    a = cam.as_array()
-    for k, f in enumerate(forwards):
-        c = rrt.CameraState(pos, f, a[2], a[3])
-        rrt.launch_raymarch_debug(out.data_ptr() + 16 * k, 2, 2, t, c, tex, fx, prm, hdr=hdr.data_ptr() + 64 * k)
-    return _host(hdr, (n, 2, 2, 4))[:, 0, 1, :3]        # image row 1 is stored row 0 (bottom-up)
 
 
 def test_every_pixel_marches_the_pinned_pinhole_path(ctx, po):
@@ -230,24 +179,14 @@ def test_graph_capture_and_side_stream(ctx):
 def test_drivers_write_the_panoramas(ctx, tmp_path, extra):
     """rrt_headless and headless.py write the same file, whose frames are launch_raymarch_pano's with the driver's cameras and clock"""
     import torch
-    from relativisticraytracer_amd import build
     from relativisticraytracer_amd import camera_paths as cp
     rrt, tex = ctx
-    exe = build.build_headless()
     w, h = (96, 48) if extra[1] == "equirect" else (64, 64)
-    a, b = tmp_path / "cpp.rgba", tmp_path / "py.rgba"
     args = ["--width", str(w), "--height", str(h), "--frames", "3", "--path", "0", "--spin", "0.9", "--all-effects"] + extra
-    r = subprocess.run([exe] + args + ["--out", str(a)], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    meta_c = json.loads(r.stdout.strip().splitlines()[-1])
-    r = subprocess.run([sys.executable, "-m", "relativisticraytracer_amd.headless"] + args + ["--out", str(b)], cwd=ROOT,
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    meta_p = json.loads(r.stdout.strip().splitlines()[-1])
+    meta_c, meta_p, a = run_drivers(tmp_path, args)
     for m in (meta_c, meta_p):
         assert m["projection"] == extra[1] and m["fov_deg"] == (200.0 if "--fov" in extra else rrt.Projection(extra[1]).fov_deg)
         assert m["vfov_deg"] == (180.0 if extra[1] == "equirect" else None)
-    assert open(a, "rb").read() == open(b, "rb").read()
     if "--glow" in extra:
         return
     data = np.fromfile(a, np.uint8).reshape(3, h, w, 4)

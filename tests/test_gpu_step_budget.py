@@ -279,7 +279,7 @@ def test_sampled_cases_end_where_they_are_meant_to(po, sky):
 def test_supersampled_frames_honour_the_budget(ctx, po, view, n):
     """launch_raymarch_ss, s = 1, 2, 4: the tree over the budgeted 1x frame of (s w) x (s h) (test_gpu_supersample.check_parity);
     s = 1 gives the single kernel's bytes in every arithmetic mode"""
-    from test_gpu_supersample import check_parity, render_ss
+    from sampled_util import check_parity_ss as check_parity, render_ss
     g, rrt, tex = ctx
     cam = camera(view)
     for arith in (0, 2):
@@ -293,7 +293,7 @@ def test_supersampled_frames_honour_the_budget(ctx, po, view, n):
 
 
 def _sub_frames(rrt, cam, k):
-    from test_gpu_motion_blur import moving_cameras
+    from sampled_util import moving_cameras
     return [T + 0.05 * j for j in range(k)], moving_cameras(rrt, {"cam": cam.as_array()}, k, step=0.35)
 
 
@@ -303,7 +303,7 @@ def test_motion_blur_honours_the_budget_in_every_sub_frame(ctx, po, view, n):
     """launch_raymarch_mb with K = 2, 8 and 16 DISTINCT times and cameras (test_gpu_motion_blur.check_parity): every sub-frame is
     the budgeted 1x frame, and the tree over k closes levels 1, 2 and 3 with data that can tell an ordering error (equal sub-frames
     cannot).  At the default budget too, on a small frame."""
-    from test_gpu_motion_blur import check_parity
+    from sampled_util import check_parity_mb as check_parity
     g, rrt, tex = ctx
     cam = camera(view)
     w, h = (W, H) if n != 2000 else (29, 17)
@@ -325,7 +325,7 @@ def test_panoramas_honour_the_budget(ctx, po, view, n):
     """launch_raymarch_pano at the budget: 128 random inside pixels per configuration march the pinned pinhole path at the same
     budget (the check of test_gpu_projection.py::test_every_pixel_marches_the_pinned_pinhole_path, with max_steps in both)"""
     import projection_ref as pr
-    from test_gpu_projection import _probe_hdr, all_fx, render_pano
+    from sampled_util import all_fx_pano as all_fx, probe_hdr_pano as _probe_hdr, render_pano
     g, rrt, tex = ctx
     rng = np.random.default_rng(n)
     cam = camera(view)
@@ -350,7 +350,7 @@ def test_stereo_frames_honour_the_budget(ctx, po, view, n):
     of test_gpu_stereo.py::test_every_pixel_marches_the_pinned_pinhole_path), and base 0 gives the mono frame in each half"""
     import projection_ref as pr
     import stereo_ref as sr
-    from test_gpu_stereo import _layout, _probe_hdr, all_fx, render_mono, render_stereo
+    from sampled_util import all_fx_stereo as all_fx, probe_hdr_stereo as _probe_hdr, render_mono, render_stereo, stereo_layout as _layout
     g, rrt, tex = ctx
     rng = np.random.default_rng(n)
     cam = camera(view)

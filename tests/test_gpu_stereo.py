@@ -4,9 +4,7 @@ whose centre pixel looks exactly along the restated D gives its HDR bit for bit)
 the 1x composite of (s w) x (s h) eyes; the eyes differ where they should; tiles, streams, graphs and both drivers.  torch is only
 the device-memory plumbing."""
 import json
-import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -14,62 +12,13 @@ import pytest
 import projection_ref as pr
 import stereo_ref as sr
 from conftest import same_bits
-from test_gpu_supersample import expected_mean, tone_map
+from gpu_util import _host, _zeros, ctx, run_drivers
+from sampled_util import (all_fx_stereo as all_fx, expected_mean, probe_hdr_stereo as _probe_hdr,
+                          render_mono, render_stereo, stereo_layout as _layout, tone_map)
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 LAYOUTS = ("top-bottom", "side-by-side")
-
-
-@pytest.fixture(scope="module")
-def ctx(sky):
-    import torch
-    assert torch.cuda.is_available(), "the -m gpu tests need a GPU"
-    import relativisticraytracer_amd as rrt
-    tex = rrt.SkyTexture(sky)
-    yield rrt, tex
-    tex.destroy()
-
-
-def _zeros(n, dtype):
-    import torch
-    return torch.zeros(n, dtype=dtype, device="cuda")
-
-
-def _host(t, shape):
-    import torch
-    torch.cuda.synchronize()
-    return t.cpu().numpy().reshape(shape)
-
-
-def all_fx(rrt, vignette_lens=True):
-    return rrt.CameraEffects(useBloom=True, useChromaticAberration=True, caAmount=0.004, useVignette=vignette_lens,
-                             vignetteIntensity=0.6, useLensDistortion=vignette_lens, distortionAmount=0.2)
-
-
-def render_stereo(rrt, tex, w, h, s, proj, st, t, cam, fx, prm, stream=None):
-    """(rgba8, hdr) of the composite, both (rows, cols, 4) bottom-up"""
-    import torch
-    cw, ch = st.composite(w, h)
-    out, hdr = _zeros(ch * cw * 4, torch.uint8), _zeros(ch * cw * 4, torch.float32)
-    rrt.launch_raymarch_stereo(out, w, h, s, proj, st, t, cam, tex, fx, prm, stream=stream, hdr=hdr)
-    return _host(out, (ch, cw, 4)), _host(hdr, (ch, cw, 4))
-
-
-def render_mono(rrt, tex, w, h, s, proj, t, cam, fx, prm):
-    """the mono frame an eye's half is defined by: _ss for a pinhole, _pano for equirect"""
-    import torch
-    out, hdr = _zeros(h * w * 4, torch.uint8), _zeros(h * w * 4, torch.float32)
-    if proj.kind == pr.PINHOLE:
-        rrt.launch_raymarch_ss(out, w, h, s, t, cam, tex, fx, prm, hdr=hdr)
-    else:
-        rrt.launch_raymarch_pano(out, w, h, s, proj, t, cam, tex, fx, prm, hdr=hdr)
-    return _host(out, (h, w, 4)), _host(hdr, (h, w, 4))
-
-
-def _layout(st):
-    return sr.TOP_BOTTOM if st.layout == 1 else sr.SIDE_BY_SIDE
 
 
 @pytest.mark.parametrize("kind", ["pinhole", "equirect"])
@@ -90,19 +39,6 @@ def test_base_zero_halves_are_the_mono_frame(ctx, kind):
             for eye in (sr.LEFT, sr.RIGHT):
                 g8, g = sr.eye_half(_layout(st), got8, eye, w, h), sr.eye_half(_layout(st), got, eye, w, h)
                 assert np.array_equal(g8, ref8) and same_bits(g, ref), (kind, layout, s, arith, nudge, eye)
-
-
-def _probe_hdr(rrt, tex, t, cam, rays, fx, prm):
-    """the post-FX HDR of pixel (1, 1) of a 2x2 pinhole frame from each (origin, forward) of `rays` (cam's right and up): u = v = 0
-    there, so its ray starts at origin and is exactly normalize(forward).  All launches first, one synchronisation."""
-    import torch
-    n = len(rays)
-    out, hdr = _zeros(n * 16, torch.uint8), _zeros(n * 16, torch.float32)
-    a = cam.as_array()
-    for k, (o, f) in enumerate(rays):
-        c = rrt.CameraState(o, f, a[2], a[3])
-        rrt.launch_raymarch_debug(out.data_ptr() + 16 * k, 2, 2, t, c, tex, fx, prm, hdr=hdr.data_ptr() + 64 * k)
-    return _host(hdr, (n, 2, 2, 4))[:, 0, 1, :3]        # image row 1 is stored row 0 (bottom-up)
 
 
 def test_every_pixel_marches_the_pinned_pinhole_path(ctx, po):
@@ -242,16 +178,10 @@ def test_drivers_write_the_stereo_composite(ctx, tmp_path, extra):
     rrt, tex = ctx
     exe = build.build_headless()
     w, h = (64, 32) if "equirect" in extra else (48, 27)
-    a, b, c = tmp_path / "cpp.rgba", tmp_path / "py.rgba", tmp_path / "coll.rgba"
+    c = tmp_path / "coll.rgba"
     args = ["--width", str(w), "--height", str(h), "--frames", "3", "--path", "0", "--spin", "0.9", "--all-effects",
             "--tile-rows", "7"] + extra
-    r = subprocess.run([exe] + args + ["--out", str(a)], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    meta_c = json.loads(r.stdout.strip().splitlines()[-1])
-    r = subprocess.run([sys.executable, "-m", "relativisticraytracer_amd.headless"] + args + ["--out", str(b)], cwd=ROOT,
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    meta_p = json.loads(r.stdout.strip().splitlines()[-1])
+    meta_c, meta_p, a = run_drivers(tmp_path, args)
     r = subprocess.run([exe] + args + ["--force-collective", "--out", str(c)], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     assert "rccl" in json.loads(r.stdout.strip().splitlines()[-1])["collective"]
@@ -260,7 +190,7 @@ def test_drivers_write_the_stereo_composite(ctx, tmp_path, extra):
     cw, ch = st.composite(w, h)
     for m in (meta_c, meta_p):
         assert (m["width"], m["height"]) == (cw, ch) and m["stereo"] == st.info(), m
-    assert open(a, "rb").read() == open(b, "rb").read() == open(c, "rb").read()
+    assert open(a, "rb").read() == open(c, "rb").read()
     data = np.fromfile(a, np.uint8).reshape(3, ch, cw, 4)
     s = 2 if "--supersample" in extra else 1
     path = cp.CameraPath(0)

@@ -2,112 +2,15 @@
 rendered by the already-pinned debug launch, reduced per s x s block in float32 in the documented order (a pairwise tree over
 the sub-samples of a sub-row, then over the row sums, times 1/s^2) and tone-mapped by the portable exp the 1x path is pinned to.
 HDR bit for bit, RGBA8 byte for byte.  torch is only the device-memory plumbing."""
-import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from conftest import same_bits
+from gpu_util import _host, _zeros, ctx, run_drivers
+from sampled_util import check_parity_ss as check_parity, render_1x, render_ss, scene
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-
-
-@pytest.fixture(scope="module")
-def ctx(sky):
-    import torch
-    assert torch.cuda.is_available(), "the -m gpu tests need a GPU"
-    import relativisticraytracer_amd as rrt
-    tex = rrt.SkyTexture(sky)
-    yield rrt, tex
-    tex.destroy()
-
-
-def _zeros(n, dtype):
-    import torch
-    return torch.zeros(n, dtype=dtype, device="cuda")
-
-
-def _host(t, shape):
-    import torch
-    torch.cuda.synchronize()
-    return t.cpu().numpy().reshape(shape)
-
-
-def render_ss(rrt, tex, w, h, s, t, cam, fx, prm):
-    """the supersampled frame: (rgba8, hdr), both (h, w, 4) bottom-up"""
-    import torch
-    out, hdr = _zeros(h * w * 4, torch.uint8), _zeros(h * w * 4, torch.float32)
-    rrt.launch_raymarch_ss(out, w, h, s, t, cam, tex, fx, prm, hdr=hdr)
-    return _host(out, (h, w, 4)), _host(hdr, (h, w, 4))
-
-
-def render_1x(rrt, tex, w, h, t, cam, fx, prm):
-    """the 1x frame through the debug launch: (rgba8, post-FX hdr), both (h, w, 4) bottom-up"""
-    import torch
-    out, hdr = _zeros(h * w * 4, torch.uint8), _zeros(h * w * 4, torch.float32)
-    rrt.launch_raymarch_debug(out, w, h, t, cam, tex, fx, prm, hdr=hdr)
-    return _host(out, (h, w, 4)), _host(hdr, (h, w, 4))
-
-
-def _tree(parts):
-    """pairwise sum in natural order: ((p0 + p1) + (p2 + p3)) ..."""
-    while len(parts) > 1:
-        parts = [parts[k] + parts[k + 1] for k in range(0, len(parts), 2)]
-    return parts[0]
-
-
-def expected_mean(big_hdr, w, h, s):
-    """the mean HDR of every s x s block of the (s h) x (s w) frame's HDR (bottom-up in, bottom-up out), in the order of the
-    contract: within each sub-row j over i, then over the row sums, then * 1/s^2"""
-    td = np.ascontiguousarray(big_hdr[::-1, :, :3], dtype=np.float32)      # top-down: row s y + j, column s x + i
-    b = td.reshape(h, s, w, s, 3)
-    rows = [_tree([b[:, j, :, i] for i in range(s)]) for j in range(s)]
-    mean = _tree(rows) * np.float32(1.0 / (s * s))
-    assert mean.dtype == np.float32
-    return mean[::-1]
-
-
-def tone_map(po, mean):
-    """(uint8)(int)((1 - exp(-mean * 0.8f)) * 255) with the portable exp (raymarcher.cu:164-173, kExposure = 0.8f)"""
-    x = (-mean).astype(np.float32) * np.float32(0.8)
-    e = po.math_fn(0, po.MATH_PORTABLE, x.ravel()).reshape(x.shape)
-    v = (np.float32(1.0) - e) * np.float32(255.0)
-    rgb = (np.trunc(v).astype(np.int64) & 255).astype(np.uint8)
-    return np.concatenate([rgb, np.full(rgb.shape[:-1] + (1,), 255, np.uint8)], axis=-1)
-
-
-def scene(rrt, rng, case, all_fx=False):
-    """a tests/scene_gen.py scene made ragged for every s (odd w and h), volumetrics on and off by turns"""
-    from scene_gen import random_scene
-    sc = random_scene(rng, case)
-    sc["w"] |= 1
-    sc["h"] |= 1
-    sc["vol"] = 0 if case % 3 == 2 else 1
-    f = sc["fx"]
-    on = lambda k: True if all_fx else bool(f[k])
-    fx = rrt.CameraEffects(useBloom=on("use_bloom"), useVignette=on("use_vignette"), useChromaticAberration=on("use_ca"),
-                           useLensDistortion=on("use_lens"), bloomThreshold=f["bloom_threshold"], bloomIntensity=f["bloom_intensity"],
-                           vignetteIntensity=f["vignette_intensity"], caAmount=f["ca_amount"] if not all_fx else max(f["ca_amount"], 0.004),
-                           distortionAmount=f["distortion_amount"])
-    a = sc["cam"]
-    return sc, rrt.CameraState(a[0], a[1], a[2], a[3]), fx
-
-
-def check_parity(po, rrt, tex, w, h, s, t, cam, fx, prm, what):
-    big8, big_hdr = render_1x(rrt, tex, s * w, s * h, t, cam, fx, prm)
-    got8, got_hdr = render_ss(rrt, tex, w, h, s, t, cam, fx, prm)
-    mean = expected_mean(big_hdr, w, h, s)
-    assert np.isfinite(mean).all(), what
-    assert same_bits(got_hdr[..., :3], mean), (what, int((got_hdr[..., :3] != mean).sum()))
-    assert np.all(got_hdr[..., 3] == 1.0), what
-    want8 = tone_map(po, mean)
-    assert np.array_equal(got8, want8), (what, int((got8 != want8).any(-1).sum()))
-    return got8, big8
 
 
 def test_s1_is_the_1x_frame(ctx, po):
@@ -237,23 +140,14 @@ def test_drivers_write_the_supersampled_frames(ctx, tmp_path):
     """rrt_headless --supersample 2 --path 0: three frames == launch_raymarch_ss with the driver's cameras and clock; headless.py
     writes the same file"""
     import torch
-    from relativisticraytracer_amd import build
     from relativisticraytracer_amd import camera_paths as cp
     rrt, tex = ctx
-    exe = build.build_headless()
     w, h = 96, 54
-    a, b = tmp_path / "cpp.rgba", tmp_path / "py.rgba"
     args = ["--width", str(w), "--height", str(h), "--frames", "3", "--path", "0", "--spin", "0.9", "--all-effects", "--supersample", "2"]
-    r = subprocess.run([exe] + args + ["--out", str(a)], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    assert json.loads(r.stdout.strip().splitlines()[-1])["supersample"] == 2
-    r = subprocess.run([sys.executable, "-m", "relativisticraytracer_amd.headless"] + args + ["--out", str(b)], cwd=ROOT,
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    meta = json.loads(r.stdout.strip().splitlines()[-1])
+    meta_c, meta, a = run_drivers(tmp_path, args)
+    assert meta_c["supersample"] == 2
     assert meta["supersample"] == 2 and meta["tile_order"] is None
     data = np.fromfile(a, np.uint8).reshape(3, h, w, 4)
-    assert open(a, "rb").read() == open(b, "rb").read()
     path = cp.CameraPath(0)
     fx = rrt.CameraEffects(useChromaticAberration=True)
     for k in (1, 2, 3):

@@ -256,7 +256,8 @@ def test_sky_sampler_bitexact(g, po, sky):
     d = rng.normal(size=(1 << 16, 3)); d /= np.linalg.norm(d, axis=1, keepdims=True)
     d = d.astype(np.float32)
     d[:4] = [[0, 1, 0], [0, -1, 0], [-1, 0, 0], [1, 0, 0]]     # poles and the +-pi seam
-    tex = g.HookSky(sky)
+    with rrt._lib.using_test_library():       # a sky of the test library's registry, the one rrt_unit_sky_sample looks handles up in
+        tex = rrt.SkyTexture(sky)
     for off in (0.0, 0.005, -0.005):
         for bits in (8, 0):
             out = torch.empty(len(d) * 4, device="cuda")
@@ -317,7 +318,8 @@ def test_noise_table_reads_equal_the_arithmetic_hash(g):
     (incl. their edges); points outside a box are counted and clamped, never read out of bounds."""
     import torch
     import relativisticraytracer_amd as rrt
-    nt = g.HookNoiseTable(8.0)
+    with rrt._lib.using_test_library():       # a table of the test library's registry (the hooks' own)
+        nt = rrt.NoiseTable(8.0)
     try:
         info = nt.info()
         rng = np.random.default_rng(23)
@@ -352,7 +354,8 @@ def test_density_functions_with_table_switches_equal_the_arithmetic_ones(g, po, 
     BANDED table layout (coverage | 16, or chosen automatically far along the clock: [495, 505 s] at full coverage)."""
     import torch
     import relativisticraytracer_amd as rrt
-    nt = g.HookNoiseTable(window[1], window[0], window[2])
+    with rrt._lib.using_test_library():
+        nt = rrt.NoiseTable(window[1], window[0], window[2])
     try:
         rng = np.random.default_rng(29)
         waves = 4096
@@ -408,7 +411,8 @@ def test_early_outs_agree_with_the_literal_densities_through_the_gate(g, po):
     y[3 * q:] = rng.uniform(-4.0, 4.0, n - 3 * q)
     pts = np.stack([rc * np.cos(ang), y, rc * np.sin(ang)], 1).astype(np.float32)
     for t in (0.0, 3.0):
-        nt = g.HookNoiseTable(8.0)
+        with rrt._lib.using_test_library():
+            nt = rrt.NoiseTable(8.0)
         try:
             d = g.dev(pts)
             got_disk, got_dust = torch.empty(n, device="cuda"), torch.empty(n, device="cuda")
