@@ -910,3 +910,11 @@ def launch_raymarch_debug(d_out, w, h, time, cam, skyboxTex, effects, params=Non
         setattr(dbg, "d_" + k, _ptr(v).value if v is not None else None)
     _call("rrt_launch_raymarch_ex", _ptr(d_out), w, h, float(time), C.byref(cam), _sky_handle(skyboxTex), C.byref(effects),
           _ref(params), C.byref(dbg), _stream(stream))
+
+
+# Y'CbCr packing for Y4M output: a library of its own (include/rrt_yuv.h, librrt_yuv.so), loaded on first use
+from . import yuv  # noqa: E402
+from .yuv import (YuvFormat, launch_yuv_from_hdr, launch_yuv_from_rgba8, y4m_header, yuv_coefficients,  # noqa: E402,F401
+                  yuv_frame_bytes, yuv_from_hdr_host, yuv_from_rgba8_host, yuv_launch_geometry)
+
+__all__ += yuv.__all__

@@ -39,6 +39,10 @@
 //                                              UP / DOWN: time constants in seconds towards a higher / lower EV, turned into
 //                                              per-frame factors with 1 / fps (default 0 0: no smoothing); LOW HIGH in per mille;
 //                                              one GPU only, single kernel, no pool; with every frame kind)
+//                [--y4m x.y4m [--y4m-chroma 420|444] [--y4m-range limited|full] [--y4m-depth 8|10]]   (also -- or, without --out,
+//                                              only -- a YUV4MPEG2 file: BT.709 Y'CbCr packed on device 0 (include/rrt_yuv.h), top-down.
+//                                              Depth 8 converts the assembled RGBA8 frame, in every mode; depth 10 converts the frame's
+//                                              linear HDR, the whole-frame HDR path of --exposure: one GPU only, not with --glow)
 //
 // Noise tables: the reference's simTime runs without bound (main.cpp:515) and a table's size grows with the times
 // it covers, so each device keeps ONE table over a window of the clock that fits --noise-table-gib (default 2;
@@ -69,6 +73,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <filesystem>
 #include <initializer_list>
 #include <mutex>
 #include <string>
@@ -76,6 +81,7 @@
 #include <vector>
 
 #include "../../include/rrt.h"
+#include "../../include/rrt_yuv.h"
 
 namespace {
 
@@ -288,6 +294,9 @@ struct Options {               // what the command line sets (parse_options), th
     double table_gib = 2.0;
     double init_timeout = 300.0, frame_timeout = 120.0;       // watchdog limits in seconds (0: none)
     std::string out_path, sky_path;
+    std::string y4m_path;                // --y4m PATH: the sequence as a YUV4MPEG2 file (include/rrt_yuv.h)
+    bool y4m_opts = false;               // one of --y4m-chroma / --y4m-range / --y4m-depth was given
+    rrt_yuv_format yuv;
 
     // derived: w x h is the frame that is sharded and written (with --stereo the composite of two ew x eh eyes)
     bool pano = false, use_stereo = false, collective = false, auto_exposure = false;
@@ -296,8 +305,12 @@ struct Options {               // what the command line sets (parse_options), th
     int dof_k = 0;                 // lens samples per sub-sample; sample m looks through dof_xy[2m], dof_xy[2m + 1]
     float dof_xy[32];
     size_t glow_bytes = 0;
+    bool y4m = false, y4m10 = false;     // y4m10: the Y4M frames come from the HDR -- the whole-frame HDR path
+    bool hdr_frame = false;              // --glow, --exposure or y4m10: the frame renders into the slot's HDR buffer
+    size_t yuv_bytes = 0;
 
     Options() {
+        rrt_yuv_format_default(&yuv);
         rrt_glow_default(&glow);
         rrt_exposure_default(&exposure);
         rrt_stereo_default(RRT_STEREO_TOP_BOTTOM, &stereo);
@@ -361,6 +374,19 @@ int parse_options(int argc, char** argv, Options& o) {
         else if (a == "--force-collective") o.force_collective = 1;     // run the RCCL exchange even with one GPU (self-check)
         else if (a == "--out" && more) o.out_path = next();
         else if (a == "--sky" && more) o.sky_path = next();
+        else if (a == "--y4m" && more) o.y4m_path = next();
+        else if (a == "--y4m-chroma") {
+            if ((j = one_of(next(), {"420", "444"})) < 0) return refuse("usage: --y4m-chroma 420 | 444");
+            o.yuv.chroma = j == 0 ? 420 : 444; o.y4m_opts = true;
+        }
+        else if (a == "--y4m-range") {
+            if ((j = one_of(next(), {"limited", "full"})) < 0) return refuse("usage: --y4m-range limited | full");
+            o.yuv.range = j; o.y4m_opts = true;
+        }
+        else if (a == "--y4m-depth") {
+            if ((j = one_of(next(), {"8", "10"})) < 0) return refuse("usage: --y4m-depth 8 | 10");
+            o.yuv.bits = j == 0 ? 8 : 10; o.y4m_opts = true;
+        }
         else if (a == "--all-effects") o.all_fx = 1; else if (a == "--fast") o.arith = RRT_ARITH_FAST;
         else if (a == "--path-window") val(o.path_window);
         else if (a == "--path-policy" && more) {
@@ -461,6 +487,11 @@ int parse_options(int argc, char** argv, Options& o) {
     return 0;
 }
 
+// `path` from the root, "." and ".." resolved by name only (os.path.abspath's rule: the file need not exist)
+std::string absolute_path(const std::string& path) {
+    return (std::filesystem::current_path() / path).lexically_normal().string();
+}
+
 // Every refusal that depends on more than one option, in the order that decides which message a command line gets, and the values
 // derived from the options.  Host arithmetic and the library's host-only queries: no device is touched before this has returned.
 int check_options(Options& o) {
@@ -546,8 +577,20 @@ int check_options(Options& o) {
             o.dof_xy[2 * m] = spiral[2 * r]; o.dof_xy[2 * m + 1] = spiral[2 * r + 1];
         }
     }
+    // Y4M output (headless.py words these alike): depth 10 reads the frame's linear HDR, whole, on one device
+    o.y4m = !o.y4m_path.empty();
+    if (!o.y4m && o.y4m_opts) return refuse("usage: --y4m-chroma / --y4m-range / --y4m-depth need --y4m PATH");
+    if (o.y4m) {
+        o.y4m10 = o.yuv.bits == 10;
+        if (o.y4m10 && o.use_glow)
+            return refuse("usage: --y4m-depth 10 reads the frame's linear HDR and the glow tone-maps H + glow without storing it: not with --glow");
+        if (o.y4m10 && o.collective) return refuse("usage: --y4m-depth 10: one GPU only (--gpus 1)");
+        if (!o.out_path.empty() && absolute_path(o.y4m_path) == absolute_path(o.out_path)) return refuse("usage: --y4m and --out name the same file");
+        if (rrt_yuv_frame_bytes(&o.yuv, o.w, o.h, &o.yuv_bytes, nullptr) != RRT_OK) return refuse("bad arguments");
+    }
+    o.hdr_frame = o.use_glow || o.use_exposure || o.y4m10;
     // a supersampled launch is always the single kernel in the static order (include/rrt.h): no pool, no path choice, no tile order
-    if (o.supersample > 1 || o.motion > 1 || o.use_glow || o.use_exposure || o.pano || o.use_stereo || o.use_dof) {
+    if (o.supersample > 1 || o.motion > 1 || o.hdr_frame || o.pano || o.use_stereo || o.use_dof) {
         o.workspace_gib = 0; o.path_window = -1; o.tile_order = 0;
     }
     return 0;
@@ -559,7 +602,9 @@ struct Slots {                 // what device 0 owns per frame slot: gathered sh
     void* gathered[kMaxSlots] = {};
     void* frame[kMaxSlots] = {};
     void* host[kMaxSlots] = {};
-    void* hdr[kMaxSlots] = {};             // --glow / --exposure: each slot's linear frame; the glow's scratch
+    void* yuv[kMaxSlots] = {};             // --y4m: each slot's packed planes on device 0, and the pinned host copy for the sink
+    void* yuv_host[kMaxSlots] = {};
+    void* hdr[kMaxSlots] = {};             // --glow / --exposure / --y4m-depth 10: each slot's linear frame; the glow's scratch
     void* glow_scratch[kMaxSlots] = {};
     void* ad_scratch[kMaxSlots] = {};      // --adaptive: each slot's list, and the pinned word its count is copied to
     void* ad_count[kMaxSlots] = {};
@@ -656,7 +701,7 @@ int create_communicators(std::vector<Device>& dev, std::thread& warm) {
     return 0;
 }
 
-// device 0's per-slot buffers (pinned host frames only with a sink) and the sequence's exposure state
+// device 0's per-slot buffers (pinned host frames only with a sink; --y4m's planes and their pinned copy) and the sequence's exposure state
 int create_slots(Slots& R, const Options& o, bool sink, hipStream_t stream0) {
     int rc;
     HIPCHK(hipSetDevice(0));
@@ -671,7 +716,8 @@ int create_slots(Slots& R, const Options& o, bool sink, hipStream_t stream0) {
     for (int s = 0; s < o.slots; ++s) {
         HIPCHK(hipMalloc(&R.gathered[s], R.shard_stride * o.gpus));
         HIPCHK(hipMalloc(&R.frame[s], R.frame_bytes));
-        if (o.use_glow || o.use_exposure) HIPCHK(hipMalloc(&R.hdr[s], R.frame_bytes * sizeof(float)));
+        if (o.hdr_frame) HIPCHK(hipMalloc(&R.hdr[s], R.frame_bytes * sizeof(float)));
+        if (o.y4m) { HIPCHK(hipMalloc(&R.yuv[s], o.yuv_bytes)); HIPCHK(hipHostMalloc(&R.yuv_host[s], o.yuv_bytes, hipHostMallocDefault)); }
         if (o.use_glow) HIPCHK(hipMalloc(&R.glow_scratch[s], o.glow_bytes));
         if (o.use_adaptive) { HIPCHK(hipMalloc(&R.ad_scratch[s], R.ad_bytes)); HIPCHK(hipHostMalloc(&R.ad_count[s], 4, hipHostMallocDefault)); }
         HIPCHK(hipEventCreateWithFlags(&R.done[s], hipEventDisableTiming));
@@ -685,7 +731,8 @@ void destroy_slots(Slots& R, int slots) {
     if (R.exposed) (void)hipEventDestroy(R.exposed);
     for (int s = 0; s < slots; ++s) {
         (void)hipFree(R.gathered[s]); (void)hipFree(R.frame[s]); (void)hipFree(R.hdr[s]); (void)hipFree(R.glow_scratch[s]);
-        (void)hipFree(R.ad_scratch[s]);
+        (void)hipFree(R.ad_scratch[s]); (void)hipFree(R.yuv[s]);
+        if (R.yuv_host[s]) (void)hipHostFree(R.yuv_host[s]);
         if (R.ad_count[s]) (void)hipHostFree(R.ad_count[s]);
         if (R.host[s]) (void)hipHostFree(R.host[s]);
         (void)hipEventDestroy(R.done[s]);
@@ -829,12 +876,12 @@ int launch_frame(Device& D, int slot, int k, const FrameView& v, const Options& 
         return rc;
     };
     int rc;
-    if (o.use_glow || o.use_exposure) {     // one device (check_options): the slot's HDR through launch_sampled, then the post passes on the same stream
+    if (o.hdr_frame) {     // one device (check_options): the slot's HDR through launch_sampled, then the post passes on the same stream
         float* lin = static_cast<float*>(R.hdr[slot]);
         rc = o.use_adaptive ? launch_adaptive(lin) : launch_sampled(false, lin);
-        if (rc == RRT_OK && o.use_exposure) {     // the bytes -- or, in front of the glow, the scaled HDR in place
+        if (rc == RRT_OK && o.use_exposure) {     // the bytes -- and, in front of the glow or a 10-bit Y4M conversion, the scaled HDR in place
             if (o.auto_exposure) HIPCHK(hipStreamWaitEvent(st, R.exposed, 0));
-            rc = rrt_launch_exposure(o.use_glow ? nullptr : dst, o.use_glow ? lin : nullptr, lin, w, h, &o.exposure, R.exposure_scratch,
+            rc = rrt_launch_exposure(o.use_glow ? nullptr : dst, o.use_glow || o.y4m10 ? lin : nullptr, lin, w, h, &o.exposure, R.exposure_scratch,
                                      R.exposure_bytes, st);
             if (o.auto_exposure) HIPCHK(hipEventRecord(R.exposed, st));
         }
@@ -1005,6 +1052,15 @@ int main(int argc, char** argv) {
     FILE* f = o.out_path.empty() ? nullptr : fopen(o.out_path.c_str(), "wb");
     if (!o.out_path.empty() && !f) { perror("fopen"); return 1; }
     if (create_slots(R, o, f != nullptr, dev[0].stream[0])) return 1;
+    FILE* fy = nullptr;
+    if (o.y4m) {
+        char header[160];
+        size_t n = 0;
+        if ((rc = rrt_y4m_header(&o.yuv, o.w, o.h, o.fps, 1, header, sizeof(header), &n)) != RRT_OK) return fail("y4m header", rc);
+        if (!(fy = fopen(o.y4m_path.c_str(), "wb"))) { perror("fopen"); return 1; }
+        if (fwrite(header, 1, n, fy) != n) { perror("fwrite"); return 1; }
+        trace(o.y4m10 ? "y4m sink ready: planes from the HDR frame" : "y4m sink ready: planes from the RGBA8 frame");
+    }
     FrameView view;
     const float start_pos[3] = {0.0f, 10.0f, -60.0f};
     rrt_camera_from_angles(start_pos, 0.0f, -10.0f, &view.cam);
@@ -1029,6 +1085,8 @@ int main(int argc, char** argv) {
                 rrt_path_chooser_report(D.chooser, delivered, ms > 0.0f ? ms : 0.0f);   // (a frame that ended before its predecessor: 0)
         }
         if (f && fwrite(R.host[slot], 1, R.frame_bytes, f) != R.frame_bytes) fprintf(stderr, "Warning: Frame write incomplete\n");
+        if (fy && (fwrite("FRAME\n", 1, 6, fy) != 6 || fwrite(R.yuv_host[slot], 1, o.yuv_bytes, fy) != o.yuv_bytes))
+            fprintf(stderr, "Warning: Frame write incomplete\n");
         return 0;
     };
 
@@ -1048,6 +1106,12 @@ int main(int argc, char** argv) {
         // hand the frame to the sink: asynchronous copy now, the write happens one frame later
         HIPCHK(hipSetDevice(0));
         if (f) HIPCHK(hipMemcpyAsync(R.host[slot], R.frame[slot], R.frame_bytes, hipMemcpyDeviceToHost, dev[0].stream[slot]));
+        if (fy) {       // the planes of the assembled frame (depth 10: of its HDR as the last pass left it), then their copy
+            rc = o.y4m10 ? rrt_launch_yuv_from_hdr(R.yuv[slot], static_cast<const float*>(R.hdr[slot]), o.w, o.h, &o.yuv, dev[0].stream[slot])
+                         : rrt_launch_yuv_from_rgba8(R.yuv[slot], R.frame[slot], o.w, o.h, &o.yuv, dev[0].stream[slot]);
+            if (rc != RRT_OK) { fprintf(stderr, "rrt_headless: y4m: %s (%s)\n", rrt_status_string(rc), rrt_yuv_last_error()); return 1; }
+            HIPCHK(hipMemcpyAsync(R.yuv_host[slot], R.yuv[slot], o.yuv_bytes, hipMemcpyDeviceToHost, dev[0].stream[slot]));
+        }
         HIPCHK(hipEventRecord(R.done[slot], dev[0].stream[slot]));
     }
     trace("all frames enqueued; draining");
@@ -1057,6 +1121,7 @@ int main(int argc, char** argv) {
     for (Device& D : dev) { HIPCHK(hipSetDevice(D.id)); HIPCHK(hipDeviceSynchronize()); }
     totals.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (f) fclose(f);
+    if (fy) fclose(fy);
     totals.final_ev = o.exposure.ev;        // the final EV: one 4-byte read of the state, after the last frame
     if (o.auto_exposure) HIPCHK(hipMemcpy(&totals.final_ev, static_cast<const uint8_t*>(R.exposure_scratch) + RRT_EXPOSURE_STATE_OFFSET, 4, hipMemcpyDeviceToHost));
     fputs(summary_line(o, dev, noise, path_name, totals).c_str(), stdout);

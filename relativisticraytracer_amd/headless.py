@@ -8,6 +8,7 @@
            [--supersample 2 --adaptive [T]]
            [--dof APERTURE [--focus Z|hole] [--dof-samples K]]
            [--exposure EV | --auto-exposure [KEY]] [--exposure-speed UP DOWN] [--exposure-range MIN MAX] [--exposure-percentiles LOW HIGH]
+           [--y4m x.y4m [--y4m-chroma 420|444] [--y4m-range limited|full] [--y4m-depth 8|10]]
     python -m torch.distributed.run --nproc-per-node 8 -m relativisticraytracer_amd.headless ...
 
 Per frame k = 1..N it does what `main()` does while recording: advance the fixed 1/24 s clock
@@ -162,6 +163,15 @@ def build_parser():
                     help="with --auto-exposure: the darkest / brightest share of the metered pixels left out of the average, in per "
                          "mille (default 400 20)")
     ap.add_argument("--out", default=None, help="x.rgba (raw, bottom-up) | dir/ (PPM per frame) | x.mp4 (needs ffmpeg)")
+    ap.add_argument("--y4m", default=None, metavar="PATH",
+                    help="also (or, without --out, only) write the sequence as a YUV4MPEG2 file: BT.709 Y'CbCr packed on the device "
+                         "(include/rrt_yuv.h), top-down, playable as it is")
+    # the three below are checked in check_args, not by argparse's `choices`: both drivers word their refusals alike
+    ap.add_argument("--y4m-chroma", default=None, metavar="420|444", help="with --y4m: chroma subsampling (default 420)")
+    ap.add_argument("--y4m-range", default=None, metavar="limited|full", help="with --y4m: code range (default limited)")
+    ap.add_argument("--y4m-depth", default=None, metavar="8|10",
+                    help="with --y4m: bits per sample (default 8).  8 converts the finished RGBA8 frame, in every mode; 10 converts the "
+                         "frame's linear HDR (the whole-frame HDR path of --exposure): one GPU only, not with --glow")
     ap.add_argument("--init-timeout", type=float, default=300.0,
                     help="several ranks: seconds the process-group bring-up may take before the run exits non-zero with "
                          "the tracebacks of all threads, instead of hanging")
@@ -232,7 +242,32 @@ def check_args(ap, args, world):
         if args.motion_blur > 1 and args.dof_samples not in (None, args.motion_blur):
             ap.error("--dof-samples: with --motion-blur M > 1 the lens samples are the shutter's sub-frames (K = M)")
         dof_k = args.motion_blur if args.motion_blur > 1 else (args.dof_samples or 8)
+    check_y4m(ap, args, world)
     return pano, use_exposure, dof_k
+
+
+def check_y4m(ap, args, world):
+    """--y4m's refusals (rrt_headless.cpp words them alike); leaves args.y4m_format: (chroma, range, bits) or None"""
+    args.y4m_format = None
+    if args.y4m is None:
+        if args.y4m_chroma is not None or args.y4m_range is not None or args.y4m_depth is not None:
+            ap.error("--y4m-chroma / --y4m-range / --y4m-depth need --y4m PATH")
+        return
+    if args.y4m_chroma not in (None, "420", "444"):
+        ap.error("--y4m-chroma 420 | 444")
+    if args.y4m_range not in (None, "limited", "full"):
+        ap.error("--y4m-range limited | full")
+    if args.y4m_depth not in (None, "8", "10"):
+        ap.error("--y4m-depth 8 | 10")
+    bits = int(args.y4m_depth or 8)
+    if bits == 10:      # the frame's linear HDR, whole, on one GPU
+        if args.glow is not None:
+            ap.error("--y4m-depth 10 reads the frame's linear HDR and the glow tone-maps H + glow without storing it: not with --glow")
+        if world > 1:
+            ap.error("--y4m-depth 10: one GPU only (WORLD_SIZE > 1)")
+    if args.out is not None and os.path.abspath(args.y4m) == os.path.abspath(args.out):
+        ap.error("--y4m and --out name the same file")
+    args.y4m_format = (int(args.y4m_chroma or 420), args.y4m_range or "limited", bits)
 
 
 def build_settings(ap, args, pano, use_exposure):
@@ -296,7 +331,8 @@ class Renderer:
         self.w, self.h = w, h = stereo.composite(ew, eh) if stereo is not None else (ew, eh)     # the frame that is sharded, gathered and written
         self.ss, self.mb = ss, mb = args.supersample, args.motion_blur
         self.sampled = proj is not None or mb > 1 or ss > 1 or stereo is not None or dof_k > 0      # launch_sampled's kinds
-        self.post = glow is not None or exposure is not None
+        self.y4m10 = args.y4m_format is not None and args.y4m_format[2] == 10     # the Y4M frames come from the HDR: its whole-frame path
+        self.post = glow is not None or exposure is not None or self.y4m10
         # supersampled, blurred, glowed, panorama, stereo: single kernel, static order, no pool
         single = self.sampled or self.post
         # sample m looks through lens point bitrev_K(m): the spiral's radius grows with its index, the shutter's times with m
@@ -392,7 +428,8 @@ class Renderer:
 
     def render_post(self):
         """the frame through launch_sampled into self.hdr, then the post passes into self.frame (bottom-up rows, not the tile layout):
-        the exposure writes the bytes -- or, in front of the glow, the scaled HDR in place -- and the glow its own"""
+        the exposure writes the bytes -- and, in front of the glow or a 10-bit Y4M conversion, the scaled HDR in place -- and the
+        glow its own"""
         glow, hdr, frame = self.glow, self.hdr, self.frame
         self.prms[0].noise_table = self.table
         if self.adaptive is not None:
@@ -400,7 +437,7 @@ class Renderer:
         else:
             self.launch_sampled(frame, self.prms[0], hdr=hdr)
         if self.exposure is not None:
-            rrt.launch_exposure(None if glow is not None else frame, hdr if glow is not None else None, hdr, self.w, self.h,
+            rrt.launch_exposure(None if glow is not None else frame, hdr if glow is not None or self.y4m10 else None, hdr, self.w, self.h,
                                 self.exposure, self.exposure_scratch)
         if glow is not None:
             rrt.launch_glow(frame, hdr, self.w, self.h, glow, self.glow_scratch)
@@ -539,10 +576,27 @@ def main(argv=None):
                                pipeline=r.n_slots if world > 1 else False)
     sink = sinks.open_sink(args.out, w, h, args.fps) if rank == 0 else None
     host = torch.empty(h * w * 4, dtype=torch.uint8, pin_memory=True) if sink else None
+    # --y4m: rank 0 packs every finished frame on the device -- the RGBA8 frame, or at 10 bits the HDR render_post left -- and
+    # copies the planes out; without --out the RGBA8 frame itself stays on the device
+    y4m = None
+    if rank == 0 and args.y4m_format is not None:
+        fmt = rrt.YuvFormat(*args.y4m_format)
+        y4m = sinks.Y4MSink(args.y4m, w, h, args.fps, fmt)
+        yuv_dev = torch.empty(y4m.frame_bytes, dtype=torch.uint8, device=dev)
+        yuv_host = torch.empty(y4m.frame_bytes, dtype=torch.uint8, pin_memory=True)
+        trace(f"y4m sink {args.y4m}: {fmt.info()}, {y4m.frame_bytes} bytes per frame")
 
     def deliver(frame):
-        host.copy_(frame, non_blocking=False)
-        sink.write(host.numpy().reshape(h, w, 4))
+        if y4m:         # on the current stream, behind the frame
+            if r.y4m10:
+                rrt.launch_yuv_from_hdr(yuv_dev, r.hdr, w, h, fmt)
+            else:
+                rrt.launch_yuv_from_rgba8(yuv_dev, frame, w, h, fmt)
+            yuv_host.copy_(yuv_dev, non_blocking=False)
+            y4m.write(yuv_host.numpy())
+        if sink:
+            host.copy_(frame, non_blocking=False)
+            sink.write(host.numpy().reshape(h, w, 4))
 
     torch.cuda.synchronize()
     trace("sky, pools, sink ready; first frame")
@@ -551,10 +605,10 @@ def main(argv=None):
         dog.arm(args.frame_timeout + (args.init_timeout if k == 1 else 0.0), f"frame {k}")    # frame 1 brings the communicator's channels up
         r.set_frame(k, nwin.table_id)
         frame = r.render_post() if r.post else (r.render_adaptive() if r.adaptive is not None else fs.step())
-        if sink and frame is not None:
+        if (sink or y4m) and frame is not None:
             deliver(frame)
     for frame in fs.drain():                # the frames still in flight, in order
-        if sink:
+        if sink or y4m:
             deliver(frame)
     torch.cuda.synchronize()
     trace("frames done")
@@ -566,6 +620,8 @@ def main(argv=None):
     if rank == 0:
         if sink:
             sink.close()
+        if y4m:
+            y4m.close()
         print(json.dumps({"frames": args.frames, "width": w, "height": h, "n_gpus": world, "seconds": round(dt, 4),
                           "fps": round(args.frames / dt, 3), "Mrays_per_s": round(args.frames * w * h / dt / 1e6, 3), **r.summary(nwin.summary())}),
               flush=True)

@@ -75,6 +75,32 @@ class FFmpegSink:
         self.p.wait()
 
 
+class Y4MSink:
+    """A YUV4MPEG2 stream (include/rrt_yuv.h, step 5): the header on open, then `FRAME` and one frame's planes per write -- the
+    bytes launch_yuv_from_rgba8 / launch_yuv_from_hdr (or their *_host forms) produce, top-down already.  BT.709; a Y4M header
+    carries no matrix tag, so a player is told: `mpv --vf=format=colormatrix=bt.709 x.y4m`."""
+
+    def __init__(self, path, width, height, fps=24, fmt=None):
+        from . import yuv
+        self.fmt = fmt if fmt is not None else yuv.YuvFormat()
+        self.frame_bytes = yuv.yuv_frame_bytes(self.fmt, width, height)
+        header = yuv.y4m_header(self.fmt, width, height, int(fps), 1)
+        self.f = open(path, "wb")
+        self.f.write(header)
+        self.width, self.height, self.frames = width, height, 0
+
+    def write(self, yuv_bytes):
+        data = memoryview(np.ascontiguousarray(yuv_bytes)).cast("B")
+        if data.nbytes != self.frame_bytes:
+            raise ValueError(f"a {self.width}x{self.height} frame of this format is {self.frame_bytes} bytes, got {data.nbytes}")
+        self.f.write(b"FRAME\n")
+        self.f.write(data)
+        self.frames += 1
+
+    def close(self):
+        self.f.close()
+
+
 def open_sink(spec, width, height, fps=24):
     """spec: None | 'x.rgba' | 'dir/' (PPM per frame) | 'x.mp4' (ffmpeg)."""
     if not spec:
