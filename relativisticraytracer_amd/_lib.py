@@ -234,6 +234,23 @@ TEST_SYMBOLS = [
     ("rrt_selfcheck_sqrt_seeded", _i, [C.c_uint32, C.c_uint32, _vp, _vp]),
 ]
 
+
+
+class rrt_test_records_table(C.Structure):
+    """include/rrt_test_records.h: the sample-record hooks of librrt_hip_test.so, one exported table instead of function exports"""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32),
+                ("sample_records", C.CFUNCTYPE(_i, _i, _vp, _vp, _f, _i, _i, _i, C.POINTER(_f), _vp, _vp, _vp, _vp, _vp, _vp, _vp)),
+                ("march_cache_fill", C.CFUNCTYPE(_i, _i, C.POINTER(C.c_uint), C.POINTER(_ull)))]
+
+
+def records_hooks():
+    """The table `rrt_test_records` of the test library.  Tests only."""
+    t = rrt_test_records_table.in_dll(load_test(), "rrt_test_records")
+    if t.struct_size < C.sizeof(rrt_test_records_table):
+        raise RRTError(-1, "rrt_test_records", "the test library's table is older than this binding")
+    return t
+
+
 _lib = None
 _test_lib = None
 

@@ -25,7 +25,7 @@ COMPAT_SRC = os.path.join(CSRC, "rrt_compat.cpp")     # launch_raymarch under th
 CAMERA_SRC = os.path.join(CSRC, "rrt_camera.cpp")     # camera basis / path playback (host only, g++)
 CHOOSER_SRC = os.path.join(CSRC, "rrt_path_chooser.cpp")   # per-window path choice of the animation drivers (host only, g++)
 HEADERS = [os.path.join(CSRC, f) for f in ("rrt_device.h", "rrt_math.h", "rrt_tile_sort.h", "rrt_kernels.h", "rrt_projection.h", "rrt_adaptive.h", "rrt_glow.h", "rrt_exposure.h", "rrt_test_hooks.h", "rrt_noise_plan.h", "rrt_tile_objects.h", "rrt_march_cache.h", "rrt_handles.h")] + [
-    COMPAT_SRC, CAMERA_SRC, CHOOSER_SRC, os.path.join(PKG, "..", "include", "rrt.h"), os.path.join(PKG, "..", "include", "rrt_test.h"),
+    COMPAT_SRC, CAMERA_SRC, CHOOSER_SRC, os.path.join(PKG, "..", "include", "rrt.h"), os.path.join(PKG, "..", "include", "rrt_test.h"), os.path.join(PKG, "..", "include", "rrt_test_records.h"),
     os.path.join(PKG, "..", "include", "raymarcher.h")]
 
 # -ffp-contract=off: the kernels' arithmetic contract (csrc/rrt_device.h).

@@ -872,15 +872,28 @@ RRT_DEV float disk_azimuth(v3 p, DiskPoint& d) {
     return d.azimuth;
 }
 
-template <bool EARLY_OUT, bool LUT, bool BANDED = false>
-RRT_DEV float accretion_density_at(v3 p, float time, DiskPoint& dp, const NoiseLut& L, unsigned* oob, const DustBands* bands = nullptr) {
+/* Both density functions have a seam where `time` first enters (densities.h:39, :90).  Above it is the HEAD: what the sample
+ * position alone decides -- the envelope, or a return of 0 before `time` is reached.  Below it is the TAIL, which reads the
+ * envelope, rc, q, sq, the height and the azimuth.  PART says how much of the one text an instance runs:
+ *   kWhole   head then tail: the function (the in-line kernels, the workspace path, the unit hooks)
+ *   kHead    returns the envelope at the seam (an early-out's 0 above it): the march cache's fill, once per retained sample
+ *   kTail    starts at the seam with `envelope` as given: every replayed frame (sample_record / eval_sample_record below);
+ *            of `p` only p.y is read, and the azimuth is the one dp holds
+ * so that the record path cannot drift from the literal one: there is no second text. */
+enum DensityPart { kWhole = 0, kHead = 1, kTail = 2 };
+
+template <bool EARLY_OUT, bool LUT, bool BANDED = false, int PART = kWhole>
+RRT_DEV float accretion_density_at(v3 p, float time, DiskPoint& dp, const NoiseLut& L, unsigned* oob, const DustBands* bands = nullptr,
+                                   float envelope_in = 0.0f) {
     /* The render kernels (EARLY_OUT) call this only inside the disk zone, |y| < 4 and r < 30 (raymarcher.cu:57), so
      * every division / square root below has tame operands once the radial gate has passed: rc in [10, 25],
      * q = 10/rc in [0.4, 1], thick in [0.5, 0.8], y*y < 16 (a y*y too small for the bare division to be exact,
      * < 2^-100, feeds exp(-0) = 1 either way). */
     constexpr bool LEAN = EARLY_OUT;
     const float rc = dp.rc, q = dp.q;
-
+    float envelope;
+    if constexpr (PART == kTail) envelope = envelope_in;
+    else {
     const float thick = kDiskH * dp.sq;                /* DISK_H_M * powf(q, 0.5f) */
     const float slab_arg = Ar<LEAN>::div(-(p.y * p.y), 2.0f * thick * thick + 1e-7f);
     /* Exact pre-test of the early-out below (round 3), before expf / powf / the rim are paid for: slab <= e^-10.5
@@ -896,7 +909,7 @@ RRT_DEV float accretion_density_at(v3 p, float time, DiskPoint& dp, const NoiseL
     }
     const float slab = rrt_expf(slab_arg);
     const float fall = rrt_powf(q, 0.4f);
-    const float envelope = slab * fall * rim;
+    envelope = slab * fall * rim;
 
     /*
      * Exact early-out (not in the reference): the streak factor is <= 6 (densities.h:59), so the
@@ -905,6 +918,9 @@ RRT_DEV float accretion_density_at(v3 p, float time, DiskPoint& dp, const NoiseL
      * never used.
      */
     if (EARLY_OUT && envelope * (0.02f + 5.0f * 6.0f) <= 0.001f) return 0.0f;
+    }
+    /* ---- the seam: with EARLY_OUT the envelope is > 3.3e-5 or a NaN here, never 0 ---- */
+    if constexpr (PART == kHead) return envelope;
 
     const float azimuth = disk_azimuth(p, dp);
     const float kepler = 3.5f * (q * dp.sq);            /* 3.5f * powf(q, 1.5f) */
@@ -961,16 +977,22 @@ RRT_DEV float accretion_density(v3 p, float time, const NoiseLut& L, unsigned* o
 
 /* getDustCloudDensity, densities.h:69-132.  LEAN (the render kernels, which call it only inside the cloud zone
  * |y| < 0.75, r < 25: raymarcher.cu:58): the same tame-operand argument as in accretion_density. */
-template <bool LUT, bool LEAN = true, bool BANDED = false>
+template <bool LUT, bool LEAN = true, bool BANDED = false, int PART = kWhole>       /* PART: see accretion_density_at */
 RRT_DEV float dust_density_at(v3 p, float time, DiskPoint& dp, const NoiseLut& L, unsigned* oob, const DustBands* bands = nullptr,
-                              const NoiseLut* acc0 = nullptr) {
+                              const NoiseLut* acc0 = nullptr, float envelope_in = 0.0f) {
     const float rc = dp.rc, q = dp.q;
+    float envelope;
+    if constexpr (PART == kTail) envelope = envelope_in;
+    else {
     const float outer = smoothstep_t<LEAN>(kDiskOut, kDiskOut * 0.8f, rc);
     const float inner = smoothstep_t<LEAN>(kIsco, kIsco + 5.0f, rc);
     const float thick = kCloudH * 0.5f * rrt_powf(q, 0.2f);
     const float slab = rrt_expf(Ar<LEAN>::div(-(p.y * p.y), 2.0f * thick * thick + 1e-7f));
-    const float envelope = slab * outer * inner;
+    envelope = slab * outer * inner;
     if (envelope < 0.001f) return 0.0f;                 /* densities.h:85 */
+    }
+    /* ---- the seam: the envelope is >= 0.001 or a NaN here, never 0 ---- */
+    if constexpr (PART == kHead) return envelope;
 
     const float azimuth = disk_azimuth(p, dp);
     const float kepler = q * dp.sq;                     /* 1.0f * powf(q, 1.5f) */
@@ -1104,8 +1126,11 @@ struct Radiance { float r, g, b, t; };
 /* Emission (ex, ey, ez) and transmittance of one sample; false when the sample contributes nothing
  * (raymarcher.cu:71 not taken).  The reference evaluates calculateRedshiftFactor(rel_p, vel) in both
  * components (:77, :92) with the same arguments; it is evaluated once here. */
+/* STORED: the redshift factor -- a function of the sample point, the ray direction and the spin only -- is `stored_g`, kept
+ * by a sample record, instead of redshift_factor_r on the raw operands (rel_p, vel and spin are not read then). */
+template <bool STORED = false>
 RRT_DEV bool sample_emission(float d_disk, float d_cloud, v3 rel_p, float r, v3 vel, float h, float spin,
-                             float& ex, float& ey, float& ez, float& step_trans) {
+                             float& ex, float& ey, float& ez, float& step_trans, float stored_g = 0.0f) {
     const bool disk_on = d_disk > 0.001f, dust_on = d_cloud > 0.001f;
     if (!(disk_on || dust_on)) return false;
     if (RRT_PROBE & 4) { ex = d_disk; ey = d_cloud; ez = 0.f; step_trans = 0.99f; return true; }
@@ -1113,7 +1138,9 @@ RRT_DEV bool sample_emission(float d_disk, float d_cloud, v3 rel_p, float r, v3 
      * r in [10, 30): the tame range of the lean divisions / square roots (their guards fall back otherwise) */
     ex = 0.f; ey = 0.f; ez = 0.f;
     float opacity = 0.f;
-    const float shift_g = redshift_factor_r<true>(rel_p, r, vel, spin);
+    float shift_g;
+    if constexpr (STORED) shift_g = stored_g;
+    else shift_g = redshift_factor_r<true>(rel_p, r, vel, spin);
     if (disk_on) {                                               /* thermal disk, raymarcher.cu:76-88 */
         const float temp = disk_temperature_t<true>(r);
         const bool tame = temp >= 1.0f;                          /* temp in [6.6e6, 1.5e7] for r in [10, 30) */
@@ -1142,6 +1169,64 @@ RRT_DEV bool sample_emission(float d_disk, float d_cloud, v3 rel_p, float r, v3 
     }
     step_trans = rrt_expf(-(opacity * h));                       /* Beer-Lambert factor of this step, :107-108 */
     return true;
+}
+
+/* ---- sample records: what `time` cannot move of one retained sample (the march cache) ----
+ * A retained sample is a fixed point with a fixed ray direction, and `time` enters its evaluation in five places only, all of
+ * them in the densities' tails (turned, drift, sheared, the detail fbm twice).  Everything above the seams is a function of
+ * (rel_p, vel, spin) and of the arithmetic that produced `r`: the cache's fill derives it once (sample_record) and every
+ * replayed frame starts from it (eval_sample_record).
+ *   rc, y, azimuth   what the tails read of the position (q and sq are recomputed from rc: one divide, one root)
+ *   shift_g          redshift_factor_r<true> on the raw operands: its fall-back branch, and the NaN a non-finite vel.y travels
+ *                    as (kRowPlanes), arrive exactly as sample_emission would have computed them
+ *   r                the march's radius: disk_temperature, the dust's `lit`, and with y the zone rule for the step length
+ *   env_acc, env_dust   the heads' envelopes; +0 wherever the literal path returns density 0 before it reaches `time` --
+ *                    outside the zone, disk_point false, slab_arg < -10.5, envelope * 30.02 <= 0.001, dust envelope < 0.001.
+ *                    An envelope that reaches its seam is never 0 (see there), so `!= 0` IS the early-out's branch.
+ * A sample whose two envelopes are both +0 has both densities 0 at every `time`: it can never be taken (prunable). */
+struct SampleRecord { float rc, y, azimuth, shift_g, r, env_acc, env_dust; };
+
+RRT_DEV bool record_prunable(const SampleRecord& s) { return !(s.env_acc != 0.0f || s.env_dust != 0.0f); }
+
+RRT_DEV SampleRecord sample_record(v3 rel_p, float r, v3 vel, float spin) {
+    SampleRecord s;
+    s.rc = 0.0f; s.y = rel_p.y; s.azimuth = 0.0f; s.shift_g = 0.0f; s.r = r; s.env_acc = 0.0f; s.env_dust = 0.0f;
+    const bool in_disk = fabsf(rel_p.y) < kDiskH * 5.0f && r < kDiskOut + 5.0f;
+    const bool in_cloud = fabsf(rel_p.y) < kCloudH * 1.5f && r < kCloudOut;
+    DiskPoint dp;
+    if (!disk_point<true>(rel_p, dp)) return s;
+    s.rc = dp.rc;
+    const NoiseLut none{};
+    if (in_disk && !(RRT_PROBE & 1)) s.env_acc = accretion_density_at<true, false, false, kHead>(rel_p, 0.0f, dp, none, nullptr);
+    if (in_cloud && !(RRT_PROBE & 2)) s.env_dust = dust_density_at<false, true, false, kHead>(rel_p, 0.0f, dp, none, nullptr);
+    if (record_prunable(s)) return s;
+    s.azimuth = disk_azimuth(rel_p, dp);
+    s.shift_g = redshift_factor_r<true>(rel_p, r, vel, spin);
+    return s;
+}
+
+/* the length of the sample's march step, by the zone rule (raymarcher.cu:56-62) */
+RRT_DEV float record_step(const SampleRecord& s, float h_near, float h_disk, float h_vac) {
+    const bool near_bh = s.r < 18.0f;
+    const bool in_disk = fabsf(s.y) < kDiskH * 5.0f && s.r < kDiskOut + 5.0f;
+    return near_bh ? h_near : (in_disk ? h_disk : h_vac);
+}
+
+/* media_densities + sample_emission of one sample, from its record; h: record_step */
+template <int MEDIA>
+RRT_DEV bool eval_sample_record(const SampleRecord& s, float time, float h, const NoiseLut& lut_acc, const NoiseLut& lut_dust,
+                                const DustBands& bands, float& ex, float& ey, float& ez, float& step_trans) {
+    if (record_prunable(s)) return false;
+    DiskPoint dp;
+    dp.rc = s.rc;
+    dp.q = Ar<true>::div(kIsco, s.rc);                  /* as disk_point: an envelope that is not 0 means rc in [10, 25] */
+    dp.sq = Ar<true>::sqrt(dp.q);
+    dp.azimuth = s.azimuth; dp.has_azimuth = true;
+    const v3 p = mk(0.0f, s.y, 0.0f);                   /* the tails read p.y only */
+    float d_disk = 0.0f, d_cloud = 0.0f;
+    if (s.env_acc != 0.0f) d_disk = accretion_density_at<true, MEDIA >= 2, MEDIA == 3, kTail>(p, time, dp, lut_acc, nullptr, &bands, s.env_acc);
+    if (s.env_dust != 0.0f) d_cloud = dust_density_at<MEDIA >= 2, true, MEDIA == 3, kTail>(p, time, dp, lut_dust, nullptr, &bands, &lut_acc, s.env_dust);
+    return sample_emission<true>(d_disk, d_cloud, p, s.r, p, h, 0.0f, ex, ey, ez, step_trans, s.shift_g);
 }
 
 /* Beer-Lambert accumulation of one sample, raymarcher.cu:109-115 */

@@ -40,6 +40,7 @@
 #include "../../include/rrt.h"
 #ifdef RRT_TEST_HOOKS
 #include "../../include/rrt_test.h"
+#include "../../include/rrt_test_records.h"     /* the sample-record hooks: one exported table, no function export */
 #endif
 #include "rrt_device.h"
 #include "rrt_tile_sort.h"              /* the native radix sort behind rrt_tile_order */
@@ -535,6 +536,8 @@ size_t march_cache_budget(MarchCacheObject& c) {
  * (tile_of_local), an rrt_tile_order (tile_perm, tile_cost) or without volumetrics (no pass 1 exists) are not cached, so those
  * fields are not in the key; the cache runs ONE chain over the whole grid (grid_rows = 0), so the grid_row_* triple is constant.
  * max_steps above the three-pass bookkeeping's limit is not cached either.
+ * The sample records the fill's pass 2 makes of the retained rows (rrt_device.h: SampleRecord) are functions of (rel_p, vel, spin,
+ * ARITH) only -- pass 1's output and two fields of the key -- and of neither MEDIA, the tables, the sky nor the effects: no new field.
  * A field added to FrameArgs trips the assertion below: decide whether pass 1 reads it BEFORE changing the number. */
 static_assert(sizeof(FrameArgs) == 416, "FrameArgs changed: does march_defer read the new field?  Then it belongs in rrt_mc::MarchKey (march_key)");
 rrt_mc::MarchKey march_key(const FrameArgs& a, const LaunchOpts& o) {

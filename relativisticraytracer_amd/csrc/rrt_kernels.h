@@ -41,7 +41,7 @@ struct DeferCounters {
     unsigned rounds_run, rounds_with_work;    /* rounds enqueued so far / rounds whose march had something to do */
     unsigned peak_blocks;                     /* most blocks any round used */
     unsigned suspended_left;                  /* waves still suspended after the last round: finished in line */
-    unsigned pad;
+    unsigned pruned_lanes;                    /* march cache fill: lanes cleared from the rows' input masks (was padding) */
     unsigned long long total_blocks;
 };
 /* state: 0 untouched, 1 marched to its end this round, 2 suspended (the pool ran out under it), 3 shaded.
@@ -62,7 +62,9 @@ constexpr unsigned kBlockRows = 8;
  * calculateRedshiftFactor's cos_theta = dot(ray_vel, gas_dir) (geodesics.h:18-19), and gas_dir.y is +0 exactly (0 / mag), so
  * vel.y only ever enters as vel.y * 0 = +-0 added to vel.x * gas_dir.x: it can change the sign of a zero cos_theta and nothing
  * else (1 - v * (+-0) = 1) -- unless vel.y is not finite, when the product is NaN; the march poisons vel.x with NaN in that
- * case, which makes cos_theta the same NaN.  17 % less pool traffic on the way in (profiles/r05_pass_counters_*.txt). */
+ * case, which makes cos_theta the same NaN.  17 % less pool traffic on the way in (profiles/r05_pass_counters_*.txt).
+ * The march cache's retained rows keep the five planes but not their meaning: its fill rewrites them to (rc, p.y, azimuth,
+ * shift_g, r) -- a sample record, see kOutBlockEnv below; the NaN in vel.x has become the NaN in shift_g by then. */
 constexpr unsigned kRowPlanes = 5;
 constexpr unsigned kRowData = kRowPlanes * 256;
 constexpr unsigned kBlockTrailer = kBlockRows * kRowData;         /* masks[kBlockRows] (u64), then next (u32) */
@@ -72,9 +74,10 @@ constexpr unsigned kNoBlock = 0xffffffffu;
 constexpr int kMaxChains = 2;
 constexpr size_t kCounterStride = 64;      /* bytes between the chains' DeferCounters at the head of the workspace */
 static_assert(sizeof(DeferCounters) <= kCounterStride, "one counter block per chain");
-/* Retained geodesics (the march cache): passes 2 and 3 instantiated with KEEP leave a row's inputs alone --
+/* Retained geodesics (the march cache): passes 2 and 3 instantiated with KEEP keep a row's place --
  * pass 2 writes (ex, ey, ez, transmittance) and the row's live mask to planes of their own, block b of the pool's slice at
- * out_blocks + b * kOutBlockBytes: kBlockRows x four float[64] planes, then the kBlockRows masks -- and pass 3 reads them there
+ * out_blocks + b * kOutBlockBytes: kBlockRows x four float[64] planes, then the kBlockRows masks, then the records' envelope
+ * planes (kOutBlockEnv) -- and pass 3 reads the first two there
  * (the links between a wave's runs stay in the input blocks).  `replay`: the rows are those an earlier launch's pass 1 left;
  * n_blocks of the slice are in use, every wave has marched to its end, the headers and counters are not written. */
 struct KeepArgs {
@@ -84,7 +87,15 @@ struct KeepArgs {
 };
 constexpr unsigned kOutRowData = 4 * 256;
 constexpr unsigned kOutBlockMasks = kBlockRows * kOutRowData;
-constexpr unsigned kOutBlockBytes = kOutBlockMasks + kBlockRows * 8;
+/* Sample records (rrt_device.h: SampleRecord).  The fill's pass 2 (KEEP, !replay) rewrites every retained row in place -- same
+ * lanes, same five planes -- from the raw (p.xyz, vel.x, vel.z) the march left to (rc, p.y, azimuth, shift_g, r), and puts the
+ * two envelopes in two more planes per row behind the out-block's masks; it clears the lanes that can never be taken from the
+ * row's input mask (pass 3 reads the out-masks only).  A replay evaluates records; a fill the pool ran out under is never
+ * replayed (rrt_mc::Policy::fill_verified) and the refill's march writes raw rows again, so no pass ever meets a row of the
+ * other kind. */
+constexpr unsigned kOutEnvData = 2 * 256;
+constexpr unsigned kOutBlockEnv = kOutBlockMasks + kBlockRows * 8;
+constexpr unsigned kOutBlockBytes = kOutBlockEnv + kBlockRows * kOutEnvData;
 /* ------------------------------------------------------------------ lattice-hash tables: box of lattice points, fill kernel */
 struct LutBox { int x0, y0, z0, nx, ny, nz; };
 
@@ -1168,6 +1179,7 @@ __global__ __launch_bounds__(256, RRT_EVAL_WAVES) void eval_sample_rows(const Fr
     /* (Round 5 also tried this loop software-pipelined by hand -- the next row's planes and the mask after it in flight while a
      * row is evaluated -- and measured nothing, 58.2 against 58.6-59.0 ms on the key-1 frame: the head-of-row round trip is not
      * what keeps this kernel at 0.62-0.65 of the VALU issue rate; profiles/r05_eval_prefetch_ab.txt.) */
+    unsigned pruned = 0u;                                              /* wave-uniform; the fill only */
     for (unsigned row = blockIdx.x * 4u + (threadIdx.x >> 6); row < total; row += n_waves) {
         uint8_t* blk = a.sample_blocks + (size_t)(row / kBlockRows) * kBlockBytes;
         const unsigned k = row % kBlockRows;
@@ -1183,7 +1195,31 @@ __global__ __launch_bounds__(256, RRT_EVAL_WAVES) void eval_sample_rows(const Fr
         float* f = reinterpret_cast<float*>(blk + k * kRowData) + lane;
         bool has = false;
         float ex = 0.f, ey = 0.f, ez = 0.f, s = 1.0f;
-        if (mine) {
+        if constexpr (KEEP) {                                          /* sample records (kOutBlockEnv) */
+            float* e = reinterpret_cast<float*>(oblk + kOutBlockEnv + k * kOutEnvData) + lane;
+            SampleRecord rec;
+            if (!kp.replay) {                                          /* the fill: raw row -> record, in place */
+                bool keep = false;
+                if (mine) {
+                    const v3 rel_p = mk(f[0], f[64], f[128]);
+                    const v3 vel = mk(f[192], 0.0f, f[256]);          /* vel.y: see kRowPlanes */
+                    float r2, r, yv;
+                    march_radius<ARITH>(rel_p, r2, r, yv);
+                    rec = sample_record(rel_p, r, vel, a.spin);
+                    f[0] = rec.rc; f[64] = rec.y; f[128] = rec.azimuth; f[192] = rec.shift_g; f[256] = rec.r;
+                    e[0] = rec.env_acc; e[64] = rec.env_dust;
+                    keep = !record_prunable(rec);
+                }
+                const unsigned long long kept = __ballot(keep);
+                if (kept != mask && lane == (int)(__ffsll((long long)mask) - 1)) *mask_p = kept;
+                pruned += (unsigned)__popcll(mask ^ kept);
+            } else if (mine) {
+                rec.rc = f[0]; rec.y = f[64]; rec.azimuth = f[128]; rec.shift_g = f[192]; rec.r = f[256];
+                rec.env_acc = e[0]; rec.env_dust = e[64];
+            }
+            if (mine) has = eval_sample_record<MEDIA>(rec, a.time, record_step(rec, kHNear, kHDisk, kHVac), a.lut_acc, a.lut_dust,
+                                                      a.dust_bands, ex, ey, ez, s);
+        } else if (mine) {
             const v3 rel_p = mk(f[0], f[64], f[128]);
             const v3 vel = mk(f[192], 0.0f, f[256]);                  /* vel.y: see kRowPlanes */
             float r2, r, yv;
@@ -1209,6 +1245,7 @@ __global__ __launch_bounds__(256, RRT_EVAL_WAVES) void eval_sample_rows(const Fr
             if (live != mask && lane == (int)(__ffsll((long long)mask) - 1)) *mask_p = live;
         }
     }
+    if (KEEP && pruned != 0u && lane == 0) atomicAdd(&a.ctr->pruned_lanes, pruned);      /* one per wave of the grid, at most */
 }
 
 /* ---- pass 3: composite each ray's samples in march order; shade the rays of wavefronts that have reached their end;

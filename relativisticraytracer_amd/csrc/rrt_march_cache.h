@@ -8,6 +8,11 @@
  * media sample points, the wave headers and the 28 B terminal state per ray.  Nothing in it depends on `time`, the sky, the
  * noise table or the effects that act after the march; passes 2 and 3 (eval_sample_rows, composite_and_shade) are re-run on it
  * every frame.
+ * The fill's pass 2 rewrites every pooled row, in place, from the raw sample (position, vel.x, vel.z) into a SAMPLE RECORD
+ * (csrc/rrt_device.h: SampleRecord; layout: kOutBlockEnv in rrt_kernels.h): the part of the sample's evaluation above the five
+ * places where `time` enters -- cylindrical radius, height, azimuth, redshift factor, radius and the two density envelopes --
+ * and clears the lanes whose envelopes are both 0 from the row's input mask.  A record depends on (rel_p, vel, spin, arith_mode)
+ * only, all of them in the key or fixed by it; not on MEDIA, the tables, the sky or the effects.  Replays evaluate records.
  */
 #ifndef RRT_MARCH_CACHE_H
 #define RRT_MARCH_CACHE_H

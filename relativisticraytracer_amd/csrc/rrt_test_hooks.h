@@ -216,6 +216,54 @@ __global__ void k_media_lut(int n, const float* p, float time, NoiseLut la, Nois
     media_densities<MEDIA>(q, time, in_disk, in_cloud, la, ld, bands, counts, out_disk[i], out_dust[i]);
 }
 
+/* The march cache's sample records (rrt_device.h: SampleRecord) against today's row evaluation, through the PRODUCTION pass 2:
+ * the hook lays the caller's samples out as pool rows (element i = lane i % 64 of row i / 64, full blocks, the rows past n with a
+ * zero mask) and launches eval_sample_rows itself -- the non-KEEP instance on the raw rows, the KEEP instance as a fill (raw row
+ * -> record in place, pruned input masks, the frame from the derived values) and as replays.  No copy of the evaluation lives here.
+ * vel is the ray's full velocity; its row form (vel.y dropped, a non-finite one as a NaN in vel.x) is made as march_defer makes it. */
+__global__ void k_rows_pack(int n, unsigned n_rows, const float* p, const float* vel, uint8_t* blocks) {
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_rows * 64u) return;
+    const unsigned row = i >> 6, lane = i & 63u;
+    uint8_t* blk = blocks + (size_t)(row / kBlockRows) * kBlockBytes;
+    const unsigned k = row % kBlockRows;
+    if (lane == 0u) {
+        const long long left = (long long)n - (long long)row * 64;
+        reinterpret_cast<unsigned long long*>(blk + kBlockTrailer)[k] = left >= 64 ? ~0ull : (left <= 0 ? 0ull : (1ull << left) - 1ull);
+    }
+    if (i >= (unsigned)n) return;
+    float* f = reinterpret_cast<float*>(blk + k * kRowData) + lane;
+    const v3 q = ld3(p, (int)i), v = ld3(vel, (int)i);
+    f[0] = q.x; f[64] = q.y; f[128] = q.z;
+    f[192] = (v.y - v.y == 0.0f) ? v.x : __builtin_nanf(""); f[256] = v.z;
+}
+/* results of pass 2: KEEP = false from the input blocks (planes 0-3 and the rewritten mask), true from the out-blocks;
+ * (0, 0, 0, 1) and has = 0 where the sample's lane has left the mask */
+template <bool KEEP>
+__global__ void k_rows_unpack(int n, const uint8_t* in_blocks, const uint8_t* out_blocks, int* has_out, float* out) {
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (unsigned)n) return;
+    const unsigned row = i >> 6, lane = i & 63u, k = row % kBlockRows;
+    const uint8_t* blk = KEEP ? out_blocks + (size_t)(row / kBlockRows) * kOutBlockBytes : in_blocks + (size_t)(row / kBlockRows) * kBlockBytes;
+    const unsigned long long m = reinterpret_cast<const unsigned long long*>(blk + (KEEP ? kOutBlockMasks : kBlockTrailer))[k];
+    const float* f = reinterpret_cast<const float*>(blk + k * (KEEP ? kOutRowData : kRowData)) + lane;
+    const bool has = (m >> lane) & 1ull;
+    has_out[i] = has ? 1 : 0;
+    out[4 * i] = has ? f[0] : 0.0f; out[4 * i + 1] = has ? f[64] : 0.0f; out[4 * i + 2] = has ? f[128] : 0.0f; out[4 * i + 3] = has ? f[192] : 1.0f;
+}
+/* the records a fill left: the five rewritten planes, the two envelope planes, and whether the lane kept its place in the input mask */
+__global__ void k_rows_records(int n, const uint8_t* in_blocks, const uint8_t* out_blocks, float* records, int* kept) {
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (unsigned)n) return;
+    const unsigned row = i >> 6, lane = i & 63u, k = row % kBlockRows;
+    const uint8_t* blk = in_blocks + (size_t)(row / kBlockRows) * kBlockBytes;
+    const float* f = reinterpret_cast<const float*>(blk + k * kRowData) + lane;
+    const float* e = reinterpret_cast<const float*>(out_blocks + (size_t)(row / kBlockRows) * kOutBlockBytes + kOutBlockEnv + k * kOutEnvData) + lane;
+    float* o = records + 7 * (size_t)i;
+    o[0] = f[0]; o[1] = f[64]; o[2] = f[128]; o[3] = f[192]; o[4] = f[256]; o[5] = e[0]; o[6] = e[64];
+    kept[i] = (int)((reinterpret_cast<const unsigned long long*>(blk + kBlockTrailer)[k] >> lane) & 1ull);
+}
+
 /*
  * Self-checks of the march loop's sqrt/divide cores against the hardware-IEEE forms (sqrtf, `/`).
  * sqrt: every float whose bit pattern lies in [lo, hi).  div: `n` pseudo-random cases shaped
@@ -589,6 +637,91 @@ int rrt_unit_media_lut(int n, const float* p, float time, int table, float* out_
     if (nt.banded) return unit_launch(n, st, [&](dim3 g, dim3 b, hipStream_t s) { hipLaunchKernelGGL(k_media_lut<3>, g, b, 0, s, n, p, time, la, ld, db, out_disk, out_dust, d_counts); });
     return unit_launch(n, st, [&](dim3 g, dim3 b, hipStream_t s) { hipLaunchKernelGGL(k_media_lut<2>, g, b, 0, s, n, p, time, la, ld, db, out_disk, out_dust, d_counts); });
 }
+
+/* sample records: pass 2 on raw rows, and as the march cache's fill (at times[0]) and replays (at times[1..]); the launch chooses
+ * MEDIA from `table` and each time as a render launch does (a time outside the table's window runs the arithmetic instance).
+ * Not exported by name: reached through the table `rrt_test_records` below (include/rrt_test_records.h). */
+static int unit_sample_records(int n, const float* p, const float* vel, float spin, int arith_mode, int table, int n_times, const float* times,
+                            int32_t* has_raw, float* out_raw, int32_t* has_rec, float* out_rec, float* records, int32_t* kept, void* st) {
+    if (n < 0 || n_times < 1 || !times) return RRT_ERR_INVALID_ARGUMENT;
+    if (n > 0 && (!p || !vel || !records || !kept || !has_raw || !out_raw || !has_rec || !out_rec)) return RRT_ERR_INVALID_ARGUMENT;
+    if (arith_mode != RRT_ARITH_STRICT && arith_mode != RRT_ARITH_FAST && arith_mode != RRT_ARITH_FMAD) return RRT_ERR_INVALID_ARGUMENT;
+    NoiseTableObject nt;
+    if (table != 0 && lookup_here(g_noise_tables, table, nt)) return RRT_ERR_BAD_HANDLE;
+    if (n == 0) return RRT_OK;
+    const hipStream_t s = static_cast<hipStream_t>(st);
+    const int arith = arith_mode == RRT_ARITH_FAST ? kArithFast : (arith_mode == RRT_ARITH_FMAD ? kArithFmad : kArithStrict);
+    const unsigned n_blocks = ((unsigned)n + 64u * kBlockRows - 1u) / (64u * kBlockRows), n_rows = n_blocks * kBlockRows;
+    /* counters | two pools of input blocks (raw path, record path) | the record path's out-blocks */
+    const size_t off_raw = 256, off_rec = off_raw + (size_t)n_blocks * kBlockBytes, off_out = off_rec + (size_t)n_blocks * kBlockBytes;
+    uint8_t* base = nullptr;
+    RRT_HIP(hipMalloc(reinterpret_cast<void**>(&base), off_out + (size_t)n_blocks * kOutBlockBytes));
+    const auto run = [&]() -> int {
+        RRT_HIP(hipMemsetAsync(base, 0, off_raw, s));
+        FrameArgs a;
+        memset(&a, 0, sizeof(a));
+        a.spin = spin;
+        a.ctr = reinterpret_cast<DeferCounters*>(base);
+        a.block_capacity = n_blocks;
+        const dim3 gp((n_rows * 64u + 255u) / 256u), gn(((unsigned)n + 255u) / 256u), b(256);
+        hipLaunchKernelGGL(k_rows_pack, gp, b, 0, s, n, n_rows, p, vel, base + off_rec);
+        {   /* ctr->next_block = n_blocks: what pass 1 would have left */
+            const unsigned nb = n_blocks;
+            RRT_HIP(hipMemcpyAsync(&a.ctr->next_block, &nb, sizeof(nb), hipMemcpyHostToDevice, s));
+            RRT_HIP(hipStreamSynchronize(s));
+        }
+        for (int t = 0; t < n_times; ++t) {
+            int media = 1;
+            a.time = times[t];
+            memset(&a.lut_acc, 0, sizeof(a.lut_acc)); memset(&a.lut_dust, 0, sizeof(a.lut_dust)); memset(&a.dust_bands, 0, sizeof(a.dust_bands));
+            if (table != 0 && a.time >= nt.t0 && a.time <= nt.t1) {
+                media = nt.banded ? 3 : 2;
+                a.lut_acc = make_lut(nt.d_cells, nt.acc, nt.acc_families);
+                a.lut_dust = make_lut(nt.d_cells + dust_cell0(nt), nt.dust, nt.dust_families);
+                a.dust_bands = make_bands(nt);
+            }
+            const size_t o = (size_t)t * (size_t)n;
+            const KeepArgs none{nullptr, 0u, 0}, keep{base + off_out, n_blocks, t == 0 ? 0 : 1};
+            hipLaunchKernelGGL(k_rows_pack, gp, b, 0, s, n, n_rows, p, vel, base + off_raw);     /* pass 2 overwrites raw rows: fresh ones per time */
+            dispatch_kernel<false>(false, media, arith, [&](auto, auto M, auto A) {
+                a.sample_blocks = base + off_raw;
+                hipLaunchKernelGGL((eval_sample_rows<decltype(A)::value, decltype(M)::value, false>), dim3(16), dim3(256), 0, s, a, none);
+                a.sample_blocks = base + off_rec;
+                hipLaunchKernelGGL((eval_sample_rows<decltype(A)::value, decltype(M)::value, true>), dim3(16), dim3(256), 0, s, a, keep);
+            });
+            RRT_HIP(hipGetLastError());
+            hipLaunchKernelGGL((k_rows_unpack<false>), gn, b, 0, s, n, base + off_raw, base + off_out, has_raw + o, out_raw + 4 * o);
+            hipLaunchKernelGGL((k_rows_unpack<true>), gn, b, 0, s, n, base + off_rec, base + off_out, has_rec + o, out_rec + 4 * o);
+            if (t == 0) hipLaunchKernelGGL(k_rows_records, gn, b, 0, s, n, base + off_rec, base + off_out, records, kept);
+            RRT_HIP(hipGetLastError());
+        }
+        RRT_HIP(hipStreamSynchronize(s));
+        return RRT_OK;
+    };
+    const int rc = run();
+    if (rc != RRT_OK) (void)hipDeviceSynchronize();
+    (void)hipFree(base);
+    return rc;
+}
+/* what the last fill of `device`'s march cache used and pruned: blocks of rows, and lanes its pass 2 cleared from the rows' input
+ * masks because neither envelope of their record can ever be non-zero.  Waits for the cache's last launch. */
+static int debug_march_cache_fill(int device, unsigned* blocks, unsigned long long* pruned_lanes) {
+    if (!test_hooks_enabled() || !blocks || !pruned_lanes) return RRT_ERR_INVALID_ARGUMENT;
+    MarchCacheObject* c = march_cache_of(march_cache_device(device), false);
+    if (!c) return RRT_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->h_stats || c->launches == 0) return RRT_ERR_INVALID_ARGUMENT;
+    RRT_HIP(hipEventSynchronize(c->chained));
+    const volatile DeferCounters* h = c->h_stats;
+    *blocks = h->peak_blocks;
+    *pruned_lanes = h->pruned_lanes;
+    return RRT_OK;
+}
+/* the one exported object of the sample-record hooks (include/rrt_test_records.h); host pass only -- a const object at namespace
+ * scope would otherwise be emitted for the device too, with host functions in it */
+#if !defined(__HIP_DEVICE_COMPILE__)
+const rrt_test_records_table rrt_test_records = {(uint32_t)sizeof(rrt_test_records_table), 0u, unit_sample_records, debug_march_cache_fill};
+#endif
 
 int rrt_selfcheck_div_const(uint32_t lo_bits, uint32_t hi_bits, unsigned long long* d_counters, void* st) {
     if (!d_counters || lo_bits > hi_bits || hi_bits > 0x7f800000u) return RRT_ERR_INVALID_ARGUMENT;
