@@ -34,6 +34,10 @@ typedef struct rrt_test_records_table {
      * from the rows' input masks because their record can never be taken.  Needs RRT_ENABLE_TEST_HOOKS=1 in the environment;
      * waits for the cache's launches. */
     int (*march_cache_fill)(int device, unsigned* blocks, unsigned long long* pruned_lanes);
+    /* the grid (workgroups of 256) of the replays' pass 2 in `device`'s march cache (< 0: the current device), in place of the one
+     * sized from the occupancy query: a replaying wave takes blocks of rows from a cursor, so any grid serves the same bytes.
+     * 0 restores the sized grid.  Stays until changed, across keys and releases.  Needs RRT_ENABLE_TEST_HOOKS=1. */
+    int (*replay_grid)(int device, unsigned blocks);
 } rrt_test_records_table;
 
 extern const rrt_test_records_table rrt_test_records;

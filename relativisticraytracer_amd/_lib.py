@@ -240,7 +240,8 @@ class rrt_test_records_table(C.Structure):
     """include/rrt_test_records.h: the sample-record hooks of librrt_hip_test.so, one exported table instead of function exports"""
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32),
                 ("sample_records", C.CFUNCTYPE(_i, _i, _vp, _vp, _f, _i, _i, _i, C.POINTER(_f), _vp, _vp, _vp, _vp, _vp, _vp, _vp)),
-                ("march_cache_fill", C.CFUNCTYPE(_i, _i, C.POINTER(C.c_uint), C.POINTER(_ull)))]
+                ("march_cache_fill", C.CFUNCTYPE(_i, _i, C.POINTER(C.c_uint), C.POINTER(_ull))),
+                ("replay_grid", C.CFUNCTYPE(_i, _i, C.c_uint))]
 
 
 def records_hooks():

@@ -322,10 +322,36 @@ void dispatch_kernel(bool spin, int media, int arith, F&& f) {
  * own (kp); with kp.replay pass 1 and the round's close are left out.  (The kernels of passes 2 and 3 take a KeepArgs whether
  * or not they are KEEP instances: one signature per kernel; the workspace path passes an empty one, which its instances never
  * read.  march_defer has no MEDIA parameter: every MEDIA launches the same instance.) */
+/* The grid of a replay's pass 2.  Its waves take blocks from a cursor (eval_sample_rows), so the grid need not equal the chip: it
+ * is what the device holds of that instance at once -- the occupancy query times the CU count, asked once per device and instance
+ * and kept in the device's MarchCacheObject.  `forced`: the test library's hook (rrt_test_records.replay_grid), 0 otherwise. */
+struct ReplayGrid {
+    unsigned blocks[3][4] = {};       /* [ARITH][MEDIA]; 0: not asked yet */
+    unsigned forced = 0;
+};
+template <int ARITH, int MEDIA>
+int replay_grid_blocks(ReplayGrid& g, unsigned& blocks) {
+    static_assert(ARITH >= 0 && ARITH < 3 && MEDIA >= 0 && MEDIA < 4, "ReplayGrid::blocks is indexed by the instance");
+    unsigned& slot = g.blocks[ARITH][MEDIA];
+    if (slot == 0u) {
+        int dev = 0, cus = 0, per_cu = 0;
+        RRT_HIP(hipGetDevice(&dev));
+        RRT_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+        RRT_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, eval_sample_rows<ARITH, MEDIA, true>, 256, 0));
+        slot = (unsigned)std::max(cus, 1) * (unsigned)std::max(per_cu, 1);
+    }
+    blocks = g.forced != 0u ? g.forced : slot;
+    return RRT_OK;
+}
+
 template <bool SPIN, int MEDIA, int ARITH, bool KEEP>
-int enqueue_rounds(const FrameArgs& a, dim3 grid, dim3 block, int rounds, hipStream_t st, const KeepArgs kp) {
+int enqueue_rounds(const FrameArgs& a, dim3 grid, dim3 block, int rounds, hipStream_t st, const KeepArgs kp, ReplayGrid* rg) {
     const bool replay = KEEP && kp.replay != 0;
     if (KEEP) rounds = 1;
+    unsigned eval_blocks = 2048u;           /* 256 CUs x 8 workgroups: the static row stride of the fill and the workspace path */
+    if constexpr (KEEP) {
+        if (replay) { const int rc = replay_grid_blocks<ARITH, MEDIA>(*rg, eval_blocks); if (rc != RRT_OK) return rc; }
+    }
     for (int r = 0; r < rounds; ++r) {
         const bool last = r == rounds - 1;
         if (!replay) {
@@ -333,7 +359,7 @@ int enqueue_rounds(const FrameArgs& a, dim3 grid, dim3 block, int rounds, hipStr
             else hipLaunchKernelGGL((march_defer<SPIN, ARITH, true>), grid, block, 0, st, a);
         }
         RRT_HIP(hipGetLastError());
-        hipLaunchKernelGGL((eval_sample_rows<ARITH, MEDIA, KEEP>), dim3(2048), dim3(256), 0, st, a, kp);
+        hipLaunchKernelGGL((eval_sample_rows<ARITH, MEDIA, KEEP>), dim3(eval_blocks), dim3(256), 0, st, a, kp);
         RRT_HIP(hipGetLastError());
         /* LAST = true for the last round enqueued; the cache's chain (KEEP) has one round, so only <LAST, KEEP> = <true, true> exists */
         if constexpr (KEEP) hipLaunchKernelGGL((composite_and_shade<SPIN, ARITH, MEDIA, true, true>), grid, block, 0, st, a, kp);
@@ -350,14 +376,14 @@ int enqueue_rounds(const FrameArgs& a, dim3 grid, dim3 block, int rounds, hipStr
 /* one chain = march -> evaluate -> composite (in rounds) over dispatch rows [row0, row1) of the launch, in its own slice
  * of the pool, on its own stream; `keep`: the march cache's chain */
 int enqueue_chain(FrameArgs a, int arith, int media, dim3 full_grid, int row0, int row_stride, int n_rows, int rounds, hipStream_t st,
-                  const KeepArgs* keep = nullptr) {
+                  const KeepArgs* keep = nullptr, ReplayGrid* replay_grid = nullptr) {
     if (n_rows <= 0) return RRT_OK;
     const dim3 block(kWGThreads), grid(full_grid.x, (unsigned)n_rows);
     a.grid_rows = (int)full_grid.y; a.grid_row_base = row0; a.grid_row_stride = row_stride;
     int rc = RRT_OK;
     dispatch_kernel<false>(a.spin != 0.0f, media, arith, [&](auto S, auto M, auto A) {
-        rc = keep ? enqueue_rounds<S, M, A, true>(a, grid, block, 1, st, *keep)
-                  : enqueue_rounds<S, M, A, false>(a, grid, block, rounds, st, KeepArgs{nullptr, 0u, 0});
+        rc = keep ? enqueue_rounds<S, M, A, true>(a, grid, block, 1, st, *keep, replay_grid)
+                  : enqueue_rounds<S, M, A, false>(a, grid, block, rounds, st, KeepArgs{nullptr, 0u, 0}, nullptr);
     });
     return rc;
 }
@@ -471,6 +497,7 @@ struct MarchCacheObject {
     PoolLayout lay{};
     size_t off_out = 0;
     unsigned cap_blocks = 0, used_blocks = 0;
+    ReplayGrid replay_grid;                /* pass 2's grid on a replay, per instance */
 };
 struct MarchCacheRegistry {
     std::mutex mu;
@@ -611,8 +638,11 @@ int march_cache_enqueue(MarchCacheObject& c, FrameArgs a, int arith, int media, 
     a.ctr = reinterpret_cast<DeferCounters*>(c.d_base);
     a.sample_blocks = c.d_base + c.lay.off_rows;
     a.block_capacity = c.cap_blocks;
+    /* (the replay's hand-out cursor, rrt_kernels.h: replay_cursor, is the second counter slot of this header region: a.ctr is
+     * the region's base on a fill and on a replay alike, the cache's one chain never uses that slot, zero_words above clears it
+     * at every fill, and ONE cursor serves replays on any stream because c.chained serialises them) */
     const KeepArgs kp{c.d_base + c.off_out, fill ? 0u : c.used_blocks, fill ? 0 : 1};
-    const int rc = enqueue_chain(a, arith, media, grid, 0, 1, (int)grid.y, 1, st, &kp);
+    const int rc = enqueue_chain(a, arith, media, grid, 0, 1, (int)grid.y, 1, st, &kp, &c.replay_grid);
     if (rc != RRT_OK) return rc;
     if (fill) RRT_HIP(hipMemcpyAsync(c.h_stats, a.ctr, sizeof(DeferCounters), hipMemcpyDeviceToHost, st));
     RRT_HIP(hipEventRecord(c.chained, st));

@@ -85,6 +85,15 @@ struct KeepArgs {
     unsigned n_blocks;
     int replay;
 };
+/* Blocks a replaying wave of pass 2 takes from the cursor at once (round 11, profiles/r11_replay_handout_ab.txt).  One counter
+ * saturates near 90 atomics per microsecond (kMaxRun above) and the 4K bench frame hands out 210 k blocks in ~2.5 ms: with 1 the
+ * replay runs at the counter's rate (3.26 ms, whatever else is resident; the static stride took 3.1-3.2 alone); with 2 it takes
+ * 2.84-2.96 ms; with 4 the last helpings are too coarse, 3.01-3.09.  Chunks that shrink towards the end (from 2: 2.86-2.96, from
+ * 4: 2.99-3.08) did not separate from the fixed 2. */
+#ifndef RRT_REPLAY_CHUNK
+#define RRT_REPLAY_CHUNK 2
+#endif
+constexpr unsigned kReplayChunk = RRT_REPLAY_CHUNK;
 constexpr unsigned kOutRowData = 4 * 256;
 constexpr unsigned kOutBlockMasks = kBlockRows * kOutRowData;
 /* Sample records (rrt_device.h: SampleRecord).  The fill's pass 2 (KEEP, !replay) rewrites every retained row in place -- same
@@ -1170,10 +1179,80 @@ __global__ void pool_next_round(DeferCounters* c, unsigned capacity, int last) {
 #ifndef RRT_EVAL_WAVES
 #define RRT_EVAL_WAVES 8
 #endif
+/* The cursor a replay's pass 2 hands its blocks out from: the counter slot of a second chain, at kCounterStride behind the
+ * launch's own counters.  The march cache runs one chain, so the slot is free there, and zero_words clears it at every fill.
+ * It is 0 whenever a replay's pass 2 starts: pass 3 of the same launch puts it back.  (Reached from a.ctr and not through a
+ * field of KeepArgs: a larger KeepArgs moves the hidden kernel arguments of every instance, KEEP or not, and with them the
+ * encodings of kernels this does not concern.) */
+__device__ __forceinline__ unsigned* replay_cursor(const FrameArgs& a) {
+    return reinterpret_cast<unsigned*>(reinterpret_cast<uint8_t*>(a.ctr) + kCounterStride);
+}
+
+/* A replay's row: row k (input mask `mask`, not empty) of retained block b holds sample records; what the row loop of
+ * eval_sample_rows below does with such a row -- same loads, same eval_sample_record, same stores, same out-mask rule.  A function
+ * of its own, and that loop left as it stands, because folding the two into one text moves registers in the non-KEEP instances
+ * (tools/kernel_bytes.py; so did round 10's attempt). */
+template <int MEDIA>
+__device__ __forceinline__ void replay_row(const FrameArgs& a, const KeepArgs& kp, unsigned b, unsigned k, unsigned long long mask, int lane) {
+    const uint8_t* blk = a.sample_blocks + (size_t)b * kBlockBytes;
+    uint8_t* const oblk = kp.out_blocks + (size_t)b * kOutBlockBytes;
+    const bool mine = (mask >> lane) & 1ull;
+    const float* f = reinterpret_cast<const float*>(blk + k * kRowData) + lane;
+    const float* e = reinterpret_cast<const float*>(oblk + kOutBlockEnv + k * kOutEnvData) + lane;
+    bool has = false;
+    float ex = 0.f, ey = 0.f, ez = 0.f, s = 1.0f;
+    if (mine) {
+        SampleRecord rec;
+        rec.rc = f[0]; rec.y = f[64]; rec.azimuth = f[128]; rec.shift_g = f[192]; rec.r = f[256];
+        rec.env_acc = e[0]; rec.env_dust = e[64];
+        has = eval_sample_record<MEDIA>(rec, a.time, record_step(rec, kHNear, kHDisk, kHVac), a.lut_acc, a.lut_dust, a.dust_bands, ex, ey, ez, s);
+    }
+    const unsigned long long live = __ballot(has);
+    float* g = reinterpret_cast<float*>(oblk + k * kOutRowData) + lane;
+    if (has) { g[0] = ex; g[64] = ey; g[128] = ez; g[192] = s; }
+    if (lane == (int)(__ffsll((long long)mask) - 1)) reinterpret_cast<unsigned long long*>(oblk + kOutBlockMasks)[k] = live;
+}
+
 template <int ARITH, int MEDIA, bool KEEP = false>
 __global__ __launch_bounds__(256, RRT_EVAL_WAVES) void eval_sample_rows(const FrameArgs a, const KeepArgs kp) {
     const int lane = threadIdx.x & 63;
     const unsigned n_blk = KEEP && kp.replay ? min(kp.n_blocks, a.block_capacity) : min(a.ctr->next_block, a.block_capacity);
+    if constexpr (KEEP) {
+        if (kp.replay) {
+            /* Round 11: a replay hands its rows out.  A wave takes kReplayChunk whole blocks at a time from one cursor (one lane's
+             * atomic, the start broadcast: wave-uniform) until the cursor has passed n_blk, so a workgroup that starts late -- the
+             * chip shares its slots with whatever else is resident -- or meets cheap rows takes fewer blocks instead of marching a
+             * fixed 1/8192 of the pool alone at the end.  ONE cursor is enough because the cache's launches are chained
+             * (MarchCacheObject::chained): no two replays' pass 2 ever run at once, on whatever streams; pass 3 of the same launch
+             * puts the cursor back to 0.  A block's eight input masks are 64 contiguous bytes: lanes 0-7 read one each, the empty
+             * rows' out-masks are cleared in one store, and only the non-empty rows are visited. */
+            for (;;) {
+                unsigned b0 = 0u;
+                if (lane == 0) b0 = atomicAdd(replay_cursor(a), kReplayChunk);
+                b0 = (unsigned)__builtin_amdgcn_readfirstlane((int)b0);
+                if (b0 >= n_blk) break;
+                const unsigned b1 = min(b0 + kReplayChunk, n_blk);
+                for (unsigned b = b0; b < b1; ++b) {
+                    unsigned long long m = 0ull;
+                    if (lane < (int)kBlockRows) {
+                        m = reinterpret_cast<const unsigned long long*>(a.sample_blocks + (size_t)b * kBlockBytes + kBlockTrailer)[lane];
+                        if (m == 0ull)                                 /* the planes hold another frame's masks */
+                            reinterpret_cast<unsigned long long*>(kp.out_blocks + (size_t)b * kOutBlockBytes + kOutBlockMasks)[lane] = 0ull;
+                    }
+                    unsigned rows = (unsigned)__ballot(m != 0ull);     /* bit k: row k has samples */
+                    const unsigned m_lo = (unsigned)m, m_hi = (unsigned)(m >> 32);
+                    while (rows != 0u) {
+                        const unsigned k = (unsigned)__ffs((int)rows) - 1u;
+                        rows &= rows - 1u;
+                        const unsigned long long mask = (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)m_lo, (int)k) |
+                                                        ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)m_hi, (int)k) << 32);
+                        replay_row<MEDIA>(a, kp, b, k, mask, lane);
+                    }
+                }
+            }
+            return;
+        }
+    }
     const unsigned total = n_blk * kBlockRows;
     const unsigned n_waves = gridDim.x * 4u;
     /* (Round 5 also tried this loop software-pipelined by hand -- the next row's planes and the mask after it in flight while a
@@ -1213,7 +1292,7 @@ __global__ __launch_bounds__(256, RRT_EVAL_WAVES) void eval_sample_rows(const Fr
                 const unsigned long long kept = __ballot(keep);
                 if (kept != mask && lane == (int)(__ffsll((long long)mask) - 1)) *mask_p = kept;
                 pruned += (unsigned)__popcll(mask ^ kept);
-            } else if (mine) {
+            } else if (mine) {                                         /* (a replay has left above: replay_row) */
                 rec.rc = f[0]; rec.y = f[64]; rec.azimuth = f[128]; rec.shift_g = f[192]; rec.r = f[256];
                 rec.env_acc = e[0]; rec.env_dust = e[64];
             }
@@ -1253,6 +1332,11 @@ __global__ __launch_bounds__(256, RRT_EVAL_WAVES) void eval_sample_rows(const Fr
 template <bool SPIN, int ARITH, int MEDIA, bool LAST, bool KEEP = false>
 __global__ __launch_bounds__(kWGThreads) void composite_and_shade(const FrameArgs a, const KeepArgs kp) {
     const bool replay = KEEP && kp.replay != 0;                             /* retained rows: one round, long finished */
+    if constexpr (KEEP) {
+        /* this launch's pass 2 has handed out all its blocks (stream order) and the cache's next launch waits for this kernel
+         * (MarchCacheObject::chained): the hand-out cursor goes back to 0 here, one lane of one workgroup */
+        if (replay && (blockIdx.x | blockIdx.y | threadIdx.x) == 0u) *replay_cursor(a) = 0u;
+    }
     if (!replay && a.ctr->rounds_run != 0u && a.ctr->last_overflow == 0u) return;      /* a later round with nothing left: all leave */
     const unsigned long long t_start = a.tile_cost ? __builtin_readcyclecounter() : 0ull;
     int x, y, out_row;

@@ -681,6 +681,9 @@ static int unit_sample_records(int n, const float* p, const float* vel, float sp
                 a.dust_bands = make_bands(nt);
             }
             const size_t o = (size_t)t * (size_t)n;
+            /* a replay hands its blocks out from a cursor that must be 0 when it starts (rrt_kernels.h: replay_cursor, the counter
+             * slot behind a.ctr): cleared behind every replay here, as a launch's pass 3 does */
+            unsigned* const cursor = reinterpret_cast<unsigned*>(base + kCounterStride);
             const KeepArgs none{nullptr, 0u, 0}, keep{base + off_out, n_blocks, t == 0 ? 0 : 1};
             hipLaunchKernelGGL(k_rows_pack, gp, b, 0, s, n, n_rows, p, vel, base + off_raw);     /* pass 2 overwrites raw rows: fresh ones per time */
             dispatch_kernel<false>(false, media, arith, [&](auto, auto M, auto A) {
@@ -690,6 +693,7 @@ static int unit_sample_records(int n, const float* p, const float* vel, float sp
                 hipLaunchKernelGGL((eval_sample_rows<decltype(A)::value, decltype(M)::value, true>), dim3(16), dim3(256), 0, s, a, keep);
             });
             RRT_HIP(hipGetLastError());
+            if (t != 0) RRT_HIP(hipMemsetAsync(cursor, 0, sizeof(unsigned), s));
             hipLaunchKernelGGL((k_rows_unpack<false>), gn, b, 0, s, n, base + off_raw, base + off_out, has_raw + o, out_raw + 4 * o);
             hipLaunchKernelGGL((k_rows_unpack<true>), gn, b, 0, s, n, base + off_rec, base + off_out, has_rec + o, out_rec + 4 * o);
             if (t == 0) hipLaunchKernelGGL(k_rows_records, gn, b, 0, s, n, base + off_rec, base + off_out, records, kept);
@@ -705,6 +709,15 @@ static int unit_sample_records(int n, const float* p, const float* vel, float sp
 }
 /* what the last fill of `device`'s march cache used and pruned: blocks of rows, and lanes its pass 2 cleared from the rows' input
  * masks because neither envelope of their record can ever be non-zero.  Waits for the cache's last launch. */
+/* overrides the replay pass-2 grid of `device`'s cache (< 0: the current device); 0 restores the sized grid */
+static int debug_replay_grid(int device, unsigned blocks) {
+    if (!test_hooks_enabled() || blocks > 65536u) return RRT_ERR_INVALID_ARGUMENT;
+    MarchCacheObject* c = march_cache_of(march_cache_device(device), true);
+    if (!c) return RRT_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->replay_grid.forced = blocks;
+    return RRT_OK;
+}
 static int debug_march_cache_fill(int device, unsigned* blocks, unsigned long long* pruned_lanes) {
     if (!test_hooks_enabled() || !blocks || !pruned_lanes) return RRT_ERR_INVALID_ARGUMENT;
     MarchCacheObject* c = march_cache_of(march_cache_device(device), false);
@@ -720,7 +733,8 @@ static int debug_march_cache_fill(int device, unsigned* blocks, unsigned long lo
 /* the one exported object of the sample-record hooks (include/rrt_test_records.h); host pass only -- a const object at namespace
  * scope would otherwise be emitted for the device too, with host functions in it */
 #if !defined(__HIP_DEVICE_COMPILE__)
-const rrt_test_records_table rrt_test_records = {(uint32_t)sizeof(rrt_test_records_table), 0u, unit_sample_records, debug_march_cache_fill};
+const rrt_test_records_table rrt_test_records = {(uint32_t)sizeof(rrt_test_records_table), 0u, unit_sample_records, debug_march_cache_fill,
+                                                 debug_replay_grid};
 #endif
 
 int rrt_selfcheck_div_const(uint32_t lo_bits, uint32_t hi_bits, unsigned long long* d_counters, void* st) {

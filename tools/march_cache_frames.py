@@ -5,6 +5,9 @@
                                                          each launch: frame 1 marches, frame 2 fills, frames 3.. are replays
     python tools/march_cache_frames.py moving [N] [W H]   N frames of camera path 0, a new camera every frame (every launch a miss):
                                                          wall ms per frame with the launches queued back to back
+    python tools/march_cache_frames.py beside [N] [W H]   the still key's replays, N per set, HIP events per frame: queued back to back
+                                                         or synchronised one at a time, alone or with rrt.clock_probe (one sleeping
+                                                         wavefront) on a side stream spanning the set; each of the four sets twice
 
 One JSON line each.  Runs against a build without the cache too (the statistics are then null): `moving` is the A/B of "a moving
 camera must never pay" -- the per-launch cost of the cache's mutex, capture query and key compare against the parent.
@@ -45,6 +48,38 @@ def main():
             torch.cuda.synchronize()
             ms.append(round(e0.elapsed_time(e1), 3))
         res["ms"] = ms
+    elif mode == "beside":
+        cam = rrt.CameraState.default()
+        side = torch.cuda.Stream()
+        cbuf = torch.zeros(2, dtype=torch.int64, device="cuda")
+        it = [0]
+
+        def frame():
+            rrt.launch_raymarch(out, w, h, 1.0 + 0.016 * it[0], cam, tex, fx, prm)
+            it[0] += 1
+
+        for _ in range(4):                     # miss, fill, two replays
+            frame()
+        torch.cuda.synchronize()
+        sets = {}
+        for rep in range(2):                   # every set twice: the order of the sets must not be what is measured
+            for name, sync_each, probe in (("queued", False, False), ("queued_probe", False, True),
+                                           ("synced", True, False), ("synced_probe", True, True)):
+                frame()                        # the probe goes out BEHIND a frame, as in bench.py (a chip that only sleeps drops its clocks)
+                if probe:
+                    rrt.clock_probe(cbuf, int(n * (8000 if sync_each else 4000)), stream=side)
+                ev = []
+                for _ in range(n):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record(); frame(); e1.record()
+                    if sync_each:
+                        e1.synchronize()
+                    ev.append((e0, e1))
+                torch.cuda.current_stream().synchronize()
+                ms = [round(a.elapsed_time(b), 3) for a, b in ev]
+                torch.cuda.synchronize()       # the probe's end
+                sets.setdefault(name, []).append(ms)
+        res["ms"] = sets
     else:
         from relativisticraytracer_amd import camera_paths
         path = camera_paths.CameraPath(0)
