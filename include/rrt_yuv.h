@@ -89,8 +89,77 @@ int rrt_launch_yuv_from_hdr(void* d_yuv, const float* d_hdr, int width, int heig
 int rrt_yuv_from_rgba8_host(void* yuv, const void* rgba8, int width, int height, const rrt_yuv_format* fmt);
 int rrt_yuv_from_hdr_host(void* yuv, const float* hdr, int width, int height, const rrt_yuv_format* fmt);
 
-/* The message of the HIP runtime call that made a launch above return RRT_ERR_HIP ("" if none did) */
+/* The message of the HIP runtime call that made a launch above or below return RRT_ERR_HIP ("" if none did) */
 const char* rrt_yuv_last_error(void);
+
+/*
+ * HDR10 OUTPUT ("HDR10 output"): the linear HDR frame as 10-bit BT.2020 non-constant-luminance Y'CbCr behind
+ * the SMPTE ST 2084 (PQ) transfer, with the two light levels an HDR10 encoder asks for (MaxCLL, MaxFALL: CTA-861.3) reduced on the
+ * device.  Everything is binary32 and uncontracted, one rounding per written operation in the written order.  Per pixel, from
+ * H = (H_R, H_G, H_B) (alpha ignored), with white = white_nits, peak = peak_nits and, derived once on the host,
+ * K = knee * peak, span = peak - K, inv = 1.0f / span (unused when knee == 1):
+ *
+ *   A. Light.    a_c = (H_c > 0.0f) ? H_c * white : 0.0f       -- NaN and negative values give 0, +inf stays +inf
+ *   B. Gamut (BT.2087, linear light).
+ *                b_R = (0.6274f*a_R + 0.3293f*a_G) + 0.0433f*a_B
+ *                b_G = (0.0691f*a_R + 0.9195f*a_G) + 0.0114f*a_B
+ *                b_B = (0.0164f*a_R + 0.0880f*a_G) + 0.8956f*a_B      -- all terms >= 0: an infinite channel gives +inf, never NaN
+ *   C. Shoulder, per channel: the renderer's own exponential curve moved to the top of the range.
+ *                b <= K: c = b;  else knee == 1: c = peak;  else c = K + span * (1.0f - rrt_expf(-((b - K) * inv)));
+ *                then c = min(c, peak).  Continuous with slope 1 at K, asymptote peak; +inf gives peak.
+ *   D. PQ.       y = c * 1.0e-4f;  p = rrt_powf(y, 0.1593017578125f);
+ *                e = rrt_powf((0.8359375f + 18.8515625f*p) / (1.0f + 18.6875f*p), 78.84375f)       -- the IEEE quotient
+ *                q = min((int)(e * 65535.0f + 0.5f), 65535)
+ *   E. Codes.    Steps 2-4 above, unchanged, with Kr = 0.2627, Kb = 0.0593, Kg = 1 - Kr - Kb.  10 bits only; both ranges, both
+ *                chroma layouts.
+ *   F. Light levels.  Per real pixel m = max(c_R, c_G, c_B) -- step C's nits, the light the file encodes -- and
+ *                fx = (uint32_t)(m * 64.0f), truncated, at most 640000.  Each pixel counts once: the edge columns and rows 4:2:0
+ *                reads twice are not metered twice.  The state is 32 bytes, 16-byte aligned, owned by the caller:
+ *                  { uint64 frame_sum; uint64 max_frame_sum; uint32 frame_max; uint32 max_cll; uint32 frames; uint32 reserved; }
+ *                The pack kernel adds every fx into frame_sum and maxes it into frame_max (integer atomics: exact in any order); a
+ *                one-thread fold kernel behind it does max_frame_sum = max(max_frame_sum, frame_sum), max_cll = max(max_cll,
+ *                frame_max), frames += 1, frame_sum = frame_max = 0.  The host resolves, in integers,
+ *                MaxCLL = ceil(max_cll / 64), MaxFALL = ceil(max_frame_sum / (64 * w * h)).
+ *   G. Stream.   Step 5's header, unchanged (C420p10 / C444p10): Y4M has no tag for primaries or transfer, so the drivers write
+ *                <path>.hdr10.json next to the file when it closes (rrt_y4m_hdr10_sidecar's bytes).
+ */
+typedef struct rrt_yuv_hdr10 {
+    uint32_t struct_size;    /* sizeof(rrt_yuv_hdr10): rrt_yuv_hdr10_default sets it; any other value is RRT_ERR_ABI_MISMATCH */
+    float white_nits;        /* the luminance of H = 1: 203 (BT.2408's reference white) */
+    float peak_nits;         /* the shoulder's asymptote and the mastering display's maximum: 1000 */
+    float knee;              /* the shoulder starts at knee * peak_nits: 0.5; 1 is a hard clip, 0 the curve from black */
+} rrt_yuv_hdr10;
+
+int rrt_yuv_hdr10_default(rrt_yuv_hdr10* hdr10);
+
+/* Step E's coefficients and offsets.  Host only.  Refuses what rrt_yuv_coefficients refuses, and bits != 10. */
+int rrt_yuv_hdr10_coefficients(const rrt_yuv_format* fmt, int64_t coef[9], int32_t off[3]);
+
+/* The size of step F's state: 32 */
+int rrt_yuv_hdr10_light_bytes(size_t* bytes);
+
+/* Steps A-F on the device.  d_light NULL: no metering, ONE kernel; otherwise the pack kernel and the fold kernel, a linear chain on
+ * the caller's stream.  No allocation, no synchronisation.  Strips and the wide / narrow rule are rrt_yuv_launch_geometry's.
+ * Refuses what rrt_launch_yuv_from_hdr refuses, and: fmt->bits != 10; hdr10 NULL; white_nits or peak_nits not finite, <= 0 or
+ * > 10000; knee outside [0, 1] (all RRT_ERR_INVALID_ARGUMENT; a wrong hdr10->struct_size is RRT_ERR_ABI_MISMATCH); a d_light that
+ * is not 16-byte aligned or overlaps d_yuv or d_hdr. */
+int rrt_launch_yuv_hdr10_from_hdr(void* d_yuv, const float* d_hdr, int width, int height, const rrt_yuv_format* fmt,
+                                  const rrt_yuv_hdr10* hdr10, void* d_light, void* stream);
+
+/* Zeroes the state (one one-thread kernel): once per film.  RRT_ERR_INVALID_ARGUMENT: NULL or not 16-byte aligned. */
+int rrt_launch_yuv_hdr10_light_reset(void* d_light, void* stream);
+
+/* The same on HOST memory, from the source the kernels run; `light` is a host state (pack and fold) or NULL.  Same refusals without
+ * the alignment rules. */
+int rrt_yuv_hdr10_from_hdr_host(void* yuv, const float* hdr, int width, int height, const rrt_yuv_format* fmt,
+                                const rrt_yuv_hdr10* hdr10, void* light);
+
+/* out[0] MaxCLL, out[1] MaxFALL, out[2] the frames folded, from a HOST copy of the state.  Host only. */
+int rrt_yuv_hdr10_light_levels(const void* state_copy, int width, int height, uint32_t out[3]);
+
+/* Step G's sidecar into buf[0 .. cap) (no terminating NUL); *len is its length.  Host only.  `levels` is
+ * rrt_yuv_hdr10_light_levels' out.  RRT_ERR_INVALID_ARGUMENT: NULL pointers, settings refused above, a cap too small. */
+int rrt_y4m_hdr10_sidecar(const rrt_yuv_hdr10* hdr10, const uint32_t levels[3], char* buf, size_t cap, size_t* len);
 
 #ifdef __cplusplus
 }

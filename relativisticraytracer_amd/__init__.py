@@ -916,5 +916,7 @@ def launch_raymarch_debug(d_out, w, h, time, cam, skyboxTex, effects, params=Non
 from . import yuv  # noqa: E402
 from .yuv import (YuvFormat, launch_yuv_from_hdr, launch_yuv_from_rgba8, y4m_header, yuv_coefficients,  # noqa: E402,F401
                   yuv_frame_bytes, yuv_from_hdr_host, yuv_from_rgba8_host, yuv_launch_geometry)
+from .yuv import (Hdr10Settings, launch_yuv_hdr10_from_hdr, launch_yuv_hdr10_light_reset, y4m_hdr10_sidecar,  # noqa: E402,F401
+                  yuv_hdr10_coefficients, yuv_hdr10_from_hdr_host, yuv_hdr10_light_bytes, yuv_hdr10_light_levels)
 
 __all__ += yuv.__all__

@@ -19,7 +19,7 @@ TEST_LIB = os.path.join(LIBDIR, "librrt_hip_test.so")   # the same sources + -DR
 SOURCES = [os.path.join(CSRC, "rrt_hip.hip")]
 YUV_LIB = os.path.join(LIBDIR, "librrt_yuv.so")         # include/rrt_yuv.h: the Y'CbCr packing, a library of its own
 YUV_SRC = os.path.join(CSRC, "rrt_yuv.hip")
-YUV_HEADERS = [os.path.join(CSRC, "rrt_yuv_core.h"), os.path.join(CSRC, "rrt_math.h"), os.path.join(PKG, "..", "include", "rrt_yuv.h"),
+YUV_HEADERS = [os.path.join(CSRC, "rrt_yuv_core.h"), os.path.join(CSRC, "rrt_hdr10_core.h"), os.path.join(CSRC, "rrt_math.h"), os.path.join(PKG, "..", "include", "rrt_yuv.h"),
                os.path.join(PKG, "..", "include", "rrt.h")]
 COMPAT_SRC = os.path.join(CSRC, "rrt_compat.cpp")     # launch_raymarch under the reference's mangled name (host only, g++)
 CAMERA_SRC = os.path.join(CSRC, "rrt_camera.cpp")     # camera basis / path playback (host only, g++)

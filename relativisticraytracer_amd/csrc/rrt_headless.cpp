@@ -43,6 +43,9 @@
 //                                              only -- a YUV4MPEG2 file: BT.709 Y'CbCr packed on device 0 (include/rrt_yuv.h), top-down.
 //                                              Depth 8 converts the assembled RGBA8 frame, in every mode; depth 10 converts the frame's
 //                                              linear HDR, the whole-frame HDR path of --exposure: one GPU only, not with --glow)
+//                [--y4m-transfer sdr|pq [--hdr-white NITS] [--hdr-peak NITS] [--hdr-knee F]]   (pq, with --y4m-depth 10: HDR10 -- the
+//                                              linear HDR as absolute light behind SMPTE ST 2084, BT.2020 -- and x.y4m.hdr10.json with
+//                                              MaxCLL / MaxFALL, metered on the device, and the encoder options)
 //
 // Noise tables: the reference's simTime runs without bound (main.cpp:515) and a table's size grows with the times
 // it covers, so each device keeps ONE table over a window of the clock that fits --noise-table-gib (default 2;
@@ -297,6 +300,10 @@ struct Options {               // what the command line sets (parse_options), th
     std::string y4m_path;                // --y4m PATH: the sequence as a YUV4MPEG2 file (include/rrt_yuv.h)
     bool y4m_opts = false;               // one of --y4m-chroma / --y4m-range / --y4m-depth was given
     rrt_yuv_format yuv;
+    int y4m_transfer = -1;               // --y4m-transfer: -1 not given, 0 sdr, 1 pq
+    bool hdr_opts = false;               // one of --hdr-white / --hdr-peak / --hdr-knee was given
+    bool hdr_nits_ok = true, hdr_knee_ok = true;
+    rrt_yuv_hdr10 hdr10;
 
     // derived: w x h is the frame that is sharded and written (with --stereo the composite of two ew x eh eyes)
     bool pano = false, use_stereo = false, collective = false, auto_exposure = false;
@@ -306,11 +313,13 @@ struct Options {               // what the command line sets (parse_options), th
     float dof_xy[32];
     size_t glow_bytes = 0;
     bool y4m = false, y4m10 = false;     // y4m10: the Y4M frames come from the HDR -- the whole-frame HDR path
+    bool y4m_pq = false;                 // ... as HDR10 (rrt_launch_yuv_hdr10_from_hdr), with the sidecar
     bool hdr_frame = false;              // --glow, --exposure or y4m10: the frame renders into the slot's HDR buffer
     size_t yuv_bytes = 0;
 
     Options() {
         rrt_yuv_format_default(&yuv);
+        rrt_yuv_hdr10_default(&hdr10);
         rrt_glow_default(&glow);
         rrt_exposure_default(&exposure);
         rrt_stereo_default(RRT_STEREO_TOP_BOTTOM, &stereo);
@@ -386,6 +395,18 @@ int parse_options(int argc, char** argv, Options& o) {
         else if (a == "--y4m-depth") {
             if ((j = one_of(next(), {"8", "10"})) < 0) return refuse("usage: --y4m-depth 8 | 10");
             o.yuv.bits = j == 0 ? 8 : 10; o.y4m_opts = true;
+        }
+        else if (a == "--y4m-transfer") {
+            if ((o.y4m_transfer = one_of(next(), {"sdr", "pq"})) < 0) return refuse("usage: --y4m-transfer sdr | pq");
+        }
+        else if (a == "--hdr-white" || a == "--hdr-peak") {
+            float& dst = a == "--hdr-white" ? o.hdr10.white_nits : o.hdr10.peak_nits;
+            if (!parse_float(next(), dst, true) || !(dst > 0.0f && dst <= 10000.0f)) o.hdr_nits_ok = false;
+            o.hdr_opts = true;
+        }
+        else if (a == "--hdr-knee") {
+            if (!parse_float(next(), o.hdr10.knee, true) || !(o.hdr10.knee >= 0.0f && o.hdr10.knee <= 1.0f)) o.hdr_knee_ok = false;
+            o.hdr_opts = true;
         }
         else if (a == "--all-effects") o.all_fx = 1; else if (a == "--fast") o.arith = RRT_ARITH_FAST;
         else if (a == "--path-window") val(o.path_window);
@@ -579,6 +600,12 @@ int check_options(Options& o) {
     }
     // Y4M output (headless.py words these alike): depth 10 reads the frame's linear HDR, whole, on one device
     o.y4m = !o.y4m_path.empty();
+    o.y4m_pq = o.y4m_transfer == 1;
+    if (!o.y4m_pq && o.hdr_opts) return refuse("usage: --hdr-white / --hdr-peak / --hdr-knee need --y4m-transfer pq");
+    if (o.y4m_pq && (!o.y4m || o.yuv.bits != 10)) return refuse("usage: --y4m-transfer pq needs --y4m PATH and --y4m-depth 10");
+    if (!o.hdr_nits_ok) return refuse("usage: --hdr-white / --hdr-peak NITS: in (0, 10000]");
+    if (!o.hdr_knee_ok) return refuse("usage: --hdr-knee F: in [0, 1]");
+    if (!o.y4m && o.y4m_transfer >= 0) return refuse("usage: --y4m-transfer needs --y4m PATH");
     if (!o.y4m && o.y4m_opts) return refuse("usage: --y4m-chroma / --y4m-range / --y4m-depth need --y4m PATH");
     if (o.y4m) {
         o.y4m10 = o.yuv.bits == 10;
@@ -616,6 +643,9 @@ struct Slots {                 // what device 0 owns per frame slot: gathered sh
     void* exposure_scratch = nullptr;
     size_t exposure_bytes = 0;
     hipEvent_t exposed = nullptr;
+    // --y4m-transfer pq: ONE light-level state for the film, in the same way -- a frame's pack and fold run behind its predecessor's
+    void* light = nullptr;
+    hipEvent_t lit = nullptr;
 };
 
 // each device's shard of the frame; the stride between shards in the gathered buffer
@@ -711,6 +741,13 @@ int create_slots(Slots& R, const Options& o, bool sink, hipStream_t stream0) {
         HIPCHK(hipEventCreateWithFlags(&R.exposed, hipEventDisableTiming));
         if ((rc = rrt_launch_exposure_reset(R.exposure_scratch, R.exposure_bytes, stream0)) != RRT_OK) return fail("exposure reset", rc);
     }
+    if (o.y4m_pq) {
+        size_t light_bytes = 0;
+        if ((rc = rrt_yuv_hdr10_light_bytes(&light_bytes)) != RRT_OK) return fail("hdr10 light state", rc);
+        HIPCHK(hipMalloc(&R.light, light_bytes));
+        HIPCHK(hipEventCreateWithFlags(&R.lit, hipEventDisableTiming));
+        if ((rc = rrt_launch_yuv_hdr10_light_reset(R.light, stream0)) != RRT_OK) return fail("hdr10 light reset", rc);
+    }
     if (o.use_adaptive && (rc = rrt_adaptive_scratch_bytes(o.w, o.h, &R.ad_bytes)) != RRT_OK) return fail("adaptive scratch", rc);
     R.frame_bytes = (size_t)o.w * o.h * 4;
     for (int s = 0; s < o.slots; ++s) {
@@ -729,6 +766,8 @@ int create_slots(Slots& R, const Options& o, bool sink, hipStream_t stream0) {
 void destroy_slots(Slots& R, int slots) {
     (void)hipFree(R.exposure_scratch);
     if (R.exposed) (void)hipEventDestroy(R.exposed);
+    (void)hipFree(R.light);
+    if (R.lit) (void)hipEventDestroy(R.lit);
     for (int s = 0; s < slots; ++s) {
         (void)hipFree(R.gathered[s]); (void)hipFree(R.frame[s]); (void)hipFree(R.hdr[s]); (void)hipFree(R.glow_scratch[s]);
         (void)hipFree(R.ad_scratch[s]); (void)hipFree(R.yuv[s]);
@@ -1107,6 +1146,12 @@ int main(int argc, char** argv) {
         HIPCHK(hipSetDevice(0));
         if (f) HIPCHK(hipMemcpyAsync(R.host[slot], R.frame[slot], R.frame_bytes, hipMemcpyDeviceToHost, dev[0].stream[slot]));
         if (fy) {       // the planes of the assembled frame (depth 10: of its HDR as the last pass left it), then their copy
+            if (o.y4m_pq) {     // metered into the film's one state, in frame order
+                if (k > 1) HIPCHK(hipStreamWaitEvent(dev[0].stream[slot], R.lit, 0));
+                rc = rrt_launch_yuv_hdr10_from_hdr(R.yuv[slot], static_cast<const float*>(R.hdr[slot]), o.w, o.h, &o.yuv, &o.hdr10, R.light,
+                                                   dev[0].stream[slot]);
+                if (rc == RRT_OK) HIPCHK(hipEventRecord(R.lit, dev[0].stream[slot]));
+            } else
             rc = o.y4m10 ? rrt_launch_yuv_from_hdr(R.yuv[slot], static_cast<const float*>(R.hdr[slot]), o.w, o.h, &o.yuv, dev[0].stream[slot])
                          : rrt_launch_yuv_from_rgba8(R.yuv[slot], R.frame[slot], o.w, o.h, &o.yuv, dev[0].stream[slot]);
             if (rc != RRT_OK) { fprintf(stderr, "rrt_headless: y4m: %s (%s)\n", rrt_status_string(rc), rrt_yuv_last_error()); return 1; }
@@ -1122,6 +1167,19 @@ int main(int argc, char** argv) {
     totals.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (f) fclose(f);
     if (fy) fclose(fy);
+    if (o.y4m_pq) {     // the film's light levels: one copy of the state, after the last frame, and the sidecar next to the file
+        alignas(16) unsigned char state[32];
+        uint32_t levels[3];
+        char text[1024];
+        size_t n = 0;
+        HIPCHK(hipMemcpy(state, R.light, sizeof(state), hipMemcpyDeviceToHost));
+        if ((rc = rrt_yuv_hdr10_light_levels(state, o.w, o.h, levels)) != RRT_OK) return fail("hdr10 light levels", rc);
+        if ((rc = rrt_y4m_hdr10_sidecar(&o.hdr10, levels, text, sizeof(text), &n)) != RRT_OK) return fail("hdr10 sidecar", rc);
+        FILE* fs = fopen((o.y4m_path + ".hdr10.json").c_str(), "wb");
+        if (!fs) { perror("fopen"); return 1; }
+        if (fwrite(text, 1, n, fs) != n) { perror("fwrite"); return 1; }
+        fclose(fs);
+    }
     totals.final_ev = o.exposure.ev;        // the final EV: one 4-byte read of the state, after the last frame
     if (o.auto_exposure) HIPCHK(hipMemcpy(&totals.final_ev, static_cast<const uint8_t*>(R.exposure_scratch) + RRT_EXPOSURE_STATE_OFFSET, 4, hipMemcpyDeviceToHost));
     fputs(summary_line(o, dev, noise, path_name, totals).c_str(), stdout);

@@ -18,6 +18,13 @@
 #include "../../include/rrt_yuv.h"
 #include "rrt_math.h"
 
+/* RRT_FN for a member function (RRT_FN itself says `static`) */
+#if defined(__HIPCC__)
+#define RRT_YUV_MEMBER __host__ __device__ __forceinline__
+#else
+#define RRT_YUV_MEMBER inline __attribute__((always_inline))
+#endif
+
 constexpr int kYuvStripW = 8, kYuvStripH = 2;
 constexpr float kYuvExposure = 0.8f;          /* == kExposure, csrc/rrt_device.h:98 */
 
@@ -76,15 +83,17 @@ RRT_FN void yuv_put(uint8_t* base, size_t i, int bits, int code) {
 }
 
 /* Strip (sx, sy), one sample per store.  Columns and rows past the frame's edge are the edge's: a 4:2:0 sum at an odd edge counts
- * the last column or row twice, as the definition says; nothing past the edge is stored. */
-template <bool HDR>
-RRT_FN void yuv_strip_narrow(uint8_t* yuv, const void* src, const YuvPlan& p, int sx, int sy) {
+ * the last column or row twice, as the definition says; nothing past the edge is stored.  `load(col, row, real, q)` gives a
+ * pixel's sixteen-bit components: the SDR inputs through YuvNarrowLoad below, the HDR10 leg through rrt_hdr10_core.h's. */
+template <class LOAD>
+RRT_FN void yuv_strip_narrow_with(uint8_t* yuv, const YuvPlan& p, int sx, int sy, const LOAD& load) {
     const int x0 = sx * kYuvStripW, r0 = sy * kYuvStripH;
     int q[kYuvStripH][kYuvStripW][3];
     for (int j = 0; j < kYuvStripH; ++j)
         for (int i = 0; i < kYuvStripW; ++i) {
+            const bool real = x0 + i < p.w && r0 + j < p.h;       /* false: the edge's pixel again, for a 4:2:0 sum */
             const int col = x0 + i < p.w ? x0 + i : p.w - 1, row = r0 + j < p.h ? r0 + j : p.h - 1;
-            yuv_load_q<HDR>(src, p.w, p.h, col, row, q[j][i]);
+            load(col, row, real, q[j][i]);
         }
     for (int j = 0; j < kYuvStripH && r0 + j < p.h; ++j)
         for (int i = 0; i < kYuvStripW && x0 + i < p.w; ++i) {
@@ -107,6 +116,19 @@ RRT_FN void yuv_strip_narrow(uint8_t* yuv, const void* src, const YuvPlan& p, in
         }
     }
 }
+
+template <bool HDR>
+struct YuvNarrowLoad {
+    const void* src;
+    int w, h;
+    RRT_YUV_MEMBER void operator()(int col, int row, bool, int q[3]) const { yuv_load_q<HDR>(src, w, h, col, row, q); }
+};
+
+template <bool HDR>
+RRT_FN void yuv_strip_narrow(uint8_t* yuv, const void* src, const YuvPlan& p, int sx, int sy) {
+    const YuvNarrowLoad<HDR> load = {src, p.w, p.h};
+    yuv_strip_narrow_with(yuv, p, sx, sy, load);
+}
 static_assert(kYuvStripH == 2 && kYuvStripW % 2 == 0, "a strip holds whole 2 x 2 chroma blocks");
 
 /* ---- host only: the format's checks, the plan, the conversion of a frame in host memory (rrt_yuv.hip's C ABI calls these) ---- */
@@ -119,8 +141,9 @@ static inline int yuv_check_format(const rrt_yuv_format* f) {
     return RRT_OK;
 }
 
-static inline void yuv_coefficients(const rrt_yuv_format& f, int64_t coef[9], int32_t off[3]) {
-    const double Kr = 0.2126, Kb = 0.0722, Kg = 1.0 - Kr - Kb;
+/* BT.709's Kr and Kb unless told otherwise (rrt_hdr10_core.h passes BT.2020's) */
+static inline void yuv_coefficients(const rrt_yuv_format& f, int64_t coef[9], int32_t off[3], double Kr = 0.2126, double Kb = 0.0722) {
+    const double Kg = 1.0 - Kr - Kb;
     const double K[9] = {Kr, Kg, Kb,
                          -Kr / (2.0 * (1.0 - Kb)), -Kg / (2.0 * (1.0 - Kb)), 0.5,
                          0.5, -Kg / (2.0 * (1.0 - Kr)), -Kb / (2.0 * (1.0 - Kr))};

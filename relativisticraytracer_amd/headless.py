@@ -8,7 +8,8 @@
            [--supersample 2 --adaptive [T]]
            [--dof APERTURE [--focus Z|hole] [--dof-samples K]]
            [--exposure EV | --auto-exposure [KEY]] [--exposure-speed UP DOWN] [--exposure-range MIN MAX] [--exposure-percentiles LOW HIGH]
-           [--y4m x.y4m [--y4m-chroma 420|444] [--y4m-range limited|full] [--y4m-depth 8|10]]
+           [--y4m x.y4m [--y4m-chroma 420|444] [--y4m-range limited|full] [--y4m-depth 8|10]
+                   [--y4m-transfer sdr|pq [--hdr-white NITS] [--hdr-peak NITS] [--hdr-knee F]]]
     python -m torch.distributed.run --nproc-per-node 8 -m relativisticraytracer_amd.headless ...
 
 Per frame k = 1..N it does what `main()` does while recording: advance the fixed 1/24 s clock
@@ -172,6 +173,14 @@ def build_parser():
     ap.add_argument("--y4m-depth", default=None, metavar="8|10",
                     help="with --y4m: bits per sample (default 8).  8 converts the finished RGBA8 frame, in every mode; 10 converts the "
                          "frame's linear HDR (the whole-frame HDR path of --exposure): one GPU only, not with --glow")
+    ap.add_argument("--y4m-transfer", default=None, metavar="sdr|pq",
+                    help="with --y4m: sdr (default) tone-maps into BT.709; pq (with --y4m-depth 10) writes HDR10 -- the linear HDR as "
+                         "absolute light behind SMPTE ST 2084, BT.2020 -- and PATH.hdr10.json with MaxCLL / MaxFALL and the encoder options")
+    ap.add_argument("--hdr-white", type=float, default=None, metavar="NITS", help="with --y4m-transfer pq: the luminance of H = 1 (default 203)")
+    ap.add_argument("--hdr-peak", type=float, default=None, metavar="NITS",
+                    help="with --y4m-transfer pq: the highlight shoulder's asymptote and the mastering display's peak (default 1000)")
+    ap.add_argument("--hdr-knee", type=float, default=None, metavar="F",
+                    help="with --y4m-transfer pq: the shoulder starts at F * peak (default 0.5; 1: a hard clip)")
     ap.add_argument("--init-timeout", type=float, default=300.0,
                     help="several ranks: seconds the process-group bring-up may take before the run exits non-zero with "
                          "the tracebacks of all threads, instead of hanging")
@@ -248,8 +257,24 @@ def check_args(ap, args, world):
 
 def check_y4m(ap, args, world):
     """--y4m's refusals (rrt_headless.cpp words them alike); leaves args.y4m_format: (chroma, range, bits) or None"""
-    args.y4m_format = None
+    args.y4m_format = args.y4m_hdr10 = None
+    if args.y4m_transfer not in (None, "sdr", "pq"):
+        ap.error("--y4m-transfer sdr | pq")
+    pq = args.y4m_transfer == "pq"
+    if not pq and (args.hdr_white is not None or args.hdr_peak is not None or args.hdr_knee is not None):
+        ap.error("--hdr-white / --hdr-peak / --hdr-knee need --y4m-transfer pq")
+    if pq and (args.y4m is None or args.y4m_depth != "10"):
+        ap.error("--y4m-transfer pq needs --y4m PATH and --y4m-depth 10")
+    for v in (args.hdr_white, args.hdr_peak):
+        if v is not None and not (math.isfinite(v) and 0.0 < v <= 10000.0):
+            ap.error("--hdr-white / --hdr-peak NITS: in (0, 10000]")
+    if args.hdr_knee is not None and not 0.0 <= args.hdr_knee <= 1.0:
+        ap.error("--hdr-knee F: in [0, 1]")
+    if pq:
+        args.y4m_hdr10 = (args.hdr_white, args.hdr_peak, args.hdr_knee)
     if args.y4m is None:
+        if args.y4m_transfer is not None:
+            ap.error("--y4m-transfer needs --y4m PATH")
         if args.y4m_chroma is not None or args.y4m_range is not None or args.y4m_depth is not None:
             ap.error("--y4m-chroma / --y4m-range / --y4m-depth need --y4m PATH")
         return
@@ -581,14 +606,20 @@ def main(argv=None):
     y4m = None
     if rank == 0 and args.y4m_format is not None:
         fmt = rrt.YuvFormat(*args.y4m_format)
-        y4m = sinks.Y4MSink(args.y4m, w, h, args.fps, fmt)
+        hdr10 = rrt.Hdr10Settings(*args.y4m_hdr10) if args.y4m_hdr10 is not None else None
+        y4m = sinks.Y4MSink(args.y4m, w, h, args.fps, fmt, hdr10)
+        if hdr10 is not None:        # the film's light levels: reset once, metered by every frame's launch, copied back after the last
+            light = torch.empty(rrt.yuv_hdr10_light_bytes(), dtype=torch.uint8, device=dev)
+            rrt.launch_yuv_hdr10_light_reset(light)
         yuv_dev = torch.empty(y4m.frame_bytes, dtype=torch.uint8, device=dev)
         yuv_host = torch.empty(y4m.frame_bytes, dtype=torch.uint8, pin_memory=True)
         trace(f"y4m sink {args.y4m}: {fmt.info()}, {y4m.frame_bytes} bytes per frame")
 
     def deliver(frame):
         if y4m:         # on the current stream, behind the frame
-            if r.y4m10:
+            if y4m.hdr10 is not None:
+                rrt.launch_yuv_hdr10_from_hdr(yuv_dev, r.hdr, w, h, fmt, y4m.hdr10, light)
+            elif r.y4m10:
                 rrt.launch_yuv_from_hdr(yuv_dev, r.hdr, w, h, fmt)
             else:
                 rrt.launch_yuv_from_rgba8(yuv_dev, frame, w, h, fmt)
@@ -621,7 +652,7 @@ def main(argv=None):
         if sink:
             sink.close()
         if y4m:
-            y4m.close()
+            y4m.close(rrt.yuv_hdr10_light_levels(light.cpu().numpy(), w, h) if y4m.hdr10 is not None else None)
         print(json.dumps({"frames": args.frames, "width": w, "height": h, "n_gpus": world, "seconds": round(dt, 4),
                           "fps": round(args.frames / dt, 3), "Mrays_per_s": round(args.frames * w * h / dt / 1e6, 3), **r.summary(nwin.summary())}),
               flush=True)

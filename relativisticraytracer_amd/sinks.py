@@ -78,10 +78,14 @@ class FFmpegSink:
 class Y4MSink:
     """A YUV4MPEG2 stream (include/rrt_yuv.h, step 5): the header on open, then `FRAME` and one frame's planes per write -- the
     bytes launch_yuv_from_rgba8 / launch_yuv_from_hdr (or their *_host forms) produce, top-down already.  BT.709; a Y4M header
-    carries no matrix tag, so a player is told: `mpv --vf=format=colormatrix=bt.709 x.y4m`."""
+    carries no matrix tag, so a player is told: `mpv --vf=format=colormatrix=bt.709 x.y4m`.
 
-    def __init__(self, path, width, height, fps=24, fmt=None):
+    With hdr10 (an Hdr10Settings) the frames are launch_yuv_hdr10_from_hdr's -- PQ, BT.2020 -- and the header cannot say so either:
+    close(levels) writes `<path>.hdr10.json` (step G's sidecar) with the settings, MaxCLL / MaxFALL and the encoder options."""
+
+    def __init__(self, path, width, height, fps=24, fmt=None, hdr10=None):
         from . import yuv
+        self.path, self.hdr10 = path, hdr10
         self.fmt = fmt if fmt is not None else yuv.YuvFormat()
         self.frame_bytes = yuv.yuv_frame_bytes(self.fmt, width, height)
         header = yuv.y4m_header(self.fmt, width, height, int(fps), 1)
@@ -97,8 +101,15 @@ class Y4MSink:
         self.f.write(data)
         self.frames += 1
 
-    def close(self):
+    def close(self, levels=None):
+        """levels: yuv_hdr10_light_levels' dict of the film -- needed, and only used, with hdr10"""
+        if self.hdr10 is not None and levels is None:
+            raise ValueError("an HDR10 sink closes with the film's light levels (yuv_hdr10_light_levels)")
         self.f.close()
+        if self.hdr10 is not None:
+            from . import yuv
+            with open(self.path + ".hdr10.json", "wb") as f:
+                f.write(yuv.y4m_hdr10_sidecar(self.hdr10, levels))
 
 
 def open_sink(spec, width, height, fps=24):
