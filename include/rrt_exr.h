@@ -1,0 +1,106 @@
+/*
+ * rrt_exr.h -- C ABI of librrt_exr.so: the frame's linear HDR packed as the scanline chunks of an OpenEXR file, half or float, on
+ * the device, so that only the bytes the file holds cross PCIe.  A library of its own, as librrt_yuv.so is: it needs nothing of the
+ * ray marcher and include/rrt.h is unchanged by it; only rrt.h's status values are shared.  It does not deflate and links no zlib:
+ * with ZIPS or ZIP it leaves the chunk filtered, and the caller is left with nothing but deflate.
+ *
+ * Conventions (rrt.h's): every function returns an rrt_status; `d_*` pointers are DEVICE pointers owned by the caller; `stream` is a
+ * hipStream_t passed as void* (NULL = the null stream).  A launch is ONE kernel on the caller's stream: no allocation, no memset,
+ * no synchronisation, no scratch -- it can be captured into a hipGraph.
+ *
+ * THE DEFINITION ("EXR output")
+ *
+ *   The source is the frame's float4 HDR plane, width x height, rows bottom-up (rrt_debug_outputs.d_hdr, the `lin` output of the
+ *   _ss launches, what rrt_launch_exposure leaves).  The file is top-down: EXR row y is source row height - 1 - y.  Alpha is not
+ *   stored.
+ *
+ *   1. Samples.  FLOAT: the binary32 bits as they are (NaN and inf included: the caller chose a format that holds them).
+ *      HALF: binary32 -> binary16, round to nearest even, subnormal halves kept, in integer arithmetic (exr_half_bits,
+ *      csrc/rrt_exr_core.h).  NaN becomes +0.  A finite magnitude that rounds above half_max, and +-inf, become +-half_max: the
+ *      file never holds an inf or a NaN that this conversion made.  -0 stays -0.
+ *   2. Chunks.  NONE and ZIPS: 1 scanline per chunk; ZIP: 16, the last chunk may be short.  Chunk i starts at row y = i * lines.
+ *      A scanline is the width samples of B, then of G, then of R (the file's alphabetical channel order), little-endian; a
+ *      chunk's raw bytes are its scanlines top-down, n = rows * width * 3 * (2 | 4) bytes, always even.
+ *   3. Filter (ZIPS and ZIP only; the format's reversible step in front of deflate), per chunk:
+ *        tmp[0 .. n/2) = raw bytes at even offsets, tmp[n/2 .. n) = raw bytes at odd offsets;
+ *        out[0] = tmp[0], out[j] = (tmp[j] - tmp[j-1] + 128) mod 256 for j >= 1 -- across the seam at n/2 too.
+ *      Every output byte depends on two samples only.
+ *   4. Payload: the chunks' bytes (raw with NONE, filtered otherwise) one behind the other, chunk i at `offset` of rrt_exr_chunk;
+ *      width * height * 3 * (2 | 4) bytes in all.
+ *   5. File (single part, scanline, version 2, no flags): rrt_exr_header's bytes; the offset table, one uint64 per chunk (the
+ *      chunk's position from the start of the file); the chunks, each int32 y, int32 size, data.  With ZIPS / ZIP the data is
+ *      the deflated (zlib stream) filtered chunk, or -- when that is not smaller than n -- the RAW chunk (rrt_exr_unfilter_host
+ *      gives it back), which a reader recognises by size == n.
+ */
+#ifndef RRT_EXR_H
+#define RRT_EXR_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "rrt.h"     /* rrt_status */
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define RRT_EXR_HALF 1           /* the file format's own pixel-type codes */
+#define RRT_EXR_FLOAT 2
+#define RRT_EXR_NONE 0           /* ... and its compression codes */
+#define RRT_EXR_ZIPS 2
+#define RRT_EXR_ZIP 3
+
+typedef struct rrt_exr_format {
+    uint32_t struct_size;    /* sizeof(rrt_exr_format): rrt_exr_format_default sets it; any other value is RRT_ERR_INVALID_ARGUMENT */
+    int32_t type;            /* RRT_EXR_HALF | RRT_EXR_FLOAT */
+    int32_t compression;     /* RRT_EXR_NONE | RRT_EXR_ZIPS | RRT_EXR_ZIP */
+    float half_max;          /* HALF: the largest magnitude written; a finite positive half (65504, the largest, by default) */
+} rrt_exr_format;
+
+/* HALF, ZIP, 65504 */
+int rrt_exr_format_default(rrt_exr_format* fmt);
+
+/* Step 4's byte count and the number of chunks.  Host only; n_chunks may be NULL.  RRT_ERR_INVALID_ARGUMENT (every function below
+ * refuses these the same way, with a message in rrt_exr_last_error): NULL pointers, a struct_size, type or compression outside the
+ * lists, a half_max that is not a finite positive half, width or height < 1, a chunk of 2^31 bytes or more. */
+int rrt_exr_frame_bytes(const rrt_exr_format* fmt, int width, int height, size_t* payload_bytes, int32_t* n_chunks);
+
+/* Chunk i: its first row y, its byte offset in the payload, its (raw = filtered) size.  Host only; i outside [0, n_chunks) is
+ * refused. */
+int rrt_exr_chunk(const rrt_exr_format* fmt, int width, int height, int i, int32_t* y, size_t* offset, size_t* bytes);
+
+/* How a launch of this size is laid out, for tests and tools.  `address_bits`: the bitwise OR of the payload's and the HDR plane's
+ * addresses (only the low four bits are looked at; 0 stands for 16-byte aligned buffers).
+ *   out[0] threads per workgroup, out[1] x out[2] its shape (x: along a row, y: rows),
+ *   out[3] pixels of a row one thread packs: 8 on the wide path; 1 on the narrow path, where a thread packs ONE sample of a pixel,
+ *   out[4] x out[5] the grid, out[6] 1 wide | 0 narrow, out[7] the passes a workgroup makes over the rows: ceil(height /
+ *   (out[2] * out[5])), > 1 where the grid's row dimension wraps.
+ * Wide: width % 8 == 0 and both buffers 16-byte aligned, so that every row of every channel starts on 16 bytes.  Host only. */
+int rrt_exr_launch_geometry(const rrt_exr_format* fmt, int width, int height, size_t address_bits, int32_t out[8]);
+
+/* Steps 1-4 on the device: d_payload receives rrt_exr_frame_bytes bytes.  Refused before any device call, as above and: d_hdr not
+ * 4-byte aligned, an output that overlaps the input.  A d_payload or d_hdr that is not 16-byte aligned is served by the narrow path. */
+int rrt_launch_exr_from_hdr(void* d_payload, const float* d_hdr, int width, int height, const rrt_exr_format* fmt, void* stream);
+
+/* The same bytes on HOST memory, from the source the kernels run (no device is touched) */
+int rrt_exr_from_hdr_host(void* payload, const float* hdr, int width, int height, const rrt_exr_format* fmt);
+
+/* Step 3's inverse: the raw bytes of a filtered chunk of n bytes (n even, 2 <= n < 2^31; raw and filtered must not overlap).  For
+ * the chunks that deflate does not shrink.  Host only. */
+int rrt_exr_unfilter_host(void* raw, const void* filtered, size_t n);
+
+/* Step 5's header into buf[0 .. cap): magic, version, the eight required attributes (channels, compression, dataWindow,
+ * displayWindow, lineOrder = INCREASING_Y, pixelAspectRatio = 1, screenWindowCenter = (0, 0), screenWindowWidth = 1), then
+ * chromaticities (BT.709 primaries, D65 white), framesPerSecond (the rational fps_num / fps_den) and software, and the closing 0.
+ * *len is its length; the offset table starts there.  Host only.  Also refused: fps_num or fps_den <= 0, a cap too small (nothing
+ * is written then). */
+int rrt_exr_header(const rrt_exr_format* fmt, int width, int height, int fps_num, int fps_den, void* buf, size_t cap, size_t* len);
+
+/* Why the last call on this thread returned RRT_ERR_INVALID_ARGUMENT, or the HIP runtime's message behind RRT_ERR_HIP ("" after a
+ * call that succeeded) */
+const char* rrt_exr_last_error(void);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* RRT_EXR_H */

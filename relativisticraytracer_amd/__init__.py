@@ -920,3 +920,10 @@ from .yuv import (Hdr10Settings, launch_yuv_hdr10_from_hdr, launch_yuv_hdr10_lig
                   yuv_hdr10_coefficients, yuv_hdr10_from_hdr_host, yuv_hdr10_light_bytes, yuv_hdr10_light_levels)
 
 __all__ += yuv.__all__
+
+# OpenEXR chunk packing for scene-linear output: a library of its own (include/rrt_exr.h, librrt_exr.so), loaded on first use
+from . import exr  # noqa: E402
+from .exr import (ExrFormat, exr_chunks, exr_frame_bytes, exr_from_hdr_host, exr_header, exr_launch_geometry,  # noqa: E402,F401
+                  exr_unfilter_host, launch_exr_from_hdr)
+
+__all__ += exr.__all__

@@ -21,6 +21,10 @@ YUV_LIB = os.path.join(LIBDIR, "librrt_yuv.so")         # include/rrt_yuv.h: the
 YUV_SRC = os.path.join(CSRC, "rrt_yuv.hip")
 YUV_HEADERS = [os.path.join(CSRC, "rrt_yuv_core.h"), os.path.join(CSRC, "rrt_hdr10_core.h"), os.path.join(CSRC, "rrt_math.h"), os.path.join(PKG, "..", "include", "rrt_yuv.h"),
                os.path.join(PKG, "..", "include", "rrt.h")]
+EXR_LIB = os.path.join(LIBDIR, "librrt_exr.so")         # include/rrt_exr.h: the OpenEXR chunk packing, a library of its own
+EXR_SRC = os.path.join(CSRC, "rrt_exr.hip")
+EXR_HEADERS = [os.path.join(CSRC, "rrt_exr_core.h"), os.path.join(CSRC, "rrt_math.h"), os.path.join(PKG, "..", "include", "rrt_exr.h"),
+               os.path.join(PKG, "..", "include", "rrt.h")]
 COMPAT_SRC = os.path.join(CSRC, "rrt_compat.cpp")     # launch_raymarch under the reference's mangled name (host only, g++)
 CAMERA_SRC = os.path.join(CSRC, "rrt_camera.cpp")     # camera basis / path playback (host only, g++)
 CHOOSER_SRC = os.path.join(CSRC, "rrt_path_chooser.cpp")   # per-window path choice of the animation drivers (host only, g++)
@@ -51,10 +55,11 @@ def hipcc_path():
 
 
 def is_stale():
-    if not os.path.exists(LIB) or not os.path.exists(TEST_LIB) or not os.path.exists(YUV_LIB):
+    libs = (LIB, TEST_LIB, YUV_LIB, EXR_LIB)
+    if not all(os.path.exists(f) for f in libs):
         return True
-    t = min(os.path.getmtime(LIB), os.path.getmtime(TEST_LIB), os.path.getmtime(YUV_LIB))
-    return any(os.path.getmtime(f) > t for f in SOURCES + HEADERS + [YUV_SRC] + YUV_HEADERS + [os.path.abspath(__file__)])
+    t = min(os.path.getmtime(f) for f in libs)
+    return any(os.path.getmtime(f) > t for f in SOURCES + HEADERS + [YUV_SRC] + YUV_HEADERS + [EXR_SRC] + EXR_HEADERS + [os.path.abspath(__file__)])
 
 
 def host_objects(outdir):
@@ -71,8 +76,8 @@ def build_lib(force=False, extra_flags=(), verbose=False):
     """librrt_hip.so (the product) and librrt_hip_test.so (+ test hooks), from the same sources.  Each hipcc compile runs in a
     directory of its own (lib/_obj_product, lib/_obj_test: flags that write fixed-name side files -- -save-temps -- cannot make
     the two collide); they run side by side, except under -save-temps, where they run one after the other.  BOTH libraries are
-    always built, so that is_stale() has one meaning -- and so is librrt_yuv.so, one translation unit with the same flags,
-    compiled next to them."""
+    always built, so that is_stale() has one meaning -- and so are librrt_yuv.so and librrt_exr.so, one translation unit
+    each with the same flags, compiled next to them."""
     if not force and not is_stale():
         return LIB
     os.makedirs(LIBDIR, exist_ok=True)
@@ -92,15 +97,16 @@ def build_lib(force=False, extra_flags=(), verbose=False):
             subprocess.run(cmd, check=True, cwd=wd)
         else:
             jobs.append((cmd, subprocess.Popen(cmd, cwd=wd)))
-    wd = os.path.join(LIBDIR, "_obj_yuv")
-    os.makedirs(wd, exist_ok=True)
-    cmd = [hipcc_path()] + HIPCC_FLAGS + list(extra_flags) + [YUV_SRC, "-o", YUV_LIB]
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    if sequential:
-        subprocess.run(cmd, check=True, cwd=wd)
-    else:
-        jobs.append((cmd, subprocess.Popen(cmd, cwd=wd)))
+    for tag, src, out in (("yuv", YUV_SRC, YUV_LIB), ("exr", EXR_SRC, EXR_LIB)):
+        wd = os.path.join(LIBDIR, "_obj_" + tag)
+        os.makedirs(wd, exist_ok=True)
+        cmd = [hipcc_path()] + HIPCC_FLAGS + list(extra_flags) + [src, "-o", out]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        if sequential:
+            subprocess.run(cmd, check=True, cwd=wd)
+        else:
+            jobs.append((cmd, subprocess.Popen(cmd, cwd=wd)))
     for cmd, pr in jobs:
         if pr.wait() != 0:
             raise subprocess.CalledProcessError(pr.returncode, cmd)
@@ -143,13 +149,14 @@ HEADLESS_BIN = os.path.join(LIBDIR, "rrt_headless")
 
 
 def build_headless(force=False):
-    """The C++ headless driver (host code only: g++, links librrt_hip.so, librrt_yuv.so, the HIP runtime and RCCL)."""
+    """The C++ headless driver (host code only: g++, links librrt_hip.so, librrt_yuv.so, librrt_exr.so, the HIP runtime, RCCL and
+    zlib, which deflates --exr's chunks)."""
     build_lib()
     if not force and os.path.exists(HEADLESS_BIN) and os.path.getmtime(HEADLESS_BIN) > max(
-            os.path.getmtime(HEADLESS_SRC), os.path.getmtime(LIB), os.path.getmtime(YUV_LIB)):
+            os.path.getmtime(HEADLESS_SRC), os.path.getmtime(LIB), os.path.getmtime(YUV_LIB), os.path.getmtime(EXR_LIB)):
         return HEADLESS_BIN
     cmd = ["g++", "-std=c++17", "-O2", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", HEADLESS_SRC,
-           "-L" + LIBDIR, "-lrrt_hip", "-lrrt_yuv", "-L/opt/rocm/lib", "-lamdhip64", "-lrccl", "-Wl,-rpath," + LIBDIR + ":/opt/rocm/lib",
+           "-L" + LIBDIR, "-lrrt_hip", "-lrrt_yuv", "-lrrt_exr", "-L/opt/rocm/lib", "-lamdhip64", "-lrccl", "-lz", "-pthread", "-Wl,-rpath," + LIBDIR + ":/opt/rocm/lib",
            "-o", HEADLESS_BIN]
     subprocess.run(cmd, check=True)
     return HEADLESS_BIN

@@ -46,6 +46,11 @@
 //                [--y4m-transfer sdr|pq [--hdr-white NITS] [--hdr-peak NITS] [--hdr-knee F]]   (pq, with --y4m-depth 10: HDR10 -- the
 //                                              linear HDR as absolute light behind SMPTE ST 2084, BT.2020 -- and x.y4m.hdr10.json with
 //                                              MaxCLL / MaxFALL, metered on the device, and the encoder options)
+//                [--exr f.%04d.exr [--exr-type half|float] [--exr-compression none|zips|zip] [--exr-level 1..9]]   (also, or only,
+//                                              one scene-linear OpenEXR file per frame (include/rrt_exr.h): the frame's linear HDR --
+//                                              after the exposure, before any tone map -- as B, G, R scanlines packed on device 0 and
+//                                              deflated with zlib on a small thread pool.  The pattern holds one frame field; a plain
+//                                              name serves --frames 1.  The whole-frame HDR path: one GPU only, not with --glow)
 //
 // Noise tables: the reference's simTime runs without bound (main.cpp:515) and a table's size grows with the times
 // it covers, so each device keeps ONE table over a window of the clock that fits --noise-table-gib (default 2;
@@ -66,7 +71,9 @@
 
 #include <dlfcn.h>
 #include <fcntl.h>
+#include <sched.h>
 #include <unistd.h>
+#include <zlib.h>
 
 #include <atomic>
 #include <chrono>
@@ -85,6 +92,7 @@
 
 #include "../../include/rrt.h"
 #include "../../include/rrt_yuv.h"
+#include "../../include/rrt_exr.h"
 
 namespace {
 
@@ -304,6 +312,10 @@ struct Options {               // what the command line sets (parse_options), th
     bool hdr_opts = false;               // one of --hdr-white / --hdr-peak / --hdr-knee was given
     bool hdr_nits_ok = true, hdr_knee_ok = true;
     rrt_yuv_hdr10 hdr10;
+    std::string exr_path;                // --exr PATTERN: one OpenEXR file per frame (include/rrt_exr.h)
+    bool exr_opts = false;               // one of --exr-type / --exr-compression / --exr-level was given
+    int exr_type = 0, exr_compression = 2, exr_level = 4;      // the lists' indices (-1: not on the list); the deflate level (0: not 1 ... 9)
+    rrt_exr_format exr;
 
     // derived: w x h is the frame that is sharded and written (with --stereo the composite of two ew x eh eyes)
     bool pano = false, use_stereo = false, collective = false, auto_exposure = false;
@@ -316,8 +328,12 @@ struct Options {               // what the command line sets (parse_options), th
     bool y4m_pq = false;                 // ... as HDR10 (rrt_launch_yuv_hdr10_from_hdr), with the sidecar
     bool hdr_frame = false;              // --glow, --exposure or y4m10: the frame renders into the slot's HDR buffer
     size_t yuv_bytes = 0;
+    bool use_exr = false;                // the EXR frames are the HDR itself: the whole-frame HDR path
+    size_t exr_bytes = 0;
+    int32_t exr_chunks = 0;
 
     Options() {
+        rrt_exr_format_default(&exr);
         rrt_yuv_format_default(&yuv);
         rrt_yuv_hdr10_default(&hdr10);
         rrt_glow_default(&glow);
@@ -408,6 +424,11 @@ int parse_options(int argc, char** argv, Options& o) {
             if (!parse_float(next(), o.hdr10.knee, true) || !(o.hdr10.knee >= 0.0f && o.hdr10.knee <= 1.0f)) o.hdr_knee_ok = false;
             o.hdr_opts = true;
         }
+        // --exr's values are checked in check_options, behind "need --exr PATTERN", as headless.py checks them
+        else if (a == "--exr" && more) o.exr_path = next();
+        else if (a == "--exr-type") { o.exr_type = one_of(next(), {"half", "float"}); o.exr_opts = true; }
+        else if (a == "--exr-compression") { o.exr_compression = one_of(next(), {"none", "zips", "zip"}); o.exr_opts = true; }
+        else if (a == "--exr-level") { o.exr_level = one_of(next(), {"1", "2", "3", "4", "5", "6", "7", "8", "9"}) + 1; o.exr_opts = true; }
         else if (a == "--all-effects") o.all_fx = 1; else if (a == "--fast") o.arith = RRT_ARITH_FAST;
         else if (a == "--path-window") val(o.path_window);
         else if (a == "--path-policy" && more) {
@@ -513,6 +534,28 @@ std::string absolute_path(const std::string& path) {
     return (std::filesystem::current_path() / path).lexically_normal().string();
 }
 
+// A file name pattern's frame fields, `%d` or `%0Nd` (sinks.py: frame_fields, frame_name).  frame_name fills every field with k;
+// with count it only counts them.
+std::string frame_name(const std::string& pattern, int k, int* count = nullptr) {
+    std::string out;
+    int fields = 0;
+    for (size_t i = 0; i < pattern.size();) {
+        size_t j = i + 1;
+        int width = 0;
+        if (pattern[i] == '%' && j < pattern.size() && pattern[j] == '0' && j + 1 < pattern.size() && isdigit((unsigned char)pattern[j + 1]))
+            for (++j; j < pattern.size() && isdigit((unsigned char)pattern[j]) && width < 100; ++j) width = width * 10 + (pattern[j] - '0');
+        if (pattern[i] == '%' && j < pattern.size() && pattern[j] == 'd') {
+            char text[128];
+            snprintf(text, sizeof(text), "%0*d", width, k);
+            out += text;
+            ++fields;
+            i = j + 1;
+        } else out += pattern[i++];
+    }
+    if (count) *count = fields;
+    return out;
+}
+
 // Every refusal that depends on more than one option, in the order that decides which message a command line gets, and the values
 // derived from the options.  Host arithmetic and the library's host-only queries: no device is touched before this has returned.
 int check_options(Options& o) {
@@ -615,7 +658,31 @@ int check_options(Options& o) {
         if (!o.out_path.empty() && absolute_path(o.y4m_path) == absolute_path(o.out_path)) return refuse("usage: --y4m and --out name the same file");
         if (rrt_yuv_frame_bytes(&o.yuv, o.w, o.h, &o.yuv_bytes, nullptr) != RRT_OK) return refuse("bad arguments");
     }
-    o.hdr_frame = o.use_glow || o.use_exposure || o.y4m10;
+    // EXR output (headless.py words these alike): the frame's linear HDR, whole, on one device
+    o.use_exr = !o.exr_path.empty();
+    if (!o.use_exr && o.exr_opts) return refuse("usage: --exr-type / --exr-compression / --exr-level need --exr PATTERN");
+    if (o.use_exr) {
+        if (o.exr_type < 0) return refuse("usage: --exr-type half | float");
+        if (o.exr_compression < 0) return refuse("usage: --exr-compression none | zips | zip");
+        if (o.exr_level < 1) return refuse("usage: --exr-level 1 ... 9");
+        if (o.use_glow) return refuse("usage: --exr reads the frame's linear HDR and the glow tone-maps H + glow without storing it: not with --glow");
+        if (o.collective) return refuse("usage: --exr: one GPU only (--gpus 1)");
+        int fields = 0;
+        frame_name(o.exr_path, 0, &fields);
+        if (fields > 1) return refuse("usage: --exr PATTERN: one frame field (%%d or %%0Nd)");
+        if (fields == 0 && o.frames > 1)
+            return refuse("usage: --exr PATTERN needs a frame field (%%04d) when --frames > 1: the frames would overwrite one another");
+        for (int k = 1; k <= (o.frames > 1 ? o.frames : 1); ++k) {
+            const std::string name = absolute_path(frame_name(o.exr_path, k));
+            if (!o.out_path.empty() && name == absolute_path(o.out_path)) return refuse("usage: --exr and --out name the same file");
+            if (o.y4m && name == absolute_path(o.y4m_path)) return refuse("usage: --exr and --y4m name the same file");
+        }
+        const int types[] = {RRT_EXR_HALF, RRT_EXR_FLOAT}, compressions[] = {RRT_EXR_NONE, RRT_EXR_ZIPS, RRT_EXR_ZIP};
+        o.exr.type = types[o.exr_type];
+        o.exr.compression = compressions[o.exr_compression];
+        if (rrt_exr_frame_bytes(&o.exr, o.w, o.h, &o.exr_bytes, &o.exr_chunks) != RRT_OK) return refuse("bad arguments");
+    }
+    o.hdr_frame = o.use_glow || o.use_exposure || o.y4m10 || o.use_exr;
     // a supersampled launch is always the single kernel in the static order (include/rrt.h): no pool, no path choice, no tile order
     if (o.supersample > 1 || o.motion > 1 || o.hdr_frame || o.pano || o.use_stereo || o.use_dof) {
         o.workspace_gib = 0; o.path_window = -1; o.tile_order = 0;
@@ -631,7 +698,9 @@ struct Slots {                 // what device 0 owns per frame slot: gathered sh
     void* host[kMaxSlots] = {};
     void* yuv[kMaxSlots] = {};             // --y4m: each slot's packed planes on device 0, and the pinned host copy for the sink
     void* yuv_host[kMaxSlots] = {};
-    void* hdr[kMaxSlots] = {};             // --glow / --exposure / --y4m-depth 10: each slot's linear frame; the glow's scratch
+    void* exr[kMaxSlots] = {};             // --exr: each slot's packed chunks on device 0, and the pinned host copy the files are made of
+    void* exr_host[kMaxSlots] = {};
+    void* hdr[kMaxSlots] = {};             // --glow / --exposure / --y4m-depth 10 / --exr: each slot's linear frame; the glow's scratch
     void* glow_scratch[kMaxSlots] = {};
     void* ad_scratch[kMaxSlots] = {};      // --adaptive: each slot's list, and the pinned word its count is copied to
     void* ad_count[kMaxSlots] = {};
@@ -755,6 +824,7 @@ int create_slots(Slots& R, const Options& o, bool sink, hipStream_t stream0) {
         HIPCHK(hipMalloc(&R.frame[s], R.frame_bytes));
         if (o.hdr_frame) HIPCHK(hipMalloc(&R.hdr[s], R.frame_bytes * sizeof(float)));
         if (o.y4m) { HIPCHK(hipMalloc(&R.yuv[s], o.yuv_bytes)); HIPCHK(hipHostMalloc(&R.yuv_host[s], o.yuv_bytes, hipHostMallocDefault)); }
+        if (o.use_exr) { HIPCHK(hipMalloc(&R.exr[s], o.exr_bytes)); HIPCHK(hipHostMalloc(&R.exr_host[s], o.exr_bytes, hipHostMallocDefault)); }
         if (o.use_glow) HIPCHK(hipMalloc(&R.glow_scratch[s], o.glow_bytes));
         if (o.use_adaptive) { HIPCHK(hipMalloc(&R.ad_scratch[s], R.ad_bytes)); HIPCHK(hipHostMalloc(&R.ad_count[s], 4, hipHostMallocDefault)); }
         HIPCHK(hipEventCreateWithFlags(&R.done[s], hipEventDisableTiming));
@@ -772,10 +842,80 @@ void destroy_slots(Slots& R, int slots) {
         (void)hipFree(R.gathered[s]); (void)hipFree(R.frame[s]); (void)hipFree(R.hdr[s]); (void)hipFree(R.glow_scratch[s]);
         (void)hipFree(R.ad_scratch[s]); (void)hipFree(R.yuv[s]);
         if (R.yuv_host[s]) (void)hipHostFree(R.yuv_host[s]);
+        (void)hipFree(R.exr[s]);
+        if (R.exr_host[s]) (void)hipHostFree(R.exr_host[s]);
         if (R.ad_count[s]) (void)hipHostFree(R.ad_count[s]);
         if (R.host[s]) (void)hipHostFree(R.host[s]);
         (void)hipEventDestroy(R.done[s]);
     }
+}
+
+// ---- EXR files (include/rrt_exr.h, step 5; sinks.py: EXRSink)
+
+// One frame's file from its payload in host memory: every chunk deflated (zlib, `level`) on up to `threads` threads -- the chunks are
+// independent --, a chunk that deflate does not shrink stored raw, un-filtered; header, offset table, chunks into NAME.tmp, renamed.
+int write_exr_file(const std::string& name, const uint8_t* payload, const Options& o, int threads) {
+    struct Piece { int32_t y = 0; size_t offset = 0, bytes = 0; std::vector<uint8_t> data; };
+    std::vector<Piece> pieces((size_t)o.exr_chunks);
+    for (int i = 0; i < o.exr_chunks; ++i)
+        if (rrt_exr_chunk(&o.exr, o.w, o.h, i, &pieces[i].y, &pieces[i].offset, &pieces[i].bytes) != RRT_OK) return 1;
+    if (o.exr.compression != RRT_EXR_NONE) {
+        std::atomic<int> next{0}, failed{0};
+        auto work = [&]() {
+            for (int i; (i = next.fetch_add(1)) < o.exr_chunks;) {
+                Piece& c = pieces[i];
+                uLongf n = compressBound((uLong)c.bytes);
+                c.data.resize(n);
+                if (compress2(c.data.data(), &n, payload + c.offset, (uLong)c.bytes, o.exr_level) != Z_OK) { failed.store(1); return; }
+                if (n < c.bytes) { c.data.resize(n); continue; }
+                c.data.resize(c.bytes);
+                if (rrt_exr_unfilter_host(c.data.data(), payload + c.offset, c.bytes) != RRT_OK) { failed.store(1); return; }
+            }
+        };
+        const int n_threads = threads < o.exr_chunks ? threads : o.exr_chunks;
+        std::vector<std::thread> pool;
+        for (int t = 1; t < n_threads; ++t) pool.emplace_back(work);
+        work();
+        for (std::thread& t : pool) t.join();
+        if (failed.load()) { fprintf(stderr, "rrt_headless: exr: deflate failed\n"); return 1; }
+    }
+    uint8_t header[1024];
+    size_t header_bytes = 0;
+    if (rrt_exr_header(&o.exr, o.w, o.h, o.fps, 1, header, sizeof(header), &header_bytes) != RRT_OK) {
+        fprintf(stderr, "rrt_headless: exr header: %s\n", rrt_exr_last_error());
+        return 1;
+    }
+    const std::string tmp = name + ".tmp";
+    FILE* f = fopen(tmp.c_str(), "wb");
+    if (!f) { perror("fopen"); return 1; }
+    bool ok = fwrite(header, 1, header_bytes, f) == header_bytes;
+    uint64_t at = header_bytes + 8 * (uint64_t)o.exr_chunks;
+    auto put = [&](uint64_t v, int n) {     // little-endian
+        uint8_t b[8];
+        for (int k = 0; k < n; ++k) b[k] = (uint8_t)(v >> (8 * k));
+        ok = ok && fwrite(b, 1, (size_t)n, f) == (size_t)n;
+    };
+    for (const Piece& c : pieces) {
+        put(at, 8);
+        at += 8 + (o.exr.compression != RRT_EXR_NONE ? c.data.size() : c.bytes);
+    }
+    for (const Piece& c : pieces) {
+        const bool raw = o.exr.compression == RRT_EXR_NONE;
+        const size_t n = raw ? c.bytes : c.data.size();
+        put((uint32_t)c.y, 4);
+        put((uint32_t)n, 4);
+        ok = ok && fwrite(raw ? payload + c.offset : c.data.data(), 1, n, f) == n;
+    }
+    ok = (fclose(f) == 0) && ok;
+    if (!ok || rename(tmp.c_str(), name.c_str()) != 0) { fprintf(stderr, "rrt_headless: exr: cannot write %s\n", name.c_str()); return 1; }
+    return 0;
+}
+
+// the deflate pool's size: the CPUs this process may run on, 16 at the most
+int deflate_threads() {
+    cpu_set_t set;
+    const int n = sched_getaffinity(0, sizeof(set), &set) == 0 ? CPU_COUNT(&set) : 1;
+    return n < 1 ? 1 : (n > 16 ? 16 : n);
 }
 
 // ---- the frame loop
@@ -918,9 +1058,9 @@ int launch_frame(Device& D, int slot, int k, const FrameView& v, const Options& 
     if (o.hdr_frame) {     // one device (check_options): the slot's HDR through launch_sampled, then the post passes on the same stream
         float* lin = static_cast<float*>(R.hdr[slot]);
         rc = o.use_adaptive ? launch_adaptive(lin) : launch_sampled(false, lin);
-        if (rc == RRT_OK && o.use_exposure) {     // the bytes -- and, in front of the glow or a 10-bit Y4M conversion, the scaled HDR in place
+        if (rc == RRT_OK && o.use_exposure) {     // the bytes -- and, in front of the glow, a 10-bit Y4M conversion or an EXR file, the scaled HDR in place
             if (o.auto_exposure) HIPCHK(hipStreamWaitEvent(st, R.exposed, 0));
-            rc = rrt_launch_exposure(o.use_glow ? nullptr : dst, o.use_glow || o.y4m10 ? lin : nullptr, lin, w, h, &o.exposure, R.exposure_scratch,
+            rc = rrt_launch_exposure(o.use_glow ? nullptr : dst, o.use_glow || o.y4m10 || o.use_exr ? lin : nullptr, lin, w, h, &o.exposure, R.exposure_scratch,
                                      R.exposure_bytes, st);
             if (o.auto_exposure) HIPCHK(hipEventRecord(R.exposed, st));
         }
@@ -1111,6 +1251,7 @@ int main(int argc, char** argv) {
     // fault is reported at the frame it belongs to, and the watchdog sees frames complete)
     Totals totals;
     int delivered = 0;
+    const int exr_threads = deflate_threads();
     auto deliver = [&](int slot) -> int {
         HIPCHK(hipEventSynchronize(R.done[slot]));
         trace("frame complete", ++delivered);
@@ -1126,6 +1267,7 @@ int main(int argc, char** argv) {
         if (f && fwrite(R.host[slot], 1, R.frame_bytes, f) != R.frame_bytes) fprintf(stderr, "Warning: Frame write incomplete\n");
         if (fy && (fwrite("FRAME\n", 1, 6, fy) != 6 || fwrite(R.yuv_host[slot], 1, o.yuv_bytes, fy) != o.yuv_bytes))
             fprintf(stderr, "Warning: Frame write incomplete\n");
+        if (o.use_exr && write_exr_file(frame_name(o.exr_path, delivered), static_cast<const uint8_t*>(R.exr_host[slot]), o, exr_threads)) return 1;
         return 0;
     };
 
@@ -1156,6 +1298,11 @@ int main(int argc, char** argv) {
                          : rrt_launch_yuv_from_rgba8(R.yuv[slot], R.frame[slot], o.w, o.h, &o.yuv, dev[0].stream[slot]);
             if (rc != RRT_OK) { fprintf(stderr, "rrt_headless: y4m: %s (%s)\n", rrt_status_string(rc), rrt_yuv_last_error()); return 1; }
             HIPCHK(hipMemcpyAsync(R.yuv_host[slot], R.yuv[slot], o.yuv_bytes, hipMemcpyDeviceToHost, dev[0].stream[slot]));
+        }
+        if (o.use_exr) {    // the chunks of the frame's HDR as the last pass left it, then their copy; the file is made when the frame is delivered
+            rc = rrt_launch_exr_from_hdr(R.exr[slot], static_cast<const float*>(R.hdr[slot]), o.w, o.h, &o.exr, dev[0].stream[slot]);
+            if (rc != RRT_OK) { fprintf(stderr, "rrt_headless: exr: %s (%s)\n", rrt_status_string(rc), rrt_exr_last_error()); return 1; }
+            HIPCHK(hipMemcpyAsync(R.exr_host[slot], R.exr[slot], o.exr_bytes, hipMemcpyDeviceToHost, dev[0].stream[slot]));
         }
         HIPCHK(hipEventRecord(R.done[slot], dev[0].stream[slot]));
     }

@@ -10,6 +10,7 @@
            [--exposure EV | --auto-exposure [KEY]] [--exposure-speed UP DOWN] [--exposure-range MIN MAX] [--exposure-percentiles LOW HIGH]
            [--y4m x.y4m [--y4m-chroma 420|444] [--y4m-range limited|full] [--y4m-depth 8|10]
                    [--y4m-transfer sdr|pq [--hdr-white NITS] [--hdr-peak NITS] [--hdr-knee F]]]
+           [--exr f.%04d.exr [--exr-type half|float] [--exr-compression none|zips|zip] [--exr-level 1..9]]
     python -m torch.distributed.run --nproc-per-node 8 -m relativisticraytracer_amd.headless ...
 
 Per frame k = 1..N it does what `main()` does while recording: advance the fixed 1/24 s clock
@@ -181,6 +182,16 @@ def build_parser():
                     help="with --y4m-transfer pq: the highlight shoulder's asymptote and the mastering display's peak (default 1000)")
     ap.add_argument("--hdr-knee", type=float, default=None, metavar="F",
                     help="with --y4m-transfer pq: the shoulder starts at F * peak (default 0.5; 1: a hard clip)")
+    ap.add_argument("--exr", default=None, metavar="PATTERN",
+                    help="also (or only) write every frame as a scene-linear OpenEXR file (include/rrt_exr.h): the frame's linear HDR -- "
+                         "after --exposure / --auto-exposure, before any tone map -- as B, G, R scanlines packed on the device.  "
+                         "PATTERN holds one frame field (f.%%04d.exr); a plain name serves --frames 1.  The whole-frame HDR path of "
+                         "--exposure: one GPU only, not with --glow")
+    # checked in check_exr, not by argparse's `choices` or `type`: both drivers word their refusals alike
+    ap.add_argument("--exr-type", default=None, metavar="half|float", help="with --exr: the samples (default half, clamped to +-65504)")
+    ap.add_argument("--exr-compression", default=None, metavar="none|zips|zip",
+                    help="with --exr: none, or deflate of 1 (zips) or 16 (zip, the default) scanlines per chunk")
+    ap.add_argument("--exr-level", default=None, metavar="1..9", help="with --exr: the deflate level (default 4)")
     ap.add_argument("--init-timeout", type=float, default=300.0,
                     help="several ranks: seconds the process-group bring-up may take before the run exits non-zero with "
                          "the tracebacks of all threads, instead of hanging")
@@ -252,6 +263,7 @@ def check_args(ap, args, world):
             ap.error("--dof-samples: with --motion-blur M > 1 the lens samples are the shutter's sub-frames (K = M)")
         dof_k = args.motion_blur if args.motion_blur > 1 else (args.dof_samples or 8)
     check_y4m(ap, args, world)
+    check_exr(ap, args, world)
     return pano, use_exposure, dof_k
 
 
@@ -293,6 +305,35 @@ def check_y4m(ap, args, world):
     if args.out is not None and os.path.abspath(args.y4m) == os.path.abspath(args.out):
         ap.error("--y4m and --out name the same file")
     args.y4m_format = (int(args.y4m_chroma or 420), args.y4m_range or "limited", bits)
+
+
+def check_exr(ap, args, world):
+    """--exr's refusals (rrt_headless.cpp words them alike); leaves args.exr_format: (type, compression, level) or None"""
+    from relativisticraytracer_amd.sinks import frame_fields, frame_name
+    args.exr_format = None
+    if args.exr is None:
+        if args.exr_type is not None or args.exr_compression is not None or args.exr_level is not None:
+            ap.error("--exr-type / --exr-compression / --exr-level need --exr PATTERN")
+        return
+    if args.exr_type not in (None, "half", "float"):
+        ap.error("--exr-type half | float")
+    if args.exr_compression not in (None, "none", "zips", "zip"):
+        ap.error("--exr-compression none | zips | zip")
+    if args.exr_level not in (None,) + tuple("123456789"):
+        ap.error("--exr-level 1 ... 9")
+    if args.glow is not None:
+        ap.error("--exr reads the frame's linear HDR and the glow tone-maps H + glow without storing it: not with --glow")
+    if world > 1:
+        ap.error("--exr: one GPU only (WORLD_SIZE > 1)")
+    fields = frame_fields(args.exr)
+    if fields > 1:
+        ap.error("--exr PATTERN: one frame field (%d or %0Nd)")
+    if fields == 0 and args.frames > 1:
+        ap.error("--exr PATTERN needs a frame field (%04d) when --frames > 1: the frames would overwrite one another")
+    for other, flag in ((args.out, "--out"), (args.y4m, "--y4m")):
+        if other is not None and any(os.path.abspath(frame_name(args.exr, k)) == os.path.abspath(other) for k in range(1, max(args.frames, 1) + 1)):
+            ap.error(f"--exr and {flag} name the same file")
+    args.exr_format = (args.exr_type or "half", args.exr_compression or "zip", int(args.exr_level or 4))
 
 
 def build_settings(ap, args, pano, use_exposure):
@@ -357,7 +398,8 @@ class Renderer:
         self.ss, self.mb = ss, mb = args.supersample, args.motion_blur
         self.sampled = proj is not None or mb > 1 or ss > 1 or stereo is not None or dof_k > 0      # launch_sampled's kinds
         self.y4m10 = args.y4m_format is not None and args.y4m_format[2] == 10     # the Y4M frames come from the HDR: its whole-frame path
-        self.post = glow is not None or exposure is not None or self.y4m10
+        self.exr = args.exr_format is not None        # the EXR frames are the HDR itself: the same path
+        self.post = glow is not None or exposure is not None or self.y4m10 or self.exr
         # supersampled, blurred, glowed, panorama, stereo: single kernel, static order, no pool
         single = self.sampled or self.post
         # sample m looks through lens point bitrev_K(m): the spiral's radius grows with its index, the shutter's times with m
@@ -453,8 +495,8 @@ class Renderer:
 
     def render_post(self):
         """the frame through launch_sampled into self.hdr, then the post passes into self.frame (bottom-up rows, not the tile layout):
-        the exposure writes the bytes -- and, in front of the glow or a 10-bit Y4M conversion, the scaled HDR in place -- and the
-        glow its own"""
+        the exposure writes the bytes -- and, in front of the glow, a 10-bit Y4M conversion or an EXR file, the scaled HDR in place --
+        and the glow its own"""
         glow, hdr, frame = self.glow, self.hdr, self.frame
         self.prms[0].noise_table = self.table
         if self.adaptive is not None:
@@ -462,7 +504,7 @@ class Renderer:
         else:
             self.launch_sampled(frame, self.prms[0], hdr=hdr)
         if self.exposure is not None:
-            rrt.launch_exposure(None if glow is not None else frame, hdr if glow is not None or self.y4m10 else None, hdr, self.w, self.h,
+            rrt.launch_exposure(None if glow is not None else frame, hdr if glow is not None or self.y4m10 or self.exr else None, hdr, self.w, self.h,
                                 self.exposure, self.exposure_scratch)
         if glow is not None:
             rrt.launch_glow(frame, hdr, self.w, self.h, glow, self.glow_scratch)
@@ -615,7 +657,20 @@ def main(argv=None):
         yuv_host = torch.empty(y4m.frame_bytes, dtype=torch.uint8, pin_memory=True)
         trace(f"y4m sink {args.y4m}: {fmt.info()}, {y4m.frame_bytes} bytes per frame")
 
+    # --exr: rank 0 packs the HDR render_post left into the file's chunks on the device, copies them out and deflates them
+    exr = None
+    if rank == 0 and args.exr_format is not None:
+        exr_fmt = rrt.ExrFormat(*args.exr_format[:2])
+        exr = sinks.EXRSink(args.exr, w, h, args.fps, exr_fmt, level=args.exr_format[2])
+        exr_dev = torch.empty(exr.frame_bytes, dtype=torch.uint8, device=dev)
+        exr_host = torch.empty(exr.frame_bytes, dtype=torch.uint8, pin_memory=True)
+        trace(f"exr sink {args.exr}: {exr_fmt.info()}, {exr.frame_bytes} bytes per frame, {exr.threads} deflate threads")
+
     def deliver(frame):
+        if exr:         # on the current stream, behind the frame's last pass
+            rrt.launch_exr_from_hdr(exr_dev, r.hdr, w, h, exr_fmt)
+            exr_host.copy_(exr_dev, non_blocking=False)
+            exr.write(exr_host.numpy())
         if y4m:         # on the current stream, behind the frame
             if y4m.hdr10 is not None:
                 rrt.launch_yuv_hdr10_from_hdr(yuv_dev, r.hdr, w, h, fmt, y4m.hdr10, light)
@@ -636,10 +691,10 @@ def main(argv=None):
         dog.arm(args.frame_timeout + (args.init_timeout if k == 1 else 0.0), f"frame {k}")    # frame 1 brings the communicator's channels up
         r.set_frame(k, nwin.table_id)
         frame = r.render_post() if r.post else (r.render_adaptive() if r.adaptive is not None else fs.step())
-        if (sink or y4m) and frame is not None:
+        if (sink or y4m or exr) and frame is not None:
             deliver(frame)
     for frame in fs.drain():                # the frames still in flight, in order
-        if sink or y4m:
+        if sink or y4m or exr:
             deliver(frame)
     torch.cuda.synchronize()
     trace("frames done")
@@ -651,6 +706,8 @@ def main(argv=None):
     if rank == 0:
         if sink:
             sink.close()
+        if exr:
+            exr.close()
         if y4m:
             y4m.close(rrt.yuv_hdr10_light_levels(light.cpu().numpy(), w, h) if y4m.hdr10 is not None else None)
         print(json.dumps({"frames": args.frames, "width": w, "height": h, "n_gpus": world, "seconds": round(dt, 4),

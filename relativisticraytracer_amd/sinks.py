@@ -4,8 +4,12 @@ src/main.cpp:29-124, which pipes glReadPixels() output into ffmpeg).
 Frames arrive as (h, w, 4) uint8 arrays in the kernel's native order: RGBA, bottom-up rows
 (raymarcher.cu:168) -- the same bytes glReadPixels hands the reference's recorder."""
 import os
+import re
 import shutil
+import struct
 import subprocess
+import zlib
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -110,6 +114,83 @@ class Y4MSink:
             from . import yuv
             with open(self.path + ".hdr10.json", "wb") as f:
                 f.write(yuv.y4m_hdr10_sidecar(self.hdr10, levels))
+
+
+_FRAME_FIELD = re.compile(r"%(0\d+)?d")
+
+
+def frame_fields(pattern):
+    """how many frame fields (`%d`, `%04d`, ...) a file name pattern holds"""
+    return len(_FRAME_FIELD.findall(pattern))
+
+
+def frame_name(pattern, k):
+    """the pattern with its frame fields filled with k (a plain name stays as it is)"""
+    return _FRAME_FIELD.sub(lambda m: m.group(0) % k, pattern)
+
+
+class EXRSink:
+    """One OpenEXR file per frame (include/rrt_exr.h, step 5): scene-linear B, G, R scanlines, half or float.  `write` takes one
+    frame's payload -- the bytes launch_exr_from_hdr (or exr_from_hdr_host) produce, chunk behind chunk, filtered already when the
+    format compresses -- and is left with nothing but deflate: every chunk through zlib at `level`, the chunks side by side on a
+    thread pool (zlib releases the GIL), and a chunk that deflate does not shrink stored raw, un-filtered, as the format asks.
+
+    `pattern` holds exactly one frame field, `%d` or `%0Nd`, filled with the frame's number (1, 2, ... in the order written, or
+    `index`); a plain name is accepted for a single frame.  A file is written as NAME.tmp and renamed when it is complete.
+    threads: the pool's size (default: min(16, the CPUs this process may run on)); 1 deflates in the caller's thread."""
+
+    def __init__(self, pattern, width, height, fps=24, fmt=None, level=4, threads=None):
+        from . import exr
+        self.exr = exr
+        if frame_fields(pattern) > 1:
+            raise ValueError(f"{pattern!r}: one frame field (%d or %0Nd), not {frame_fields(pattern)}")
+        if not 1 <= int(level) <= 9:
+            raise ValueError("level: 1 ... 9")
+        self.pattern, self.level = pattern, int(level)
+        self.fmt = fmt if fmt is not None else exr.ExrFormat()
+        self.frame_bytes = exr.exr_frame_bytes(self.fmt, width, height)
+        self.chunks = exr.exr_chunks(self.fmt, width, height)
+        self.header = exr.exr_header(self.fmt, width, height, int(fps), 1)
+        self.compressed = self.fmt.compression != exr.NONE
+        workers = int(threads) if threads is not None else min(16, len(os.sched_getaffinity(0)))
+        self.pool = ThreadPoolExecutor(workers) if self.compressed and workers > 1 and len(self.chunks) > 1 else None
+        self.width, self.height, self.frames, self.threads = width, height, 0, max(workers, 1)
+        self.stored_raw = 0          # chunks that deflate did not shrink, over all frames
+
+    def _chunk(self, piece):
+        z = zlib.compress(piece, self.level)
+        return z if len(z) < len(piece) else self.exr.exr_unfilter_host(piece).tobytes()
+
+    def write(self, payload, index=None):
+        data = memoryview(np.ascontiguousarray(payload)).cast("B")
+        if data.nbytes != self.frame_bytes:
+            raise ValueError(f"a {self.width}x{self.height} frame of this format is {self.frame_bytes} bytes, got {data.nbytes}")
+        k = self.frames + 1 if index is None else int(index)
+        if self.frames > 0 and frame_fields(self.pattern) == 0:
+            raise ValueError(f"{self.pattern!r} has no frame field: a second frame would overwrite the first")
+        pieces = [data[off:off + n] for _, off, n in self.chunks]
+        if self.compressed:
+            pieces = list(self.pool.map(self._chunk, pieces)) if self.pool is not None else [self._chunk(p) for p in pieces]
+            self.stored_raw += sum(len(p) == n for p, (_, _, n) in zip(pieces, self.chunks))
+        at, table = len(self.header) + 8 * len(pieces), []
+        for p in pieces:
+            table.append(at)
+            at += 8 + len(p)
+        name = frame_name(self.pattern, k)
+        with open(name + ".tmp", "wb") as f:
+            f.write(self.header)
+            f.write(struct.pack(f"<{len(table)}Q", *table))
+            for (y, _, _), p in zip(self.chunks, pieces):
+                f.write(struct.pack("<ii", y, len(p)))
+                f.write(p)
+        os.replace(name + ".tmp", name)
+        self.frames += 1
+        return name
+
+    def close(self):
+        if self.pool is not None:
+            self.pool.shutdown()
+            self.pool = None
 
 
 def open_sink(spec, width, height, fps=24):
