@@ -32,6 +32,35 @@
  *      the deflated (zlib stream) filtered chunk, or -- when that is not smaller than n -- the RAW chunk (rrt_exr_unfilter_host
  *      gives it back), which a reader recognises by size == n.
  */
+/*
+ * DATA LAYERS ("EXR data layers"): per-ray planes next to B, G, R, as further channels of the same scanlines
+ *
+ *   A layered frame is described by one rrt_exr_layers: the compression and half_max of rrt_exr_format, up to RRT_EXR_MAX_SOURCES
+ *   sources and up to RRT_EXR_MAX_CHANNELS channels.
+ *
+ *   A source is a device plane of width x height pixels, `words` (1, 3 or 4) 32-bit words per pixel, 4-byte aligned, of binary32
+ *   (RRT_EXR_SRC_F32) or int32 (RRT_EXR_SRC_I32) values.  bottom_up = 1: EXR row y is source row height - 1 - y (the HDR plane);
+ *   0: row y (rrt_debug_outputs' d_rad, d_pos, d_vel, d_steps, d_hit).
+ *
+ *   A channel is a name -- 1 to 31 bytes of [A-Za-z0-9_.], neither starting nor ending with '.' --, the stored type (RRT_EXR_UINT,
+ *   HALF or FLOAT: the file's codes), a source and a word of that source's pixel.  Channels arrive in strictly ascending strcmp
+ *   order (unsigned bytes): the order the file stores them, so "channel i" means one thing everywhere.  Unsorted or duplicate names
+ *   are refused, with the offending pair in rrt_exr_last_error.
+ *
+ *   1'. Samples (exr_layer_sample, csrc/rrt_exr_core.h):
+ *         F32 -> FLOAT  the bits as they are            I32 -> UINT   the value; a negative value becomes 0
+ *         F32 -> HALF   step 1's conversion             I32 -> FLOAT  (float)v, round to nearest even
+ *         F32 -> UINT   refused                         I32 -> HALF   (float)v, then step 1's conversion
+ *   2'. A scanline is the channels in order, each `width` samples of 2 (HALF) or 4 (FLOAT, UINT) bytes, little-endian; chunks of 1
+ *       or 16 scanlines as in step 2; a chunk's raw bytes are n = rows * width * (the sum of the channels' sample sizes).
+ *   3'. Step 3 as it is, byte-wise over the whole chunk.  With mixed sample sizes the predecessor of a channel's first sample in a
+ *       row is the LAST TWO BYTES of the previous channel's last sample, whatever its type (exr_layer_tail).
+ *   4', 5'. As steps 4 and 5; rrt_exr_layers_header writes rrt_exr_header's attributes in its order with the layers' channel list
+ *       (pLinear 0, samplings 1, 1).
+ *
+ *   The layer set {B, G, R} from one bottom-up 4-word F32 source, words 2, 1, 0, gives the payload, chunk table and header of
+ *   rrt_launch_exr_from_hdr, rrt_exr_from_hdr_host and rrt_exr_header byte for byte, in all six formats.
+ */
 #ifndef RRT_EXR_H
 #define RRT_EXR_H
 
@@ -95,6 +124,71 @@ int rrt_exr_unfilter_host(void* raw, const void* filtered, size_t n);
  * *len is its length; the offset table starts there.  Host only.  Also refused: fps_num or fps_den <= 0, a cap too small (nothing
  * is written then). */
 int rrt_exr_header(const rrt_exr_format* fmt, int width, int height, int fps_num, int fps_den, void* buf, size_t cap, size_t* len);
+
+/* ---- data layers (the second block comment above) ---- */
+
+#define RRT_EXR_UINT 0           /* the file format's third pixel type */
+#define RRT_EXR_SRC_F32 0        /* a source's words: binary32 ... */
+#define RRT_EXR_SRC_I32 1        /* ... or int32 */
+#define RRT_EXR_MAX_SOURCES 8
+#define RRT_EXR_MAX_CHANNELS 16
+
+typedef struct rrt_exr_source {
+    const void* d_data;      /* width * height * words 32-bit words; a DEVICE pointer for the launch, a host pointer for rrt_exr_layers_host */
+    int32_t words;           /* 32-bit words per pixel: 1 | 3 | 4 */
+    int32_t kind;            /* RRT_EXR_SRC_F32 | RRT_EXR_SRC_I32 */
+    int32_t bottom_up;       /* 1: EXR row y is source row height - 1 - y; 0: row y */
+    int32_t reserved;        /* 0 */
+} rrt_exr_source;
+
+typedef struct rrt_exr_channel {
+    char name[32];           /* NUL-terminated, 1 ... 31 bytes */
+    int32_t type;            /* RRT_EXR_UINT | RRT_EXR_HALF | RRT_EXR_FLOAT */
+    int32_t source;          /* an index into sources */
+    int32_t word;            /* < that source's words */
+    int32_t reserved;        /* 0 */
+} rrt_exr_channel;
+
+typedef struct rrt_exr_layers {
+    uint32_t struct_size;    /* sizeof(rrt_exr_layers): rrt_exr_layers_default sets it; any other value is RRT_ERR_INVALID_ARGUMENT */
+    int32_t compression;     /* RRT_EXR_NONE | RRT_EXR_ZIPS | RRT_EXR_ZIP */
+    float half_max;          /* as rrt_exr_format's */
+    int32_t n_sources;       /* 1 ... RRT_EXR_MAX_SOURCES */
+    int32_t n_channels;      /* 1 ... RRT_EXR_MAX_CHANNELS */
+    int32_t reserved;        /* 0 */
+    rrt_exr_source sources[RRT_EXR_MAX_SOURCES];
+    rrt_exr_channel channels[RRT_EXR_MAX_CHANNELS];
+} rrt_exr_layers;
+
+/* zero sources and channels, ZIP, 65504 */
+int rrt_exr_layers_default(rrt_exr_layers* layers);
+
+/* rrt_exr_frame_bytes and rrt_exr_chunk for a layered frame.  Host only; the sources' d_data are not looked at.  Refused like a
+ * format and: n_sources or n_channels outside their ranges, a source's words or kind outside the lists, a channel name that breaks
+ * the rule, names not strictly ascending, a type outside the list, a source or word out of range, an F32 source stored as UINT, a
+ * chunk of 2^31 bytes or more. */
+int rrt_exr_layers_frame_bytes(const rrt_exr_layers* layers, int width, int height, size_t* payload_bytes, int32_t* n_chunks);
+int rrt_exr_layers_chunk(const rrt_exr_layers* layers, int width, int height, int i, int32_t* y, size_t* offset, size_t* bytes);
+
+/* out[8] with the meanings of rrt_exr_launch_geometry; `address_bits`: the OR of the payload's and every source's address.
+ *   Narrow (out[6] = 0): a thread packs ONE sample; out[4] covers width * n_channels threads along a row.
+ *   Wide (out[6] = 1 | 2): width % 8 == 0, the payload and every source 16-byte aligned.  A thread packs 8 pixels of a row: it reads
+ *   each source once, in 16-byte loads, and stores 16 bytes per channel (HALF, raw), 2 x 16 (FLOAT / UINT, raw) or -- filtered --
+ *   one store into each half of the chunk, 8 bytes for HALF and 16 for FLOAT / UINT.  A channel's place in each half of a filtered
+ *   chunk is a multiple of 8 only: width x (half the sample bytes of the rows and channels in front).  So where a filtered layout
+ *   holds both a HALF and a 4-byte channel and width % 16 == 8, EVERY 4-byte channel is stored in 8-byte stores, two into each
+ *   half: out[6] = 2.  Every other wide layout (raw rows always) is 16-byte aligned throughout: out[6] = 1. */
+int rrt_exr_layers_launch_geometry(const rrt_exr_layers* layers, int width, int height, size_t address_bits, int32_t out[8]);
+
+/* Steps 1'-4' on the device: ONE kernel on `stream`, no allocation, memset, synchronisation or scratch.  Refused before any device
+ * call, as above and: NULL pointers, a source not 4-byte aligned, a payload that overlaps any source. */
+int rrt_launch_exr_layers(void* d_payload, const rrt_exr_layers* layers, int width, int height, void* stream);
+
+/* The same bytes on HOST memory (the sources' d_data are host pointers), from the source the kernels run; no device is touched */
+int rrt_exr_layers_host(void* payload, const rrt_exr_layers* layers, int width, int height);
+
+/* rrt_exr_header with the layers' channel list; cap 2048 always suffices */
+int rrt_exr_layers_header(const rrt_exr_layers* layers, int width, int height, int fps_num, int fps_den, void* buf, size_t cap, size_t* len);
 
 /* Why the last call on this thread returned RRT_ERR_INVALID_ARGUMENT, or the HIP runtime's message behind RRT_ERR_HIP ("" after a
  * call that succeeded) */

@@ -925,5 +925,7 @@ __all__ += yuv.__all__
 from . import exr  # noqa: E402
 from .exr import (ExrFormat, exr_chunks, exr_frame_bytes, exr_from_hdr_host, exr_header, exr_launch_geometry,  # noqa: E402,F401
                   exr_unfilter_host, launch_exr_from_hdr)
+from .exr import (ExrLayers, exr_layers_chunks, exr_layers_frame_bytes, exr_layers_header, exr_layers_host,  # noqa: E402,F401
+                  exr_layers_launch_geometry, launch_exr_layers)
 
 __all__ += exr.__all__

@@ -16,6 +16,9 @@
  *
  * The wide kernel converts to half with the hardware instruction (exr_convert); the narrow kernel and the host run exr_half_bits'
  * integer arithmetic, the definition.
+ *
+ * Data layers (rrt_launch_exr_layers) are a second pair, exr_layers_wide<FILTER> and exr_layers_narrow, further down: the same
+ * workgroup and grid, any channel list over any sources.  The kernels above are not routed through them.
  */
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
@@ -131,6 +134,110 @@ static __global__ __launch_bounds__(kExrBlockX * kExrBlockY) void exr_pack_narro
         exr_put_sample(payload, hdr, p, (int)y, c, x);
 }
 
+/* ---- data layers: any channel list over any sources (include/rrt_exr.h, the second block comment) --------------------------- */
+
+/* exr_layer_sample with the hardware converts: v_cvt_f32_i32 rounds to nearest even as the host's (float)v does */
+__device__ __forceinline__ uint32_t exr_layer_convert(int kind, int type, uint32_t u, uint32_t max_half) {
+    if (kind == RRT_EXR_SRC_I32) {
+        const int32_t v = (int32_t)u;
+        if (type == RRT_EXR_UINT) return v < 0 ? 0u : u;
+        u = __float_as_uint((float)v);
+    }
+    return type == RRT_EXR_HALF ? exr_convert<RRT_EXR_HALF>(__uint_as_float(u), max_half) : u;
+}
+
+/* A thread packs kExrWidePixels pixels of a row.  Source by source (a wave-uniform loop): 2 * words 16-byte loads, ONCE, then every
+ * channel that reads the source -- word, kind and type are wave-uniform, the registers are indexed by constants only -- converted,
+ * filtered and stored at the channel's own place in the scanline.  The filter's predecessor of a thread's first sample is one
+ * more 4-byte load per channel (exr_layer_pred_of): a word the left neighbour's 16-byte loads fetch anyway.  Launched only where
+ * the geometry says wide; p.store8 is its out[6] == 2. */
+template <bool FILTER>
+__global__ __launch_bounds__(kExrBlockX * kExrBlockY) void exr_layers_wide(uint8_t* __restrict__ payload, ExrLayersPlan p) {
+    constexpr int W = kExrWidePixels;
+    const uint32_t sx = blockIdx.x * kExrBlockX + threadIdx.x;
+    if (sx >= (uint32_t)(p.w / W)) return;
+    const int x0 = (int)sx * W;
+    const size_t w = (size_t)p.w;
+    for (uint32_t yy = blockIdx.y * kExrBlockY + threadIdx.y; yy < (uint32_t)p.h; yy += gridDim.y * kExrBlockY) {
+        const int y = (int)yy;
+        int y0 = 0, rows = 0;
+        size_t offset = 0;
+        if constexpr (FILTER) exr_layer_chunk_of(p, y, y0, rows, offset);
+        for (int s = 0; s < p.n_src; ++s) {
+            const int words = p.src_words[s], kind = p.src_kind[s];
+            const size_t row = (size_t)(p.src_bottom_up[s] ? p.h - 1 - y : y);
+            const uint4* ptr = reinterpret_cast<const uint4*>(p.src[s] + (row * w + (size_t)x0) * (size_t)words);
+            uint32_t r[4 * W];          /* the 8 pixels' words, as they lie */
+#pragma unroll
+            for (int j = 0; j < W; ++j) {
+                uint4 t = make_uint4(0u, 0u, 0u, 0u);
+                if (j < 2 * words) t = ptr[j];
+                r[4 * j] = t.x; r[4 * j + 1] = t.y; r[4 * j + 2] = t.z; r[4 * j + 3] = t.w;
+            }
+            for (int c = 0; c < p.n_ch; ++c) {
+                if (p.ch_src[c] != s) continue;
+                const int k = p.ch_word[c], type = p.ch_type[c];
+                uint32_t v[W];
+#pragma unroll
+                for (int i = 0; i < W; ++i) {
+                    uint32_t u;
+                    if (words == 4) u = k == 0 ? r[4 * i] : k == 1 ? r[4 * i + 1] : k == 2 ? r[4 * i + 2] : r[4 * i + 3];
+                    else if (words == 3) u = k == 0 ? r[3 * i] : k == 1 ? r[3 * i + 1] : r[3 * i + 2];
+                    else u = r[i];
+                    v[i] = exr_layer_convert(kind, type, u, p.max_half);
+                }
+                if constexpr (!FILTER) {
+                    uint8_t* dst = payload + ((size_t)y * (size_t)p.sum_bps + (size_t)p.ch_pre[c]) * w + (size_t)x0 * (size_t)exr_layer_bps(type);
+                    if (type == RRT_EXR_HALF) {
+                        *reinterpret_cast<uint4*>(dst) = make_uint4(v[0] | (v[1] << 16), v[2] | (v[3] << 16), v[4] | (v[5] << 16), v[6] | (v[7] << 16));
+                    } else {
+                        reinterpret_cast<uint4*>(dst)[0] = make_uint4(v[0], v[1], v[2], v[3]);
+                        reinterpret_cast<uint4*>(dst)[1] = make_uint4(v[4], v[5], v[6], v[7]);
+                    }
+                } else {
+                    int py, pc, px;
+                    bool first;
+                    exr_layer_pred_of(p, y, c, x0, y0, rows, py, pc, px, first);
+                    const uint32_t t = exr_layer_tail(p.ch_type[pc], exr_layer_convert(p.src_kind[p.ch_src[pc]], p.ch_type[pc], exr_layer_word(p, py, pc, px), p.max_half));
+                    const int bps = exr_layer_bps(type);
+                    uint32_t lo[W], hi[W];      /* a sample's bytes in each half: one (HALF) or two, in the low bits */
+#pragma unroll
+                    for (int i = 0; i < W; ++i)
+                        exr_layer_filter_sample(bps, v[i], i == 0 ? t : exr_layer_tail(type, v[i - 1]), i == 0 && first, lo[i], hi[i]);
+                    uint8_t* lo_dst = payload + offset + ((size_t)(y - y0) * (size_t)p.sum_bps + (size_t)p.ch_pre[c]) / 2u * w + (size_t)x0 * (size_t)(bps / 2);
+                    uint8_t* hi_dst = lo_dst + (size_t)rows * w * (size_t)p.sum_bps / 2u;      /* + n / 2 */
+                    if (type == RRT_EXR_HALF) {
+                        *reinterpret_cast<uint2*>(lo_dst) = make_uint2(lo[0] | (lo[1] << 8) | (lo[2] << 16) | (lo[3] << 24),
+                                                                       lo[4] | (lo[5] << 8) | (lo[6] << 16) | (lo[7] << 24));
+                        *reinterpret_cast<uint2*>(hi_dst) = make_uint2(hi[0] | (hi[1] << 8) | (hi[2] << 16) | (hi[3] << 24),
+                                                                       hi[4] | (hi[5] << 8) | (hi[6] << 16) | (hi[7] << 24));
+                    } else {
+                        const uint4 a = make_uint4(lo[0] | (lo[1] << 16), lo[2] | (lo[3] << 16), lo[4] | (lo[5] << 16), lo[6] | (lo[7] << 16));
+                        const uint4 b = make_uint4(hi[0] | (hi[1] << 16), hi[2] | (hi[3] << 16), hi[4] | (hi[5] << 16), hi[6] | (hi[7] << 16));
+                        if (p.store8) {         /* this channel's place in a half may be 8 past a multiple of 16 */
+                            reinterpret_cast<uint2*>(lo_dst)[0] = make_uint2(a.x, a.y);
+                            reinterpret_cast<uint2*>(lo_dst)[1] = make_uint2(a.z, a.w);
+                            reinterpret_cast<uint2*>(hi_dst)[0] = make_uint2(b.x, b.y);
+                            reinterpret_cast<uint2*>(hi_dst)[1] = make_uint2(b.z, b.w);
+                        } else {
+                            *reinterpret_cast<uint4*>(lo_dst) = a;
+                            *reinterpret_cast<uint4*>(hi_dst) = b;
+                        }
+                    }
+                }
+            }
+        }
+    }
+}
+
+static __global__ __launch_bounds__(kExrBlockX * kExrBlockY) void exr_layers_narrow(uint8_t* payload, ExrLayersPlan p) {
+    const uint32_t u = blockIdx.x * kExrBlockX + threadIdx.x;         /* width * n_channels < 2^31: a row of samples is less than a chunk */
+    if (u >= (uint32_t)p.n_ch * (uint32_t)p.w) return;
+    const int c = (int)(u / (uint32_t)p.w), x = (int)(u - (uint32_t)c * (uint32_t)p.w);
+    for (uint32_t y = blockIdx.y * kExrBlockY + threadIdx.y; y < (uint32_t)p.h; y += gridDim.y * kExrBlockY)
+        exr_layer_put_sample(payload, p, (int)y, c, x);
+}
+
 /* ---- C ABI ----------------------------------------------------------------------------------------------------------------- */
 
 #define RRT_EXR_EXPORT extern "C" __attribute__((visibility("default")))
@@ -213,6 +320,79 @@ RRT_EXR_EXPORT int rrt_exr_unfilter_host(void* raw, const void* filtered, size_t
 
 RRT_EXR_EXPORT int rrt_exr_header(const rrt_exr_format* fmt, int width, int height, int fps_num, int fps_den, void* buf, size_t cap, size_t* len) {
     return exr_header(fmt, width, height, fps_num, fps_den, buf, cap, len);
+}
+
+RRT_EXR_EXPORT int rrt_exr_layers_default(rrt_exr_layers* layers) {
+    g_exr_err[0] = 0;
+    if (!layers) return exr_refuse("layers is NULL");
+    memset(layers, 0, sizeof(*layers));
+    layers->struct_size = sizeof(rrt_exr_layers);
+    layers->compression = RRT_EXR_ZIP;
+    layers->half_max = 65504.0f;
+    return RRT_OK;
+}
+
+RRT_EXR_EXPORT int rrt_exr_layers_frame_bytes(const rrt_exr_layers* layers, int width, int height, size_t* payload_bytes, int32_t* n_chunks) {
+    ExrLayersPlan p;
+    const int rc = exr_layers_plan(layers, width, height, p);
+    if (rc != RRT_OK) return rc;
+    if (!payload_bytes) return exr_refuse("payload_bytes is NULL");
+    *payload_bytes = (size_t)exr_layers_bytes(p);
+    if (n_chunks) *n_chunks = p.n_chunks;
+    return RRT_OK;
+}
+
+RRT_EXR_EXPORT int rrt_exr_layers_chunk(const rrt_exr_layers* layers, int width, int height, int i, int32_t* y, size_t* offset, size_t* bytes) {
+    ExrLayersPlan p;
+    const int rc = exr_layers_plan(layers, width, height, p);
+    if (rc != RRT_OK) return rc;
+    if (!y || !offset || !bytes) return exr_refuse("y, offset or bytes is NULL");
+    if (i < 0 || i >= p.n_chunks) return exr_refuse("i: a chunk in [0, n_chunks)");
+    int y0, rows;
+    exr_layer_chunk_of(p, i * p.lines, y0, rows, *offset);
+    *y = y0;
+    *bytes = (size_t)rows * (size_t)p.w * (size_t)p.sum_bps;
+    return RRT_OK;
+}
+
+RRT_EXR_EXPORT int rrt_exr_layers_launch_geometry(const rrt_exr_layers* layers, int width, int height, size_t address_bits, int32_t out[8]) {
+    ExrLayersPlan p;
+    const int rc = exr_layers_plan(layers, width, height, p);
+    if (rc != RRT_OK) return rc;
+    if (!out) return exr_refuse("out is NULL");
+    exr_layers_geometry(p, address_bits, out);
+    return RRT_OK;
+}
+
+RRT_EXR_EXPORT int rrt_launch_exr_layers(void* d_payload, const rrt_exr_layers* layers, int width, int height, void* stream) {
+    ExrLayersPlan p;
+    int rc = exr_layers_plan(layers, width, height, p);
+    if (rc != RRT_OK) return rc;
+    size_t bits;
+    rc = exr_layers_buffers(d_payload, p, bits);
+    if (rc != RRT_OK) return rc;
+    int32_t g[8];
+    exr_layers_geometry(p, bits, g);
+    const dim3 grid((uint32_t)g[4], (uint32_t)g[5]), block(kExrBlockX, kExrBlockY);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    uint8_t* dst = static_cast<uint8_t*>(d_payload);
+    if (!g[6]) hipLaunchKernelGGL(exr_layers_narrow, grid, block, 0, st, dst, p);
+    else if (p.compression == RRT_EXR_NONE) hipLaunchKernelGGL((exr_layers_wide<false>), grid, block, 0, st, dst, p);
+    else hipLaunchKernelGGL((exr_layers_wide<true>), grid, block, 0, st, dst, p);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        snprintf(g_exr_err, sizeof(g_exr_err), "exr_layers: %s", hipGetErrorString(e));
+        return RRT_ERR_HIP;
+    }
+    return RRT_OK;
+}
+
+RRT_EXR_EXPORT int rrt_exr_layers_host(void* payload, const rrt_exr_layers* layers, int width, int height) {
+    return exr_layers_host(payload, layers, width, height);
+}
+
+RRT_EXR_EXPORT int rrt_exr_layers_header(const rrt_exr_layers* layers, int width, int height, int fps_num, int fps_den, void* buf, size_t cap, size_t* len) {
+    return exr_layers_header(layers, width, height, fps_num, fps_den, buf, cap, len);
 }
 
 RRT_EXR_EXPORT const char* rrt_exr_last_error(void) { return g_exr_err; }

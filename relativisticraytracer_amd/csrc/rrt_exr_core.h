@@ -6,6 +6,10 @@
  * A chunk's samples are numbered s = (row_in_chunk * 3 + channel) * width + x, channel 0 = B, 1 = G, 2 = R: the order of its raw
  * bytes.  exr_put_sample packs ONE sample -- the narrow path, at any size and alignment; the wide kernel of rrt_exr.hip calls the
  * same exr_sample / exr_filter_sample with vector loads and stores.
+ *
+ * The second half of the file is the same for data layers (any channel list over any sources: exr_layer_*, exr_layers_*), and
+ * tests/exr/exr_layers_exerciser.cpp runs it.  The B, G, R functions above are not expressed through it: the identity between the
+ * two is a test (tests/test_exr_layers_host.py), and the dedicated kernels keep their constants.
  */
 #ifndef RRT_EXR_CORE_H
 #define RRT_EXR_CORE_H
@@ -286,6 +290,283 @@ static inline int exr_header(const rrt_exr_format* fmt, int w, int h, int fps_nu
     o.attribute("software", "string", (int32_t)(sizeof(kExrSoftware) - 1));
     o.bytes(kExrSoftware, sizeof(kExrSoftware) - 1);
     o.u8(0);                                            /* end of the header */
+    if (o.at > sizeof(tmp) || o.at > cap) return exr_refuse("cap is smaller than the header");
+    memcpy(buf, tmp, o.at);
+    *len = o.at;
+    return RRT_OK;
+}
+
+/* ==== data layers (include/rrt_exr.h, the second block comment): any channel list over any sources ========================== */
+
+/* What a layers launch needs, checked and computed once on the host (exr_layers_plan) and passed by value.  Channel c's samples lie
+ * ch_pre[c] * w bytes into each raw scanline: ch_pre is the sum of the sample sizes of the channels in front of it. */
+struct ExrLayersPlan {
+    int32_t w, h;
+    int32_t compression, lines, n_chunks;
+    int32_t n_src, n_ch;
+    int32_t sum_bps;                                  /* bytes of one pixel over all channels: even */
+    int32_t store8;                                   /* the wide path stores filtered 4-byte channels 8 bytes at a time (rrt_exr_layers_launch_geometry) */
+    uint32_t max_half;
+    const uint32_t* src[RRT_EXR_MAX_SOURCES];
+    int32_t src_words[RRT_EXR_MAX_SOURCES], src_kind[RRT_EXR_MAX_SOURCES], src_bottom_up[RRT_EXR_MAX_SOURCES];
+    int32_t ch_type[RRT_EXR_MAX_CHANNELS], ch_src[RRT_EXR_MAX_CHANNELS], ch_word[RRT_EXR_MAX_CHANNELS], ch_pre[RRT_EXR_MAX_CHANNELS];
+};
+
+RRT_FN int exr_layer_bps(int type) { return type == RRT_EXR_HALF ? 2 : 4; }
+
+/* Step 1': the stored bits of one source word u.  F32 -> UINT never arrives here: exr_layers_plan refuses it. */
+RRT_FN uint32_t exr_layer_sample(int kind, int type, uint32_t u, uint32_t max_half) {
+    if (kind == RRT_EXR_SRC_I32) {
+        const int32_t v = (int32_t)u;
+        if (type == RRT_EXR_UINT) return v < 0 ? 0u : u;
+        u = exr_float_bits((float)v);                 /* round to nearest even */
+    }
+    return type == RRT_EXR_HALF ? exr_half_bits(u, max_half) : u;
+}
+
+/* the last two bytes of a stored sample: what step 3 subtracts from the sample behind it, whatever either's type */
+RRT_FN uint32_t exr_layer_tail(int type, uint32_t v) { return type == RRT_EXR_HALF ? v & 0xffffu : v >> 16; }
+
+/* the source word behind channel c of the pixel at EXR row y, column x */
+RRT_FN uint32_t exr_layer_word(const ExrLayersPlan& p, int y, int c, int x) {
+    const int s = p.ch_src[c];
+    const size_t row = (size_t)(p.src_bottom_up[s] ? p.h - 1 - y : y);
+    return p.src[s][(row * (size_t)p.w + (size_t)x) * (size_t)p.src_words[s] + (size_t)p.ch_word[c]];
+}
+
+/* ... and its stored sample */
+RRT_FN uint32_t exr_layer_load(const ExrLayersPlan& p, int y, int c, int x) {
+    return exr_layer_sample(p.src_kind[p.ch_src[c]], p.ch_type[c], exr_layer_word(p, y, c, x), p.max_half);
+}
+
+/* the chunk that holds row y, as exr_chunk_of */
+RRT_FN void exr_layer_chunk_of(const ExrLayersPlan& p, int y, int& y0, int& rows, size_t& offset) {
+    y0 = y - y % p.lines;
+    rows = p.h - y0 < p.lines ? p.h - y0 : p.lines;
+    offset = (size_t)y0 * (size_t)p.w * (size_t)p.sum_bps;
+}
+
+/* exr_filter_sample for any pair of types: v is a sample of `bps` bytes, t the TAIL of its predecessor (t & 255 the last byte at
+ * an even offset, t >> 8 the last at an odd one).  `first`: v is the chunk's sample 0 and t the tail of its LAST sample.  lo: the
+ * sample's bytes in the chunk's first half, one (2-byte samples) or two, the earlier in bits 0-7; hi: those in the second half. */
+RRT_FN void exr_layer_filter_sample(int bps, uint32_t v, uint32_t t, bool first, uint32_t& lo, uint32_t& hi) {
+    const uint32_t v0 = v & 255u, v1 = (v >> 8) & 255u, te = t & 255u, to = (t >> 8) & 255u;
+    lo = (first ? v0 : v0 - te + 128u) & 255u;
+    hi = (v1 - (first ? te : to) + 128u) & 255u;
+    if (bps == 4) {
+        const uint32_t v2 = (v >> 16) & 255u, v3 = v >> 24;
+        lo |= ((v2 - v0 + 128u) & 255u) << 8;
+        hi |= ((v3 - v1 + 128u) & 255u) << 8;
+    }
+}
+
+/* exr_load_pred for any channel list -- where the predecessor of sample (y, c, x) in its chunk's order lies: the sample to the
+ * left; at a row's start the previous channel's last sample; for channel 0 the last channel's of the row above; for the chunk's
+ * sample 0, its last sample (first = true) */
+RRT_FN void exr_layer_pred_of(const ExrLayersPlan& p, int y, int c, int x, int y0, int rows, int& py, int& pc, int& px, bool& first) {
+    first = false;
+    py = y;
+    pc = c;
+    px = x - 1;
+    if (x == 0) {
+        px = p.w - 1;
+        pc = c - 1;
+        if (c == 0) {
+            pc = p.n_ch - 1;
+            py = y - 1;
+            if (y == y0) { first = true; py = y0 + rows - 1; }
+        }
+    }
+}
+
+RRT_FN uint32_t exr_layer_pred_tail(const ExrLayersPlan& p, int y, int c, int x, int y0, int rows, bool& first) {
+    int py, pc, px;
+    exr_layer_pred_of(p, y, c, x, y0, rows, py, pc, px, first);
+    return exr_layer_tail(p.ch_type[pc], exr_layer_load(p, py, pc, px));
+}
+
+/* One sample, one byte per store: the narrow path and the host conversion */
+RRT_FN void exr_layer_put_sample(uint8_t* payload, const ExrLayersPlan& p, int y, int c, int x) {
+    const uint32_t v = exr_layer_load(p, y, c, x);
+    const int bps = exr_layer_bps(p.ch_type[c]);
+    if (p.compression == RRT_EXR_NONE) {
+        uint8_t* dst = payload + ((size_t)y * (size_t)p.sum_bps + (size_t)p.ch_pre[c]) * (size_t)p.w + (size_t)x * (size_t)bps;
+        for (int b = 0; b < bps; ++b) dst[b] = (uint8_t)(v >> (8 * b));
+        return;
+    }
+    int y0, rows;
+    size_t offset;
+    exr_layer_chunk_of(p, y, y0, rows, offset);
+    bool first;
+    const uint32_t t = exr_layer_pred_tail(p, y, c, x, y0, rows, first);
+    uint32_t lo, hi;
+    exr_layer_filter_sample(bps, v, t, first, lo, hi);
+    const size_t per = (size_t)bps / 2u;                                      /* bytes of the sample in each half */
+    uint8_t* a = payload + offset + ((size_t)(y - y0) * (size_t)p.sum_bps + (size_t)p.ch_pre[c]) / 2u * (size_t)p.w + (size_t)x * per;
+    uint8_t* b = a + (size_t)rows * (size_t)p.w * (size_t)p.sum_bps / 2u;     /* + n / 2 */
+    a[0] = (uint8_t)lo;
+    b[0] = (uint8_t)hi;
+    if (per == 2) { a[1] = (uint8_t)(lo >> 8); b[1] = (uint8_t)(hi >> 8); }
+}
+
+/* ---- host only ---- */
+
+static inline bool exr_layer_name_ok(const char* name) {
+    size_t n = 0;
+    while (n < 32 && name[n]) ++n;
+    if (n < 1 || n > 31 || name[0] == '.' || name[n - 1] == '.') return false;
+    for (size_t i = 0; i < n; ++i) {
+        const char ch = name[i];
+        if (!((ch >= 'A' && ch <= 'Z') || (ch >= 'a' && ch <= 'z') || (ch >= '0' && ch <= '9') || ch == '_' || ch == '.')) return false;
+    }
+    return true;
+}
+
+/* the checks every layers function makes (the sources' addresses apart) and the plan */
+static inline int exr_layers_plan(const rrt_exr_layers* L, int w, int h, ExrLayersPlan& p) {
+    g_exr_err[0] = 0;
+    if (!L) return exr_refuse("layers is NULL");
+    if (L->struct_size != sizeof(rrt_exr_layers)) return exr_refuse("layers->struct_size is not sizeof(rrt_exr_layers)");
+    rrt_exr_format f = {(uint32_t)sizeof(rrt_exr_format), RRT_EXR_FLOAT, L->compression, L->half_max};
+    ExrPlan q;
+    const int rc = exr_plan(&f, 1, 1, q);             /* the compression and half_max rules, in exr_plan's words */
+    if (rc != RRT_OK) return rc;
+    if (w < 1 || h < 1) return exr_refuse("width and height >= 1");
+    if (L->n_sources < 1 || L->n_sources > RRT_EXR_MAX_SOURCES) return exr_refuse("layers->n_sources: 1 ... 8");
+    if (L->n_channels < 1 || L->n_channels > RRT_EXR_MAX_CHANNELS) return exr_refuse("layers->n_channels: 1 ... 16");
+    p = ExrLayersPlan();
+    p.w = w;
+    p.h = h;
+    p.compression = L->compression;
+    p.lines = q.lines;
+    p.max_half = q.max_half;
+    p.n_src = L->n_sources;
+    p.n_ch = L->n_channels;
+    for (int s = 0; s < p.n_src; ++s) {
+        const rrt_exr_source& src = L->sources[s];
+        if (src.words != 1 && src.words != 3 && src.words != 4) return exr_refuse("a source's words: 1 | 3 | 4");
+        if (src.kind != RRT_EXR_SRC_F32 && src.kind != RRT_EXR_SRC_I32) return exr_refuse("a source's kind: RRT_EXR_SRC_F32 (0) | RRT_EXR_SRC_I32 (1)");
+        p.src[s] = static_cast<const uint32_t*>(src.d_data);
+        p.src_words[s] = src.words;
+        p.src_kind[s] = src.kind;
+        p.src_bottom_up[s] = src.bottom_up != 0;
+    }
+    int halves = 0, fours = 0;
+    for (int c = 0; c < p.n_ch; ++c) {
+        const rrt_exr_channel& ch = L->channels[c];
+        if (!exr_layer_name_ok(ch.name)) return exr_refuse("a channel's name: 1 ... 31 bytes of [A-Za-z0-9_.], no '.' at either end");
+        if (c > 0 && strcmp(L->channels[c - 1].name, ch.name) >= 0) {      /* the names are ASCII: strcmp's order is the unsigned bytes' */
+            snprintf(g_exr_err, sizeof(g_exr_err), "channel names must ascend strictly: \"%s\" is followed by \"%s\"", L->channels[c - 1].name, ch.name);
+            return RRT_ERR_INVALID_ARGUMENT;
+        }
+        if (ch.type != RRT_EXR_UINT && ch.type != RRT_EXR_HALF && ch.type != RRT_EXR_FLOAT)
+            return exr_refuse("a channel's type: RRT_EXR_UINT (0) | RRT_EXR_HALF (1) | RRT_EXR_FLOAT (2)");
+        if (ch.source < 0 || ch.source >= p.n_src) return exr_refuse("a channel's source: an index in [0, n_sources)");
+        if (ch.word < 0 || ch.word >= p.src_words[ch.source]) return exr_refuse("a channel's word: in [0, words) of its source");
+        if (ch.type == RRT_EXR_UINT && p.src_kind[ch.source] == RRT_EXR_SRC_F32) return exr_refuse("an F32 source is not stored as UINT");
+        p.ch_type[c] = ch.type;
+        p.ch_src[c] = ch.source;
+        p.ch_word[c] = ch.word;
+        p.ch_pre[c] = p.sum_bps;
+        p.sum_bps += exr_layer_bps(ch.type);
+        ++(ch.type == RRT_EXR_HALF ? halves : fours);
+    }
+    const uint64_t rows = (uint64_t)(h < p.lines ? h : p.lines);
+    if (rows * (uint64_t)w * (uint64_t)p.sum_bps >= ((uint64_t)1 << 31)) return exr_refuse("a chunk of 2^31 bytes or more");
+    p.n_chunks = (int32_t)(((int64_t)h + p.lines - 1) / p.lines);
+    p.store8 = p.compression != RRT_EXR_NONE && halves > 0 && fours > 0 && w % 16 == 8;
+    return RRT_OK;
+}
+
+static inline uint64_t exr_layers_bytes(const ExrLayersPlan& p) { return (uint64_t)p.w * (uint64_t)p.h * (uint64_t)p.sum_bps; }
+
+/* out[8] of rrt_exr_layers_launch_geometry */
+static inline void exr_layers_geometry(const ExrLayersPlan& p, size_t address_bits, int32_t out[8]) {
+    const bool wide = p.w % kExrWidePixels == 0 && (address_bits & 15u) == 0;
+    const int64_t units = wide ? p.w / kExrWidePixels : (int64_t)p.w * p.n_ch;
+    const int64_t gy = ((int64_t)p.h + kExrBlockY - 1) / kExrBlockY;
+    out[0] = kExrBlockX * kExrBlockY;
+    out[1] = kExrBlockX;
+    out[2] = kExrBlockY;
+    out[3] = wide ? kExrWidePixels : 1;
+    out[4] = (int32_t)((units + kExrBlockX - 1) / kExrBlockX);
+    out[5] = (int32_t)(gy < kExrMaxGridY ? gy : kExrMaxGridY);
+    out[6] = !wide ? 0 : p.store8 ? 2 : 1;
+    const int64_t per_pass = (int64_t)out[5] * kExrBlockY;
+    out[7] = (int32_t)(((int64_t)p.h + per_pass - 1) / per_pass);
+}
+
+/* NULL, alignment and overlap of the payload and every source: what the launch and the host conversion check alike */
+static inline int exr_layers_buffers(const void* payload, const ExrLayersPlan& p, size_t& address_bits) {
+    if (!payload) return exr_refuse("payload is NULL");
+    address_bits = (size_t)(uintptr_t)payload;
+    for (int s = 0; s < p.n_src; ++s) {
+        const uintptr_t in = (uintptr_t)p.src[s];
+        if (!in) return exr_refuse("a source's d_data is NULL");
+        if ((in & 3u) != 0) return exr_refuse("a source's d_data is not 4-byte aligned");
+        if (exr_overlap((uintptr_t)payload, exr_layers_bytes(p), in, (uint64_t)p.w * (uint64_t)p.h * 4u * (uint64_t)p.src_words[s]))
+            return exr_refuse("the payload overlaps a source");
+        address_bits |= (size_t)in;
+    }
+    return RRT_OK;
+}
+
+static inline int exr_layers_host(void* payload, const rrt_exr_layers* L, int w, int h) {
+    ExrLayersPlan p;
+    int rc = exr_layers_plan(L, w, h, p);
+    if (rc != RRT_OK) return rc;
+    size_t bits;
+    rc = exr_layers_buffers(payload, p, bits);
+    if (rc != RRT_OK) return rc;
+    for (int y = 0; y < h; ++y)
+        for (int c = 0; c < p.n_ch; ++c)
+            for (int x = 0; x < w; ++x) exr_layer_put_sample(static_cast<uint8_t*>(payload), p, y, c, x);
+    return RRT_OK;
+}
+
+/* exr_header's attributes, in its order, around the layers' channel list */
+static inline int exr_layers_header(const rrt_exr_layers* L, int w, int h, int fps_num, int fps_den, void* buf, size_t cap, size_t* len) {
+    ExrLayersPlan p;
+    const int rc = exr_layers_plan(L, w, h, p);
+    if (rc != RRT_OK) return rc;
+    if (!buf || !len) return exr_refuse("buf or len is NULL");
+    if (fps_num <= 0 || fps_den <= 0) return exr_refuse("fps_num and fps_den > 0");
+    uint8_t tmp[2048];
+    ExrWriter o = {tmp, sizeof(tmp), 0};
+    const uint8_t magic[4] = {0x76, 0x2f, 0x31, 0x01};
+    o.bytes(magic, 4);
+    o.i32(2);
+    int32_t list = 1;
+    for (int c = 0; c < p.n_ch; ++c) list += (int32_t)strlen(L->channels[c].name) + 1 + 16;
+    o.attribute("channels", "chlist", list);
+    for (int c = 0; c < p.n_ch; ++c) {
+        o.text(L->channels[c].name);
+        o.i32(p.ch_type[c]);
+        o.u8(0); o.u8(0); o.u8(0); o.u8(0);             /* pLinear, reserved */
+        o.i32(1); o.i32(1);                             /* xSampling, ySampling */
+    }
+    o.u8(0);
+    o.attribute("compression", "compression", 1);
+    o.u8((uint8_t)p.compression);
+    for (const char* name : {"dataWindow", "displayWindow"}) {
+        o.attribute(name, "box2i", 16);
+        o.i32(0); o.i32(0); o.i32(w - 1); o.i32(h - 1);
+    }
+    o.attribute("lineOrder", "lineOrder", 1);
+    o.u8(0);
+    o.attribute("pixelAspectRatio", "float", 4);
+    o.f32(1.0f);
+    o.attribute("screenWindowCenter", "v2f", 8);
+    o.f32(0.0f); o.f32(0.0f);
+    o.attribute("screenWindowWidth", "float", 4);
+    o.f32(1.0f);
+    o.attribute("chromaticities", "chromaticities", 32);
+    for (float v : {0.64f, 0.33f, 0.30f, 0.60f, 0.15f, 0.06f, 0.3127f, 0.3290f}) o.f32(v);
+    o.attribute("framesPerSecond", "rational", 8);
+    o.i32(fps_num); o.i32(fps_den);
+    o.attribute("software", "string", (int32_t)(sizeof(kExrSoftware) - 1));
+    o.bytes(kExrSoftware, sizeof(kExrSoftware) - 1);
+    o.u8(0);
     if (o.at > sizeof(tmp) || o.at > cap) return exr_refuse("cap is smaller than the header");
     memcpy(buf, tmp, o.at);
     *len = o.at;

@@ -51,6 +51,10 @@
 //                                              after the exposure, before any tone map -- as B, G, R scanlines packed on device 0 and
 //                                              deflated with zlib on a small thread pool.  The pattern holds one frame field; a plain
 //                                              name serves --frames 1.  The whole-frame HDR path: one GPU only, not with --glow)
+//                [--exr-layers steps,horizon,transmittance,emission,direction,position|all]   (with --exr: per-ray data layers next
+//                                              to B, G, R in every file.  The frame is rendered by the debug launch, whose planes the
+//                                              layers read as the march left them; the exposure scales B, G, R only.  The 1x pinhole
+//                                              frame only)
 //
 // Noise tables: the reference's simTime runs without bound (main.cpp:515) and a table's size grows with the times
 // it covers, so each device keeps ONE table over a window of the clock that fits --noise-table-gib (default 2;
@@ -82,6 +86,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <algorithm>
 #include <cstring>
 #include <filesystem>
 #include <initializer_list>
@@ -316,6 +321,8 @@ struct Options {               // what the command line sets (parse_options), th
     bool exr_opts = false;               // one of --exr-type / --exr-compression / --exr-level was given
     int exr_type = 0, exr_compression = 2, exr_level = 4;      // the lists' indices (-1: not on the list); the deflate level (0: not 1 ... 9)
     rrt_exr_format exr;
+    std::string exr_layers_arg;          // --exr-layers LIST
+    bool exr_layers_given = false;
 
     // derived: w x h is the frame that is sharded and written (with --stereo the composite of two ew x eh eyes)
     bool pano = false, use_stereo = false, collective = false, auto_exposure = false;
@@ -331,8 +338,13 @@ struct Options {               // what the command line sets (parse_options), th
     bool use_exr = false;                // the EXR frames are the HDR itself: the whole-frame HDR path
     size_t exr_bytes = 0;
     int32_t exr_chunks = 0;
+    bool use_layers = false;             // --exr-layers: the frame comes from the debug launch, the files from rrt_launch_exr_layers
+    int layer_planes = 0;                // the debug planes the layers read: bit p of kLayerPlanes
+    int layer_source[8] = {};            // ... and plane p's index in layers.sources
+    rrt_exr_layers layers;               // the channel list and the sources' shapes; the sources' addresses are the slot's (slot_layers)
 
     Options() {
+        rrt_exr_layers_default(&layers);
         rrt_exr_format_default(&exr);
         rrt_yuv_format_default(&yuv);
         rrt_yuv_hdr10_default(&hdr10);
@@ -428,6 +440,7 @@ int parse_options(int argc, char** argv, Options& o) {
         else if (a == "--exr" && more) o.exr_path = next();
         else if (a == "--exr-type") { o.exr_type = one_of(next(), {"half", "float"}); o.exr_opts = true; }
         else if (a == "--exr-compression") { o.exr_compression = one_of(next(), {"none", "zips", "zip"}); o.exr_opts = true; }
+        else if (a == "--exr-layers" && more) { o.exr_layers_arg = next(); o.exr_layers_given = true; }
         else if (a == "--exr-level") { o.exr_level = one_of(next(), {"1", "2", "3", "4", "5", "6", "7", "8", "9"}) + 1; o.exr_opts = true; }
         else if (a == "--all-effects") o.all_fx = 1; else if (a == "--fast") o.arith = RRT_ARITH_FAST;
         else if (a == "--path-window") val(o.path_window);
@@ -558,6 +571,77 @@ std::string frame_name(const std::string& pattern, int k, int* count = nullptr) 
 
 // Every refusal that depends on more than one option, in the order that decides which message a command line gets, and the values
 // derived from the options.  Host arithmetic and the library's host-only queries: no device is touched before this has returned.
+// --exr-layers: the debug launch's planes the layers read, and the standard layers' channels (headless.py: EXR_LAYERS).  type -1:
+// --exr-type's
+enum { kPlaneRad, kPlaneVel, kPlanePos, kPlaneSteps, kPlaneHit, kLayerPlaneCount };
+struct LayerPlane { int words, kind; };
+const LayerPlane kLayerPlanes[kLayerPlaneCount] = {{4, RRT_EXR_SRC_F32}, {3, RRT_EXR_SRC_F32}, {3, RRT_EXR_SRC_F32}, {1, RRT_EXR_SRC_I32}, {1, RRT_EXR_SRC_I32}};
+struct LayerChannel { const char* layer; const char* name; int type, plane, word; };
+const LayerChannel kLayerChannels[] = {
+    {"steps", "steps", RRT_EXR_UINT, kPlaneSteps, 0},
+    {"horizon", "horizon", RRT_EXR_HALF, kPlaneHit, 0},
+    {"transmittance", "transmittance", -1, kPlaneRad, 3},
+    {"emission", "emission.B", -1, kPlaneRad, 2}, {"emission", "emission.G", -1, kPlaneRad, 1}, {"emission", "emission.R", -1, kPlaneRad, 0},
+    {"direction", "direction.X", RRT_EXR_FLOAT, kPlaneVel, 0}, {"direction", "direction.Y", RRT_EXR_FLOAT, kPlaneVel, 1},
+    {"direction", "direction.Z", RRT_EXR_FLOAT, kPlaneVel, 2},
+    {"position", "position.X", RRT_EXR_FLOAT, kPlanePos, 0}, {"position", "position.Y", RRT_EXR_FLOAT, kPlanePos, 1},
+    {"position", "position.Z", RRT_EXR_FLOAT, kPlanePos, 2},
+};
+
+// --exr-layers' refusals (headless.py words them alike) and o.layers: B, G, R of --exr-type from source 0, the HDR plane, next to the
+// named layers' channels, in the names' byte order -- the file's
+int check_exr_layers(Options& o) {
+    int mask = 0;       // bit i: the layer of kLayerNames[i]
+    const char* const kLayerNames[] = {"steps", "horizon", "transmittance", "emission", "direction", "position"};
+    if (o.exr_layers_arg == "all") mask = 63;
+    else for (size_t at = 0; at <= o.exr_layers_arg.size();) {
+        size_t end = o.exr_layers_arg.find(',', at);
+        if (end == std::string::npos) end = o.exr_layers_arg.size();
+        const std::string name = o.exr_layers_arg.substr(at, end - at);
+        int i = 0;
+        while (i < 6 && name != kLayerNames[i]) ++i;
+        if (i == 6) return refuse("usage: --exr-layers LIST: a comma-separated subset of steps,horizon,transmittance,emission,direction,position, or all");
+        if (mask & (1 << i)) return refuse("usage: --exr-layers LIST names a layer twice");
+        mask |= 1 << i;
+        at = end + 1;
+    }
+    const char* with = o.use_adaptive ? "--adaptive" : o.use_dof ? "--dof" : o.use_stereo ? "--stereo" : o.pano ? "--projection equirect | fisheye"
+                     : o.motion > 1 ? "--motion-blur > 1" : o.supersample > 1 ? "--supersample > 1" : nullptr;
+    if (with) return refuse("usage: --exr-layers stores per-ray data of the 1x pinhole frame: not with %s", with);
+    std::vector<rrt_exr_channel> list;
+    auto channel = [&](const char* name, int type, int source, int word) {
+        rrt_exr_channel c = {};
+        snprintf(c.name, sizeof(c.name), "%s", name);
+        c.type = type; c.source = source; c.word = word;
+        list.push_back(c);
+    };
+    o.layers.compression = o.exr.compression;
+    o.layers.half_max = o.exr.half_max;
+    o.layers.sources[0].words = 4; o.layers.sources[0].kind = RRT_EXR_SRC_F32; o.layers.sources[0].bottom_up = 1;
+    o.layers.n_sources = 1;
+    channel("B", o.exr.type, 0, 2); channel("G", o.exr.type, 0, 1); channel("R", o.exr.type, 0, 0);
+    int* source_of = o.layer_source;
+    for (int p = 0; p < kLayerPlaneCount; ++p) source_of[p] = -1;
+    for (const LayerChannel& c : kLayerChannels) {
+        int i = 0;
+        while (strcmp(kLayerNames[i], c.layer) != 0) ++i;
+        if (!(mask & (1 << i))) continue;
+        if (source_of[c.plane] < 0) {
+            rrt_exr_source& src = o.layers.sources[o.layers.n_sources];
+            src.words = kLayerPlanes[c.plane].words; src.kind = kLayerPlanes[c.plane].kind; src.bottom_up = 0;
+            source_of[c.plane] = o.layers.n_sources++;
+            o.layer_planes |= 1 << c.plane;
+        }
+        channel(c.name, c.type < 0 ? o.exr.type : c.type, source_of[c.plane], c.word);
+    }
+    std::sort(list.begin(), list.end(), [](const rrt_exr_channel& a, const rrt_exr_channel& b) { return strcmp(a.name, b.name) < 0; });
+    o.layers.n_channels = (int32_t)list.size();
+    for (size_t i = 0; i < list.size(); ++i) o.layers.channels[i] = list[i];
+    if (rrt_exr_layers_frame_bytes(&o.layers, o.w, o.h, &o.exr_bytes, &o.exr_chunks) != RRT_OK) return refuse("bad arguments");
+    o.use_layers = true;
+    return 0;
+}
+
 int check_options(Options& o) {
     if (o.w <= 0 || o.h <= 0 || o.frames < 0 || o.fps <= 0 || o.gpus < 1 || o.tile_rows < 1 || o.slots < 1 || o.slots > kMaxSlots)
         return refuse("bad arguments");
@@ -682,6 +766,8 @@ int check_options(Options& o) {
         o.exr.compression = compressions[o.exr_compression];
         if (rrt_exr_frame_bytes(&o.exr, o.w, o.h, &o.exr_bytes, &o.exr_chunks) != RRT_OK) return refuse("bad arguments");
     }
+    if (!o.use_exr && o.exr_layers_given) return refuse("usage: --exr-layers needs --exr PATTERN");
+    if (o.exr_layers_given) { const int rc = check_exr_layers(o); if (rc) return rc; }
     o.hdr_frame = o.use_glow || o.use_exposure || o.y4m10 || o.use_exr;
     // a supersampled launch is always the single kernel in the static order (include/rrt.h): no pool, no path choice, no tile order
     if (o.supersample > 1 || o.motion > 1 || o.hdr_frame || o.pano || o.use_stereo || o.use_dof) {
@@ -700,6 +786,7 @@ struct Slots {                 // what device 0 owns per frame slot: gathered sh
     void* yuv_host[kMaxSlots] = {};
     void* exr[kMaxSlots] = {};             // --exr: each slot's packed chunks on device 0, and the pinned host copy the files are made of
     void* exr_host[kMaxSlots] = {};
+    void* layer_plane[kLayerPlaneCount][kMaxSlots] = {};      // --exr-layers: each slot's planes of the debug launch
     void* hdr[kMaxSlots] = {};             // --glow / --exposure / --y4m-depth 10 / --exr: each slot's linear frame; the glow's scratch
     void* glow_scratch[kMaxSlots] = {};
     void* ad_scratch[kMaxSlots] = {};      // --adaptive: each slot's list, and the pinned word its count is copied to
@@ -825,6 +912,8 @@ int create_slots(Slots& R, const Options& o, bool sink, hipStream_t stream0) {
         if (o.hdr_frame) HIPCHK(hipMalloc(&R.hdr[s], R.frame_bytes * sizeof(float)));
         if (o.y4m) { HIPCHK(hipMalloc(&R.yuv[s], o.yuv_bytes)); HIPCHK(hipHostMalloc(&R.yuv_host[s], o.yuv_bytes, hipHostMallocDefault)); }
         if (o.use_exr) { HIPCHK(hipMalloc(&R.exr[s], o.exr_bytes)); HIPCHK(hipHostMalloc(&R.exr_host[s], o.exr_bytes, hipHostMallocDefault)); }
+        for (int p = 0; p < kLayerPlaneCount; ++p)
+            if (o.layer_planes & (1 << p)) HIPCHK(hipMalloc(&R.layer_plane[p][s], (size_t)o.w * o.h * 4 * kLayerPlanes[p].words));
         if (o.use_glow) HIPCHK(hipMalloc(&R.glow_scratch[s], o.glow_bytes));
         if (o.use_adaptive) { HIPCHK(hipMalloc(&R.ad_scratch[s], R.ad_bytes)); HIPCHK(hipHostMalloc(&R.ad_count[s], 4, hipHostMallocDefault)); }
         HIPCHK(hipEventCreateWithFlags(&R.done[s], hipEventDisableTiming));
@@ -843,6 +932,7 @@ void destroy_slots(Slots& R, int slots) {
         (void)hipFree(R.ad_scratch[s]); (void)hipFree(R.yuv[s]);
         if (R.yuv_host[s]) (void)hipHostFree(R.yuv_host[s]);
         (void)hipFree(R.exr[s]);
+        for (int p = 0; p < kLayerPlaneCount; ++p) (void)hipFree(R.layer_plane[p][s]);
         if (R.exr_host[s]) (void)hipHostFree(R.exr_host[s]);
         if (R.ad_count[s]) (void)hipHostFree(R.ad_count[s]);
         if (R.host[s]) (void)hipHostFree(R.host[s]);
@@ -858,7 +948,8 @@ int write_exr_file(const std::string& name, const uint8_t* payload, const Option
     struct Piece { int32_t y = 0; size_t offset = 0, bytes = 0; std::vector<uint8_t> data; };
     std::vector<Piece> pieces((size_t)o.exr_chunks);
     for (int i = 0; i < o.exr_chunks; ++i)
-        if (rrt_exr_chunk(&o.exr, o.w, o.h, i, &pieces[i].y, &pieces[i].offset, &pieces[i].bytes) != RRT_OK) return 1;
+        if ((o.use_layers ? rrt_exr_layers_chunk(&o.layers, o.w, o.h, i, &pieces[i].y, &pieces[i].offset, &pieces[i].bytes)
+                          : rrt_exr_chunk(&o.exr, o.w, o.h, i, &pieces[i].y, &pieces[i].offset, &pieces[i].bytes)) != RRT_OK) return 1;
     if (o.exr.compression != RRT_EXR_NONE) {
         std::atomic<int> next{0}, failed{0};
         auto work = [&]() {
@@ -879,9 +970,10 @@ int write_exr_file(const std::string& name, const uint8_t* payload, const Option
         for (std::thread& t : pool) t.join();
         if (failed.load()) { fprintf(stderr, "rrt_headless: exr: deflate failed\n"); return 1; }
     }
-    uint8_t header[1024];
+    uint8_t header[2048];
     size_t header_bytes = 0;
-    if (rrt_exr_header(&o.exr, o.w, o.h, o.fps, 1, header, sizeof(header), &header_bytes) != RRT_OK) {
+    if ((o.use_layers ? rrt_exr_layers_header(&o.layers, o.w, o.h, o.fps, 1, header, sizeof(header), &header_bytes)
+                      : rrt_exr_header(&o.exr, o.w, o.h, o.fps, 1, header, sizeof(header), &header_bytes)) != RRT_OK) {
         fprintf(stderr, "rrt_headless: exr header: %s\n", rrt_exr_last_error());
         return 1;
     }
@@ -1057,7 +1149,17 @@ int launch_frame(Device& D, int slot, int k, const FrameView& v, const Options& 
     int rc;
     if (o.hdr_frame) {     // one device (check_options): the slot's HDR through launch_sampled, then the post passes on the same stream
         float* lin = static_cast<float*>(R.hdr[slot]);
-        rc = o.use_adaptive ? launch_adaptive(lin) : launch_sampled(false, lin);
+        if (o.use_layers) {     // the 1x pinhole frame (check_exr_layers): its HDR is the debug launch's d_hdr, next to the planes the layers read
+            rrt_debug_outputs dbg = {};
+            dbg.d_hdr = lin;
+            dbg.d_rad = static_cast<float*>(R.layer_plane[kPlaneRad][slot]);
+            dbg.d_vel = static_cast<float*>(R.layer_plane[kPlaneVel][slot]);
+            dbg.d_pos = static_cast<float*>(R.layer_plane[kPlanePos][slot]);
+            dbg.d_steps = static_cast<int32_t*>(R.layer_plane[kPlaneSteps][slot]);
+            dbg.d_hit = static_cast<int32_t*>(R.layer_plane[kPlaneHit][slot]);
+            rc = rrt_launch_raymarch_ex(dst, w, h, v.sim_t, &v.cam, D.sky, &fx, &prm, &dbg, st);
+        }
+        else rc = o.use_adaptive ? launch_adaptive(lin) : launch_sampled(false, lin);
         if (rc == RRT_OK && o.use_exposure) {     // the bytes -- and, in front of the glow, a 10-bit Y4M conversion or an EXR file, the scaled HDR in place
             if (o.auto_exposure) HIPCHK(hipStreamWaitEvent(st, R.exposed, 0));
             rc = rrt_launch_exposure(o.use_glow ? nullptr : dst, o.use_glow || o.y4m10 || o.use_exr ? lin : nullptr, lin, w, h, &o.exposure, R.exposure_scratch,
@@ -1300,7 +1402,14 @@ int main(int argc, char** argv) {
             HIPCHK(hipMemcpyAsync(R.yuv_host[slot], R.yuv[slot], o.yuv_bytes, hipMemcpyDeviceToHost, dev[0].stream[slot]));
         }
         if (o.use_exr) {    // the chunks of the frame's HDR as the last pass left it, then their copy; the file is made when the frame is delivered
-            rc = rrt_launch_exr_from_hdr(R.exr[slot], static_cast<const float*>(R.hdr[slot]), o.w, o.h, &o.exr, dev[0].stream[slot]);
+            if (o.use_layers) {     // ... next to the data layers, from the slot's planes
+                rrt_exr_layers layers = o.layers;
+                layers.sources[0].d_data = R.hdr[slot];
+                for (int p = 0; p < kLayerPlaneCount; ++p)
+                    if (o.layer_planes & (1 << p)) layers.sources[o.layer_source[p]].d_data = R.layer_plane[p][slot];
+                rc = rrt_launch_exr_layers(R.exr[slot], &layers, o.w, o.h, dev[0].stream[slot]);
+            }
+            else rc = rrt_launch_exr_from_hdr(R.exr[slot], static_cast<const float*>(R.hdr[slot]), o.w, o.h, &o.exr, dev[0].stream[slot]);
             if (rc != RRT_OK) { fprintf(stderr, "rrt_headless: exr: %s (%s)\n", rrt_status_string(rc), rrt_exr_last_error()); return 1; }
             HIPCHK(hipMemcpyAsync(R.exr_host[slot], R.exr[slot], o.exr_bytes, hipMemcpyDeviceToHost, dev[0].stream[slot]));
         }

@@ -10,7 +10,8 @@
            [--exposure EV | --auto-exposure [KEY]] [--exposure-speed UP DOWN] [--exposure-range MIN MAX] [--exposure-percentiles LOW HIGH]
            [--y4m x.y4m [--y4m-chroma 420|444] [--y4m-range limited|full] [--y4m-depth 8|10]
                    [--y4m-transfer sdr|pq [--hdr-white NITS] [--hdr-peak NITS] [--hdr-knee F]]]
-           [--exr f.%04d.exr [--exr-type half|float] [--exr-compression none|zips|zip] [--exr-level 1..9]]
+           [--exr f.%04d.exr [--exr-type half|float] [--exr-compression none|zips|zip] [--exr-level 1..9]
+                   [--exr-layers steps,horizon,transmittance,emission,direction,position|all]]
     python -m torch.distributed.run --nproc-per-node 8 -m relativisticraytracer_amd.headless ...
 
 Per frame k = 1..N it does what `main()` does while recording: advance the fixed 1/24 s clock
@@ -192,6 +193,10 @@ def build_parser():
     ap.add_argument("--exr-compression", default=None, metavar="none|zips|zip",
                     help="with --exr: none, or deflate of 1 (zips) or 16 (zip, the default) scanlines per chunk")
     ap.add_argument("--exr-level", default=None, metavar="1..9", help="with --exr: the deflate level (default 4)")
+    ap.add_argument("--exr-layers", default=None, metavar="LIST",
+                    help="with --exr: per-ray data layers next to B, G, R in every file -- a comma-separated subset of "
+                         "steps,horizon,transmittance,emission,direction,position, or all.  The frame is rendered by the debug launch; "
+                         "the layers are stored as the march left them (the exposure scales B, G, R only).  The 1x pinhole frame only")
     ap.add_argument("--init-timeout", type=float, default=300.0,
                     help="several ranks: seconds the process-group bring-up may take before the run exits non-zero with "
                          "the tracebacks of all threads, instead of hanging")
@@ -310,10 +315,12 @@ def check_y4m(ap, args, world):
 def check_exr(ap, args, world):
     """--exr's refusals (rrt_headless.cpp words them alike); leaves args.exr_format: (type, compression, level) or None"""
     from relativisticraytracer_amd.sinks import frame_fields, frame_name
-    args.exr_format = None
+    args.exr_format, args.exr_layer_names = None, ()
     if args.exr is None:
         if args.exr_type is not None or args.exr_compression is not None or args.exr_level is not None:
             ap.error("--exr-type / --exr-compression / --exr-level need --exr PATTERN")
+        if args.exr_layers is not None:
+            ap.error("--exr-layers needs --exr PATTERN")
         return
     if args.exr_type not in (None, "half", "float"):
         ap.error("--exr-type half | float")
@@ -334,6 +341,37 @@ def check_exr(ap, args, world):
         if other is not None and any(os.path.abspath(frame_name(args.exr, k)) == os.path.abspath(other) for k in range(1, max(args.frames, 1) + 1)):
             ap.error(f"--exr and {flag} name the same file")
     args.exr_format = (args.exr_type or "half", args.exr_compression or "zip", int(args.exr_level or 4))
+    if args.exr_layers is not None:
+        names = list(EXR_LAYERS) if args.exr_layers == "all" else args.exr_layers.split(",")
+        if any(n not in EXR_LAYERS for n in names):
+            ap.error("--exr-layers LIST: a comma-separated subset of " + ",".join(EXR_LAYERS) + ", or all")
+        if len(set(names)) != len(names):
+            ap.error("--exr-layers LIST names a layer twice")
+        for on, what in ((args.adaptive is not None, "--adaptive"), (args.dof is not None, "--dof"), (args.stereo is not None, "--stereo"),
+                         (args.projection != "pinhole", "--projection equirect | fisheye"), (args.motion_blur > 1, "--motion-blur > 1"),
+                         (args.supersample > 1, "--supersample > 1")):
+            if on:
+                ap.error("--exr-layers stores per-ray data of the 1x pinhole frame: not with " + what)
+        args.exr_layer_names = tuple(n for n in EXR_LAYERS if n in names)
+
+
+# --exr-layers' names, in the order `all` lists them, and each one's channels: (name, type -- None: --exr-type's --, plane, word)
+EXR_LAYERS = {"steps": [("steps", "uint", "steps", 0)],
+              "horizon": [("horizon", "half", "hit", 0)],
+              "transmittance": [("transmittance", None, "rad", 3)],
+              "emission": [("emission.B", None, "rad", 2), ("emission.G", None, "rad", 1), ("emission.R", None, "rad", 0)],
+              "direction": [("direction.X", "float", "vel", 0), ("direction.Y", "float", "vel", 1), ("direction.Z", "float", "vel", 2)],
+              "position": [("position.X", "float", "pos", 0), ("position.Y", "float", "pos", 1), ("position.Z", "float", "pos", 2)]}
+EXR_PLANES = {"steps": ("int32", 1), "hit": ("int32", 1), "rad": ("float32", 4), "vel": ("float32", 3), "pos": ("float32", 3)}
+
+
+def exr_layer_list(names, beauty, hdr, planes):
+    """ExrLayers' list for B, G, R of type `beauty` from the bottom-up HDR plane and the named layers from the debug launch's
+    top-down planes {"steps" | "hit" | "rad" | "vel" | "pos": tensor}"""
+    out = [("B", beauty, hdr, 2, True), ("G", beauty, hdr, 1, True), ("R", beauty, hdr, 0, True)]
+    for name in names:
+        out += [(ch, type_ or beauty, planes[plane], word, False) for ch, type_, plane, word in EXR_LAYERS[name]]
+    return out
 
 
 def build_settings(ap, args, pano, use_exposure):
@@ -441,6 +479,13 @@ class Renderer:
             self.frame = torch.zeros(h * w * 4, dtype=torch.uint8, device=dev)
         if glow is not None:
             self.glow_scratch = torch.empty(rrt.glow_scratch_bytes(w, h, glow), dtype=torch.uint8, device=dev)
+        # --exr-layers: the frame comes from the debug launch, which leaves the per-ray planes the layers read next to the HDR
+        self.layer_planes = {}
+        for name in args.exr_layer_names:
+            for _, _, plane, _ in EXR_LAYERS[name]:
+                if plane not in self.layer_planes:
+                    dtype, words = EXR_PLANES[plane]
+                    self.layer_planes[plane] = torch.zeros(h * w * words, dtype=getattr(torch, dtype), device=dev)
         self.exposure_scratch = None
         if exposure is not None and exposure.mode == rrt.EXPOSURE_AUTO:     # the state the sequence's frames share
             self.exposure_scratch = torch.empty(rrt.exposure_scratch_bytes(), dtype=torch.uint8, device=dev)
@@ -501,6 +546,8 @@ class Renderer:
         self.prms[0].noise_table = self.table
         if self.adaptive is not None:
             self.render_adaptive(hdr)
+        elif self.layer_planes:     # the 1x pinhole frame (check_exr): its HDR is the debug launch's d_hdr
+            rrt.launch_raymarch_debug(frame, self.w, self.h, self.t, self.cam, self.tex, self.fx, self.prms[0], hdr=hdr, **self.layer_planes)
         else:
             self.launch_sampled(frame, self.prms[0], hdr=hdr)
         if self.exposure is not None:
@@ -661,14 +708,20 @@ def main(argv=None):
     exr = None
     if rank == 0 and args.exr_format is not None:
         exr_fmt = rrt.ExrFormat(*args.exr_format[:2])
-        exr = sinks.EXRSink(args.exr, w, h, args.fps, exr_fmt, level=args.exr_format[2])
+        exr_layers = None
+        if args.exr_layer_names:
+            exr_layers = rrt.ExrLayers(exr_fmt, w, h, exr_layer_list(args.exr_layer_names, args.exr_format[0], r.hdr, r.layer_planes))
+        exr = sinks.EXRSink(args.exr, w, h, args.fps, exr_fmt, level=args.exr_format[2], layers=exr_layers)
         exr_dev = torch.empty(exr.frame_bytes, dtype=torch.uint8, device=dev)
         exr_host = torch.empty(exr.frame_bytes, dtype=torch.uint8, pin_memory=True)
         trace(f"exr sink {args.exr}: {exr_fmt.info()}, {exr.frame_bytes} bytes per frame, {exr.threads} deflate threads")
 
     def deliver(frame):
         if exr:         # on the current stream, behind the frame's last pass
-            rrt.launch_exr_from_hdr(exr_dev, r.hdr, w, h, exr_fmt)
+            if exr_layers is not None:
+                rrt.launch_exr_layers(exr_dev, exr_layers)
+            else:
+                rrt.launch_exr_from_hdr(exr_dev, r.hdr, w, h, exr_fmt)
             exr_host.copy_(exr_dev, non_blocking=False)
             exr.write(exr_host.numpy())
         if y4m:         # on the current stream, behind the frame

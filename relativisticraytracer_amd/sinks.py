@@ -137,9 +137,11 @@ class EXRSink:
 
     `pattern` holds exactly one frame field, `%d` or `%0Nd`, filled with the frame's number (1, 2, ... in the order written, or
     `index`); a plain name is accepted for a single frame.  A file is written as NAME.tmp and renamed when it is complete.
-    threads: the pool's size (default: min(16, the CPUs this process may run on)); 1 deflates in the caller's thread."""
+    threads: the pool's size (default: min(16, the CPUs this process may run on)); 1 deflates in the caller's thread.
+    layers: an exr.ExrLayers -- the files hold its channels (data layers next to B, G, R) and `write` takes launch_exr_layers'
+    payload; None: B, G, R of `fmt`, as ever."""
 
-    def __init__(self, pattern, width, height, fps=24, fmt=None, level=4, threads=None):
+    def __init__(self, pattern, width, height, fps=24, fmt=None, level=4, threads=None, layers=None):
         from . import exr
         self.exr = exr
         if frame_fields(pattern) > 1:
@@ -148,10 +150,18 @@ class EXRSink:
             raise ValueError("level: 1 ... 9")
         self.pattern, self.level = pattern, int(level)
         self.fmt = fmt if fmt is not None else exr.ExrFormat()
-        self.frame_bytes = exr.exr_frame_bytes(self.fmt, width, height)
-        self.chunks = exr.exr_chunks(self.fmt, width, height)
-        self.header = exr.exr_header(self.fmt, width, height, int(fps), 1)
-        self.compressed = self.fmt.compression != exr.NONE
+        if layers is not None:      # an exr.ExrLayers: its channel list, and its compression in place of fmt's
+            if (layers.w, layers.h) != (width, height):
+                raise ValueError(f"the layers are for {layers.w}x{layers.h} frames, not {width}x{height}")
+            self.frame_bytes = exr.exr_layers_frame_bytes(layers)
+            self.chunks = exr.exr_layers_chunks(layers)
+            self.header = exr.exr_layers_header(layers, int(fps), 1)
+            self.compressed = layers.compression != exr.NONE
+        else:
+            self.frame_bytes = exr.exr_frame_bytes(self.fmt, width, height)
+            self.chunks = exr.exr_chunks(self.fmt, width, height)
+            self.header = exr.exr_header(self.fmt, width, height, int(fps), 1)
+            self.compressed = self.fmt.compression != exr.NONE
         workers = int(threads) if threads is not None else min(16, len(os.sched_getaffinity(0)))
         self.pool = ThreadPoolExecutor(workers) if self.compressed and workers > 1 and len(self.chunks) > 1 else None
         self.width, self.height, self.frames, self.threads = width, height, 0, max(workers, 1)
