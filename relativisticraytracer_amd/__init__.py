@@ -929,3 +929,8 @@ from .exr import (ExrLayers, exr_layers_chunks, exr_layers_frame_bytes, exr_laye
                   exr_layers_launch_geometry, launch_exr_layers)
 
 __all__ += exr.__all__
+# PNG scanline filtering for still-image output: a library of its own (include/rrt_png.h, librrt_png.so), loaded on first use
+from . import png  # noqa: E402
+from .png import (PngFormat, launch_png_from_hdr, launch_png_from_rgba8, png_adler32, png_frame_bytes, png_from_hdr_host,  # noqa: E402,F401
+                  png_from_rgba8_host, png_header, png_launch_geometry, png_slices, png_unfilter_host)
+__all__ += png.__all__

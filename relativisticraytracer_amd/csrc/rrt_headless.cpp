@@ -55,6 +55,11 @@
 //                                              to B, G, R in every file.  The frame is rendered by the debug launch, whose planes the
 //                                              layers read as the march left them; the exposure scales B, G, R only.  The 1x pinhole
 //                                              frame only)
+//                [--png f.%04d.png [--png-depth 8|16] [--png-filter adaptive|none|sub|up|average|paeth] [--png-level 1..9]]   (also,
+//                                              or only, one PNG file per frame (include/rrt_png.h): RGB scanlines filtered, scored and
+//                                              summed on device 0, deflated in slices with zlib on the same thread pool.  Depth 8
+//                                              converts the assembled RGBA8 frame, in every mode; depth 16 tone-maps the frame's
+//                                              linear HDR to 16 bits -- the whole-frame HDR path: one GPU only, not with --glow)
 //
 // Noise tables: the reference's simTime runs without bound (main.cpp:515) and a table's size grows with the times
 // it covers, so each device keeps ONE table over a window of the clock that fits --noise-table-gib (default 2;
@@ -98,6 +103,7 @@
 #include "../../include/rrt.h"
 #include "../../include/rrt_yuv.h"
 #include "../../include/rrt_exr.h"
+#include "../../include/rrt_png.h"
 
 namespace {
 
@@ -321,6 +327,13 @@ struct Options {               // what the command line sets (parse_options), th
     bool exr_opts = false;               // one of --exr-type / --exr-compression / --exr-level was given
     int exr_type = 0, exr_compression = 2, exr_level = 4;      // the lists' indices (-1: not on the list); the deflate level (0: not 1 ... 9)
     rrt_exr_format exr;
+    std::string png_path;                // --png PATTERN: one PNG file per frame (include/rrt_png.h)
+    bool png_opts = false;               // one of --png-depth / --png-filter / --png-level was given
+    int png_depth = 0, png_filter = 0, png_level = 4;          // the lists' indices (-1: not on the list); the deflate level (0: not 1 ... 9)
+    rrt_png_format png;
+    bool use_png = false, png16 = false; // depth 16 reads the frame's linear HDR: the whole-frame HDR path
+    size_t png_bytes = 0, png_stride = 0, png_sum_bytes = 0;
+    int32_t png_slice_rows = 0, png_slices = 0;
     std::string exr_layers_arg;          // --exr-layers LIST
     bool exr_layers_given = false;
 
@@ -346,6 +359,7 @@ struct Options {               // what the command line sets (parse_options), th
     Options() {
         rrt_exr_layers_default(&layers);
         rrt_exr_format_default(&exr);
+        rrt_png_format_default(&png);
         rrt_yuv_format_default(&yuv);
         rrt_yuv_hdr10_default(&hdr10);
         rrt_glow_default(&glow);
@@ -440,6 +454,11 @@ int parse_options(int argc, char** argv, Options& o) {
         else if (a == "--exr" && more) o.exr_path = next();
         else if (a == "--exr-type") { o.exr_type = one_of(next(), {"half", "float"}); o.exr_opts = true; }
         else if (a == "--exr-compression") { o.exr_compression = one_of(next(), {"none", "zips", "zip"}); o.exr_opts = true; }
+        // --png's values are checked in check_options as well, behind "need --png PATTERN"
+        else if (a == "--png" && more) o.png_path = next();
+        else if (a == "--png-depth") { o.png_depth = one_of(next(), {"8", "16"}); o.png_opts = true; }
+        else if (a == "--png-filter") { o.png_filter = one_of(next(), {"adaptive", "none", "sub", "up", "average", "paeth"}); o.png_opts = true; }
+        else if (a == "--png-level") { o.png_level = one_of(next(), {"1", "2", "3", "4", "5", "6", "7", "8", "9"}) + 1; o.png_opts = true; }
         else if (a == "--exr-layers" && more) { o.exr_layers_arg = next(); o.exr_layers_given = true; }
         else if (a == "--exr-level") { o.exr_level = one_of(next(), {"1", "2", "3", "4", "5", "6", "7", "8", "9"}) + 1; o.exr_opts = true; }
         else if (a == "--all-effects") o.all_fx = 1; else if (a == "--fast") o.arith = RRT_ARITH_FAST;
@@ -768,7 +787,36 @@ int check_options(Options& o) {
     }
     if (!o.use_exr && o.exr_layers_given) return refuse("usage: --exr-layers needs --exr PATTERN");
     if (o.exr_layers_given) { const int rc = check_exr_layers(o); if (rc) return rc; }
-    o.hdr_frame = o.use_glow || o.use_exposure || o.y4m10 || o.use_exr;
+    // PNG output (headless.py words these alike): depth 8 converts the assembled RGBA8 frame, in every mode; depth 16 reads the
+    // frame's linear HDR, whole, on one device
+    o.use_png = !o.png_path.empty();
+    if (!o.use_png && o.png_opts) return refuse("usage: --png-depth / --png-filter / --png-level need --png PATTERN");
+    if (o.use_png) {
+        if (o.png_depth < 0) return refuse("usage: --png-depth 8 | 16");
+        if (o.png_filter < 0) return refuse("usage: --png-filter adaptive | none | sub | up | average | paeth");
+        if (o.png_level < 1) return refuse("usage: --png-level 1 ... 9");
+        o.png16 = o.png_depth == 1;
+        if (o.png16 && o.use_glow)
+            return refuse("usage: --png-depth 16 reads the frame's linear HDR and the glow tone-maps H + glow without storing it: not with --glow");
+        if (o.png16 && o.collective) return refuse("usage: --png-depth 16: one GPU only (--gpus 1)");
+        int fields = 0;
+        frame_name(o.png_path, 0, &fields);
+        if (fields > 1) return refuse("usage: --png PATTERN: one frame field (%%d or %%0Nd)");
+        if (fields == 0 && o.frames > 1)
+            return refuse("usage: --png PATTERN needs a frame field (%%04d) when --frames > 1: the frames would overwrite one another");
+        for (int k = 1; k <= (o.frames > 1 ? o.frames : 1); ++k) {
+            const std::string name = absolute_path(frame_name(o.png_path, k));
+            if (!o.out_path.empty() && name == absolute_path(o.out_path)) return refuse("usage: --png and --out name the same file");
+            if (o.y4m && name == absolute_path(o.y4m_path)) return refuse("usage: --png and --y4m name the same file");
+            if (o.use_exr && name == absolute_path(frame_name(o.exr_path, k))) return refuse("usage: --png and --exr name the same file");
+        }
+        const int filters[] = {RRT_PNG_ADAPTIVE, RRT_PNG_NONE, RRT_PNG_SUB, RRT_PNG_UP, RRT_PNG_AVERAGE, RRT_PNG_PAETH};
+        o.png.depth = o.png16 ? 16 : 8;
+        o.png.filter = filters[o.png_filter];
+        if (rrt_png_frame_bytes(&o.png, o.w, o.h, &o.png_bytes, &o.png_stride, &o.png_sum_bytes) != RRT_OK ||
+            rrt_png_slices(&o.png, o.w, o.h, &o.png_slice_rows, &o.png_slices) != RRT_OK) return refuse("bad arguments");
+    }
+    o.hdr_frame = o.use_glow || o.use_exposure || o.y4m10 || o.use_exr || o.png16;
     // a supersampled launch is always the single kernel in the static order (include/rrt.h): no pool, no path choice, no tile order
     if (o.supersample > 1 || o.motion > 1 || o.hdr_frame || o.pano || o.use_stereo || o.use_dof) {
         o.workspace_gib = 0; o.path_window = -1; o.tile_order = 0;
@@ -778,6 +826,9 @@ int check_options(Options& o) {
 
 // ---- the run's resources
 
+// --png: a slot's buffer holds the payload, then -- on the next 16 bytes -- the row sums; one copy brings both to the host
+size_t png_table_offset(const Options& o) { return (o.png_bytes + 15) & ~(size_t)15; }
+
 struct Slots {                 // what device 0 owns per frame slot: gathered shards + assembled frame, the pinned host frame for the sink
     void* gathered[kMaxSlots] = {};
     void* frame[kMaxSlots] = {};
@@ -786,6 +837,8 @@ struct Slots {                 // what device 0 owns per frame slot: gathered sh
     void* yuv_host[kMaxSlots] = {};
     void* exr[kMaxSlots] = {};             // --exr: each slot's packed chunks on device 0, and the pinned host copy the files are made of
     void* exr_host[kMaxSlots] = {};
+    void* png[kMaxSlots] = {};             // --png: each slot's filtered scanlines, then its row sums, on device 0, and their pinned host copy
+    void* png_host[kMaxSlots] = {};
     void* layer_plane[kLayerPlaneCount][kMaxSlots] = {};      // --exr-layers: each slot's planes of the debug launch
     void* hdr[kMaxSlots] = {};             // --glow / --exposure / --y4m-depth 10 / --exr: each slot's linear frame; the glow's scratch
     void* glow_scratch[kMaxSlots] = {};
@@ -912,6 +965,10 @@ int create_slots(Slots& R, const Options& o, bool sink, hipStream_t stream0) {
         if (o.hdr_frame) HIPCHK(hipMalloc(&R.hdr[s], R.frame_bytes * sizeof(float)));
         if (o.y4m) { HIPCHK(hipMalloc(&R.yuv[s], o.yuv_bytes)); HIPCHK(hipHostMalloc(&R.yuv_host[s], o.yuv_bytes, hipHostMallocDefault)); }
         if (o.use_exr) { HIPCHK(hipMalloc(&R.exr[s], o.exr_bytes)); HIPCHK(hipHostMalloc(&R.exr_host[s], o.exr_bytes, hipHostMallocDefault)); }
+        if (o.use_png) {
+            HIPCHK(hipMalloc(&R.png[s], png_table_offset(o) + o.png_sum_bytes));
+            HIPCHK(hipHostMalloc(&R.png_host[s], png_table_offset(o) + o.png_sum_bytes, hipHostMallocDefault));
+        }
         for (int p = 0; p < kLayerPlaneCount; ++p)
             if (o.layer_planes & (1 << p)) HIPCHK(hipMalloc(&R.layer_plane[p][s], (size_t)o.w * o.h * 4 * kLayerPlanes[p].words));
         if (o.use_glow) HIPCHK(hipMalloc(&R.glow_scratch[s], o.glow_bytes));
@@ -932,6 +989,8 @@ void destroy_slots(Slots& R, int slots) {
         (void)hipFree(R.ad_scratch[s]); (void)hipFree(R.yuv[s]);
         if (R.yuv_host[s]) (void)hipHostFree(R.yuv_host[s]);
         (void)hipFree(R.exr[s]);
+        (void)hipFree(R.png[s]);
+        if (R.png_host[s]) (void)hipHostFree(R.png_host[s]);
         for (int p = 0; p < kLayerPlaneCount; ++p) (void)hipFree(R.layer_plane[p][s]);
         if (R.exr_host[s]) (void)hipHostFree(R.exr_host[s]);
         if (R.ad_count[s]) (void)hipHostFree(R.ad_count[s]);
@@ -1000,6 +1059,70 @@ int write_exr_file(const std::string& name, const uint8_t* payload, const Option
     }
     ok = (fclose(f) == 0) && ok;
     if (!ok || rename(tmp.c_str(), name.c_str()) != 0) { fprintf(stderr, "rrt_headless: exr: cannot write %s\n", name.c_str()); return 1; }
+    return 0;
+}
+
+// ---- PNG files (include/rrt_png.h, step 6; sinks.py: PNGSink)
+
+// One frame's file from its payload and row sums in host memory: the slices deflated (zlib, `level`, Z_FILTERED as PNGSink; raw
+// streams that end on a sync flush, the last on a finish) on up to `threads` threads, one IDAT each; the Adler-32 from the row sums.
+int write_png_file(const std::string& name, const uint8_t* payload, const uint32_t* row_sums, const Options& o, int threads) {
+    std::vector<std::vector<uint8_t>> pieces((size_t)o.png_slices);
+    uint32_t adler = 0;
+    if (rrt_png_adler32(row_sums, o.w, o.h, &o.png, &adler) != RRT_OK) return 1;
+    const size_t step = (size_t)o.png_slice_rows * o.png_stride;
+    std::atomic<int> next{0}, failed{0};
+    auto work = [&]() {
+        for (int i; (i = next.fetch_add(1)) < o.png_slices;) {
+            const bool first = i == 0, last = i == o.png_slices - 1;
+            const size_t from = (size_t)i * step, n = last ? o.png_bytes - from : step;
+            z_stream z;
+            memset(&z, 0, sizeof(z));
+            if (deflateInit2(&z, o.png_level, Z_DEFLATED, -15, 8, Z_FILTERED) != Z_OK) { failed.store(1); return; }
+            std::vector<uint8_t>& out = pieces[i];
+            out.resize((first ? 2 : 0) + deflateBound(&z, (uLong)n) + 16 + (last ? 4 : 0));
+            if (first) { out[0] = 0x78; out[1] = 0x01; }
+            z.next_in = const_cast<Bytef*>(payload + from);
+            z.avail_in = (uInt)n;
+            z.next_out = out.data() + (first ? 2 : 0);
+            z.avail_out = (uInt)(out.size() - (first ? 2 : 0) - (last ? 4 : 0));
+            const int rc = deflate(&z, last ? Z_FINISH : Z_SYNC_FLUSH);
+            const bool done = last ? rc == Z_STREAM_END : (rc == Z_OK && z.avail_in == 0 && z.avail_out != 0);
+            size_t at = (first ? 2 : 0) + (size_t)z.total_out;
+            deflateEnd(&z);
+            if (!done) { failed.store(1); return; }
+            if (last) for (int b = 3; b >= 0; --b) out[at++] = (uint8_t)(adler >> (8 * b));
+            out.resize(at);
+        }
+    };
+    const int n_threads = threads < o.png_slices ? threads : o.png_slices;
+    std::vector<std::thread> pool;
+    for (int t = 1; t < n_threads; ++t) pool.emplace_back(work);
+    work();
+    for (std::thread& t : pool) t.join();
+    if (failed.load()) { fprintf(stderr, "rrt_headless: png: deflate failed\n"); return 1; }
+    uint8_t header[256];
+    size_t header_bytes = 0;
+    if (rrt_png_header(&o.png, o.w, o.h, header, sizeof(header), &header_bytes) != RRT_OK) {
+        fprintf(stderr, "rrt_headless: png header: %s\n", rrt_png_last_error());
+        return 1;
+    }
+    const std::string tmp = name + ".tmp";
+    FILE* f = fopen(tmp.c_str(), "wb");
+    if (!f) { perror("fopen"); return 1; }
+    bool ok = fwrite(header, 1, header_bytes, f) == header_bytes;
+    auto chunk = [&](const char* type, const uint8_t* data, size_t n) {       // length, type, data, CRC-32 of type and data; big-endian
+        uint8_t b[8] = {(uint8_t)(n >> 24), (uint8_t)(n >> 16), (uint8_t)(n >> 8), (uint8_t)n, (uint8_t)type[0], (uint8_t)type[1], (uint8_t)type[2], (uint8_t)type[3]};
+        uLong crc = crc32(0L, b + 4, 4);
+        if (n) crc = crc32(crc, data, (uInt)n);
+        ok = ok && fwrite(b, 1, 8, f) == 8 && (n == 0 || fwrite(data, 1, n, f) == n);
+        const uint8_t c[4] = {(uint8_t)(crc >> 24), (uint8_t)(crc >> 16), (uint8_t)(crc >> 8), (uint8_t)crc};
+        ok = ok && fwrite(c, 1, 4, f) == 4;
+    };
+    for (const std::vector<uint8_t>& piece : pieces) chunk("IDAT", piece.data(), piece.size());
+    chunk("IEND", nullptr, 0);
+    ok = (fclose(f) == 0) && ok;
+    if (!ok || rename(tmp.c_str(), name.c_str()) != 0) { fprintf(stderr, "rrt_headless: png: cannot write %s\n", name.c_str()); return 1; }
     return 0;
 }
 
@@ -1162,7 +1285,7 @@ int launch_frame(Device& D, int slot, int k, const FrameView& v, const Options& 
         else rc = o.use_adaptive ? launch_adaptive(lin) : launch_sampled(false, lin);
         if (rc == RRT_OK && o.use_exposure) {     // the bytes -- and, in front of the glow, a 10-bit Y4M conversion or an EXR file, the scaled HDR in place
             if (o.auto_exposure) HIPCHK(hipStreamWaitEvent(st, R.exposed, 0));
-            rc = rrt_launch_exposure(o.use_glow ? nullptr : dst, o.use_glow || o.y4m10 || o.use_exr ? lin : nullptr, lin, w, h, &o.exposure, R.exposure_scratch,
+            rc = rrt_launch_exposure(o.use_glow ? nullptr : dst, o.use_glow || o.y4m10 || o.use_exr || o.png16 ? lin : nullptr, lin, w, h, &o.exposure, R.exposure_scratch,
                                      R.exposure_bytes, st);
             if (o.auto_exposure) HIPCHK(hipEventRecord(R.exposed, st));
         }
@@ -1370,6 +1493,10 @@ int main(int argc, char** argv) {
         if (fy && (fwrite("FRAME\n", 1, 6, fy) != 6 || fwrite(R.yuv_host[slot], 1, o.yuv_bytes, fy) != o.yuv_bytes))
             fprintf(stderr, "Warning: Frame write incomplete\n");
         if (o.use_exr && write_exr_file(frame_name(o.exr_path, delivered), static_cast<const uint8_t*>(R.exr_host[slot]), o, exr_threads)) return 1;
+        if (o.use_png) {
+            const uint8_t* png = static_cast<const uint8_t*>(R.png_host[slot]);
+            if (write_png_file(frame_name(o.png_path, delivered), png, reinterpret_cast<const uint32_t*>(png + png_table_offset(o)), o, exr_threads)) return 1;
+        }
         return 0;
     };
 
@@ -1412,6 +1539,14 @@ int main(int argc, char** argv) {
             else rc = rrt_launch_exr_from_hdr(R.exr[slot], static_cast<const float*>(R.hdr[slot]), o.w, o.h, &o.exr, dev[0].stream[slot]);
             if (rc != RRT_OK) { fprintf(stderr, "rrt_headless: exr: %s (%s)\n", rrt_status_string(rc), rrt_exr_last_error()); return 1; }
             HIPCHK(hipMemcpyAsync(R.exr_host[slot], R.exr[slot], o.exr_bytes, hipMemcpyDeviceToHost, dev[0].stream[slot]));
+        }
+        if (o.use_png) {    // the filtered scanlines and row sums of the assembled frame (depth 16: of its HDR as the last pass left it), then their copy
+            uint8_t* png = static_cast<uint8_t*>(R.png[slot]);
+            uint32_t* sums = reinterpret_cast<uint32_t*>(png + png_table_offset(o));
+            rc = o.png16 ? rrt_launch_png_from_hdr(png, sums, static_cast<const float*>(R.hdr[slot]), o.w, o.h, &o.png, dev[0].stream[slot])
+                         : rrt_launch_png_from_rgba8(png, sums, R.frame[slot], o.w, o.h, &o.png, dev[0].stream[slot]);
+            if (rc != RRT_OK) { fprintf(stderr, "rrt_headless: png: %s (%s)\n", rrt_status_string(rc), rrt_png_last_error()); return 1; }
+            HIPCHK(hipMemcpyAsync(R.png_host[slot], R.png[slot], png_table_offset(o) + o.png_sum_bytes, hipMemcpyDeviceToHost, dev[0].stream[slot]));
         }
         HIPCHK(hipEventRecord(R.done[slot], dev[0].stream[slot]));
     }

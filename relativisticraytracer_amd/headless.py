@@ -12,6 +12,7 @@
                    [--y4m-transfer sdr|pq [--hdr-white NITS] [--hdr-peak NITS] [--hdr-knee F]]]
            [--exr f.%04d.exr [--exr-type half|float] [--exr-compression none|zips|zip] [--exr-level 1..9]
                    [--exr-layers steps,horizon,transmittance,emission,direction,position|all]]
+           [--png f.%04d.png [--png-depth 8|16] [--png-filter adaptive|none|sub|up|average|paeth] [--png-level 1..9]]
     python -m torch.distributed.run --nproc-per-node 8 -m relativisticraytracer_amd.headless ...
 
 Per frame k = 1..N it does what `main()` does while recording: advance the fixed 1/24 s clock
@@ -197,6 +198,17 @@ def build_parser():
                     help="with --exr: per-ray data layers next to B, G, R in every file -- a comma-separated subset of "
                          "steps,horizon,transmittance,emission,direction,position, or all.  The frame is rendered by the debug launch; "
                          "the layers are stored as the march left them (the exposure scales B, G, R only).  The 1x pinhole frame only")
+    ap.add_argument("--png", default=None, metavar="PATTERN",
+                    help="also (or only) write every frame as a PNG file (include/rrt_png.h): RGB scanlines filtered, scored and summed "
+                         "on the device, deflated in slices on a thread pool.  PATTERN holds one frame field (f.%%04d.png); a plain "
+                         "name serves --frames 1")
+    # checked in check_png, not by argparse's `choices` or `type`: both drivers word their refusals alike
+    ap.add_argument("--png-depth", default=None, metavar="8|16",
+                    help="with --png: bits per sample (default 8).  8 converts the finished RGBA8 frame, in every mode; 16 tone-maps the "
+                         "frame's linear HDR to 16 bits (the whole-frame HDR path of --exposure): one GPU only, not with --glow")
+    ap.add_argument("--png-filter", default=None, metavar="adaptive|none|sub|up|average|paeth",
+                    help="with --png: the scanline filter -- adaptive (default) scores all five per row and keeps the best")
+    ap.add_argument("--png-level", default=None, metavar="1..9", help="with --png: the deflate level (default 4)")
     ap.add_argument("--init-timeout", type=float, default=300.0,
                     help="several ranks: seconds the process-group bring-up may take before the run exits non-zero with "
                          "the tracebacks of all threads, instead of hanging")
@@ -269,6 +281,7 @@ def check_args(ap, args, world):
         dof_k = args.motion_blur if args.motion_blur > 1 else (args.dof_samples or 8)
     check_y4m(ap, args, world)
     check_exr(ap, args, world)
+    check_png(ap, args, world)
     return pano, use_exposure, dof_k
 
 
@@ -355,6 +368,39 @@ def check_exr(ap, args, world):
         args.exr_layer_names = tuple(n for n in EXR_LAYERS if n in names)
 
 
+def check_png(ap, args, world):
+    """--png's refusals (rrt_headless.cpp words them alike); leaves args.png_format: (depth, filter, level) or None"""
+    from relativisticraytracer_amd.sinks import frame_fields, frame_name
+    args.png_format = None
+    if args.png is None:
+        if args.png_depth is not None or args.png_filter is not None or args.png_level is not None:
+            ap.error("--png-depth / --png-filter / --png-level need --png PATTERN")
+        return
+    if args.png_depth not in (None, "8", "16"):
+        ap.error("--png-depth 8 | 16")
+    if args.png_filter not in (None, "adaptive", "none", "sub", "up", "average", "paeth"):
+        ap.error("--png-filter adaptive | none | sub | up | average | paeth")
+    if args.png_level not in (None,) + tuple("123456789"):
+        ap.error("--png-level 1 ... 9")
+    depth = int(args.png_depth or 8)
+    if depth == 16:      # the frame's linear HDR, whole, on one GPU
+        if args.glow is not None:
+            ap.error("--png-depth 16 reads the frame's linear HDR and the glow tone-maps H + glow without storing it: not with --glow")
+        if world > 1:
+            ap.error("--png-depth 16: one GPU only (WORLD_SIZE > 1)")
+    fields = frame_fields(args.png)
+    if fields > 1:
+        ap.error("--png PATTERN: one frame field (%d or %0Nd)")
+    if fields == 0 and args.frames > 1:
+        ap.error("--png PATTERN needs a frame field (%04d) when --frames > 1: the frames would overwrite one another")
+    for k in range(1, max(args.frames, 1) + 1):
+        name = os.path.abspath(frame_name(args.png, k))
+        for other, flag in ((args.out, "--out"), (args.y4m, "--y4m"), (frame_name(args.exr, k) if args.exr is not None else None, "--exr")):
+            if other is not None and name == os.path.abspath(other):
+                ap.error(f"--png and {flag} name the same file")
+    args.png_format = (depth, args.png_filter or "adaptive", int(args.png_level or 4))
+
+
 # --exr-layers' names, in the order `all` lists them, and each one's channels: (name, type -- None: --exr-type's --, plane, word)
 EXR_LAYERS = {"steps": [("steps", "uint", "steps", 0)],
               "horizon": [("horizon", "half", "hit", 0)],
@@ -437,7 +483,8 @@ class Renderer:
         self.sampled = proj is not None or mb > 1 or ss > 1 or stereo is not None or dof_k > 0      # launch_sampled's kinds
         self.y4m10 = args.y4m_format is not None and args.y4m_format[2] == 10     # the Y4M frames come from the HDR: its whole-frame path
         self.exr = args.exr_format is not None        # the EXR frames are the HDR itself: the same path
-        self.post = glow is not None or exposure is not None or self.y4m10 or self.exr
+        self.png16 = args.png_format is not None and args.png_format[0] == 16      # the 16-bit PNG frames are tone-mapped from the HDR: the same path
+        self.post = glow is not None or exposure is not None or self.y4m10 or self.exr or self.png16
         # supersampled, blurred, glowed, panorama, stereo: single kernel, static order, no pool
         single = self.sampled or self.post
         # sample m looks through lens point bitrev_K(m): the spiral's radius grows with its index, the shutter's times with m
@@ -551,7 +598,7 @@ class Renderer:
         else:
             self.launch_sampled(frame, self.prms[0], hdr=hdr)
         if self.exposure is not None:
-            rrt.launch_exposure(None if glow is not None else frame, hdr if glow is not None or self.y4m10 or self.exr else None, hdr, self.w, self.h,
+            rrt.launch_exposure(None if glow is not None else frame, hdr if glow is not None or self.y4m10 or self.exr or self.png16 else None, hdr, self.w, self.h,
                                 self.exposure, self.exposure_scratch)
         if glow is not None:
             rrt.launch_glow(frame, hdr, self.w, self.h, glow, self.glow_scratch)
@@ -716,7 +763,26 @@ def main(argv=None):
         exr_host = torch.empty(exr.frame_bytes, dtype=torch.uint8, pin_memory=True)
         trace(f"exr sink {args.exr}: {exr_fmt.info()}, {exr.frame_bytes} bytes per frame, {exr.threads} deflate threads")
 
+    # --png: rank 0 filters the finished frame -- the RGBA8 frame, or at 16 bits the HDR render_post left -- into the file's scanlines
+    # on the device; the row sums travel behind the payload in the same copy, and the host is left with deflate
+    png = None
+    if rank == 0 and args.png_format is not None:
+        png_fmt = rrt.PngFormat(*args.png_format[:2])
+        png = sinks.PNGSink(args.png, w, h, png_fmt, level=args.png_format[2])
+        png_table = (png.frame_bytes + 15) & ~15
+        png_dev = torch.empty(png_table + png.row_sum_bytes, dtype=torch.uint8, device=dev)
+        png_host = torch.empty(png_table + png.row_sum_bytes, dtype=torch.uint8, pin_memory=True)
+        trace(f"png sink {args.png}: {png_fmt.info()}, {png.frame_bytes} bytes per frame in {png.n_slices} slices, {png.threads} deflate threads")
+
     def deliver(frame):
+        if png:         # on the current stream, behind the frame's last pass
+            if r.png16:
+                rrt.launch_png_from_hdr(png_dev, png_dev[png_table:], r.hdr, w, h, png_fmt)
+            else:
+                rrt.launch_png_from_rgba8(png_dev, png_dev[png_table:], frame, w, h, png_fmt)
+            png_host.copy_(png_dev, non_blocking=False)
+            data = png_host.numpy()
+            png.write(data[:png.frame_bytes], data[png_table:].view("uint32"))
         if exr:         # on the current stream, behind the frame's last pass
             if exr_layers is not None:
                 rrt.launch_exr_layers(exr_dev, exr_layers)
@@ -744,10 +810,10 @@ def main(argv=None):
         dog.arm(args.frame_timeout + (args.init_timeout if k == 1 else 0.0), f"frame {k}")    # frame 1 brings the communicator's channels up
         r.set_frame(k, nwin.table_id)
         frame = r.render_post() if r.post else (r.render_adaptive() if r.adaptive is not None else fs.step())
-        if (sink or y4m or exr) and frame is not None:
+        if (sink or y4m or exr or png) and frame is not None:
             deliver(frame)
     for frame in fs.drain():                # the frames still in flight, in order
-        if sink or y4m or exr:
+        if sink or y4m or exr or png:
             deliver(frame)
     torch.cuda.synchronize()
     trace("frames done")
@@ -761,6 +827,8 @@ def main(argv=None):
             sink.close()
         if exr:
             exr.close()
+        if png:
+            png.close()
         if y4m:
             y4m.close(rrt.yuv_hdr10_light_levels(light.cpu().numpy(), w, h) if y4m.hdr10 is not None else None)
         print(json.dumps({"frames": args.frames, "width": w, "height": h, "n_gpus": world, "seconds": round(dt, 4),

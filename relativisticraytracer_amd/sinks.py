@@ -203,6 +203,72 @@ class EXRSink:
             self.pool = None
 
 
+class PNGSink:
+    """One PNG file per frame (include/rrt_png.h, step 6): RGB, 8 or 16 bits.  `write` takes one frame's payload and row sums -- what
+    launch_png_from_rgba8 / launch_png_from_hdr (or their *_host forms) produce: the scanlines filtered already, the Adler-32 a fold
+    of the sums -- and is left with nothing but deflate: the payload in slices of png_slices rows, each a raw deflate stream of its
+    own that ends on a byte boundary (sync flush; the last one finishes), one IDAT per slice, side by side on a thread pool (zlib
+    releases the GIL).  The cut depends on the frame alone, so a file's bytes do not depend on `threads`.
+
+    `pattern`, NAME.tmp then rename, and `threads` as EXRSink's.  level: zlib's 1 ... 9; the strategy is STRATEGY for every file
+    (rrt_headless uses the same; DESIGN.md section 4, "PNG output", has the sizes behind the choice)."""
+
+    STRATEGY = zlib.Z_FILTERED
+
+    def __init__(self, pattern, width, height, fmt=None, level=4, threads=None):
+        from . import png
+        self.png = png
+        if frame_fields(pattern) > 1:
+            raise ValueError(f"{pattern!r}: one frame field (%d or %0Nd), not {frame_fields(pattern)}")
+        if not 1 <= int(level) <= 9:
+            raise ValueError("level: 1 ... 9")
+        self.pattern, self.level = pattern, int(level)
+        self.fmt = fmt if fmt is not None else png.PngFormat()
+        self.frame_bytes, self.stride, self.row_sum_bytes = png.png_frame_bytes(self.fmt, width, height, layout=True)
+        self.rows_per_slice, self.n_slices = png.png_slices(self.fmt, width, height)
+        self.header = png.png_header(self.fmt, width, height)
+        workers = int(threads) if threads is not None else min(16, len(os.sched_getaffinity(0)))
+        self.pool = ThreadPoolExecutor(workers) if workers > 1 and self.n_slices > 1 else None
+        self.width, self.height, self.frames, self.threads = width, height, 0, max(workers, 1)
+
+    def _slice(self, job):
+        piece, last = job
+        z = zlib.compressobj(self.level, zlib.DEFLATED, -15, 8, self.STRATEGY)
+        return z.compress(piece) + z.flush(zlib.Z_FINISH if last else zlib.Z_SYNC_FLUSH)
+
+    @staticmethod
+    def _chunk(kind, data):
+        return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data))
+
+    def write(self, payload, row_sums, index=None):
+        data = memoryview(np.ascontiguousarray(payload)).cast("B")
+        if data.nbytes != self.frame_bytes:
+            raise ValueError(f"a {self.width}x{self.height} frame of this format is {self.frame_bytes} bytes, got {data.nbytes}")
+        k = self.frames + 1 if index is None else int(index)
+        if self.frames > 0 and frame_fields(self.pattern) == 0:
+            raise ValueError(f"{self.pattern!r} has no frame field: a second frame would overwrite the first")
+        adler = self.png.png_adler32(row_sums, self.fmt, self.width, self.height)
+        step = self.rows_per_slice * self.stride
+        jobs = [(data[i * step:(i + 1) * step], i == self.n_slices - 1) for i in range(self.n_slices)]
+        pieces = list(self.pool.map(self._slice, jobs)) if self.pool is not None else [self._slice(j) for j in jobs]
+        pieces[0] = b"\x78\x01" + pieces[0]
+        pieces[-1] = pieces[-1] + struct.pack(">I", adler)
+        name = frame_name(self.pattern, k)
+        with open(name + ".tmp", "wb") as f:
+            f.write(self.header)
+            for p in pieces:
+                f.write(self._chunk(b"IDAT", p))
+            f.write(self._chunk(b"IEND", b""))
+        os.replace(name + ".tmp", name)
+        self.frames += 1
+        return name
+
+    def close(self):
+        if self.pool is not None:
+            self.pool.shutdown()
+            self.pool = None
+
+
 def open_sink(spec, width, height, fps=24):
     """spec: None | 'x.rgba' | 'dir/' (PPM per frame) | 'x.mp4' (ffmpeg)."""
     if not spec:
