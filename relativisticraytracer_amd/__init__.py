@@ -934,3 +934,8 @@ from . import png  # noqa: E402
 from .png import (PngFormat, launch_png_from_hdr, launch_png_from_rgba8, png_adler32, png_frame_bytes, png_from_hdr_host,  # noqa: E402,F401
                   png_from_rgba8_host, png_header, png_launch_geometry, png_slices, png_unfilter_host)
 __all__ += png.__all__
+
+# deflate streams made on the device: a library of its own (include/rrt_deflate.h, librrt_deflate.so), loaded on first use
+from . import deflate  # noqa: E402
+from .deflate import deflate_code_lengths, deflate_host, deflate_launch_geometry, deflate_plan, launch_deflate  # noqa: E402,F401
+__all__ += deflate.__all__

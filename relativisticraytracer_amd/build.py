@@ -29,6 +29,10 @@ PNG_LIB = os.path.join(LIBDIR, "librrt_png.so")         # include/rrt_png.h: the
 PNG_SRC = os.path.join(CSRC, "rrt_png.hip")
 PNG_HEADERS = [os.path.join(CSRC, "rrt_png_core.h"), os.path.join(CSRC, "rrt_yuv_core.h"), os.path.join(CSRC, "rrt_math.h"), os.path.join(PKG, "..", "include", "rrt_png.h"),
                os.path.join(PKG, "..", "include", "rrt.h")]
+DEFLATE_LIB = os.path.join(LIBDIR, "librrt_deflate.so")     # include/rrt_deflate.h: deflate streams on the device, a library of its own
+DEFLATE_SRC = os.path.join(CSRC, "rrt_deflate.hip")
+DEFLATE_HEADERS = [os.path.join(CSRC, "rrt_deflate_core.h"), os.path.join(CSRC, "rrt_math.h"), os.path.join(PKG, "..", "include", "rrt_deflate.h"),
+                   os.path.join(PKG, "..", "include", "rrt.h")]
 COMPAT_SRC = os.path.join(CSRC, "rrt_compat.cpp")     # launch_raymarch under the reference's mangled name (host only, g++)
 CAMERA_SRC = os.path.join(CSRC, "rrt_camera.cpp")     # camera basis / path playback (host only, g++)
 CHOOSER_SRC = os.path.join(CSRC, "rrt_path_chooser.cpp")   # per-window path choice of the animation drivers (host only, g++)
@@ -59,11 +63,11 @@ def hipcc_path():
 
 
 def is_stale():
-    libs = (LIB, TEST_LIB, YUV_LIB, EXR_LIB, PNG_LIB)
+    libs = (LIB, TEST_LIB, YUV_LIB, EXR_LIB, PNG_LIB, DEFLATE_LIB)
     if not all(os.path.exists(f) for f in libs):
         return True
     t = min(os.path.getmtime(f) for f in libs)
-    return any(os.path.getmtime(f) > t for f in SOURCES + HEADERS + [YUV_SRC] + YUV_HEADERS + [EXR_SRC] + EXR_HEADERS + [PNG_SRC] + PNG_HEADERS + [os.path.abspath(__file__)])
+    return any(os.path.getmtime(f) > t for f in SOURCES + HEADERS + [YUV_SRC] + YUV_HEADERS + [EXR_SRC] + EXR_HEADERS + [PNG_SRC] + PNG_HEADERS + [DEFLATE_SRC] + DEFLATE_HEADERS + [os.path.abspath(__file__)])
 
 
 def host_objects(outdir):
@@ -80,7 +84,7 @@ def build_lib(force=False, extra_flags=(), verbose=False):
     """librrt_hip.so (the product) and librrt_hip_test.so (+ test hooks), from the same sources.  Each hipcc compile runs in a
     directory of its own (lib/_obj_product, lib/_obj_test: flags that write fixed-name side files -- -save-temps -- cannot make
     the two collide); they run side by side, except under -save-temps, where they run one after the other.  BOTH libraries are
-    always built, so that is_stale() has one meaning -- and so are librrt_yuv.so, librrt_exr.so and librrt_png.so, one translation unit
+    always built, so that is_stale() has one meaning -- and so are librrt_yuv.so, librrt_exr.so, librrt_png.so and librrt_deflate.so, one translation unit
     each with the same flags, compiled next to them."""
     if not force and not is_stale():
         return LIB
@@ -101,7 +105,7 @@ def build_lib(force=False, extra_flags=(), verbose=False):
             subprocess.run(cmd, check=True, cwd=wd)
         else:
             jobs.append((cmd, subprocess.Popen(cmd, cwd=wd)))
-    for tag, src, out in (("yuv", YUV_SRC, YUV_LIB), ("exr", EXR_SRC, EXR_LIB), ("png", PNG_SRC, PNG_LIB)):
+    for tag, src, out in (("yuv", YUV_SRC, YUV_LIB), ("exr", EXR_SRC, EXR_LIB), ("png", PNG_SRC, PNG_LIB), ("deflate", DEFLATE_SRC, DEFLATE_LIB)):
         wd = os.path.join(LIBDIR, "_obj_" + tag)
         os.makedirs(wd, exist_ok=True)
         cmd = [hipcc_path()] + HIPCC_FLAGS + list(extra_flags) + [src, "-o", out]
@@ -153,14 +157,14 @@ HEADLESS_BIN = os.path.join(LIBDIR, "rrt_headless")
 
 
 def build_headless(force=False):
-    """The C++ headless driver (host code only: g++, links librrt_hip.so, librrt_yuv.so, librrt_exr.so, librrt_png.so, the HIP runtime, RCCL
+    """The C++ headless driver (host code only: g++, links librrt_hip.so, librrt_yuv.so, librrt_exr.so, librrt_png.so, librrt_deflate.so, the HIP runtime, RCCL
     and zlib, which deflates --exr's chunks and --png's slices)."""
     build_lib()
     if not force and os.path.exists(HEADLESS_BIN) and os.path.getmtime(HEADLESS_BIN) > max(
-            os.path.getmtime(HEADLESS_SRC), os.path.getmtime(LIB), os.path.getmtime(YUV_LIB), os.path.getmtime(EXR_LIB), os.path.getmtime(PNG_LIB)):
+            os.path.getmtime(HEADLESS_SRC), os.path.getmtime(LIB), os.path.getmtime(YUV_LIB), os.path.getmtime(EXR_LIB), os.path.getmtime(PNG_LIB), os.path.getmtime(DEFLATE_LIB)):
         return HEADLESS_BIN
     cmd = ["g++", "-std=c++17", "-O2", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", HEADLESS_SRC,
-           "-L" + LIBDIR, "-lrrt_hip", "-lrrt_yuv", "-lrrt_exr", "-lrrt_png", "-L/opt/rocm/lib", "-lamdhip64", "-lrccl", "-lz", "-pthread", "-Wl,-rpath," + LIBDIR + ":/opt/rocm/lib",
+           "-L" + LIBDIR, "-lrrt_hip", "-lrrt_yuv", "-lrrt_exr", "-lrrt_png", "-lrrt_deflate", "-L/opt/rocm/lib", "-lamdhip64", "-lrccl", "-lz", "-pthread", "-Wl,-rpath," + LIBDIR + ":/opt/rocm/lib",
            "-o", HEADLESS_BIN]
     subprocess.run(cmd, check=True)
     return HEADLESS_BIN

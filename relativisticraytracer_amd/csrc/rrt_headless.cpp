@@ -55,7 +55,7 @@
 //                                              to B, G, R in every file.  The frame is rendered by the debug launch, whose planes the
 //                                              layers read as the march left them; the exposure scales B, G, R only.  The 1x pinhole
 //                                              frame only)
-//                [--png f.%04d.png [--png-depth 8|16] [--png-filter adaptive|none|sub|up|average|paeth] [--png-level 1..9]]   (also,
+//                [--png f.%04d.png [--png-depth 8|16] [--png-filter adaptive|none|sub|up|average|paeth] [--png-level 1..9] [--png-deflate host|device]]   (also,
 //                                              or only, one PNG file per frame (include/rrt_png.h): RGB scanlines filtered, scored and
 //                                              summed on device 0, deflated in slices with zlib on the same thread pool.  Depth 8
 //                                              converts the assembled RGBA8 frame, in every mode; depth 16 tone-maps the frame's
@@ -104,6 +104,7 @@
 #include "../../include/rrt_yuv.h"
 #include "../../include/rrt_exr.h"
 #include "../../include/rrt_png.h"
+#include "../../include/rrt_deflate.h"
 
 namespace {
 
@@ -334,6 +335,9 @@ struct Options {               // what the command line sets (parse_options), th
     bool use_png = false, png16 = false; // depth 16 reads the frame's linear HDR: the whole-frame HDR path
     size_t png_bytes = 0, png_stride = 0, png_sum_bytes = 0;
     int32_t png_slice_rows = 0, png_slices = 0;
+    int png_deflate = 0;                 // --png-deflate: 0 host (zlib on the thread pool) | 1 device (include/rrt_deflate.h) | -1: not on the list
+    bool png_deflate_opt = false, png_level_opt = false;
+    size_t dfl_bound = 0, dfl_scratch = 0;          // --png-deflate device: the most bytes a frame's streams take; the launch's scratch
     std::string exr_layers_arg;          // --exr-layers LIST
     bool exr_layers_given = false;
 
@@ -458,7 +462,8 @@ int parse_options(int argc, char** argv, Options& o) {
         else if (a == "--png" && more) o.png_path = next();
         else if (a == "--png-depth") { o.png_depth = one_of(next(), {"8", "16"}); o.png_opts = true; }
         else if (a == "--png-filter") { o.png_filter = one_of(next(), {"adaptive", "none", "sub", "up", "average", "paeth"}); o.png_opts = true; }
-        else if (a == "--png-level") { o.png_level = one_of(next(), {"1", "2", "3", "4", "5", "6", "7", "8", "9"}) + 1; o.png_opts = true; }
+        else if (a == "--png-level") { o.png_level = one_of(next(), {"1", "2", "3", "4", "5", "6", "7", "8", "9"}) + 1; o.png_opts = true; o.png_level_opt = true; }
+        else if (a == "--png-deflate") { o.png_deflate = one_of(next(), {"host", "device"}); o.png_deflate_opt = true; }
         else if (a == "--exr-layers" && more) { o.exr_layers_arg = next(); o.exr_layers_given = true; }
         else if (a == "--exr-level") { o.exr_level = one_of(next(), {"1", "2", "3", "4", "5", "6", "7", "8", "9"}) + 1; o.exr_opts = true; }
         else if (a == "--all-effects") o.all_fx = 1; else if (a == "--fast") o.arith = RRT_ARITH_FAST;
@@ -791,10 +796,13 @@ int check_options(Options& o) {
     // frame's linear HDR, whole, on one device
     o.use_png = !o.png_path.empty();
     if (!o.use_png && o.png_opts) return refuse("usage: --png-depth / --png-filter / --png-level need --png PATTERN");
+    if (!o.use_png && o.png_deflate_opt) return refuse("usage: --png-deflate needs --png PATTERN");
     if (o.use_png) {
         if (o.png_depth < 0) return refuse("usage: --png-depth 8 | 16");
         if (o.png_filter < 0) return refuse("usage: --png-filter adaptive | none | sub | up | average | paeth");
         if (o.png_level < 1) return refuse("usage: --png-level 1 ... 9");
+        if (o.png_deflate < 0) return refuse("usage: --png-deflate host | device");
+        if (o.png_deflate == 1 && o.png_level_opt) return refuse("usage: --png-level is the host zlib's level: not with --png-deflate device");
         o.png16 = o.png_depth == 1;
         if (o.png16 && o.use_glow)
             return refuse("usage: --png-depth 16 reads the frame's linear HDR and the glow tone-maps H + glow without storing it: not with --glow");
@@ -815,6 +823,8 @@ int check_options(Options& o) {
         o.png.filter = filters[o.png_filter];
         if (rrt_png_frame_bytes(&o.png, o.w, o.h, &o.png_bytes, &o.png_stride, &o.png_sum_bytes) != RRT_OK ||
             rrt_png_slices(&o.png, o.w, o.h, &o.png_slice_rows, &o.png_slices) != RRT_OK) return refuse("bad arguments");
+        if (o.png_deflate == 1 && rrt_deflate_plan(o.png_bytes, (size_t)o.png_slice_rows * o.png_stride, nullptr, nullptr, &o.dfl_bound, &o.dfl_scratch) != RRT_OK)
+            return refuse("bad arguments");
     }
     o.hdr_frame = o.use_glow || o.use_exposure || o.y4m10 || o.use_exr || o.png16;
     // a supersampled launch is always the single kernel in the static order (include/rrt.h): no pool, no path choice, no tile order
@@ -828,6 +838,10 @@ int check_options(Options& o) {
 
 // --png: a slot's buffer holds the payload, then -- on the next 16 bytes -- the row sums; one copy brings both to the host
 size_t png_table_offset(const Options& o) { return (o.png_bytes + 15) & ~(size_t)15; }
+// --png-deflate device: the payload stays on the device.  A small buffer holds the streams' sizes and -- on the next 16 bytes -- the row
+// sums; it is copied first, and then exactly the streams' bytes, which land behind it in the pinned buffer
+size_t png_meta_offset(const Options& o) { return (4 * (size_t)o.png_slices + 15) & ~(size_t)15; }
+size_t png_meta_bytes(const Options& o) { return (png_meta_offset(o) + o.png_sum_bytes + 15) & ~(size_t)15; }
 
 struct Slots {                 // what device 0 owns per frame slot: gathered shards + assembled frame, the pinned host frame for the sink
     void* gathered[kMaxSlots] = {};
@@ -839,6 +853,9 @@ struct Slots {                 // what device 0 owns per frame slot: gathered sh
     void* exr_host[kMaxSlots] = {};
     void* png[kMaxSlots] = {};             // --png: each slot's filtered scanlines, then its row sums, on device 0, and their pinned host copy
     void* png_host[kMaxSlots] = {};
+    void* png_meta[kMaxSlots] = {};        // --png-deflate device: sizes and row sums, the streams, the launch's scratch
+    void* dfl_out[kMaxSlots] = {};
+    void* dfl_scratch[kMaxSlots] = {};
     void* layer_plane[kLayerPlaneCount][kMaxSlots] = {};      // --exr-layers: each slot's planes of the debug launch
     void* hdr[kMaxSlots] = {};             // --glow / --exposure / --y4m-depth 10 / --exr: each slot's linear frame; the glow's scratch
     void* glow_scratch[kMaxSlots] = {};
@@ -967,7 +984,12 @@ int create_slots(Slots& R, const Options& o, bool sink, hipStream_t stream0) {
         if (o.use_exr) { HIPCHK(hipMalloc(&R.exr[s], o.exr_bytes)); HIPCHK(hipHostMalloc(&R.exr_host[s], o.exr_bytes, hipHostMallocDefault)); }
         if (o.use_png) {
             HIPCHK(hipMalloc(&R.png[s], png_table_offset(o) + o.png_sum_bytes));
-            HIPCHK(hipHostMalloc(&R.png_host[s], png_table_offset(o) + o.png_sum_bytes, hipHostMallocDefault));
+            HIPCHK(hipHostMalloc(&R.png_host[s], o.png_deflate == 1 ? png_meta_bytes(o) + o.dfl_bound : png_table_offset(o) + o.png_sum_bytes, hipHostMallocDefault));
+            if (o.png_deflate == 1) {
+                HIPCHK(hipMalloc(&R.png_meta[s], png_meta_bytes(o)));
+                HIPCHK(hipMalloc(&R.dfl_out[s], o.dfl_bound));
+                HIPCHK(hipMalloc(&R.dfl_scratch[s], o.dfl_scratch));
+            }
         }
         for (int p = 0; p < kLayerPlaneCount; ++p)
             if (o.layer_planes & (1 << p)) HIPCHK(hipMalloc(&R.layer_plane[p][s], (size_t)o.w * o.h * 4 * kLayerPlanes[p].words));
@@ -990,6 +1012,9 @@ void destroy_slots(Slots& R, int slots) {
         if (R.yuv_host[s]) (void)hipHostFree(R.yuv_host[s]);
         (void)hipFree(R.exr[s]);
         (void)hipFree(R.png[s]);
+        (void)hipFree(R.png_meta[s]);
+        (void)hipFree(R.dfl_out[s]);
+        (void)hipFree(R.dfl_scratch[s]);
         if (R.png_host[s]) (void)hipHostFree(R.png_host[s]);
         for (int p = 0; p < kLayerPlaneCount; ++p) (void)hipFree(R.layer_plane[p][s]);
         if (R.exr_host[s]) (void)hipHostFree(R.exr_host[s]);
@@ -1064,6 +1089,33 @@ int write_exr_file(const std::string& name, const uint8_t* payload, const Option
 
 // ---- PNG files (include/rrt_png.h, step 6; sinks.py: PNGSink)
 
+// the file around its IDAT pieces: the header's chunks, one IDAT per piece, IEND; NAME.tmp, then renamed
+int write_png_pieces(const std::string& name, const std::vector<std::vector<uint8_t>>& pieces, const Options& o) {
+    uint8_t header[256];
+    size_t header_bytes = 0;
+    if (rrt_png_header(&o.png, o.w, o.h, header, sizeof(header), &header_bytes) != RRT_OK) {
+        fprintf(stderr, "rrt_headless: png header: %s\n", rrt_png_last_error());
+        return 1;
+    }
+    const std::string tmp = name + ".tmp";
+    FILE* f = fopen(tmp.c_str(), "wb");
+    if (!f) { perror("fopen"); return 1; }
+    bool ok = fwrite(header, 1, header_bytes, f) == header_bytes;
+    auto chunk = [&](const char* type, const uint8_t* data, size_t n) {       // length, type, data, CRC-32 of type and data; big-endian
+        uint8_t b[8] = {(uint8_t)(n >> 24), (uint8_t)(n >> 16), (uint8_t)(n >> 8), (uint8_t)n, (uint8_t)type[0], (uint8_t)type[1], (uint8_t)type[2], (uint8_t)type[3]};
+        uLong crc = crc32(0L, b + 4, 4);
+        if (n) crc = crc32(crc, data, (uInt)n);
+        ok = ok && fwrite(b, 1, 8, f) == 8 && (n == 0 || fwrite(data, 1, n, f) == n);
+        const uint8_t c[4] = {(uint8_t)(crc >> 24), (uint8_t)(crc >> 16), (uint8_t)(crc >> 8), (uint8_t)crc};
+        ok = ok && fwrite(c, 1, 4, f) == 4;
+    };
+    for (const std::vector<uint8_t>& piece : pieces) chunk("IDAT", piece.data(), piece.size());
+    chunk("IEND", nullptr, 0);
+    ok = (fclose(f) == 0) && ok;
+    if (!ok || rename(tmp.c_str(), name.c_str()) != 0) { fprintf(stderr, "rrt_headless: png: cannot write %s\n", name.c_str()); return 1; }
+    return 0;
+}
+
 // One frame's file from its payload and row sums in host memory: the slices deflated (zlib, `level`, Z_FILTERED as PNGSink; raw
 // streams that end on a sync flush, the last on a finish) on up to `threads` threads, one IDAT each; the Adler-32 from the row sums.
 int write_png_file(const std::string& name, const uint8_t* payload, const uint32_t* row_sums, const Options& o, int threads) {
@@ -1101,29 +1153,24 @@ int write_png_file(const std::string& name, const uint8_t* payload, const uint32
     work();
     for (std::thread& t : pool) t.join();
     if (failed.load()) { fprintf(stderr, "rrt_headless: png: deflate failed\n"); return 1; }
-    uint8_t header[256];
-    size_t header_bytes = 0;
-    if (rrt_png_header(&o.png, o.w, o.h, header, sizeof(header), &header_bytes) != RRT_OK) {
-        fprintf(stderr, "rrt_headless: png header: %s\n", rrt_png_last_error());
-        return 1;
+    return write_png_pieces(name, pieces, o);
+}
+
+// The same file from slices that are deflated already (--png-deflate device; sinks.py: PNGSink.write_streams): `streams` holds them back
+// to back, sizes[i] bytes each
+int write_png_streams(const std::string& name, const uint8_t* streams, const uint32_t* sizes, const uint32_t* row_sums, const Options& o) {
+    std::vector<std::vector<uint8_t>> pieces((size_t)o.png_slices);
+    uint32_t adler = 0;
+    if (rrt_png_adler32(row_sums, o.w, o.h, &o.png, &adler) != RRT_OK) return 1;
+    size_t at = 0;
+    for (int i = 0; i < o.png_slices; ++i) {
+        std::vector<uint8_t>& out = pieces[(size_t)i];
+        if (i == 0) { out.push_back(0x78); out.push_back(0x01); }
+        out.insert(out.end(), streams + at, streams + at + sizes[i]);
+        at += sizes[i];
+        if (i == o.png_slices - 1) for (int b = 3; b >= 0; --b) out.push_back((uint8_t)(adler >> (8 * b)));
     }
-    const std::string tmp = name + ".tmp";
-    FILE* f = fopen(tmp.c_str(), "wb");
-    if (!f) { perror("fopen"); return 1; }
-    bool ok = fwrite(header, 1, header_bytes, f) == header_bytes;
-    auto chunk = [&](const char* type, const uint8_t* data, size_t n) {       // length, type, data, CRC-32 of type and data; big-endian
-        uint8_t b[8] = {(uint8_t)(n >> 24), (uint8_t)(n >> 16), (uint8_t)(n >> 8), (uint8_t)n, (uint8_t)type[0], (uint8_t)type[1], (uint8_t)type[2], (uint8_t)type[3]};
-        uLong crc = crc32(0L, b + 4, 4);
-        if (n) crc = crc32(crc, data, (uInt)n);
-        ok = ok && fwrite(b, 1, 8, f) == 8 && (n == 0 || fwrite(data, 1, n, f) == n);
-        const uint8_t c[4] = {(uint8_t)(crc >> 24), (uint8_t)(crc >> 16), (uint8_t)(crc >> 8), (uint8_t)crc};
-        ok = ok && fwrite(c, 1, 4, f) == 4;
-    };
-    for (const std::vector<uint8_t>& piece : pieces) chunk("IDAT", piece.data(), piece.size());
-    chunk("IEND", nullptr, 0);
-    ok = (fclose(f) == 0) && ok;
-    if (!ok || rename(tmp.c_str(), name.c_str()) != 0) { fprintf(stderr, "rrt_headless: png: cannot write %s\n", name.c_str()); return 1; }
-    return 0;
+    return write_png_pieces(name, pieces, o);
 }
 
 // the deflate pool's size: the CPUs this process may run on, 16 at the most
@@ -1493,7 +1540,18 @@ int main(int argc, char** argv) {
         if (fy && (fwrite("FRAME\n", 1, 6, fy) != 6 || fwrite(R.yuv_host[slot], 1, o.yuv_bytes, fy) != o.yuv_bytes))
             fprintf(stderr, "Warning: Frame write incomplete\n");
         if (o.use_exr && write_exr_file(frame_name(o.exr_path, delivered), static_cast<const uint8_t*>(R.exr_host[slot]), o, exr_threads)) return 1;
-        if (o.use_png) {
+        if (o.use_png && o.png_deflate == 1) {      // the sizes and the row sums are here; the streams' bytes, and no more, follow now
+            const uint8_t* meta = static_cast<const uint8_t*>(R.png_host[slot]);
+            const uint32_t* sizes = reinterpret_cast<const uint32_t*>(meta);
+            size_t total = 0;
+            for (int i = 0; i < o.png_slices; ++i) total += sizes[i];
+            if (total > o.dfl_bound) { fprintf(stderr, "rrt_headless: png: the streams' sizes exceed their bound\n"); return 1; }
+            uint8_t* streams = static_cast<uint8_t*>(R.png_host[slot]) + png_meta_bytes(o);
+            HIPCHK(hipSetDevice(0));
+            HIPCHK(hipMemcpyAsync(streams, R.dfl_out[slot], total, hipMemcpyDeviceToHost, dev[0].stream[slot]));
+            HIPCHK(hipStreamSynchronize(dev[0].stream[slot]));
+            if (write_png_streams(frame_name(o.png_path, delivered), streams, sizes, reinterpret_cast<const uint32_t*>(meta + png_meta_offset(o)), o)) return 1;
+        } else if (o.use_png) {
             const uint8_t* png = static_cast<const uint8_t*>(R.png_host[slot]);
             if (write_png_file(frame_name(o.png_path, delivered), png, reinterpret_cast<const uint32_t*>(png + png_table_offset(o)), o, exr_threads)) return 1;
         }
@@ -1542,10 +1600,17 @@ int main(int argc, char** argv) {
         }
         if (o.use_png) {    // the filtered scanlines and row sums of the assembled frame (depth 16: of its HDR as the last pass left it), then their copy
             uint8_t* png = static_cast<uint8_t*>(R.png[slot]);
-            uint32_t* sums = reinterpret_cast<uint32_t*>(png + png_table_offset(o));
+            uint32_t* sums = o.png_deflate == 1 ? reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(R.png_meta[slot]) + png_meta_offset(o))
+                                                : reinterpret_cast<uint32_t*>(png + png_table_offset(o));
             rc = o.png16 ? rrt_launch_png_from_hdr(png, sums, static_cast<const float*>(R.hdr[slot]), o.w, o.h, &o.png, dev[0].stream[slot])
                          : rrt_launch_png_from_rgba8(png, sums, R.frame[slot], o.w, o.h, &o.png, dev[0].stream[slot]);
             if (rc != RRT_OK) { fprintf(stderr, "rrt_headless: png: %s (%s)\n", rrt_status_string(rc), rrt_png_last_error()); return 1; }
+            if (o.png_deflate == 1) {   // deflate behind the filtering, on the same stream; the payload is not copied
+                rc = rrt_launch_deflate(R.dfl_out[slot], static_cast<uint32_t*>(R.png_meta[slot]), R.dfl_scratch[slot], png, o.png_bytes,
+                                        (size_t)o.png_slice_rows * o.png_stride, 1, dev[0].stream[slot]);
+                if (rc != RRT_OK) { fprintf(stderr, "rrt_headless: png deflate: %s (%s)\n", rrt_status_string(rc), rrt_deflate_last_error()); return 1; }
+                HIPCHK(hipMemcpyAsync(R.png_host[slot], R.png_meta[slot], png_meta_bytes(o), hipMemcpyDeviceToHost, dev[0].stream[slot]));
+            } else
             HIPCHK(hipMemcpyAsync(R.png_host[slot], R.png[slot], png_table_offset(o) + o.png_sum_bytes, hipMemcpyDeviceToHost, dev[0].stream[slot]));
         }
         HIPCHK(hipEventRecord(R.done[slot], dev[0].stream[slot]));

@@ -12,7 +12,7 @@
                    [--y4m-transfer sdr|pq [--hdr-white NITS] [--hdr-peak NITS] [--hdr-knee F]]]
            [--exr f.%04d.exr [--exr-type half|float] [--exr-compression none|zips|zip] [--exr-level 1..9]
                    [--exr-layers steps,horizon,transmittance,emission,direction,position|all]]
-           [--png f.%04d.png [--png-depth 8|16] [--png-filter adaptive|none|sub|up|average|paeth] [--png-level 1..9]]
+           [--png f.%04d.png [--png-depth 8|16] [--png-filter adaptive|none|sub|up|average|paeth] [--png-level 1..9] [--png-deflate host|device]]
     python -m torch.distributed.run --nproc-per-node 8 -m relativisticraytracer_amd.headless ...
 
 Per frame k = 1..N it does what `main()` does while recording: advance the fixed 1/24 s clock
@@ -209,6 +209,10 @@ def build_parser():
     ap.add_argument("--png-filter", default=None, metavar="adaptive|none|sub|up|average|paeth",
                     help="with --png: the scanline filter -- adaptive (default) scores all five per row and keeps the best")
     ap.add_argument("--png-level", default=None, metavar="1..9", help="with --png: the deflate level (default 4)")
+    ap.add_argument("--png-deflate", default=None, metavar="host|device",
+                    help="with --png: where the slices are deflated -- host (default): zlib on a thread pool; device: include/rrt_deflate.h, "
+                         "Huffman codes and run lengths in HIP behind the filtering launch, so that only finished streams are copied and "
+                         "the host's threads stay free (larger files on noiseless frames; not with --png-level, which is zlib's)")
     ap.add_argument("--init-timeout", type=float, default=300.0,
                     help="several ranks: seconds the process-group bring-up may take before the run exits non-zero with "
                          "the tracebacks of all threads, instead of hanging")
@@ -375,6 +379,8 @@ def check_png(ap, args, world):
     if args.png is None:
         if args.png_depth is not None or args.png_filter is not None or args.png_level is not None:
             ap.error("--png-depth / --png-filter / --png-level need --png PATTERN")
+        if args.png_deflate is not None:
+            ap.error("--png-deflate needs --png PATTERN")
         return
     if args.png_depth not in (None, "8", "16"):
         ap.error("--png-depth 8 | 16")
@@ -382,6 +388,10 @@ def check_png(ap, args, world):
         ap.error("--png-filter adaptive | none | sub | up | average | paeth")
     if args.png_level not in (None,) + tuple("123456789"):
         ap.error("--png-level 1 ... 9")
+    if args.png_deflate not in (None, "host", "device"):
+        ap.error("--png-deflate host | device")
+    if args.png_deflate == "device" and args.png_level is not None:
+        ap.error("--png-level is the host zlib's level: not with --png-deflate device")
     depth = int(args.png_depth or 8)
     if depth == 16:      # the frame's linear HDR, whole, on one GPU
         if args.glow is not None:
@@ -399,6 +409,7 @@ def check_png(ap, args, world):
             if other is not None and name == os.path.abspath(other):
                 ap.error(f"--png and {flag} name the same file")
     args.png_format = (depth, args.png_filter or "adaptive", int(args.png_level or 4))
+    args.png_on_device = args.png_deflate == "device"
 
 
 # --exr-layers' names, in the order `all` lists them, and each one's channels: (name, type -- None: --exr-type's --, plane, word)
@@ -773,9 +784,36 @@ def main(argv=None):
         png_dev = torch.empty(png_table + png.row_sum_bytes, dtype=torch.uint8, device=dev)
         png_host = torch.empty(png_table + png.row_sum_bytes, dtype=torch.uint8, pin_memory=True)
         trace(f"png sink {args.png}: {png_fmt.info()}, {png.frame_bytes} bytes per frame in {png.n_slices} slices, {png.threads} deflate threads")
+        if args.png_on_device:
+            # --png-deflate device: the payload stays on the device.  One small buffer holds the streams' sizes and, on the next 16 bytes,
+            # the row sums: it is copied first, then exactly the streams' bytes
+            png_cut = png.rows_per_slice * png.stride
+            png_plan = rrt.deflate_plan(png.frame_bytes, png_cut)
+            png_sizes = (4 * png.n_slices + 15) & ~15
+            png_dev = torch.empty(png.frame_bytes, dtype=torch.uint8, device=dev)
+            png_meta = torch.empty(png_sizes + png.row_sum_bytes, dtype=torch.uint8, device=dev)
+            png_meta_host = torch.empty(png_sizes + png.row_sum_bytes, dtype=torch.uint8, pin_memory=True)
+            png_out = torch.empty(png_plan["out_bound"], dtype=torch.uint8, device=dev)
+            png_out_host = torch.empty(png_plan["out_bound"], dtype=torch.uint8, pin_memory=True)
+            png_scratch = torch.empty(png_plan["scratch_bytes"], dtype=torch.uint8, device=dev)
+            trace(f"png deflate on the device: {png_plan['segments']} segments, at most {png_plan['out_bound']} bytes per frame")
 
     def deliver(frame):
-        if png:         # on the current stream, behind the frame's last pass
+        if png and args.png_on_device:      # filtering, then deflate, on the current stream, behind the frame's last pass
+            sums = png_meta[png_sizes:]
+            if r.png16:
+                rrt.launch_png_from_hdr(png_dev, sums, r.hdr, w, h, png_fmt)
+            else:
+                rrt.launch_png_from_rgba8(png_dev, sums, frame, w, h, png_fmt)
+            rrt.launch_deflate(png_out, png_meta, png_scratch, png_dev, png.frame_bytes, png_cut, True)
+            png_meta_host.copy_(png_meta, non_blocking=False)
+            meta = png_meta_host.numpy()
+            sizes = meta[:4 * png.n_slices].view("uint32").astype("int64")
+            total = int(sizes.sum())
+            png_out_host[:total].copy_(png_out[:total], non_blocking=False)
+            streams, ends = png_out_host.numpy(), sizes.cumsum()
+            png.write_streams([streams[e - n:e] for n, e in zip(sizes.tolist(), ends.tolist())], meta[png_sizes:].view("uint32"))
+        elif png:       # on the current stream, behind the frame's last pass
             if r.png16:
                 rrt.launch_png_from_hdr(png_dev, png_dev[png_table:], r.hdr, w, h, png_fmt)
             else:

@@ -210,6 +210,8 @@ class PNGSink:
     own that ends on a byte boundary (sync flush; the last one finishes), one IDAT per slice, side by side on a thread pool (zlib
     releases the GIL).  The cut depends on the frame alone, so a file's bytes do not depend on `threads`.
 
+    `write_streams` takes the slices deflated already (include/rrt_deflate.h) and writes the same file around them.
+
     `pattern`, NAME.tmp then rename, and `threads` as EXRSink's.  level: zlib's 1 ... 9; the strategy is STRATEGY for every file
     (rrt_headless uses the same; DESIGN.md section 4, "PNG output", has the sizes behind the choice)."""
 
@@ -251,6 +253,21 @@ class PNGSink:
         step = self.rows_per_slice * self.stride
         jobs = [(data[i * step:(i + 1) * step], i == self.n_slices - 1) for i in range(self.n_slices)]
         pieces = list(self.pool.map(self._slice, jobs)) if self.pool is not None else [self._slice(j) for j in jobs]
+        return self._file(pieces, adler, k)
+
+    def write_streams(self, streams, row_sums, index=None):
+        """The same file from slices that are deflated already: `streams` holds one raw deflate stream per slice of png_slices, each
+        ending on a byte boundary, the last one finished -- what launch_deflate (or deflate_host) makes of the payload with
+        stream_bytes = rows_per_slice * stride.  Nothing is deflated here and no thread is used."""
+        pieces = [bytes(s) for s in streams]
+        if len(pieces) != self.n_slices:
+            raise ValueError(f"a {self.width}x{self.height} frame of this format is {self.n_slices} streams, got {len(pieces)}")
+        k = self.frames + 1 if index is None else int(index)
+        if self.frames > 0 and frame_fields(self.pattern) == 0:
+            raise ValueError(f"{self.pattern!r} has no frame field: a second frame would overwrite the first")
+        return self._file(pieces, self.png.png_adler32(row_sums, self.fmt, self.width, self.height), k)
+
+    def _file(self, pieces, adler, k):
         pieces[0] = b"\x78\x01" + pieces[0]
         pieces[-1] = pieces[-1] + struct.pack(">I", adler)
         name = frame_name(self.pattern, k)

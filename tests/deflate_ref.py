@@ -1,0 +1,402 @@
+"""The definition of include/rrt_deflate.h restated in Python, from the header's text and RFC 1951 alone: the cuts, the greedy
+distance-1 tokens, lengths(counts, limit), the canonical codes, the run-length coded header, the stored fallback, the trailer.
+Sequential and plain: nothing here knows of chunks, threads or scans.  Also the fixtures the host and the GPU tests share, and
+zlib's own Z_RLE streams at the same cuts, the yardstick of the size condition."""
+import zlib
+
+import numpy as np
+
+SEGMENT = 32768
+CHUNK = 128                    # bytes per thread of the kernel: the fixtures put run ends on both sides of its multiples
+LL_SYMBOLS = 286
+EOB = 256
+CL_ORDER = (16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15)
+# RFC 1951, section 3.2.5: symbols 257 ... 285
+LENGTH_BASE = (3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258)
+LENGTH_EXTRA = (0,) * 8 + (1,) * 4 + (2,) * 4 + (3,) * 4 + (4,) * 4 + (5,) * 4 + (0,)
+
+
+def cuts(n, stream_bytes):
+    """[[(start, end) of every segment] of every stream]"""
+    if n == 0:
+        return [[(0, 0)]]
+    out = []
+    for s0 in range(0, n, stream_bytes):
+        s1 = min(s0 + stream_bytes, n)
+        out.append([(a, min(a + SEGMENT, s1)) for a in range(s0, s1, SEGMENT)])
+    return out
+
+
+def tokens(b):
+    """step 2: literals as 0 ... 255, match(L) as 1000 + L"""
+    m = len(b)
+    if m == 0:
+        return []
+    a = np.frombuffer(bytes(b), np.uint8)
+    change = np.flatnonzero(a[1:] != a[:-1]) + 1
+    ends = np.empty(m, np.int64)                     # the end of the run of equal bytes each position lies in
+    bounds = np.concatenate(([0], change, [m]))
+    for lo, hi in zip(bounds[:-1], bounds[1:]):
+        ends[lo:hi] = hi
+    out, p = [], 0
+    raw = a.tolist()
+    ends = ends.tolist()
+    while p < m:
+        L = 0
+        if p > 0 and raw[p] == raw[p - 1]:
+            L = min(ends[p] - p, 258)
+        if L >= 3:
+            out.append(1000 + L)
+            p += L
+        else:
+            out.append(raw[p])
+            p += 1
+    return out
+
+
+def length_symbol(L):
+    """(symbol, extra bits, extra value) of a match of L bytes"""
+    if L == 258:
+        return 285, 0, 0
+    k = max(i for i, base in enumerate(LENGTH_BASE[:-1]) if base <= L)
+    return 257 + k, LENGTH_EXTRA[k], L - LENGTH_BASE[k]
+
+
+def lengths(counts, limit):
+    """step 4: (lengths, halvings)"""
+    c = [int(x) for x in counts]
+    if sum(1 for x in c if x) == 1:
+        c[min(i for i, x in enumerate(c) if x == 0)] = 1
+    halvings = 0
+    while True:
+        leaves = sorted((x, i) for i, x in enumerate(c) if x)
+        k = len(leaves)
+        if k == 0:
+            return [0] * len(c), 0
+        weight = [x for x, _ in leaves]
+        parent = [0] * (2 * k - 1)
+        leaf, inner = 0, k
+        for node in range(k, 2 * k - 1):
+            total = 0
+            for _ in range(2):
+                if leaf < k and (inner >= len(weight) or weight[leaf] <= weight[inner]):
+                    v, leaf = leaf, leaf + 1
+                else:
+                    v, inner = inner, inner + 1
+                total += weight[v]
+                parent[v] = node
+            weight.append(total)
+        depth = [0] * (2 * k - 1)
+        for v in range(2 * k - 3, -1, -1):
+            depth[v] = depth[parent[v]] + 1
+        if max(depth[:k]) > limit:
+            c = [(x + 1) >> 1 if x else 0 for x in c]
+            halvings += 1
+            continue
+        out = [0] * len(c)
+        for r, (_, i) in enumerate(leaves):
+            out[i] = depth[r]
+        return out, halvings
+
+
+def codes(lens):
+    """step 5: RFC 1951 section 3.2.2, then bit-reversed"""
+    per = [0] * 17
+    for l in lens:
+        per[l] += 1
+    per[0] = 0
+    nxt, code = [0] * 17, 0
+    for bits in range(1, 16):
+        code = (code + per[bits - 1]) << 1
+        nxt[bits] = code
+    out = []
+    for l in lens:
+        if l == 0:
+            out.append(0)
+            continue
+        c = nxt[l]
+        nxt[l] += 1
+        out.append(int(format(c, f"0{l}b")[::-1], 2))
+    return out
+
+
+def code_length_sequence(seq):
+    """step 6's run-length rule: [(symbol, extra value)]"""
+    out, i = [], 0
+    while i < len(seq):
+        v, run = seq[i], 1
+        while i + run < len(seq) and seq[i + run] == v:
+            run += 1
+        i += run
+        if v == 0:
+            while run >= 11:
+                t = min(run, 138)
+                out.append((18, t - 11))
+                run -= t
+            if run >= 3:
+                out.append((17, run - 3))
+                run = 0
+            out += [(0, 0)] * run
+        else:
+            out.append((v, 0))
+            run -= 1
+            while run >= 3:
+                t = min(run, 6)
+                out.append((16, t - 3))
+                run -= t
+            out += [(v, 0)] * run
+    return out
+
+
+class Bits:
+    """an LSB-first bit stream: (value, bits) pairs, packed at the end"""
+
+    def __init__(self):
+        self.values, self.sizes = [], []
+
+    def put(self, value, bits):
+        if bits:
+            self.values.append(value)
+            self.sizes.append(bits)
+
+    def total(self):
+        return sum(self.sizes)
+
+    def pad(self):
+        self.put(0, -self.total() % 8)
+
+    def bytes(self):
+        v, s = np.array(self.values, np.int64), np.array(self.sizes, np.int64)
+        pos = np.concatenate(([0], np.cumsum(s)[:-1]))
+        bit = np.zeros(int(s.sum()), np.uint8)
+        for k in range(int(s.max()) if len(s) else 0):
+            sel = s > k
+            bit[pos[sel] + k] = (v[sel] >> k) & 1
+        return np.packbits(bit, bitorder="little").tobytes()
+
+
+def fragment(b, final, info=None):
+    """the fragment of segment b; `info` receives what the tests ask the restatement about"""
+    b = bytes(b)
+    m = len(b)
+    out = Bits()
+    note = {"m": m, "stored": False, "ll_halvings": 0, "cl_halvings": 0, "margin": None}
+    if m > 0:
+        toks = tokens(b)
+        counts = [0] * LL_SYMBOLS
+        counts[EOB] = 1
+        for t in toks:
+            counts[t if t < 1000 else length_symbol(t - 1000)[0]] += 1
+        ll, note["ll_halvings"] = lengths(counts, 15)
+        ll_code = codes(ll)
+        nll = max(257, max(i for i, l in enumerate(ll) if l) + 1)
+        seq = code_length_sequence(ll[:nll] + [1, 1])
+        cl_counts = [0] * 19
+        for sym, _ in seq:
+            cl_counts[sym] += 1
+        cl, note["cl_halvings"] = lengths(cl_counts, 7)
+        cl_code = codes(cl)
+        ncl = max(4, max(i for i, sym in enumerate(CL_ORDER) if cl[sym]) + 1)
+        out.put(0, 1)
+        out.put(2, 2)
+        out.put(nll - 257, 5)
+        out.put(1, 5)
+        out.put(ncl - 4, 4)
+        for sym in CL_ORDER[:ncl]:
+            out.put(cl[sym], 3)
+        for sym, extra in seq:
+            out.put(cl_code[sym], cl[sym])
+            out.put(extra, {16: 2, 17: 3, 18: 7}.get(sym, 0))
+        for t in toks:
+            if t < 1000:
+                out.put(ll_code[t], ll[t])
+            else:
+                sym, eb, extra = length_symbol(t - 1000)
+                out.put(ll_code[sym], ll[sym])
+                out.put(extra, eb)
+                out.put(0, 1)                      # distance 1
+        out.put(ll_code[EOB], ll[EOB])
+        D = (out.total() + 3 + 7) // 8 + 4
+        note["margin"] = D - (m + 10)
+        if D >= m + 10:
+            note["stored"] = True
+            out = Bits()
+            out.put(0, 3)
+            out.pad()
+            out.put(m, 16)
+            out.put(m ^ 0xffff, 16)
+            for v in b:
+                out.put(v, 8)
+    out.put(1 if final else 0, 1)
+    out.put(0, 2)
+    out.pad()
+    out.put(0, 16)
+    out.put(0xffff, 16)
+    if info is not None:
+        info.append(note)
+    return out.bytes()
+
+
+_cache = {}
+
+
+def deflate(data, stream_bytes, finish, info=None):
+    """the streams of `data`: a list of bytes objects"""
+    data = bytes(data)
+    layout = cuts(len(data), stream_bytes)
+    streams = []
+    for j, segs in enumerate(layout):
+        parts = []
+        for i, (a, b) in enumerate(segs):
+            final = bool(finish) and j == len(layout) - 1 and i == len(segs) - 1
+            key = (data[a:b], final)
+            if key not in _cache:
+                notes = []
+                _cache[key] = (fragment(data[a:b], final, notes), notes[0])
+            parts.append(_cache[key][0])
+            if info is not None:
+                info.append(_cache[key][1])
+        streams.append(b"".join(parts))
+    return streams
+
+
+def zlib_rle_size(data, stream_bytes, finish):
+    """zlib's own size: level 4, Z_RLE, a full flush at every cut of `cuts` (a finish at the last one when asked)"""
+    data = bytes(data)
+    layout = cuts(len(data), stream_bytes)
+    total = 0
+    for j, segs in enumerate(layout):
+        z = zlib.compressobj(4, zlib.DEFLATED, -15, 8, zlib.Z_RLE)
+        for i, (a, b) in enumerate(segs):
+            last = bool(finish) and j == len(layout) - 1 and i == len(segs) - 1
+            total += len(z.compress(data[a:b])) + len(z.flush(zlib.Z_FINISH if last else zlib.Z_FULL_FLUSH))
+    return total
+
+
+# ---- fixtures
+
+def ramp(n, step=7, start=3, values=251):
+    """bytes without two equal neighbours, `values` different ones"""
+    return ((np.arange(n, dtype=np.int64) * step + start) % values).astype(np.uint8)
+
+
+def put_run(a, lo, hi):
+    """bytes lo ... hi - 1 of `a` become one value that differs from both neighbours: a maximal run of exactly hi - lo"""
+    around = {int(a[lo - 1]) if lo > 0 else -1, int(a[hi]) if hi < len(a) else -1}
+    a[lo:hi] = next(v for v in (0, 255, 254) if v not in around)
+
+
+RUNS = (3, 4, 258, 259, 260, 261, 262, 517, 520)
+
+
+def laplace(rng, n, scale=3.0):
+    return np.round(rng.laplace(0.0, scale, n)).astype(np.int64).astype(np.uint8)
+
+
+def fibonacci_bytes(k):
+    """k byte values with Fibonacci counts 1, 2, 3, 5, ... -- end-of-block is the sequence's first 1: with a second byte of count 1
+    every merge would meet a tie that the leaf wins, and the tree would stay shallow --, arranged so that no three equal bytes are
+    adjacent (all literals): the Huffman tree is a chain of depth k"""
+    fib = [1, 1]
+    while len(fib) < k + 1:
+        fib.append(fib[-1] + fib[-2])
+    left = {v: fib[v + 1] for v in range(k)}
+    out = []
+    while any(left.values()):
+        banned = out[-1] if len(out) >= 2 and out[-1] == out[-2] else None
+        v = max((s for s in left if left[s] and s != banned), key=lambda s: left[s])
+        out.append(v)
+        left[v] -= 1
+    return np.array(out, np.uint8)
+
+
+def alphabet_noise(rng, n, size):
+    return rng.integers(0, size, n).astype(np.uint8)
+
+
+def decision_pair(rng_seed=11, m=400):
+    """two inputs of m bytes on either side of step 8's decision, the closest the search finds: (dynamic, stored), with their margins
+    D - (m + 10) (negative: dynamic)"""
+    best = {}
+    for size in range(2, 257, 2):
+        data = alphabet_noise(np.random.default_rng(rng_seed), m, size)
+        notes = []
+        fragment(data.tobytes(), False, notes)
+        side, margin = notes[0]["stored"], notes[0]["margin"]
+        if side not in best or abs(margin) < abs(best[side][1]):
+            best[side] = (data, margin)
+    return best[False], best[True]
+
+
+def synthetic_fixtures():
+    """{name: (bytes as uint8 array, stream_bytes)}: every case of the issue but the real payloads"""
+    rng = np.random.default_rng(1951)
+    fx = {}
+    for n in range(5):
+        fx[f"n={n}"] = (rng.integers(0, 256, n).astype(np.uint8), 7)                    # stream_bytes > n, too
+    # runs at the start of a segment: streams of 600 bytes, each led by one run.  The filler has 13 values: a few hundred bytes of
+    # 251 equally likely ones are a case for fixed-code blocks, which zlib has and the definition has not (35 bytes over the size
+    # condition on this fixture) -- the condition's margin allows for that on tiny inputs only
+    a = np.concatenate([ramp(600, 5, 17 + i, 13) for i in range(len(RUNS))])
+    for i, r in enumerate(RUNS):
+        put_run(a, 600 * i, 600 * i + r)
+    fx["runs at segment starts"] = (a, 600)
+    a = ramp(700 * len(RUNS))
+    for i, r in enumerate(RUNS):
+        put_run(a, 700 * i + 1 + i, 700 * i + 1 + i + r)
+    fx["runs behind another byte"] = (a, len(a) + 5)
+    # runs across the kernel's 128-byte chunks: both ends off the grid, an end on it, a start on it, several chunks long
+    a = ramp(4096)
+    for lo, hi in ((120, 140), (250, 262), (380, 900), (1000, 1024), (1152, 1160), (1279, 1281), (1400, 1400 + 258 + 1), (2047, 2049 + 258)):
+        put_run(a, lo, hi)
+    fx["runs across chunk boundaries"] = (a, 1 << 20)
+    a = ramp(40000)
+    put_run(a, 32700, 32900)                                    # the second segment restarts with a literal
+    fx["run across the segment boundary"] = (a, 1 << 20)
+    for n in (32767, 32768, 32769, 65541):
+        fx[f"n={n}"] = (laplace(rng, n), 1 << 20)
+    for bpp, rows, per in ((3, 9, 4), (6, 9, 2)):                 # stride-like odd cuts
+        stride = 1 + bpp * 67
+        fx[f"stride {stride}"] = (laplace(rng, stride * rows, 1.5), stride * per)
+    fx["last stream of 1 byte"] = (laplace(rng, 1001), 500)
+    fx["300 streams of 1 byte"] = (rng.integers(0, 4, 300).astype(np.uint8), 1)
+    fx["noise"] = (rng.integers(0, 256, 5000).astype(np.uint8), 1 << 20)
+    (dyn, _), (sto, _) = decision_pair()
+    fx["decision: dynamic"] = (dyn, 1 << 20)
+    fx["decision: stored"] = (sto, 1 << 20)
+    fx["zeros"] = (np.zeros(70000, np.uint8), 1 << 20)
+    fx["two values"] = (np.tile(np.array([3, 200], np.uint8), 3000), 4000)
+    # 16 byte values and end-of-block are 17 leaves in a chain: a literal tree 16 deep, the smallest that exceeds 15.  (The arrangement
+    # is largest-count-first, so the input is far from stationary.  zlib starts a new block every 16 383 tokens, with a tree of its
+    # own; the definition has one block per segment.  With 19 values, 17 709 literals, that second tree alone makes zlib's stream 6.9 %
+    # smaller -- 5443 against 5820 bytes, and 5818 with memLevel 9, where zlib keeps one block too.  The size condition's yardstick is
+    # zlib as it is, so this fixture stays below one zlib block; the halving rule itself costs 4 bytes here.)
+    fx["fibonacci"] = (fibonacci_bytes(16), 1 << 20)
+    runs = rng.integers(0, 6, 3000).astype(np.uint8)
+    fx["random runs"] = (np.repeat(runs, rng.integers(1, 40, 3000)), 30011)
+    return fx
+
+
+def payload_fixtures(po):
+    """the PNG library's restated payloads at 67x9 and 131x40, depth 8 and 16, all six filter settings, cut as PNGSink cuts them"""
+    import png_ref as pr
+    rng = np.random.default_rng(2026)
+    fx = {}
+    for w, h in ((67, 9), (131, 40)):
+        f8, f16 = pr.rgba8_frame(rng, w, h), pr.hdr_frame(rng, w, h)
+        for depth, raw in ((8, pr.raw_from_rgba8(f8)), (16, pr.raw_from_hdr(po, f16))):
+            for name in pr.FILTERS:
+                pay, _, _ = pr.payload(raw, 3 * depth // 8, name)
+                rows, _ = pr.slices(pay.shape[1], h)
+                fx[f"png {w}x{h} depth {depth} {name}"] = (np.ascontiguousarray(pay).ravel(), rows * pay.shape[1])
+    return fx
+
+
+_fixtures = {}
+
+
+def fixtures(po):
+    if not _fixtures:
+        _fixtures.update(synthetic_fixtures())
+        _fixtures.update(payload_fixtures(po))
+    return _fixtures
