@@ -85,7 +85,8 @@ int rrt_deflate_code_lengths_host(const uint32_t* counts, int n_symbols, int lim
 
 /* The definition on the device: d_out receives the streams back to back, compacted (at most out_bound bytes; nothing beyond the
  * streams' total is written), d_stream_sizes one uint32 per stream, both from d_src's n bytes (d_src may be NULL when n = 0).
- * d_scratch: scratch_bytes bytes, 16-byte aligned; its contents before and after are meaningless.  finish: 0 | 1, step 9's F. */
+ * d_scratch: scratch_bytes bytes, 16-byte aligned; its contents before and after are meaningless -- another launch's leftovers are
+ * as good as any.  d_out and d_src need no alignment; no byte in front of d_out is written.  finish: 0 | 1, step 9's F. */
 int rrt_launch_deflate(void* d_out, uint32_t* d_stream_sizes, void* d_scratch, const void* d_src, size_t n, size_t stream_bytes, int finish, void* stream);
 
 /* The same bytes and sizes on HOST memory, from the source the kernels run; *total (may be NULL) receives the streams' bytes */

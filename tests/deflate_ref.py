@@ -240,8 +240,8 @@ def fragment(b, final, info=None):
 _cache = {}
 
 
-def deflate(data, stream_bytes, finish, info=None):
-    """the streams of `data`: a list of bytes objects"""
+def fragments(data, stream_bytes, finish, info=None):
+    """[[the fragment of every segment] of every stream]"""
     data = bytes(data)
     layout = cuts(len(data), stream_bytes)
     streams = []
@@ -256,8 +256,29 @@ def deflate(data, stream_bytes, finish, info=None):
             parts.append(_cache[key][0])
             if info is not None:
                 info.append(_cache[key][1])
-        streams.append(b"".join(parts))
+        streams.append(parts)
     return streams
+
+
+def deflate(data, stream_bytes, finish, info=None):
+    """the streams of `data`: a list of bytes objects"""
+    return [b"".join(parts) for parts in fragments(data, stream_bytes, finish, info)]
+
+
+def first_difference(got, data, stream_bytes, finish):
+    """where streams `got` first leave the restatement's: (stream, segment of that stream, byte of that segment's fragment), or None"""
+    for j, (x, parts) in enumerate(zip(got, fragments(data, stream_bytes, finish))):
+        want = b"".join(parts)
+        if x == want:
+            continue
+        k = min(len(x), len(want))
+        differ = np.flatnonzero(np.frombuffer(x, np.uint8)[:k] != np.frombuffer(want, np.uint8)[:k])
+        at = int(differ[0]) if differ.size else k
+        for i, part in enumerate(parts):
+            if at < len(part) or i == len(parts) - 1:
+                return j, i, at
+            at -= len(part)
+    return None
 
 
 def zlib_rle_size(data, stream_bytes, finish):
@@ -391,6 +412,84 @@ def payload_fixtures(po):
                 fx[f"png {w}x{h} depth {depth} {name}"] = (np.ascontiguousarray(pay).ravel(), rows * pay.shape[1])
     return fx
 
+
+# ---- the large fixtures: full-size segments, by the hundred.  Not part of fixtures(): tests of their own run them.
+
+LARGE_SEED = 1952
+POOL = ("laplace 3", "laplace 1.5", "noise", "250 values", "zeros", "random runs", "two values", "every symbol")
+# {name: (stream_bytes, streams before the last, the last stream's bytes)}.  `three per stream`: 541 segments, three rounds of
+# deflate_offsets whose boundaries 256 and 512 fall inside streams, a last stream of 1 segment against 3.  `two per stream`: 599
+# segments in 300 streams, the size loop's second round at per_stream = 2, full fragments next to 11-byte ones.  `frame cut`: a 4K
+# frame's shape in small, 34 segments per stream and a last stream of 16; 543 full-size segments, more than 2 x 256 CUs hold at once
+# (tests/test_deflate_geometry.py keeps each on its branch)
+LARGE_CUTS = {
+    "three per stream": (2 * SEGMENT + 40, 180, 100),
+    "two per stream": (SEGMENT + 1, 299, SEGMENT),
+    "frame cut": (33 * SEGMENT + 199, 16, 16 * SEGMENT - 5),
+}
+LARGE_SINGLE = {"full segment stored": "noise", "full segment near stored": "250 values", "full segment every symbol": "every symbol"}
+
+
+def margin(block):
+    """step 8's D - (m + 10) of one segment"""
+    notes = []
+    fragment(bytes(block), False, notes)
+    return notes[0]["margin"]
+
+
+def every_symbol_block():
+    """a segment whose tokens use all 286 literal/length symbols: a ramp over the 256 byte values, and one run of base + 1 bytes --
+    a literal and match(base) -- per length symbol 257 ... 285"""
+    a = ramp(SEGMENT, 7, 3, 256)
+    for k, base in enumerate(LENGTH_BASE):
+        put_run(a, 100 + 1000 * k, 100 + 1000 * k + base + 1)
+    return a
+
+
+_pool = {}
+
+
+def pool():
+    """{name: a block of SEGMENT bytes}, seeded"""
+    if not _pool:
+        rng = np.random.default_rng(LARGE_SEED)
+        _pool["laplace 3"] = laplace(rng, SEGMENT, 3.0)
+        _pool["laplace 1.5"] = laplace(rng, SEGMENT, 1.5)
+        _pool["noise"] = alphabet_noise(rng, SEGMENT, 256)
+        # 250 equally likely values: a dynamic block a few dozen bytes short of the stored one.  The first seed whose margin is -200 ... -1
+        _pool["250 values"] = next(b for b in (alphabet_noise(np.random.default_rng(LARGE_SEED + k), SEGMENT, 250) for k in range(64))
+                                   if -200 <= margin(b) <= -1)
+        _pool["zeros"] = np.zeros(SEGMENT, np.uint8)
+        runs = rng.integers(0, 6, SEGMENT).astype(np.uint8)
+        _pool["random runs"] = np.repeat(runs, rng.integers(1, 40, SEGMENT))[:SEGMENT].copy()
+        _pool["two values"] = np.tile(np.array([3, 200], np.uint8), SEGMENT // 2)
+        _pool["every symbol"] = every_symbol_block()
+        assert tuple(_pool) == POOL and all(b.size == SEGMENT and b.dtype == np.uint8 for b in _pool.values())
+    return _pool
+
+
+_large = {}
+
+
+def large_fixtures():
+    """{name: (bytes as uint8 array, stream_bytes)}: the three inputs of LARGE_CUTS -- every full segment a block of the pool by a
+    seeded choice, every short tail a ramp --, and three blocks of the pool alone"""
+    if not _large:
+        blocks = list(pool().values())
+        rng = np.random.default_rng(LARGE_SEED + 1)
+        for name, (stream_bytes, streams, last) in LARGE_CUTS.items():
+            n = stream_bytes * streams + last
+            a = np.empty(n, np.uint8)
+            for segs in cuts(n, stream_bytes):
+                for lo, hi in segs:
+                    a[lo:hi] = blocks[int(rng.integers(len(blocks)))] if hi - lo == SEGMENT else ramp(hi - lo)
+            _large[name] = (a, stream_bytes)
+        for name, block in LARGE_SINGLE.items():
+            _large[name] = (pool()[block], 1 << 20)
+    return _large
+
+
+LARGE_NAMES = tuple(LARGE_CUTS) + tuple(LARGE_SINGLE)
 
 _fixtures = {}
 

@@ -144,6 +144,89 @@ def test_streams_are_no_larger_than_zlibs_rle_streams_allow(name, fixtures):
         assert size <= z + z // 100 + 8 * segments, (size, z, segments)
 
 
+# ---- the large fixtures (tests/deflate_ref.py: large_fixtures): full-size segments by the hundred, at a frame's cut
+
+def test_the_pool_blocks_stay_in_their_classes():
+    """on the restatement alone: the stored block, the dynamic block a few dozen bytes short of it, the block of every symbol"""
+    pool = dr.pool()
+    assert tuple(pool) == dr.POOL and len(pool) == 8
+
+    def note(name):
+        info = []
+        out = dr.fragment(pool[name].tobytes(), False, info)
+        return len(out), info[0]
+    size, n = note("noise")
+    assert n["stored"] and n["margin"] >= 0 and size == dr.SEGMENT + 10
+    size, n = note("250 values")
+    assert not n["stored"] and -200 <= n["margin"] <= -1 and size == dr.SEGMENT + 10 + n["margin"], n
+    size, n = note("zeros")
+    assert not n["stored"] and size == 50
+    for name in ("laplace 3", "laplace 1.5", "random runs", "two values", "every symbol"):
+        size, n = note(name)
+        assert not n["stored"] and size < dr.SEGMENT, name
+    assert note("laplace 1.5")[0] < note("laplace 3")[0]
+    assert set(pool["two values"].tolist()) == {3, 200} and all(t < 256 for t in dr.tokens(pool["two values"].tobytes()))
+    assert any(t >= 1000 for t in dr.tokens(pool["random runs"].tobytes()))
+    toks = dr.tokens(pool["every symbol"].tobytes())
+    assert {t for t in toks if t < 256} == set(range(256))
+    matches = sorted(dr.length_symbol(t - 1000)[0] for t in toks if t >= 1000)
+    assert matches == list(range(257, 286))                          # one match per length symbol: nll = 286
+    counts = [0] * dr.LL_SYMBOLS
+    for t in toks:
+        counts[t if t < 256 else dr.length_symbol(t - 1000)[0]] += 1
+    counts[dr.EOB] = 1
+    assert all(dr.lengths(counts, 15)[0])
+
+
+def test_the_large_fixtures_have_the_cuts_they_are_there_for():
+    large = dr.large_fixtures()
+    assert tuple(large) == dr.LARGE_NAMES
+    want = {"three per stream": (11803780, 181, 541), "two per stream": (9830699, 300, 599), "frame cut": (17828971, 17, 560)}
+    pool = [b.tobytes() for b in dr.pool().values()]
+    for name, (n, streams, segments) in want.items():
+        data, stream_bytes = large[name]
+        layout = dr.cuts(data.size, stream_bytes)
+        assert (data.size, len(layout), sum(len(s) for s in layout)) == (n, streams, segments), name
+        assert len(layout[-1]) < len(layout[0])                      # a last stream shorter than the rest
+        raw = data.tobytes()
+        full = [raw[a:b] for segs in layout for a, b in segs if b - a == dr.SEGMENT]
+        assert set(full) == set(pool), name                          # every block of the pool is drawn
+        info = []
+        dr.deflate(raw, stream_bytes, 1, info)
+        assert any(i["stored"] and i["m"] == dr.SEGMENT for i in info) and any(-200 <= i["margin"] <= -1 for i in info if i["m"] == dr.SEGMENT)
+    assert sum(b - a == dr.SEGMENT for segs in dr.cuts(17828971, large["frame cut"][1]) for a, b in segs) == 543
+    two = dr.fragments(large["two per stream"][0].tobytes(), large["two per stream"][1], 0)
+    assert all(len(parts) == 2 and len(parts[1]) == 11 for parts in two[:-1]) and len(two[-1]) == 1      # a stored fragment of one byte
+    for name, block in dr.LARGE_SINGLE.items():
+        assert large[name][0] is dr.pool()[block] and dr.cuts(dr.SEGMENT, large[name][1]) == [[(0, dr.SEGMENT)]]
+
+
+@pytest.mark.parametrize("name", dr.LARGE_NAMES)
+def test_host_streams_of_the_large_fixtures_equal_the_restatement_and_inflate(name):
+    rrt = _rrt()
+    data, stream_bytes = dr.large_fixtures()[name]
+    raw = data.tobytes()
+    layout = dr.cuts(len(raw), stream_bytes)
+    segments = sum(len(s) for s in layout)
+    plan = rrt.deflate_plan(len(raw), stream_bytes)
+    assert (plan["streams"], plan["segments"]) == (len(layout), segments)
+    assert plan["out_bound"] == sum(b - a + 10 for segs in layout for a, b in segs)
+    for finish in (1, 0):
+        want = dr.deflate(raw, stream_bytes, finish)
+        got = rrt.deflate_host(data, stream_bytes, finish)
+        assert [len(s) for s in got] == [len(s) for s in want]
+        assert got == want, dr.first_difference(got, raw, stream_bytes, finish)
+        assert plan["out_bound"] >= sum(len(s) for s in got)
+        for j, (s, segs) in enumerate(zip(got, layout)):
+            z = zlib.decompressobj(-15)
+            assert z.decompress(s) == raw[segs[0][0]:segs[-1][1]], j
+            assert z.eof == (bool(finish) and j == len(layout) - 1) and z.unused_data == b"" and z.unconsumed_tail == b""
+        # the size condition of test_streams_are_no_larger_than_zlibs_rle_streams_allow: zlib is the yardstick
+        size, z = sum(len(s) for s in got), dr.zlib_rle_size(raw, stream_bytes, finish)
+        print(name, finish, size, z, z + z // 100 + 8 * segments)
+        assert size <= z + z // 100 + 8 * segments, (size, z, segments)
+
+
 def test_host_streams_do_not_depend_on_where_the_input_lies(fixtures):
     rrt = _rrt()
     for name in ("runs across chunk boundaries", "n=32769", "stride 403"):
@@ -289,6 +372,22 @@ def test_shared_source_under_sanitizers_equals_the_restatement(exerciser, fixtur
         for finish in (1, 0):
             shift = (3 * k + finish) % 16
             text.append(f"{finish} {stream_bytes} {shift} {data.size}\n{data.tobytes().hex() or '-'}\n")
+            streams = dr.deflate(data.tobytes(), stream_bytes, finish)
+            want += [" ".join(str(len(s)) for s in streams), b"".join(streams).hex()]
+    assert exerciser("streams", "".join(text)) == want
+
+
+def test_shared_source_under_sanitizers_on_full_size_segments(exerciser):
+    """the eight blocks of the pool, each a full segment, and one stream of `two per stream`: a full block and one byte.  (The three
+    large inputs stay out: their text would be tens of megabytes.)"""
+    pool = dr.pool()
+    cases = [(block, 1 << 20) for block in pool.values()]
+    cases.append((np.concatenate([pool["noise"], dr.ramp(1), pool["250 values"], dr.ramp(1)]), dr.SEGMENT + 1))
+    text, want = [], []
+    for k, (data, stream_bytes) in enumerate(cases):
+        for finish in (1, 0):
+            shift = (5 * k + finish) % 16
+            text.append(f"{finish} {stream_bytes} {shift} {data.size}\n{data.tobytes().hex()}\n")
             streams = dr.deflate(data.tobytes(), stream_bytes, finish)
             want += [" ".join(str(len(s)) for s in streams), b"".join(streams).hex()]
     assert exerciser("streams", "".join(text)) == want
